@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- star-likelihood evals/sec of the MI355X-native BASE-9 log-posterior path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run does what the headline needs and nothing else: it sets up, pre-warms and warms up, times the K steps and
+prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`, `accept_rate`).
+`--full` adds everything else described below: the roofline (HIP-event brackets inside the timed region), the sustained
+legs, the CPU baseline with its parity checks and the marginalised-mode leg.  `--dump-outputs DIR` writes, after the
+timed steps, what the timed path hands its caller after its last step -- the ensemble state of the sampler (walker
+positions and log-posteriors, the adapted proposal, the counters) -- as float64 DIR/<name>.npy; the inputs are fixed by
+seeds, so two builds run with the same arguments can be compared output for output.
 
 Workload (BASELINE.json metric: "star-likelihood evals/sec ... on synthetic 50k-star x 8-filter clusters at 1 GPU,
 with 1/2/4/8-GPU walker-parallel throughput"; configs[2] sharded 8 ways): 50 000 stars x 8 filters, PARSEC-shaped
@@ -487,6 +495,16 @@ def marginalised_leg(pack, stars, priors, truth, local_rank, source_hash, with_c
     return out
 
 
+def dump_outputs(directory: str, st: dict) -> None:
+    """--dump-outputs: the sampler's state right after the last timed step (what a caller of the timed path receives), float64."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"walker_params": st["all_params"], "walker_logpost": st["all_logpost"], "proposal_chol": st["chol"],
+              "proposal_scale": [st["scale"]], "steps_done": [st["steps"]], "accepted_local": [st["accepted_local"]]}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -494,12 +512,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--force-ranks", action="store_true",
                     help="with --gpus 1: take the multi-rank route anyway (self-launched child, RCCL communicator of one rank)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-marginalised", action="store_true", help="diagnostic: skip the marginalised-mode leg")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="diagnostic: skip the HIP-event bracketing of k_mcmc_step")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, sustained legs, CPU baseline and parity, marginalised-mode leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed path's outputs after its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-marginalised", action="store_true", help="diagnostic, with --full: skip the marginalised-mode leg")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="diagnostic, with --full: skip the HIP-event bracketing of k_mcmc_step")
     ap.add_argument("--no-prewarm", action="store_true", help="diagnostic: skip the untimed pre-warm block")
-    ap.add_argument("--no-sustained", action="store_true", help="diagnostic: skip the sustained legs")
+    ap.add_argument("--no-sustained", action="store_true", help="diagnostic, with --full: skip the sustained legs")
     args = ap.parse_args()
+    full = args.full
 
     is_rank = "RANK" in os.environ or "B9_RANK" in os.environ
     if (args.gpus > 1 or args.force_ranks) and not is_rank:
@@ -538,7 +560,8 @@ def main():
         sampler.run(prewarm)                # untimed and not part of W: clocks, first touch, RCCL channels
     sampler.run(args.warmup)                # the W untimed warm-up steps
     acc0 = sampler.state()["accepted_local"]
-    eng.enable_timing(0 if args.no_kernel_timing else TIMING_EVERY)     # also pre-creates the HIP-event pool
+    # (the roofline's HIP-event brackets inside the timed region: --full only)
+    eng.enable_timing(TIMING_EVERY if full and not args.no_kernel_timing else 0)     # also pre-creates the HIP-event pool
     eng.kernel_time_ms(reset=True)
     barrier()
     t0 = time.perf_counter()
@@ -547,15 +570,17 @@ def main():
     dt_local = time.perf_counter() - t0
     k_ms, k_n = eng.kernel_time_ms(reset=True)
     eng.enable_timing(0)
-    bracket_ms = eng.calibrate_timing()     # event bracket around an empty kernel, same stream
+    bracket_ms = eng.calibrate_timing() if full else None     # event bracket around an empty kernel, same stream
     dt = exchange.max(dt_local)             # max over ranks (RCCL all-reduce)
     st = sampler.state()                    # (the state the parity check below reads: right after the K timed steps)
     if world > 1:
         check_group(world, exchange.comm_ranks, exchange.devices)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, st)
     # ---- sustained leg: the same loop over 140 000 steps (>= 2 s), timed the same way, with the shader clock stamped on the stream at
     # both ends (in-kernel s_memtime against the 100 MHz s_memrealtime: what the chip ran at, not what sysfs says)
     sustained = None
-    if not args.no_sustained:
+    if full and not args.no_sustained:
         barrier()
         t0 = time.perf_counter()
         eng.clock_stamp(0)
@@ -570,33 +595,7 @@ def main():
                              "on both sides, max over ranks; the two clock stamps are inside the timed stretch"}
 
     if rank == 0:
-        source_hash = build.source_hash()
         evals = float(N_STARS) * n_walkers * args.steps
-        star_evals_launch = float(N_STARS) * WALKERS_PER_GPU
-        # The HIP-event bracket spans 8 consecutive launches; its time / 8 is the kernel's launch PERIOD (duration +
-        # the ~1.5 us dispatch boundary), a little above rocprofv3's kernel-only average of the same command (profiles/).
-        k_avg_s = (k_ms / max(k_n, 1)) * 1e-3
-        ops = useful_lane_ops(N_FILT, eng.max_eep(), float(np.mean(np.asarray(cl["mass_ratio"]) > 0.0)))
-        roof = valu_roofline(profile_counters("k_mcmc_step", source_hash), k_avg_s if k_n else None, ops["mean"] * star_evals_launch)
-        alg152, alg_layout = 152.0, float(eng.bytes_per_star_eval())
-        kernel_ms = 1e3 * k_avg_s * args.steps if k_n else None
-        roof.update({"kernel": "k_mcmc_step", "launches_timed": k_n, "timed_every": TIMING_EVERY, "launches_per_bracket": 8,
-                     "avg_launch_us": 1e6 * k_avg_s, "empty_kernel_bracket_us": 1e3 * bracket_ms,
-                     "useful_ops_per_star_eval": ops,
-                     "algorithmic": {"bytes_per_star_eval_survey_8d": alg152, "bytes_per_star_eval_layout": alg_layout,
-                                     "star_evals_per_launch": star_evals_launch,
-                                     "rate_GBps_8d": star_evals_launch * alg152 / k_avg_s / 1e9 if k_n else None,
-                                     "frac_of_hbm_peak_8d": star_evals_launch * alg152 / k_avg_s / 1e9 / HBM_PEAK_GBS if k_n else None,
-                                     "note": "an L2-served rate: the 8 walkers of a GPU re-read a star tile from the XCD-local L2, "
-                                             "so these bytes never cross HBM 8 times; NOT an HBM fraction"},
-                     "note": "launch duration measured live (HIP events on the launch stream); frac = issue-slot occupancy from the "
-                             "committed rocprofv3 PMC passes of this command (counters.source / .commit; null when the kernel sources "
-                             "differ from the profiled ones); useful_frac = algorithmic fp64 lane-operations (DESIGN.md section 3) "
-                             "x star-evals / launch time / (1024 SIMDs x 16 lanes x 2.4 GHz) -- needs no counter"})
-        if sustained and sustained["clock"]["mhz"] > 0:
-            scale = CLOCK_GHZ * 1e3 / sustained["clock"]["mhz"]
-            roof["frac_at_observed_clock"] = roof["frac"] * scale if roof.get("frac") is not None else None
-            roof["useful_frac_at_observed_clock"] = roof["useful_frac"] * scale if roof.get("useful_frac") is not None else None
         out = {
             "metric": "star-likelihood evals/sec", "value": evals / dt, "unit": "star-likelihood evals/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -612,7 +611,7 @@ def main():
                        "n_stars": N_STARS, "n_filters": N_FILT, "walkers_per_gpu": WALKERS_PER_GPU,
                        "walkers_total": n_walkers, "parallelism": f"walkers{world}", "ranks": exchange.world,
                        "rccl_ranks": exchange.comm_ranks, "devices": exchange.devices, "forced_ranks": bool(args.force_ranks),
-                       "mcmc_block": MCMC_BLOCK, "driver": "C++ host library (b9h::WalkerSampler), one call for the K steps",
+                       "full": full, "mcmc_block": MCMC_BLOCK, "driver": "C++ host library (b9h::WalkerSampler), one call for the K steps",
                        "collective": (exchange.name + "; one all-gather of [logpost, position, moments] rows per block") if use_rccl else "none",
                        "wd_tracks": "rectangular cooling table (wc_uniform path); the bench cluster has no WD-stage stars -- the ragged-track "
                                     "path of real cooling models is timed in profiles/ (config sweep, row C3r)",
@@ -621,22 +620,51 @@ def main():
                        "steps_per_launch_note": "Metropolis steps of every chain per k_mcmc_step / k_mcmc_tree launch: 1 at 8 walkers x 50k stars (the "
                                                 "launch is full); the single-chain BASELINE shapes run the tree-speculative launch, 3 steps each "
                                                 "(profiles/ config sweep)"},
-            "roofline": roof,
-            "timed_region_breakdown": {"kernel_ms": kernel_ms, "host_and_block_fixed_ms": (1e3 * dt - kernel_ms) if kernel_ms else None,
-                                       "wall_ms": 1e3 * dt, "ms_per_step_over_launch_period": (1e3 * dt / args.steps) / (1e3 * k_avg_s) if k_n else None},
             "accept_rate": (st["accepted_local"] - acc0) / float(WALKERS_PER_GPU * args.steps),
-            "sustained": sustained,
-            "clock_mhz_observed": sustained["clock"]["mhz"] if sustained else None,
-            "clock_note": "shader clock over the sustained leg (median over compute units of delta s_memtime / delta s_memrealtime x 100 MHz); the "
-                          "roofline peaks are quoted at the 2.4 GHz maximum -- roofline.frac_at_observed_clock rescales them",
-            "parity": "vs this repo's CPU oracle (BASE-9 parity unpinned: reference source not mounted)",
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(pack_d, cl, truth, eng=eng, sampler_state=st)
-            out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
-        if world == 1 and not args.no_marginalised:
-            out["marginalised_mode"] = marginalised_leg(pack, stars, priors, truth, local_rank, source_hash,
-                                                        with_cpu=not args.no_cpu_baseline, sustained=not args.no_sustained)
+        if full:
+            source_hash = build.source_hash()
+            star_evals_launch = float(N_STARS) * WALKERS_PER_GPU
+            # The HIP-event bracket spans 8 consecutive launches; its time / 8 is the kernel's launch PERIOD (duration +
+            # the ~1.5 us dispatch boundary), a little above rocprofv3's kernel-only average of the same command (profiles/).
+            k_avg_s = (k_ms / max(k_n, 1)) * 1e-3
+            ops = useful_lane_ops(N_FILT, eng.max_eep(), float(np.mean(np.asarray(cl["mass_ratio"]) > 0.0)))
+            roof = valu_roofline(profile_counters("k_mcmc_step", source_hash), k_avg_s if k_n else None, ops["mean"] * star_evals_launch)
+            alg152, alg_layout = 152.0, float(eng.bytes_per_star_eval())
+            kernel_ms = 1e3 * k_avg_s * args.steps if k_n else None
+            roof.update({"kernel": "k_mcmc_step", "launches_timed": k_n, "timed_every": TIMING_EVERY, "launches_per_bracket": 8,
+                         "avg_launch_us": 1e6 * k_avg_s, "empty_kernel_bracket_us": 1e3 * bracket_ms,
+                         "useful_ops_per_star_eval": ops,
+                         "algorithmic": {"bytes_per_star_eval_survey_8d": alg152, "bytes_per_star_eval_layout": alg_layout,
+                                         "star_evals_per_launch": star_evals_launch,
+                                         "rate_GBps_8d": star_evals_launch * alg152 / k_avg_s / 1e9 if k_n else None,
+                                         "frac_of_hbm_peak_8d": star_evals_launch * alg152 / k_avg_s / 1e9 / HBM_PEAK_GBS if k_n else None,
+                                         "note": "an L2-served rate: the 8 walkers of a GPU re-read a star tile from the XCD-local L2, "
+                                                 "so these bytes never cross HBM 8 times; NOT an HBM fraction"},
+                         "note": "launch duration measured live (HIP events on the launch stream); frac = issue-slot occupancy from the "
+                                 "committed rocprofv3 PMC passes of this command (counters.source / .commit; null when the kernel sources "
+                                 "differ from the profiled ones); useful_frac = algorithmic fp64 lane-operations (DESIGN.md section 3) "
+                                 "x star-evals / launch time / (1024 SIMDs x 16 lanes x 2.4 GHz) -- needs no counter"})
+            if sustained and sustained["clock"]["mhz"] > 0:
+                scale = CLOCK_GHZ * 1e3 / sustained["clock"]["mhz"]
+                roof["frac_at_observed_clock"] = roof["frac"] * scale if roof.get("frac") is not None else None
+                roof["useful_frac_at_observed_clock"] = roof["useful_frac"] * scale if roof.get("useful_frac") is not None else None
+            out.update({
+                "roofline": roof,
+                "timed_region_breakdown": {"kernel_ms": kernel_ms, "host_and_block_fixed_ms": (1e3 * dt - kernel_ms) if kernel_ms else None,
+                                           "wall_ms": 1e3 * dt, "ms_per_step_over_launch_period": (1e3 * dt / args.steps) / (1e3 * k_avg_s) if k_n else None},
+                "sustained": sustained,
+                "clock_mhz_observed": sustained["clock"]["mhz"] if sustained else None,
+                "clock_note": "shader clock over the sustained leg (median over compute units of delta s_memtime / delta s_memrealtime x 100 MHz); the "
+                              "roofline peaks are quoted at the 2.4 GHz maximum -- roofline.frac_at_observed_clock rescales them",
+                "parity": "vs this repo's CPU oracle (BASE-9 parity unpinned: reference source not mounted)",
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(pack_d, cl, truth, eng=eng, sampler_state=st)
+                out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
+            if world == 1 and not args.no_marginalised:
+                out["marginalised_mode"] = marginalised_leg(pack, stars, priors, truth, local_rank, source_hash,
+                                                            with_cpu=not args.no_cpu_baseline, sustained=not args.no_sustained)
         print(json.dumps(out), flush=True)
     exchange.barrier()
     sampler.close()

@@ -377,13 +377,43 @@ def test_bench_forced_ranks_on_one_gpu():
     ncclAllGather; the line names the collective and carries what the communicator itself reports."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "B9_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-ranks", "--steps", "20", "--warmup", "5",
-                        "--no-cpu-baseline", "--no-marginalised"], capture_output=True, text=True, timeout=600, env=env)
+                        "--full", "--no-cpu-baseline", "--no-marginalised"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     cfg = line["config"]
     assert line["n_gpus"] == 1 and cfg["ranks"] == 1 and cfg["forced_ranks"] is True
     assert "RCCL" in cfg["collective"] and cfg["rccl_ranks"] == 1 and len(cfg["devices"]) == 1 and ":" in cfg["devices"][0]
     assert line["value"] > 0 and line["roofline"]["useful_frac"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs_repeat(tmp_path):
+    """A plain `bench.py` run prints the headline only (the --full figures stay out) and `--dump-outputs` writes the timed
+    path's state after its last step as float64 .npy files: two runs with the same arguments write the same arrays, and
+    those arrays are the oracle's log-posteriors at the dumped positions."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "B9_RANK")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 20 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+        assert line["dtype"] == "f64" and line["config"]["full"] is False
+        assert not {"roofline", "sustained", "cpu_baseline", "marginalised_mode"} & set(line)
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    assert set(dumps[0]) == {"walker_params", "walker_logpost", "proposal_chol", "proposal_scale", "steps_done", "accepted_local"}
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float64 and np.all(np.isfinite(a)), name
+        np.testing.assert_array_equal(a, dumps[1][name], err_msg=name)
+    assert dumps[0]["walker_params"].shape == (8, abi.B9_NPARAM) and dumps[0]["steps_done"][0] == 1000 + 5 + 20
+    import bench
+    pack_d = synth.make_pack("parsec", bench.N_FILT)
+    truth = synth.default_params(pack_d)
+    cl = synth.make_cluster(pack_d, bench.N_STARS, seed=9003, truth=truth)
+    want = oracle.Oracle(abi.make_pack(pack_d), abi.make_stars(cl), synth.default_priors(pack_d, truth),
+                         abi.make_options()).logpost(dumps[0]["walker_params"])
+    np.testing.assert_allclose(dumps[0]["walker_logpost"], want, rtol=1e-9)
 
 
 def test_bench_under_torchrun_with_an_rccl_communicator():
@@ -394,7 +424,7 @@ def test_bench_under_torchrun_with_an_rccl_communicator():
     env["B9_FORCE_RANKS"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--no-cpu-baseline", "--no-marginalised", "--no-sustained"], capture_output=True, text=True, timeout=900, env=env)
+                        "--full", "--no-cpu-baseline", "--no-marginalised", "--no-sustained"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     cfg = line["config"]
