@@ -1,5 +1,6 @@
 // b9_capi_eval.cpp -- one log-posterior evaluation through the C ABI: derive -> stars -> finalize (b9_logpost,
-// b9_logpost_device), the per-star mass draws (b9_sample_mass) and the isochrone dump (b9_derive_isochrone).
+// b9_logpost_device), the per-star mass draws (b9_sample_mass), the isochrone dump (b9_derive_isochrone) and the forward
+// model alone (b9_predict_mags).
 #include "b9_ctx.h"
 #include <atomic>
 
@@ -234,6 +235,66 @@ int b9_derive_isochrone(b9_ctx *ctx, const double *param_row, int32_t pop, int32
     HIPCHK(ctx, hipMemcpy(buf.data(), ctx->d_iso + ctx->mass_cap, sizeof(double) * buf.size(), hipMemcpyDeviceToHost));
     for (int e = 0; e < h.n; ++e) std::memcpy(&out_mags[(size_t)e * nf], &buf[(size_t)e * nfp], sizeof(double) * nf);
     *out_n = h.n; *out_first_eep = h.first_eep; *out_agb_tip = h.agb_tip;
+    return B9_OK;
+}
+
+int b9_predict_mags(b9_ctx *ctx, const double *param_row, int64_t n, const double *mass1, const double *mass_ratio,
+                    const int32_t *wd_type, const int32_t *pop, double *out_mags, int32_t *out_stage)
+{
+    if (!ctx || !param_row || n < 0 || (n > 0 && (!mass1 || !mass_ratio || !out_mags))) return B9_ERR_INVALID;
+    if (!ctx->have_pack) return fail(ctx, B9_ERR_STATE, "load the pack first");
+    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
+    int n_pops = 1;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!std::isfinite(mass1[i]) || !std::isfinite(mass_ratio[i]) || mass_ratio[i] < 0.0)
+            return fail(ctx, B9_ERR_INVALID, "b9_predict_mags: system " + std::to_string(i) + " has a non-finite mass or a negative mass ratio");
+        if (pop && (pop[i] < 0 || pop[i] > 1)) return fail(ctx, B9_ERR_INVALID, "b9_predict_mags: a population is 0 or 1");
+        if (pop && pop[i] == 1) n_pops = 2;        // the second isochrone is derived only when some system needs it
+    }
+    if (n == 0) return B9_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const DevPack &pk = ctx->pk;
+    const int nf = pk.nf, mass_cap = (pk.max_eep + 1) & ~1;
+    const long long iso_stride = (long long)mass_cap * (pk.nfp + 1);
+    if (b9k_predict_lds(pk.nfp, mass_cap, n_pops) > 160 * 1024)
+        return fail(ctx, B9_ERR_CAPACITY, "b9_predict_mags: the derived isochrones do not fit the kernel's LDS");
+    if (!ctx->d_pred_hdr) {
+        HIPCHK(ctx, hipMalloc((void **)&ctx->d_pred_hdr, sizeof(IsoHdr) * 2));
+        HIPCHK(ctx, hipMalloc((void **)&ctx->d_pred_par, sizeof(double) * B9_NPARAM));
+    }
+    if ((size_t)(2 * iso_stride) > ctx->pred_iso_cap) {
+        if (ctx->d_pred_iso) (void)hipFree(ctx->d_pred_iso);
+        ctx->d_pred_iso = nullptr; ctx->pred_iso_cap = 0;
+        HIPCHK(ctx, hipMalloc((void **)&ctx->d_pred_iso, sizeof(double) * 2 * iso_stride));
+        ctx->pred_iso_cap = (size_t)(2 * iso_stride);
+    }
+    // systems in chunks of at most 2^20 (every system's result depends on that system alone, so the chunking is invisible)
+    const int64_t chunk = std::min<int64_t>(n, (int64_t)1 << 20);
+    const size_t o_q = sizeof(double) * chunk, o_mags = 2 * o_q, o_wd = o_mags + sizeof(double) * chunk * nf;
+    const size_t o_pop = o_wd + sizeof(int) * chunk, o_stage = o_pop + sizeof(int) * chunk, bytes = o_stage + sizeof(int) * chunk;
+    if (bytes > ctx->pred_io_cap) {
+        if (ctx->d_pred_io) (void)hipFree(ctx->d_pred_io);
+        ctx->d_pred_io = nullptr; ctx->pred_io_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->d_pred_io, bytes));
+        ctx->pred_io_cap = bytes;
+    }
+    char *io = static_cast<char *>(ctx->d_pred_io);
+    double *d_m1 = reinterpret_cast<double *>(io), *d_q = reinterpret_cast<double *>(io + o_q), *d_mags = reinterpret_cast<double *>(io + o_mags);
+    int *d_wd = reinterpret_cast<int *>(io + o_wd), *d_pop = reinterpret_cast<int *>(io + o_pop), *d_stage = reinterpret_cast<int *>(io + o_stage);
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, b9k_derive_iso_rows(pk, param_row, ctx->d_pred_par, 1, n_pops, ctx->d_pred_hdr, ctx->d_pred_iso, iso_stride, mass_cap, s));
+    for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+        const int64_t m = std::min(chunk, n - i0);
+        HIPCHK(ctx, hipMemcpyAsync(d_m1, mass1 + i0, sizeof(double) * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(d_q, mass_ratio + i0, sizeof(double) * m, hipMemcpyHostToDevice, s));
+        if (wd_type) HIPCHK(ctx, hipMemcpyAsync(d_wd, wd_type + i0, sizeof(int) * m, hipMemcpyHostToDevice, s));
+        if (pop) HIPCHK(ctx, hipMemcpyAsync(d_pop, pop + i0, sizeof(int) * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, b9k_predict_mags(pk, ctx->d_pred_hdr, ctx->d_pred_iso, iso_stride, mass_cap, n_pops, ctx->d_pred_par, m, d_m1, d_q,
+                                     wd_type ? d_wd : nullptr, pop ? d_pop : nullptr, d_mags, d_stage, 4 * ctx->n_cu, s));
+        HIPCHK(ctx, hipMemcpyAsync(out_mags + (size_t)i0 * nf, d_mags, sizeof(double) * m * nf, hipMemcpyDeviceToHost, s));
+        if (out_stage) HIPCHK(ctx, hipMemcpyAsync(out_stage + i0, d_stage, sizeof(int) * m, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));      // (the host arrays of the next chunk reuse the same device buffers)
+    }
     return B9_OK;
 }
 

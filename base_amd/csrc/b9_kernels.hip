@@ -23,6 +23,8 @@
 //                                     of step t+1 on extra workgroups
 //   k_finalize     row a8              fixed-order sum of the partials + cluster prior (+ the accept
 //                                     of a two-launch sampler block's last step)
+//   k_predict_mags rows a4-a7, a9      b9_predict_mags: the forward model alone (no observations) --
+//                                     one lane per system, predicted apparent magnitudes + stage
 //
 // The kernels live in the *.hip.h files included below (one translation unit); this file holds
 // k_finalize and the host-callable launch wrappers.
@@ -61,6 +63,7 @@ namespace tree_kd5 {
 #undef B9_TREE_KD
 #include "b9_star_marg.hip.h"
 #include "b9_marg_step.hip.h"
+#include "b9_predict.hip.h"
 
 // ------------------------------------------------------------------------------------------
 // k_finalize: one workgroup per walker: fixed-order sum of the partials + prior -> logpost[w]
@@ -182,6 +185,40 @@ hipError_t b9k_finalize(const IsoHdr *hdr, const double *partial, int n_partial,
     hipLaunchKernelGGL(k_finalize, dim3(n_walkers), dim3(256), 0, stream, hdr, partial, n_partial, partial_stride,
                        n_pops, d_params, pr, d_logpost, perstar, n_stars, mc, done_flag, done_seq);
     return hipGetLastError();
+}
+
+template <int NFP>
+static hipError_t launch_predict_mags(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                                      int n_pops, const double *d_params, long long n, const double *mass1, const double *mass_ratio,
+                                      const int *wd_type, const int *pop, double *out_mags, int *out_stage, int n_wgs, hipStream_t stream)
+{
+    const size_t lds = sizeof(double) * (size_t)n_pops * mass_cap * (NFP + 1);
+    auto kern = k_predict_mags<NFP>;
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const long long need = (n + 255) / 256;
+    hipLaunchKernelGGL(kern, dim3((unsigned)std::max(1ll, std::min<long long>(need, n_wgs))), dim3(256), lds, stream, pk, hdr, iso_data,
+                       iso_stride, mass_cap, n_pops, d_params, n, mass1, mass_ratio, wd_type, pop, out_mags, out_stage);
+    return hipGetLastError();
+}
+
+size_t b9k_predict_lds(int nfp, int mass_cap, int n_pops) { return sizeof(double) * (size_t)n_pops * mass_cap * (nfp + 1); }
+
+hipError_t b9k_predict_mags(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap, int n_pops,
+                            const double *d_params, long long n, const double *mass1, const double *mass_ratio, const int *wd_type,
+                            const int *pop, double *out_mags, int *out_stage, int n_wgs, hipStream_t stream)
+{
+#define PM_ARGS pk, hdr, iso_data, iso_stride, mass_cap, n_pops, d_params, n, mass1, mass_ratio, wd_type, pop, out_mags, out_stage, n_wgs, stream
+    switch (pk.nfp) {
+    case 4:  return launch_predict_mags<4>(PM_ARGS);
+    case 8:  return launch_predict_mags<8>(PM_ARGS);
+    case 16: return launch_predict_mags<16>(PM_ARGS);
+    default: return hipErrorInvalidValue;
+    }
+#undef PM_ARGS
 }
 
 // doubles of one (walker, population)'s node table (MargLayout, b9_device.h)

@@ -99,6 +99,13 @@ hipError_t b9k_tree_begin(const double *host_up, double *dev, int up_words, cons
 // summary rows of a two-launch block from its chain record on the device (sd: d, n_walkers, n_steps, samples, free_idx, row_origin, rows)
 hipError_t b9k_chain_rows(const StepDev &sd, const double *cur_fin, const double *lp_fin, hipStream_t stream);
 
+// b9_predict_mags: n systems at the ONE row d_params whose isochrone(s) hdr / iso_data hold (n_pops of them, population k at
+// iso_data + k iso_stride); device pointers; out_mags [n][pk.nf] (real filters only), out_stage [n]; at most n_wgs workgroups
+hipError_t b9k_predict_mags(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap, int n_pops,
+                            const double *d_params, long long n, const double *mass1, const double *mass_ratio, const int *wd_type /* nullable */,
+                            const int *pop /* nullable */, double *out_mags, int *out_stage, int n_wgs, hipStream_t stream);
+size_t b9k_predict_lds(int nfp, int mass_cap, int n_pops);      // its dynamic LDS per workgroup, bytes (at most 160 KB launches)
+
 hipError_t b9k_noop(hipStream_t stream);
 hipError_t b9k_spin(double microseconds, hipStream_t stream);
 constexpr int B9_CLOCK_SLOTS = 8 * 256;      // (XCD, HW_ID[15:8]) -> one slot per compute unit

@@ -182,6 +182,28 @@ class Engine:
         k = n.value
         return first.value, mass[:k].copy(), mags[:k * self.n_filt].reshape(k, self.n_filt).copy(), tip.value
 
+    def predict_mags(self, param_row: np.ndarray, mass1, mass_ratio, wd_type=None, pop=None) -> Tuple[np.ndarray, np.ndarray]:
+        """b9_predict_mags: predicted apparent magnitudes [n, n_filt] and stages [n] of n systems at one parameter row
+        (B9_MAG_NOFLUX / B9_STAGE_DNE where the row lies outside the grid).  wd_type / pop: None = all DA / all population 0."""
+        row = np.ascontiguousarray(param_row, dtype=np.float64).reshape(abi.B9_NPARAM)
+        m1 = np.ascontiguousarray(mass1, dtype=np.float64).ravel()
+        q = np.ascontiguousarray(mass_ratio, dtype=np.float64).ravel()
+        n = m1.size
+        if q.size != n:
+            raise ValueError("mass1 and mass_ratio differ in length")
+        wt = None if wd_type is None else np.ascontiguousarray(wd_type, dtype=np.int32).ravel()
+        pp = None if pop is None else np.ascontiguousarray(pop, dtype=np.int32).ravel()
+        for a in (wt, pp):
+            if a is not None and a.size != n:
+                raise ValueError("wd_type / pop differ in length from mass1")
+        mags = np.empty((n, self.n_filt))
+        stage = np.empty(n, dtype=np.int32)
+        self._check(self.lib.b9_predict_mags(self._ctx, row.ctypes.data_as(_dp), n, m1.ctypes.data_as(_dp), q.ctypes.data_as(_dp),
+                                             wt.ctypes.data_as(_ip) if wt is not None else None,
+                                             pp.ctypes.data_as(_ip) if pp is not None else None,
+                                             mags.ctypes.data_as(_dp), stage.ctypes.data_as(_ip)))
+        return mags, stage
+
     # -- introspection --------------------------------------------------------------------
     def bytes_per_star_eval(self) -> int:
         return int(self.lib.b9_bytes_per_star_eval(self._ctx))

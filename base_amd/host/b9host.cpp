@@ -125,6 +125,13 @@ const std::map<std::string, std::string> &Settings::flag_map()
         {"mode", "gpu.mode"}, {"marginalise", "gpu.marginalise"}, {"forceRanks", "gpu.forceRanks"}, {"tilesPerBlock", "gpu.tilesPerBlock"},
         {"resComment", "gpu.resComment"},
         {"margIsoIncrem", "sampleMass.margIsoIncrem"}, {"nMassRatios", "sampleMass.nMassRatios"},
+        {"nStars", "simCluster.nStars"}, {"percentBinary", "simCluster.percentBinary"}, {"percentDB", "simCluster.percentDB"},
+        {"nFieldStars", "simCluster.nFieldStars"}, {"minMass", "simCluster.minMass"}, {"maxMass", "simCluster.maxMass"},
+        {"minMassRatio", "simCluster.minMassRatio"}, {"memberPrior", "simCluster.memberPrior"}, {"nPops", "simCluster.nPops"},
+        {"brightLimit", "scatterCluster.brightLimit"}, {"faintLimit", "scatterCluster.faintLimit"},
+        {"relevantFilt", "scatterCluster.relevantFilt"}, {"limitS2N", "scatterCluster.limitS2N"},
+        {"sigmaFloor", "scatterCluster.sigmaFloor"}, {"sigmaAtLimit", "scatterCluster.sigmaAtLimit"},
+        {"scatterSeed", "scatterCluster.seed"},
     };
     return m;
 }

@@ -4,10 +4,12 @@
 #include "../../include/base9_host.h"
 #include "b9host.hpp"
 #include "b9sampler.hpp"
+#include "b9sim.hpp"
 #include "cli_common.hpp"
 
 #include <hip/hip_runtime_api.h>
 
+#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
@@ -64,6 +66,70 @@ int b9h_settings_dump(int argc, char **argv, char *out, int cap)
         std::string d = st.dump();
         std::strncpy(out, d.c_str(), (size_t)cap - 1);
         out[cap - 1] = '\0';
+    });
+}
+
+// ---- simCluster / scatterCluster draws (b9sim.hpp) -----------------------------------------------------------------
+namespace {
+std::string g17(double v)
+{
+    char b[40];
+    std::snprintf(b, sizeof b, "%.17g", v);
+    return b;
+}
+}  // namespace
+
+int b9h_sim_draw_systems(uint64_t seed, int64_t i0, int64_t n, double min_mass, double max_mass, double percent_binary,
+                         double min_mass_ratio, double percent_db, int n_pops, double lambda, const double *tip,
+                         double *mass1, double *mass_ratio, int32_t *wd_type, int32_t *pop)
+{
+    return guard([&] {
+        b9h::Settings st;              // through the settings, so that the values are checked as simCluster checks them
+        st.set("simCluster.minMass", g17(min_mass)); st.set("simCluster.maxMass", g17(max_mass));
+        st.set("simCluster.percentBinary", g17(percent_binary)); st.set("simCluster.minMassRatio", g17(min_mass_ratio));
+        st.set("simCluster.percentDB", g17(percent_db)); st.set("simCluster.nPops", std::to_string(n_pops));
+        b9h::SimConfig c = b9h::sim_config(st);
+        c.seed = seed;
+        const double tips[2] = {tip[0], n_pops == 2 ? tip[1] : tip[0]};
+        b9h::sim_draw_systems(c, lambda, tips, i0, n, mass1, mass_ratio, wd_type, pop);
+    });
+}
+
+int b9h_sim_field_mags(uint64_t seed, int64_t i0, int64_t n, int n_filt, const double *lo, const double *hi, double *mags)
+{
+    return guard([&] { b9h::sim_field_mags(seed, i0, n, n_filt, lo, hi, mags); });
+}
+
+int b9h_scatter(uint64_t seed, const int64_t *ids, int64_t n, int n_filt, const double *mags, double sigma_floor,
+                double sigma_at_limit, double faint_limit, double *sigma, double *obs)
+{
+    return guard([&] {
+        b9h::ScatterConfig c;
+        c.seed = seed; c.sigma_floor = sigma_floor; c.sigma_at_limit = sigma_at_limit; c.faint_limit = faint_limit;
+        b9h::scatter_noise(c, ids, n, n_filt, mags, sigma, obs);
+    });
+}
+
+int b9h_sim_settings(int program, int argc, char **argv, char *out, int cap)
+{
+    return guard([&] {
+        b9h::Settings st;
+        st.parse_args(argc, argv);
+        std::string d;
+        if (program == 0) {
+            const b9h::SimConfig c = b9h::sim_config(st);
+            d = "nStars = " + std::to_string(c.n_stars) + "\nnFieldStars = " + std::to_string(c.n_field) +
+                "\npercentBinary = " + g17(c.percent_binary) + "\npercentDB = " + g17(c.percent_db) + "\nminMass = " + g17(c.min_mass) +
+                "\nmaxMass = " + g17(c.max_mass) + "\nminMassRatio = " + g17(c.min_mass_ratio) + "\nmemberPrior = " + g17(c.member_prior) +
+                "\nnPops = " + std::to_string(c.n_pops) + "\nseed = " + std::to_string(c.seed) + "\n";
+        } else {
+            const b9h::ScatterConfig c = b9h::scatter_config(st);
+            d = "brightLimit = " + g17(c.bright_limit) + "\nfaintLimit = " + g17(c.faint_limit) + "\nrelevantFilt = " +
+                std::to_string(c.relevant_filt) + "\nlimitS2N = " + g17(c.limit_s2n) + "\nsigmaFloor = " + g17(c.sigma_floor) +
+                "\nsigmaAtLimit = " + g17(c.sigma_at_limit) + "\nmemberPrior = " + g17(c.member_prior) + "\nseed = " + std::to_string(c.seed) + "\n";
+        }
+        if ((int)d.size() >= cap) throw std::runtime_error("b9h_sim_settings: output buffer too small");
+        std::memcpy(out, d.c_str(), d.size() + 1);
     });
 }
 

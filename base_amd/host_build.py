@@ -1,5 +1,5 @@
 """Builds the C++ host programs (base_amd/host/): libbase9host.so + singlePopMcmc, multiPopMcmc,
-makeCMD, sampleMass.  Plain g++ against the C ABI; they link libbase9hip.so by rpath."""
+makeCMD, sampleMass, simCluster, scatterCluster.  Plain g++ against the C ABI; they link libbase9hip.so by rpath."""
 from __future__ import annotations
 
 import os
@@ -33,10 +33,10 @@ def build_host(force: bool = False) -> None:
     """libbase9host.so = parsers + sampler (g++) + the RCCL exchange and the C surface (hipcc as a host compiler, for the
     HIP / RCCL headers: neither file holds device code); it links libbase9hip.so, librccl and libamdhip64."""
     os.makedirs(BIN, exist_ok=True)
-    hdrs = [os.path.join(HOST, f) for f in ("b9host.hpp", "cli_common.hpp", "b9sampler.hpp", "b9dist.hpp")] + \
+    hdrs = [os.path.join(HOST, f) for f in ("b9host.hpp", "cli_common.hpp", "b9sampler.hpp", "b9dist.hpp", "b9sim.hpp")] + \
         [os.path.join(HERE, "..", "include", f) for f in ("base9_hip.h", "base9_host.h")]
     lib = os.path.join(HOST, "libbase9host.so")
-    gxx_src = ["b9host.cpp", "b9sampler.cpp", "cli_common.cpp"]
+    gxx_src = ["b9host.cpp", "b9sampler.cpp", "cli_common.cpp", "b9sim.cpp"]
     hip_src = ["b9dist.cpp", "capi_host.cpp"]
     link = ["-L" + CSRC, "-lbase9hip", "-Wl,-rpath," + CSRC, "-Wl,-rpath,$ORIGIN/../../csrc"]
     if force or _stale(lib, [os.path.join(HOST, f) for f in gxx_src + hip_src] + hdrs):
@@ -53,7 +53,8 @@ def build_host(force: bool = False) -> None:
         _run(["g++", "-shared", "-o", lib] + objs + link + ["-L" + os.path.join(ROCM, "lib"), "-lrccl", "-lamdhip64",
                                                             "-Wl,-rpath," + os.path.join(ROCM, "lib")])
     progs = {"singlePopMcmc": ("mcmc_main.cpp", ["-DB9_N_POPS=1"]), "multiPopMcmc": ("mcmc_main.cpp", ["-DB9_N_POPS=2"]),
-             "makeCMD": ("makecmd_main.cpp", []), "sampleMass": ("samplemass_main.cpp", [])}
+             "makeCMD": ("makecmd_main.cpp", []), "sampleMass": ("samplemass_main.cpp", []),
+             "simCluster": ("simcluster_main.cpp", []), "scatterCluster": ("scattercluster_main.cpp", [])}
     for name, (src, defs) in progs.items():
         exe = os.path.join(BIN, name)
         srcp = os.path.join(HOST, src)

@@ -35,6 +35,7 @@ HOST_SYMBOLS = [
     "b9h_sampler_create", "b9h_sampler_create_callback", "b9h_sampler_free", "b9h_sampler_initialise", "b9h_sampler_run",
     "b9h_sampler_n_local", "b9h_sampler_state", "b9h_summary_rows",
     "b9h_load_pack", "b9h_free_pack", "b9h_read_phot", "b9h_free_phot", "b9h_settings_dump", "b9h_merge_parts",
+    "b9h_sim_draw_systems", "b9h_sim_field_mags", "b9h_scatter", "b9h_sim_settings",
 ]
 
 _lib = None
@@ -81,6 +82,11 @@ def load() -> C.CDLL:
     lib.b9h_free_phot.argtypes = [vp]
     lib.b9h_settings_dump.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     lib.b9h_merge_parts.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_long]
+    lib.b9h_sim_draw_systems.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                         C.c_int, C.c_double, _dp, _dp, _dp, _ip, _ip]
+    lib.b9h_sim_field_mags.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int, _dp, _dp, _dp]
+    lib.b9h_scatter.argtypes = [C.c_uint64, C.POINTER(C.c_int64), C.c_int64, C.c_int, _dp, C.c_double, C.c_double, C.c_double, _dp, _dp]
+    lib.b9h_sim_settings.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     _lib = lib
     return lib
 
@@ -277,3 +283,52 @@ def summary_rows(samples: np.ndarray, params_end: np.ndarray, logpost_end: np.nd
     _check(load().b9h_summary_rows(samples.ctypes.data_as(_dp), pe.ctypes.data_as(_dp), le.ctypes.data_as(_dp), n, wl, d,
                                    og.ctypes.data_as(_dp), rows.ctypes.data_as(_dp)))
     return rows
+
+
+# ------------------------------------------------------------------------------------------
+# simCluster / scatterCluster draws (b9sim.hpp; docs/FORMATS.md "Simulation draws")
+# ------------------------------------------------------------------------------------------
+def sim_draw_systems(seed: int, i0: int, n: int, tip, min_mass: float = 0.1, max_mass: float = 8.0, percent_binary: float = 0.0,
+                     min_mass_ratio: float = 0.0, percent_db: float = 0.0, n_pops: int = 1, lam: float = 0.5):
+    """Systems i0 .. i0+n-1 of simCluster: (mass1, mass_ratio, wd_type, pop).  tip: AGB-tip mass per population."""
+    t = np.atleast_1d(np.asarray(tip, dtype=np.float64))
+    tips = np.array([t[0], t[-1]])
+    m1, q = np.empty(n), np.empty(n)
+    wt, pop = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+    _check(load().b9h_sim_draw_systems(int(seed), int(i0), int(n), float(min_mass), float(max_mass), float(percent_binary),
+                                       float(min_mass_ratio), float(percent_db), int(n_pops), float(lam), tips.ctypes.data_as(_dp),
+                                       m1.ctypes.data_as(_dp), q.ctypes.data_as(_dp), wt.ctypes.data_as(_ip), pop.ctypes.data_as(_ip)))
+    return m1, q, wt, pop
+
+
+def sim_field_mags(seed: int, i0: int, n: int, lo, hi) -> np.ndarray:
+    """Field-star magnitudes [n, n_filt] of systems i0 .. i0+n-1: uniform in [lo, hi] per filter."""
+    lo = np.ascontiguousarray(lo, dtype=np.float64)
+    hi = np.ascontiguousarray(hi, dtype=np.float64)
+    out = np.empty((n, lo.size))
+    _check(load().b9h_sim_field_mags(int(seed), int(i0), int(n), lo.size, lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp),
+                                     out.ctypes.data_as(_dp)))
+    return out
+
+
+def scatter(seed: int, ids, mags, sigma_floor: float, sigma_at_limit: float, faint_limit: float):
+    """scatterCluster's noise: (sigma, obs), each [n, n_filt], for systems `ids` with noiseless magnitudes `mags`."""
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    mags = np.ascontiguousarray(mags, dtype=np.float64).reshape(ids.size, -1)
+    sigma, obs = np.empty_like(mags), np.empty_like(mags)
+    _check(load().b9h_scatter(int(seed), ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size, mags.shape[1], mags.ctypes.data_as(_dp),
+                              float(sigma_floor), float(sigma_at_limit), float(faint_limit), sigma.ctypes.data_as(_dp), obs.ctypes.data_as(_dp)))
+    return sigma, obs
+
+
+def sim_settings(program: str, args: Sequence[str]) -> dict:
+    """The resolved, checked settings of a simCluster / scatterCluster command line (args without the program name)."""
+    argv = [program.encode()] + [a.encode() for a in args]
+    arr = (C.c_char_p * len(argv))(*argv)
+    buf = C.create_string_buffer(8192)
+    _check(load().b9h_sim_settings(0 if program == "simCluster" else 1, len(argv), arr, buf, len(buf)))
+    out = {}
+    for line in buf.value.decode().splitlines():
+        k, v = line.split(" = ", 1)
+        out[k] = float(v)
+    return out

@@ -324,6 +324,28 @@ int b9_derive_isochrone(b9_ctx *ctx, const double *param_row, int32_t pop, int32
                         double *out_mass, double *out_mags,
                         int32_t *out_first_eep, int32_t *out_n, double *out_agb_tip);
 
+/*
+ * Predicted apparent magnitudes of n stellar systems at one parameter row (the forward half of rows a4-a7, a9; [RECALL]
+ * what simCluster evaluates per star).  Added in ABI 6 without a version change: it is purely additive, and nothing
+ * else in this header changed.  Needs a loaded pack, not loaded stars, and never touches the stars or the work buffers
+ * a sampler block uses (a B9_BLOCK_CONTINUE block enqueued after this call gives the same bits as one enqueued without
+ * it); B9_ERR_STATE while a block is outstanding.  All pointers are host pointers; synchronous, like b9_sample_mass.
+ * System i: primary ZAMS mass mass1[i] (finite), mass ratio mass_ratio[i] >= 0 (0 = single), wd_type[i] (0 DA, 1 DB;
+ * NULL = all DA), pop[i] (0 uses B9_P_Y, 1 uses B9_P_Y2 as b9_derive_isochrone does; NULL = all 0; the second
+ * isochrone is derived only when some system needs it).  out_mags [n * n_filt] receives exactly what the likelihood
+ * compares with obs: the primary's magnitudes (MS/RGB, the WD branch, or B9_MAG_NOFLUX below the isochrone's first mass
+ * and above m_wd_up), flux-combined with the secondary at mass_ratio * mass1 when mass_ratio > 0, plus
+ * mod + (abs_coeff - 1) * Av -- except that a filter in which neither component gives flux is exactly B9_MAG_NOFLUX.
+ * out_stage (nullable, [n]): B9_STAGE_MSRG for mass1 <= the population's AGB tip, B9_STAGE_WD up to m_wd_up,
+ * B9_STAGE_NSBH above.  A row outside the grid (for a system's population) is not an error: that system's magnitudes
+ * are all B9_MAG_NOFLUX and its stage B9_STAGE_DNE.  Every system's result depends on that system alone, so results are
+ * the same bits however the systems are batched or ordered; n is unbounded (the call works in chunks of 2^20).
+ */
+int b9_predict_mags(b9_ctx *ctx, const double *param_row, int64_t n,
+                    const double *mass1, const double *mass_ratio,
+                    const int32_t *wd_type /* nullable: all DA */, const int32_t *pop /* nullable: all 0 */,
+                    double *out_mags /* [n * n_filt] */, int32_t *out_stage /* nullable, [n] */);
+
 /* ---- introspection (used by bench/tests; no compute) --------------------------------- */
 int b9_max_eep(const b9_ctx *ctx);           /* longest isochrone in the loaded pack        */
 int b9_device_id(const b9_ctx *ctx);

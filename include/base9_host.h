@@ -81,6 +81,22 @@ int b9h_read_phot(const char *path, double min_mag, double max_mag, int index, v
                   char *filters_out, int filters_cap);
 void b9h_free_phot(void *handle);
 int b9h_settings_dump(int argc, char **argv, char *out, int cap);
+/* ---- simCluster / scatterCluster draws (docs/FORMATS.md "Simulation draws"; libbase9host's one definition of them) -------- */
+/* Counter-based Philox4x32-10, key = (seed lo, seed hi), counter = (i lo, i hi, purpose, j): every value of system i is a
+ * function of (seed, i, settings) alone.  Systems i0 .. i0+n-1: primary mass (purpose 0), mass ratio (1; 0 above tip[pop]),
+ * DB atmosphere (2), population (3; n_pops == 2: 1 when u >= lambda).  tip: [2] AGB-tip masses of the populations'
+ * isochrones (tip[1] is read only when n_pops == 2).  Settings are checked as simCluster checks them. */
+int b9h_sim_draw_systems(uint64_t seed, int64_t i0, int64_t n, double min_mass, double max_mass, double percent_binary,
+                         double min_mass_ratio, double percent_db, int n_pops, double lambda, const double *tip,
+                         double *mass1, double *mass_ratio, int32_t *wd_type, int32_t *pop);
+/* field-star magnitudes of systems i0 .. i0+n-1 (purpose 4): mags[k][f] uniform in [lo[f], hi[f]] */
+int b9h_sim_field_mags(uint64_t seed, int64_t i0, int64_t n, int n_filt, const double *lo, const double *hi, double *mags);
+/* scatterCluster's noise (purpose 5) of the systems ids[0 .. n): sigma = sqrt(floor^2 + (at_limit 10^(0.2 (m - faint)))^2),
+ * obs = m + sigma z; mags / sigma / obs [n][n_filt] */
+int b9h_scatter(uint64_t seed, const int64_t *ids, int64_t n, int n_filt, const double *mags, double sigma_floor,
+                double sigma_at_limit, double faint_limit, double *sigma, double *obs);
+/* the resolved and checked simCluster (program 0) / scatterCluster (program 1) settings of a command line, "key = value" lines */
+int b9h_sim_settings(int program, int argc, char **argv, char *out, int cap);
 /* rank 0's merge of <final_path>.part<r> into <final_path> after a --gpus N run (b9h::merge_result_parts; exposed for tests) */
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part);
 
