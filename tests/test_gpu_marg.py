@@ -49,8 +49,8 @@ def test_marginalised_mcmc_block_runs():
 
 @pytest.mark.parametrize("n_pops", [1, 2])
 def test_marginalised_device_block_matches_host_twin(n_pops):
-    """The two-launch sampler step (what marginalised mode runs) against the host twin driving the same
-    marginalised log-posterior: same chain."""
+    """The marginalised sampler block (the fused k_marg_step on this pack; the two-launch step only where marg_fused_ok
+    fails) against the host twin driving the same marginalised log-posterior: same chain."""
     from base_amd import engine, mcmc
     pack_d, cl, pack, stars, priors, _ = build_problem("dsed", 5, n_stars=120, wd_frac=0.05, n_y=3 if n_pops == 2 else 1,
                                                        n_pops=n_pops, n_feh=3, n_age=5, n_eep=40, seed=6)

@@ -10,6 +10,7 @@ import pytest
 
 import oracle
 from base_amd import abi, hostlib, mcmc, synth
+from chain_check import oracle_delta as _oracle_delta
 from conftest import build_problem
 
 pytestmark = pytest.mark.gpu
@@ -212,20 +213,6 @@ def test_rank_count_invariance_at_50k_stars(n_walkers):
         np.testing.assert_array_equal(st["all_logpost"], st1["all_logpost"])
 
 
-def _oracle_delta(orc, template_row, free, samples, lps):
-    """max relative |delta| between recorded chain log-posteriors and the oracle at the recorded positions; every
-    DISTINCT visited state is evaluated once (a rejected step repeats its predecessor's row)."""
-    flat = samples.reshape(-1, samples.shape[-1])
-    uniq, inverse = np.unique(flat, axis=0, return_inverse=True)
-    rows = np.repeat(np.asarray(template_row, dtype=np.float64)[None, :], len(uniq), axis=0)
-    rows[:, list(free)] = uniq
-    want = orc.logpost(rows)[inverse.ravel()]
-    got = lps.reshape(-1)
-    assert np.array_equal(np.isfinite(got), np.isfinite(want))
-    fin = np.isfinite(want)
-    return float(np.max(np.abs(got[fin] - want[fin]) / np.maximum(1.0, np.abs(want[fin])))), len(uniq)
-
-
 @pytest.mark.parametrize("name", ["C0", "C1", "C2", "C3", "C4"])
 def test_sampler_logposts_match_oracle_full_size(name):
     """The TIMED path -- k_mcmc_step driven by the C++ sampler (b9h::WalkerSampler: fused one-launch steps, pipelined
@@ -259,7 +246,8 @@ def test_sampler_logposts_match_oracle_full_size(name):
 
 
 def test_marginalised_mode_through_the_sampler():
-    """Marginalised mode runs the same pipelined blocks as given-mass mode (two launches per step instead of one):
+    """Marginalised mode runs the same pipelined blocks as given-mass mode (one k_marg_step launch per step, or the two-launch
+    step when its node-table builders would not fit the fused step's LDS budget):
     B9_BLOCK_ASYNC | CONTINUE, summary rows condensed on the device (k_chain_rows) and read from HBM by a one-rank RCCL
     all-gather.  Chain log-posteriors equal the oracle's marginalised ones; the device rows equal the host statement;
     two continued blocks equal one block of twice the length; the RCCL exchange changes nothing."""
