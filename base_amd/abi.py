@@ -192,7 +192,7 @@ ABI_SYMBOLS = [
     "b9_abi_version", "b9_ctx_create", "b9_ctx_destroy", "b9_last_error",
     "b9_load_pack", "b9_load_stars", "b9_set_priors", "b9_set_options", "b9_set_tuning", "b9_get_tuning",
     "b9_logpost", "b9_logpost_device", "b9_mcmc_run_block", "b9_mcmc_wait", "b9_sample_mass", "b9_derive_isochrone",
-    "b9_predict_mags", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
+    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
     "b9_enable_timing", "b9_kernel_time_ms", "b9_calibrate_timing", "b9_clock_stamp", "b9_clock_mhz",
 ]
 
@@ -225,6 +225,8 @@ def load_hip_library(path: Optional[str] = None) -> C.CDLL:
     lib.b9_sample_mass.argtypes = [vp, _dp, C.c_int32, C.c_uint64, C.c_int64, _dp, _dp, _dp, _ip]
     lib.b9_derive_isochrone.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, _dp, _ip, _ip, _dp]
     lib.b9_predict_mags.argtypes = [vp, _dp, C.c_int64, _dp, _dp, _ip, _ip, _dp, _ip]
+    lib.b9_n_wd_stars.argtypes = [vp]
+    lib.b9_sample_wd_mass.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]
     lib.b9_max_eep.argtypes = [vp]
     lib.b9_device_id.argtypes = [vp]
     lib.b9_bytes_per_star_eval.argtypes = [vp]

@@ -182,7 +182,7 @@ void b9_ctx_destroy(b9_ctx *ctx)
     free_all(ctx->marg_plan_allocs);
     void *bufs[] = {ctx->d_hdr, ctx->d_iso, ctx->d_partial, ctx->d_params, ctx->d_logpost, ctx->d_perstar, ctx->d_marg_tab, ctx->d_marg_wd_tab, ctx->d_marg_shares,
                     ctx->d_tree_hdr, ctx->d_tree_iso, ctx->d_tree_par, ctx->d_tree_partial,
-                    ctx->d_pred_hdr, ctx->d_pred_iso, ctx->d_pred_par, ctx->d_pred_io};
+                    ctx->d_pred_hdr, ctx->d_pred_iso, ctx->d_pred_par, ctx->d_pred_io, ctx->d_wds};
     for (void *p : bufs) if (p) (void)hipFree(p);
     for (auto &sl : ctx->slot) {
         if (sl.d) (void)hipFree(sl.d);

@@ -1,7 +1,8 @@
 // b9_capi_eval.cpp -- one log-posterior evaluation through the C ABI: derive -> stars -> finalize (b9_logpost,
 // b9_logpost_device), the per-star mass draws (b9_sample_mass), the isochrone dump (b9_derive_isochrone) and the forward
-// model alone (b9_predict_mags).
+// model alone (b9_predict_mags) and the WD-stage stars' posterior draws (b9_sample_wd_mass).
 #include "b9_ctx.h"
+#include <algorithm>
 #include <atomic>
 
 using namespace b9i;
@@ -294,6 +295,82 @@ int b9_predict_mags(b9_ctx *ctx, const double *param_row, int64_t n, const doubl
         HIPCHK(ctx, hipMemcpyAsync(out_mags + (size_t)i0 * nf, d_mags, sizeof(double) * m * nf, hipMemcpyDeviceToHost, s));
         if (out_stage) HIPCHK(ctx, hipMemcpyAsync(out_stage + i0, d_stage, sizeof(int) * m, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipStreamSynchronize(s));      // (the host arrays of the next chunk reuse the same device buffers)
+    }
+    return B9_OK;
+}
+
+int b9_n_wd_stars(const b9_ctx *ctx)
+{
+    if (!ctx) return B9_ERR_INVALID;
+    if (!ctx->have_stars) return B9_ERR_STATE;
+    return ctx->n_wd_stage;
+}
+
+// Rows are worked in chunks: at most 256 rows, and as few as keep the chunk's node table within B9_WDS_TABLE_BYTES (one
+// row's table, whatever its size, when that alone is larger).
+#define B9_WDS_TABLE_BYTES ((size_t)64 << 20)
+#define B9_WDS_MAX_ROWS 256
+
+int b9_sample_wd_mass(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_nodes, uint64_t seed, int64_t row0,
+                      double *out_zams, double *out_wd_mass, double *out_prec_log_age, double *out_log_cool_age,
+                      double *out_log_teff, double *out_logg, double *out_member, int32_t *out_pop)
+{
+    if (!ctx || !params || n_rows < 1 || n_nodes < 1 || !out_zams || !out_member) return B9_ERR_INVALID;
+    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
+    if (!ctx->have_pack || !ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
+    const int n_wd = ctx->st.n_wd, n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
+    if (n_wd == 0) return B9_OK;
+    const DevPack &pk = ctx->pk;
+    const int mass_cap = (pk.max_eep + 1) & ~1;
+    const long long iso_stride = (long long)mass_cap * (pk.nfp + 1);
+    const size_t tab_row = (size_t)n_pops * (size_t)b9k_wd_table_doubles(pk.nfp, n_nodes);       // doubles per row
+    if (tab_row > ((size_t)8 << 30) / sizeof(double)) return fail(ctx, B9_ERR_CAPACITY, "b9_sample_wd_mass: one row's node table would exceed 8 GiB");
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_rows, (size_t)B9_WDS_MAX_ROWS, B9_WDS_TABLE_BYTES / (tab_row * sizeof(double))}));
+    // one allocation: [params][headers][isochrones][table][7 outputs][pop][columns], every part on a 256-byte boundary
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t per = (size_t)chunk * n_wd;
+    const size_t o_hdr = up(sizeof(double) * B9_NPARAM * chunk), o_iso = o_hdr + up(sizeof(IsoHdr) * chunk * n_pops);
+    const size_t o_tab = o_iso + up(sizeof(double) * (size_t)chunk * n_pops * iso_stride), o_out = o_tab + up(sizeof(double) * chunk * tab_row);
+    const size_t o_pop = o_out + up(sizeof(double) * per * 7), o_rank = o_pop + up(sizeof(int) * per), bytes = o_rank + up(sizeof(int) * n);
+    if (bytes > ctx->wds_cap) {
+        if (ctx->d_wds) (void)hipFree(ctx->d_wds);
+        ctx->d_wds = nullptr; ctx->wds_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->d_wds, bytes));
+        ctx->wds_cap = bytes;
+    }
+    char *base = static_cast<char *>(ctx->d_wds);
+    double *d_par = reinterpret_cast<double *>(base), *d_iso = reinterpret_cast<double *>(base + o_iso);
+    double *d_tab = reinterpret_cast<double *>(base + o_tab), *d_out = reinterpret_cast<double *>(base + o_out);
+    IsoHdr *d_hdr = reinterpret_cast<IsoHdr *>(base + o_hdr);
+    int *d_pop = reinterpret_cast<int *>(base + o_pop), *d_rank = reinterpret_cast<int *>(base + o_rank);
+    std::vector<int> rank(n);
+    for (int i = 0, k = 0; i < n; ++i) { rank[i] = k; k += ctx->hs.stage[i] == B9_STAGE_WD; }
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(d_rank, rank.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
+    double *const host[7] = {out_zams, out_member, out_wd_mass, out_prec_log_age, out_log_cool_age, out_log_teff, out_logg};
+    const McmcDev off{};
+    for (int r0 = 0; r0 < n_rows; r0 += chunk) {
+        const int m = std::min(chunk, n_rows - r0);
+        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * per * 7, s));        // rows outside the grid write nothing
+        HIPCHK(ctx, hipMemsetAsync(d_pop, 0, sizeof(int) * per, s));
+        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, B9Prev{nullptr, 0, 0, nullptr, nullptr}, s));
+        B9WdSample smp{};
+        smp.zams = d_out; smp.member = d_out + per;
+        smp.wd_mass = out_wd_mass ? d_out + 2 * per : nullptr; smp.prec_log_age = out_prec_log_age ? d_out + 3 * per : nullptr;
+        smp.log_cool_age = out_log_cool_age ? d_out + 4 * per : nullptr; smp.log_teff = out_log_teff ? d_out + 5 * per : nullptr;
+        smp.logg = out_logg ? d_out + 6 * per : nullptr;
+        smp.pop = d_pop; smp.wd_rank = d_rank;
+        smp.k0 = (unsigned)(seed & 0xFFFFFFFFull); smp.k1 = (unsigned)(seed >> 32); smp.row0 = (long long)(row0 + r0);
+        // the kernel indexes its outputs [row][n_wd] with the launch's own rows: they are contiguous for any m
+        HIPCHK(ctx, b9k_wd_sample(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, n_nodes, d_tab, smp, s));
+        const size_t cnt = (size_t)m * n_wd, o = (size_t)r0 * n_wd;
+        for (int q = 0; q < 7; ++q)
+            if (host[q]) HIPCHK(ctx, hipMemcpyAsync(host[q] + o, d_out + q * per, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
+        if (out_pop) HIPCHK(ctx, hipMemcpyAsync(out_pop + o, d_pop, sizeof(int) * cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));      // (the next chunk reuses the same device buffers)
     }
     return B9_OK;
 }

@@ -419,6 +419,7 @@ int b9_load_stars(b9_ctx *ctx, const b9_stars *s)
     h.fmax.assign(s->filter_prior_max, s->filter_prior_max + nf);
     if (s->stage) h.stage.assign(s->stage, s->stage + n); else h.stage.assign(n, B9_STAGE_MSRG);
     if (s->wd_type) h.wd_type.assign(s->wd_type, s->wd_type + n); else h.wd_type.assign(n, 0);
+    ctx->n_wd_stage = (int)std::count(h.stage.begin(), h.stage.end(), (int32_t)B9_STAGE_WD);      // (b9_n_wd_stars answers before the stars are staged)
     ctx->have_stars = true;
     ctx->stars_dirty = true;
     return B9_OK;

@@ -4,7 +4,7 @@
 //   b9_capi_stage.cpp   validation and staging of the model pack and the star catalogue into HBM (b9_load_pack, b9_load_stars)
 //   b9_capi_plan.cpp    launch plans: canonical tile groups, the fused step's and the tree step's plans
 //   b9_capi_margplan.cpp  the marginalised mode's catalogue plan: measured dispatch order, pieces of small catalogues
-//   b9_capi_eval.cpp    b9_logpost / b9_logpost_device / b9_sample_mass / b9_derive_isochrone / b9_predict_mags
+//   b9_capi_eval.cpp    b9_logpost / b9_logpost_device / b9_sample_mass / b9_derive_isochrone / b9_predict_mags / b9_sample_wd_mass
 //   b9_capi_blocks.cpp  the sampler's device-resident blocks (fused, tree-speculative, two-launch), b9_mcmc_run_block / b9_mcmc_wait
 #pragma once
 #include "../../include/base9_hip.h"
@@ -120,6 +120,11 @@ struct b9_ctx {
     size_t pred_iso_cap = 0;         // doubles of d_pred_iso
     void *d_pred_io = nullptr;       // one chunk of systems: mass1, mass ratio, magnitudes, then wd_type, pop, stage
     size_t pred_io_cap = 0;          // bytes
+
+    // b9_sample_wd_mass: one allocation of its own (grown on demand, never shrunk), for the same reason: a chunk of rows'
+    // parameters, headers, derived isochrones and node table, the chunk's outputs, the stars' columns
+    void *d_wds = nullptr;
+    size_t wds_cap = 0;              // bytes
 
     // timing of the dominant kernel
     int timing = 0;            // 0 off, n > 0: bracket every n-th launch of the dominant kernel with events

@@ -25,6 +25,8 @@
 //                                     of a two-launch sampler block's last step)
 //   k_predict_mags rows a4-a7, a9      b9_predict_mags: the forward model alone (no observations) --
 //                                     one lane per system, predicted apparent magnitudes + stage
+//   k_wd_node_table / k_wd_sample      b9_sample_wd_mass: the WD chain once per node of the call's own grid with its
+//                                     derived values kept, then one lane per WD-stage star against the table
 //
 // The kernels live in the *.hip.h files included below (one translation unit); this file holds
 // k_finalize and the host-callable launch wrappers.
@@ -64,6 +66,7 @@ namespace tree_kd5 {
 #include "b9_star_marg.hip.h"
 #include "b9_marg_step.hip.h"
 #include "b9_predict.hip.h"
+#include "b9_wd_sample.hip.h"
 
 // ------------------------------------------------------------------------------------------
 // k_finalize: one workgroup per walker: fixed-order sum of the partials + prior -> logpost[w]
@@ -219,6 +222,39 @@ hipError_t b9k_predict_mags(const DevPack &pk, const IsoHdr *hdr, const double *
     default: return hipErrorInvalidValue;
     }
 #undef PM_ARGS
+}
+
+// ---- b9_sample_wd_mass: the node table of a chunk of rows, then the WD-stage stars against it -----------------------------
+long long b9k_wd_table_doubles(int nfp, long long n_nodes) { return n_nodes * B9_WDS_NODE_DOUBLES(nfp); }       // per (row, population)
+
+template <int NFP, int NPOPS>
+static hipError_t launch_wd_sample(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride,
+                                   int mass_cap, const double *d_params, int n_rows, int n_nodes, double *tab, const B9WdSample &smp,
+                                   hipStream_t stream)
+{
+    if (!tab || n_rows < 1 || n_nodes < 1 || st.n_wd < 1 || n_rows * NPOPS > 65535) return hipErrorInvalidValue;
+    const int n_wp = n_rows * NPOPS;
+    hipLaunchKernelGGL((k_wd_node_table<NFP>), dim3((n_nodes + 63) / 64, n_wp), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride, mass_cap,
+                       NPOPS, d_params, n_nodes, tab, n_wp);
+    WdSampleOut out{};
+    out.zams = smp.zams; out.member = smp.member; out.pop = smp.pop; out.wd_rank = smp.wd_rank;
+    out.der[0] = smp.wd_mass; out.der[1] = smp.prec_log_age; out.der[2] = smp.log_cool_age; out.der[3] = smp.log_teff; out.der[4] = smp.logg;
+    out.k0 = smp.k0; out.k1 = smp.k1; out.row0 = smp.row0;
+    hipLaunchKernelGGL((k_wd_sample<NFP, NPOPS>), dim3((st.n_wd + 63) / 64, n_rows), dim3(64), 0, stream, pk, st, hdr, d_params, n_nodes,
+                       (const double *)tab, n_wp, out);
+    return hipGetLastError();
+}
+
+hipError_t b9k_wd_sample(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                         const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const B9WdSample &smp, hipStream_t stream)
+{
+#define WS_ARGS pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, n_nodes, tab, smp, stream
+#define WS2(NFP) launch_wd_sample<NFP, 2>(WS_ARGS)
+#define WS1(NFP) launch_wd_sample<NFP, 1>(WS_ARGS)
+    B9_SWITCH_NFP(WS2, WS1)
+#undef WS1
+#undef WS2
+#undef WS_ARGS
 }
 
 // doubles of one (walker, population)'s node table (MargLayout, b9_device.h)

@@ -106,6 +106,20 @@ hipError_t b9k_predict_mags(const DevPack &pk, const IsoHdr *hdr, const double *
                             const int *pop /* nullable */, double *out_mags, int *out_stage, int n_wgs, hipStream_t stream);
 size_t b9k_predict_lds(int nfp, int mass_cap, int n_pops);      // its dynamic LDS per workgroup, bytes (at most 160 KB launches)
 
+// b9_sample_wd_mass: where the draws go (device pointers, [n_rows][st.n_wd]; the five derived ones and pop nullable), the column of
+// every star (wd_rank[original index]: the WD-stage stars before it), RNG key and the global index of row 0
+struct B9WdSample {
+    double *zams, *wd_mass, *prec_log_age, *log_cool_age, *log_teff, *logg, *member;
+    int *pop;
+    const int *wd_rank;
+    unsigned k0, k1;
+    long long row0;
+};
+// k_wd_node_table + k_wd_sample on n_rows derived rows (n_rows * n_pops <= 65535); tab: n_rows * n_pops * b9k_wd_table_doubles doubles
+hipError_t b9k_wd_sample(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                         const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const B9WdSample &smp, hipStream_t stream);
+long long b9k_wd_table_doubles(int nfp, long long n_nodes);      // per (row, population)
+
 hipError_t b9k_noop(hipStream_t stream);
 hipError_t b9k_spin(double microseconds, hipStream_t stream);
 constexpr int B9_CLOCK_SLOTS = 8 * 256;      // (XCD, HW_ID[15:8]) -> one slot per compute unit

@@ -375,32 +375,46 @@ __device__ __forceinline__ void prec_corners(const DevPack &pk, const double *co
         if (heavy[c]) out[c] = log_age[0] - 2.7 * log10(m / tips[c][0]);
 }
 
-// SURVEY 8a row a7: IFMR -> WD cooling model -> atmosphere table.  Only the stars above the AGB
-// tip take this branch; k_finalize runs it (the hot kernel never does).
-template <int NFP>
-__device__ __forceinline__ void wd_mags(const DevPack &pk, const WdAxes &ax, const IsoView<NFP> &iso,
-                                     const double *__restrict__ par, double m, int wd_type,
-                                     double (&out)[NFP])
+// The WD chain up to the atmosphere lookup: precursor age -> IFMR -> cooling age -> (Teff, radius) -> log g.
+// ONE function: wd_mags forms its magnitudes from what it returns, and k_wd_node_table (b9_wd_sample.hip.h) keeps the values.
+//   status 0: the pack holds no WD models (magnitudes B9_MAG_NOFLUX; nothing else is set)
+//          1: the precursor has not died yet, prec >= logAge (magnitudes -4.0; wd_mass and prec are set, the rest is 0)
+//          2: a white dwarf; every field is set
+struct WdChain { int status; double wd_mass, prec, log_cool, log_teff, logg; };
+
+__device__ __forceinline__ WdChain wd_chain(const DevPack &pk, const WdAxes &ax, double t_feh, double t_y,
+                                            const double *__restrict__ par, double m)
 {
-    if (pk.n_wc_mass < 2 || pk.n_at_teff < 2) { fill<NFP>(out, B9_MAG_NOFLUX); return; }
+    WdChain c; c.status = 0; c.wd_mass = 0.0; c.prec = 0.0; c.log_cool = 0.0; c.log_teff = 0.0; c.logg = 0.0;
+    if (pk.n_wc_mass < 2 || pk.n_at_teff < 2) return c;
     const int ny = pk.n_y > 1 ? 2 : 1;
     // (fully unrolled: a run-time index into ax.tips[] would put the pointer array in scratch memory)
     const double v00 = prec_log_age_corner(pk, ax.tips[0], ax.log_age, m), v10 = prec_log_age_corner(pk, ax.tips[2], ax.log_age, m);
     double vf0 = v00, vf1 = v10;
     if (ny == 2) {
-        vf0 = lerp(v00, prec_log_age_corner(pk, ax.tips[1], ax.log_age, m), iso.t_y);
-        vf1 = lerp(v10, prec_log_age_corner(pk, ax.tips[3], ax.log_age, m), iso.t_y);
+        vf0 = lerp(v00, prec_log_age_corner(pk, ax.tips[1], ax.log_age, m), t_y);
+        vf1 = lerp(v10, prec_log_age_corner(pk, ax.tips[3], ax.log_age, m), t_y);
     }
-    const double prec = lerp(vf0, vf1, iso.t_feh);
+    const double prec = lerp(vf0, vf1, t_feh);
     const double log_age = par[B9_P_LOGAGE];
-    if (prec >= log_age) { fill<NFP>(out, -4.0); return; }
-    const double wd_mass = ifmr(pk.ifmr_id, par, m);
-    const double log_cool = log10(exp10(log_age) - exp10(prec));
+    c.prec = prec;
+    c.wd_mass = ifmr(pk.ifmr_id, par, m);
+    if (prec >= log_age) { c.status = 1; return c; }
+    c.log_cool = log10(exp10(log_age) - exp10(prec));
 
     double tr[2];
-    wd_cooling(pk, ax, par, wd_mass, log_cool, tr[0], tr[1]);
-    const double log_teff = tr[0];
-    const double logg = LOG_G_PLUS_LOG_MSUN + log10(wd_mass) - 2.0 * tr[1];
+    wd_cooling(pk, ax, par, c.wd_mass, c.log_cool, tr[0], tr[1]);
+    c.log_teff = tr[0];
+    c.logg = LOG_G_PLUS_LOG_MSUN + log10(c.wd_mass) - 2.0 * tr[1];
+    c.status = 2;
+    return c;
+}
+
+// The last step of the WD branch: the atmosphere table at wd_chain's (log Teff, log g), atmosphere type ty (0 DA, 1 DB).
+template <int NFP>
+__device__ __forceinline__ void wd_atmosphere(const DevPack &pk, const WdAxes &ax, const WdChain &c, int wd_type, double (&out)[NFP])
+{
+    const double log_teff = c.log_teff, logg = c.logg;
     const int ty = (wd_type > 0 && pk.n_at_type > 1) ? 1 : 0;
     const int it = bracket(ax.at_log_teff, pk.n_at_teff, log_teff);
     const double tt = (log_teff - ax.at_log_teff[it]) / (ax.at_log_teff[it + 1] - ax.at_log_teff[it]);
@@ -414,6 +428,19 @@ __device__ __forceinline__ void wd_mags(const DevPack &pk, const WdAxes &ax, con
         double v1 = lerp(g1[f], g1[NFP + f], tt);
         out[f] = lerp(v0, v1, tg);
     }
+}
+
+// SURVEY 8a row a7: IFMR -> WD cooling model -> atmosphere table.  Only the stars above the AGB
+// tip take this branch; k_finalize runs it (the hot kernel never does).
+template <int NFP>
+__device__ __forceinline__ void wd_mags(const DevPack &pk, const WdAxes &ax, const IsoView<NFP> &iso,
+                                     const double *__restrict__ par, double m, int wd_type,
+                                     double (&out)[NFP])
+{
+    const WdChain c = wd_chain(pk, ax, iso.t_feh, iso.t_y, par, m);
+    if (c.status == 0) { fill<NFP>(out, B9_MAG_NOFLUX); return; }
+    if (c.status == 1) { fill<NFP>(out, -4.0); return; }
+    wd_atmosphere<NFP>(pk, ax, c, wd_type, out);
 }
 
 // which branch a ZAMS mass is on ([RECALL] Star::getStatus) -- the general form, used by k_finalize

@@ -71,6 +71,7 @@ class Engine:
     def load_stars(self, stars: abi.Pinned) -> None:
         self._check(self.lib.b9_load_stars(self._ctx, stars.byref()))
         self.n_stars = stars.struct.n_stars
+        self.wd_index = np.flatnonzero(np.asarray(stars.keep["stage"]) == abi.STAGE_WD)
 
     def set_priors(self, priors: abi.b9_priors) -> None:
         self._check(self.lib.b9_set_priors(self._ctx, C.byref(priors)))
@@ -170,6 +171,32 @@ class Engine:
                                             mass.ctypes.data_as(_dp), ratio.ctypes.data_as(_dp), member.ctypes.data_as(_dp),
                                             pop.ctypes.data_as(C.POINTER(C.c_int32))))
         return mass, ratio, member, pop
+
+    WD_DERIVED = ("wd_mass", "prec_log_age", "log_cool_age", "log_teff", "logg")
+
+    def n_wd_stars(self) -> int:
+        r = int(self.lib.b9_n_wd_stars(self._ctx))
+        if r < 0:
+            self._check(r)
+        return r
+
+    def sample_wd_mass(self, params: np.ndarray, n_nodes: int, seed: int = 1, row0: int = 0, derived=WD_DERIVED):
+        """b9_sample_wd_mass: per (row, WD-stage star) one Gumbel-max draw of the ZAMS mass on n_nodes equal steps above the
+        AGB tip, the membership probability and the quantities that follow from the drawn mass.  Returns a dict of
+        [rows, n_wd] arrays -- zams, member, pop and the `derived` ones (any subset of WD_DERIVED; the others are not
+        computed) -- plus star_index, the WD-stage stars' indices in the catalogue."""
+        params = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        nr, n_wd = params.shape[0], self.n_wd_stars()
+        names = ("zams",) + self.WD_DERIVED + ("member",)
+        out = {k: (np.zeros((nr, n_wd)) if k in ("zams", "member") or k in derived else None) for k in names}
+        pop = np.zeros((nr, n_wd), dtype=np.int32)
+        ptr = [out[k].ctypes.data_as(_dp) if out[k] is not None else None for k in names]
+        self._check(self.lib.b9_sample_wd_mass(self._ctx, params.ctypes.data_as(_dp), nr, int(n_nodes), int(seed), int(row0),
+                                               *ptr, pop.ctypes.data_as(_ip)))
+        res = {k: v for k, v in out.items() if v is not None}
+        res["pop"] = pop
+        res["star_index"] = self.wd_index.copy()
+        return res
 
     def derive_isochrone(self, param_row: np.ndarray, pop: int = 0, cap: int = 4096) -> Tuple[int, np.ndarray, np.ndarray, float]:
         row = np.ascontiguousarray(param_row, dtype=np.float64)

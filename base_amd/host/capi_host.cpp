@@ -133,6 +133,16 @@ int b9h_sim_settings(int program, int argc, char **argv, char *out, int cap)
     });
 }
 
+int b9h_read_res_rows(const char *path, const double *start_row, int stage, double *rows, long cap_rows, long *n_rows)
+{
+    return guard([&] {
+        if (!path || !start_row || !n_rows) throw std::runtime_error("b9h_read_res_rows: NULL argument");
+        const std::vector<double> r = b9h::read_res_rows(path, std::vector<double>(start_row, start_row + B9_NPARAM), stage);
+        *n_rows = (long)(r.size() / B9_NPARAM);
+        if (rows) std::memcpy(rows, r.data(), sizeof(double) * B9_NPARAM * (size_t)std::max(0l, std::min(*n_rows, cap_rows)));
+    });
+}
+
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part)
 {
     return guard([&] { b9h::merge_result_parts(final_path, world, walkers_per_rank, rows_per_part); });

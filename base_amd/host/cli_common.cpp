@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <sstream>
 #include <stdexcept>
 
 #include <cerrno>
@@ -393,6 +394,43 @@ McmcResult run_mcmc(Session &s, Exchange &ex, const std::vector<std::string> &co
         ex.barrier();
     }
     return res;
+}
+
+std::vector<double> read_res_rows(const std::string &res_path, const std::vector<double> &start, int stage)
+{
+    if ((int)start.size() < B9_NPARAM) throw std::runtime_error("read_res_rows: the starting row needs B9_NPARAM values");
+    std::ifstream in(res_path);
+    if (!in) throw std::runtime_error("cannot read " + res_path + " (run singlePopMcmc first)");
+    std::string line;
+    do {                                                     // (leading "# ..." lines say how the chain was made)
+        if (!std::getline(in, line)) throw std::runtime_error(res_path + " is empty");
+    } while (!line.empty() && line[0] == '#');
+    std::vector<int> col_param;
+    {
+        std::istringstream hs(line);
+        std::string name;
+        while (hs >> name) {
+            if (name == "logPost" || name == "stage") { col_param.push_back(-1); continue; }
+            int idx = -2;
+            for (int k = 0; k < B9_NPARAM; ++k) if (name == param_name(k)) idx = k;
+            if (idx < 0) throw std::runtime_error("unknown column '" + name + "' in " + res_path);
+            col_param.push_back(idx);
+        }
+    }
+    if (col_param.size() < 3) throw std::runtime_error(res_path + ": malformed header");
+    std::vector<double> rows;
+    while (std::getline(in, line)) {
+        std::istringstream ls(line);
+        std::vector<double> v(col_param.size());
+        bool ok = true;
+        for (double &x : v) ok = ok && (bool)(ls >> x);
+        if (!ok) continue;
+        if ((int)v.back() != stage) continue;
+        std::vector<double> row(start.begin(), start.begin() + B9_NPARAM);
+        for (size_t c = 0; c < col_param.size(); ++c) if (col_param[c] >= 0) row[col_param[c]] = v[c];
+        rows.insert(rows.end(), row.begin(), row.end());
+    }
+    return rows;
 }
 
 int report_and_exit_code(const char *prog, const std::exception &e)

@@ -1,4 +1,4 @@
-// cli_common.hpp -- what singlePopMcmc / multiPopMcmc / makeCMD / sampleMass share: settings -> context, and the
+// cli_common.hpp -- what singlePopMcmc / multiPopMcmc / makeCMD / sampleMass / sampleWDMass share: settings -> context, and the
 // sampling run (walker-parallel over the GPUs of one node when launched with --gpus N).
 #pragma once
 #include "b9host.hpp"
@@ -54,6 +54,13 @@ McmcResult run_mcmc(Session &s, Exchange &exchange, const std::vector<std::strin
 // leaving no merged file -- when a part is short, long or unreadable, or the output cannot be written; removes the parts
 // only after the merged file is complete.
 void merge_result_parts(const std::string &final_path, int world, int per, long rows_per_part);
+
+// The rows of a chain file (.res) whose stage column equals `stage` (3 = main run), as full parameter rows: B9_NPARAM doubles
+// each, `start` with the file's sampled columns written over it.  Leading lines starting with '#' are skipped; the header
+// names the sampled parameters, then "logPost stage"; a column that is no parameter name is an error; data lines that do
+// not hold one number per column are skipped.  Throws when the file cannot be read, is empty or has a malformed header.
+// What sampleMass and sampleWDMass read (libbase9host exports it as b9h_read_res_rows).
+std::vector<double> read_res_rows(const std::string &res_path, const std::vector<double> &start, int stage);
 
 int report_and_exit_code(const char *prog, const std::exception &e);
 

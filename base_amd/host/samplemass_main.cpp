@@ -28,37 +28,7 @@ int main(int argc, char **argv)
 
         // ---- the chain: header names the sampled parameters, then "logPost stage"; stage 3 = main run
         const std::string res_path = s.output_base + ".res";
-        std::ifstream in(res_path);
-        if (!in) throw std::runtime_error("cannot read " + res_path + " (run singlePopMcmc first)");
-        std::string line;
-        do {                                                     // (leading "# ..." lines say how the chain was made)
-            if (!std::getline(in, line)) throw std::runtime_error(res_path + " is empty");
-        } while (!line.empty() && line[0] == '#');
-        std::vector<int> col_param;
-        {
-            std::istringstream hs(line);
-            std::string name;
-            while (hs >> name) {
-                if (name == "logPost" || name == "stage") { col_param.push_back(-1); continue; }
-                int idx = -2;
-                for (int k = 0; k < B9_NPARAM; ++k) if (name == b9h::param_name(k)) idx = k;
-                if (idx < 0) throw std::runtime_error("unknown column '" + name + "' in " + res_path);
-                col_param.push_back(idx);
-            }
-        }
-        if (col_param.size() < 3) throw std::runtime_error(res_path + ": malformed header");
-        std::vector<double> rows;
-        while (std::getline(in, line)) {
-            std::istringstream ls(line);
-            std::vector<double> v(col_param.size());
-            bool ok = true;
-            for (double &x : v) ok = ok && (bool)(ls >> x);
-            if (!ok) continue;
-            if ((int)v.back() != 3) continue;
-            std::vector<double> row(s.start.begin(), s.start.begin() + B9_NPARAM);
-            for (size_t c = 0; c < col_param.size(); ++c) if (col_param[c] >= 0) row[col_param[c]] = v[c];
-            rows.insert(rows.end(), row.begin(), row.end());
-        }
+        const std::vector<double> rows = b9h::read_res_rows(res_path, s.start, 3);
         const long n_rows = (long)(rows.size() / B9_NPARAM);
         if (n_rows == 0) throw std::runtime_error(res_path + " holds no main-run (stage 3) rows");
 

@@ -35,7 +35,7 @@ HOST_SYMBOLS = [
     "b9h_sampler_create", "b9h_sampler_create_callback", "b9h_sampler_free", "b9h_sampler_initialise", "b9h_sampler_run",
     "b9h_sampler_n_local", "b9h_sampler_state", "b9h_summary_rows",
     "b9h_load_pack", "b9h_free_pack", "b9h_read_phot", "b9h_free_phot", "b9h_settings_dump", "b9h_merge_parts",
-    "b9h_sim_draw_systems", "b9h_sim_field_mags", "b9h_scatter", "b9h_sim_settings",
+    "b9h_sim_draw_systems", "b9h_sim_field_mags", "b9h_scatter", "b9h_sim_settings", "b9h_read_res_rows",
 ]
 
 _lib = None
@@ -82,6 +82,7 @@ def load() -> C.CDLL:
     lib.b9h_free_phot.argtypes = [vp]
     lib.b9h_settings_dump.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     lib.b9h_merge_parts.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_long]
+    lib.b9h_read_res_rows.argtypes = [C.c_char_p, _dp, C.c_int, _dp, C.c_long, C.POINTER(C.c_long)]
     lib.b9h_sim_draw_systems.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_int, C.c_double, _dp, _dp, _dp, _ip, _ip]
     lib.b9h_sim_field_mags.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int, _dp, _dp, _dp]
@@ -282,6 +283,18 @@ def summary_rows(samples: np.ndarray, params_end: np.ndarray, logpost_end: np.nd
     rows = np.empty((wl, abi.row_doubles(d)))
     _check(load().b9h_summary_rows(samples.ctypes.data_as(_dp), pe.ctypes.data_as(_dp), le.ctypes.data_as(_dp), n, wl, d,
                                    og.ctypes.data_as(_dp), rows.ctypes.data_as(_dp)))
+    return rows
+
+
+def read_res_rows(path: str, start_row, stage: int = 3) -> np.ndarray:
+    """b9h_read_res_rows: the rows of a .res whose stage column equals `stage`, as full parameter rows [n, B9_NPARAM]
+    (start_row with the file's sampled columns written over it) -- what sampleMass and sampleWDMass read."""
+    start = np.ascontiguousarray(start_row, dtype=np.float64).reshape(12)
+    n = C.c_long(0)
+    _check(load().b9h_read_res_rows(path.encode(), start.ctypes.data_as(_dp), int(stage), None, 0, C.byref(n)))
+    rows = np.empty((n.value, 12))
+    if n.value:
+        _check(load().b9h_read_res_rows(path.encode(), start.ctypes.data_as(_dp), int(stage), rows.ctypes.data_as(_dp), n.value, C.byref(n)))
     return rows
 
 

@@ -346,6 +346,49 @@ int b9_predict_mags(b9_ctx *ctx, const double *param_row, int64_t n,
                     const int32_t *wd_type /* nullable: all DA */, const int32_t *pop /* nullable: all 0 */,
                     double *out_mags /* [n * n_filt] */, int32_t *out_stage /* nullable, [n] */);
 
+/*
+ * Posterior draws of the WD-stage stars on a mass grid of the call's own, with the quantities that follow from the
+ * drawn mass (the sampleWDMass counterpart).  Added in ABI 6 without a version change, as b9_predict_mags
+ * was: purely additive.  b9_n_wd_stars: the stars of stage B9_STAGE_WD in the loaded catalogue (or a negative b9_status).
+ *
+ * All pointers are host pointers; synchronous.  Outputs are [n_rows][n_wd], the WD-stage stars in the caller's star
+ * order (n_wd = b9_n_wd_stars); any of the five derived outputs (wd_mass, prec_log_age, log_cool_age, log_teff, logg)
+ * and out_pop may be NULL.  Needs a loaded pack and loaded stars; honours b9_options.n_pops (1 or 2) and ignores mode,
+ * marg_iso_increm and marg_n_q.  B9_ERR_STATE while a sampler block is outstanding; B9_ERR_INVALID for n_nodes < 1;
+ * n_wd == 0 is B9_OK with nothing written.  The call uses buffers of its own: a B9_BLOCK_CONTINUE block enqueued after
+ * it gives the same bits as one enqueued without it.  Rows are worked in chunks of at most 256 rows, and of as few rows
+ * as keep the chunk's node table (n_pops * n_nodes * (2 * padded filters + 6) doubles per row) within 64 MiB -- one row
+ * at a time when one row's table is larger than that (B9_ERR_CAPACITY beyond 8 GiB per row); n_rows is otherwise
+ * unbounded, and every (row, star) result depends on that row and star alone.
+ *
+ * Definition.  For row r (global number row = row0 + r), WD-stage star i (its index in the caller's catalogue) and
+ * population k:
+ *   - nodes j = 1 .. n_nodes, dM = (m_wd_up - agb_tip_k) / n_nodes, m_j = agb_tip_k + dM * j;
+ *   - term_j = log_prior_mass(m_j) + sum_f Gaussian log-density(obs_f | wd magnitudes of m_j + mod + (abs_coeff_f - 1) Av)
+ *     + log(dM): no companion, the star's own wd_type; a node whose chi-square is not finite does not take part (a node
+ *     that rounding puts above m_wd_up has no flux, B9_MAG_NOFLUX, as everywhere in this library);
+ *   - drawn node = argmax over (k, j) of term_j [+ log lambda_k] + gumbel(seed, row, i, j, k), the counter coding
+ *     b9_sample_mass uses for WD nodes (node = j).  Equal keys: lowest k, then lowest j;
+ *   - out_member = p_i L_i / (p_i L_i + (1 - p_i) fieldLike), L_i the log-sum-exp of the terms (two populations: the
+ *     lambda mixture), as b9_sample_mass forms it; a star's terms are summed in ascending j, so the value is a function
+ *     of the data only;
+ *   - at the drawn node: out_zams = m_j; out_wd_mass = ifmr(m_j); out_prec_log_age the precursor log-age;
+ *     out_log_cool_age = log10(10^logAge - 10^prec); out_log_teff, out_logg as the WD branch forms them before the
+ *     atmosphere lookup -- the values the node's magnitudes were computed FROM, not a second evaluation;
+ *   - a node whose precursor has not yet died (prec >= logAge: magnitudes -4.0) can be drawn; it reports zams, wd_mass
+ *     and prec_log_age as above and log_cool_age = log_teff = logg = 0.  A pack without WD models (every node
+ *     B9_MAG_NOFLUX) and a node above m_wd_up report the five derived values as 0;
+ *   - a row outside the grid, dM <= 0, or a star with no live node: every output of that (row, star) is 0.
+ * Consequence: for n_nodes = 8 K the drawn ZAMS mass, the population and the membership are the ones b9_sample_mass
+ * gives that star at marg_iso_increm = K.
+ */
+int b9_n_wd_stars(const b9_ctx *ctx);
+int b9_sample_wd_mass(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_nodes,
+                      uint64_t seed, int64_t row0,
+                      double *out_zams, double *out_wd_mass, double *out_prec_log_age,
+                      double *out_log_cool_age, double *out_log_teff, double *out_logg,
+                      double *out_member, int32_t *out_pop /* nullable */);
+
 /* ---- introspection (used by bench/tests; no compute) --------------------------------- */
 int b9_max_eep(const b9_ctx *ctx);           /* longest isochrone in the loaded pack        */
 int b9_device_id(const b9_ctx *ctx);

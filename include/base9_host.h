@@ -97,6 +97,10 @@ int b9h_scatter(uint64_t seed, const int64_t *ids, int64_t n, int n_filt, const 
                 double sigma_at_limit, double faint_limit, double *sigma, double *obs);
 /* the resolved and checked simCluster (program 0) / scatterCluster (program 1) settings of a command line, "key = value" lines */
 int b9h_sim_settings(int program, int argc, char **argv, char *out, int cap);
+/* the rows of a chain file (.res) whose stage column equals `stage`, as full parameter rows (b9h::read_res_rows, what sampleMass
+ * and sampleWDMass read; exposed for tests): start_row [B9_NPARAM] with the file's sampled columns written over it.  *n_rows
+ * receives their number; rows (nullable: count only) receives the first min(*n_rows, cap_rows) of them, [row][B9_NPARAM] */
+int b9h_read_res_rows(const char *path, const double *start_row, int stage, double *rows, long cap_rows, long *n_rows);
 /* rank 0's merge of <final_path>.part<r> into <final_path> after a --gpus N run (b9h::merge_result_parts; exposed for tests) */
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part);
 
