@@ -127,7 +127,8 @@ class HostBlockRunner:
 class DeviceBlockRunner:
     """The whole block on the GPU (b9_mcmc_run_block): one launch per step in given-mass mode (the
     fused step: previous step's accept/reject + this step's star likelihood + both candidate
-    isochrone sets of the next step), two in marginalised mode; no host round trip until the block ends."""
+    isochrone sets of the next step), one k_marg_step launch in marginalised mode (two where its node tables do not fit the
+    fused step); no host round trip until the block ends."""
 
     def __init__(self, engine, record: bool = True):
         self.engine, self.record = engine, record

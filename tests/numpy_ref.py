@@ -66,10 +66,11 @@ def logpost(pack_d, cl, priors, par, n_pops=1):
     return lp + v.sum(), v
 
 
-def marg_perstar(pack_d, cl, par, K, Q, pop=0):
-    """Brute-force numpy statement of the marginalised per-star log-likelihood of MS/RGB-stage stars
-    (WD-stage stars: marg_perstar_wd): log sum over primary nodes (K sub-steps per EEP interval, left endpoints) and mass
-    ratios j/Q of  prior(M1) * dM/Q * prod_f N(obs_f | combined_f, sigma_f^2).  Independent of the C oracle."""
+def marg_terms(pack_d, cl, par, K, Q, pop=0):
+    """The terms of marg_perstar's sum, kept:  (terms[star, node], mass[node], ratio[node])  with
+    terms = log(prior(M1) * dM/Q * prod_f N(obs_f | combined_f, sigma_f^2))  over every primary node (K sub-steps per EEP
+    interval, left endpoints) and every mass ratio j/Q -- ratio-major: node = j * n_primary + primary.  mass is the node's
+    primary mass, ratio its j/Q.  exp(terms - logsumexp(terms)) is the star's posterior over the grid."""
     first, imass, imags = synth.derive_isochrone(pack_d, par[abi.P_LOGAGE], par[abi.P_FEH], par[abi.P_Y2 if pop else abi.P_Y])
     m_nodes, w_nodes = [], []
     for e in range(len(imass) - 1):
@@ -83,38 +84,47 @@ def marg_perstar(pack_d, cl, par, K, Q, pop=0):
     n = len(cl["mass1"])
     sig = np.asarray(cl["sigma"]); used = sig > 0
     var = np.where(used, sig ** 2, 1.0)
-    out = np.full(n, -np.inf)
     lpm = log_prior_mass(m_nodes, pack_d["m_wd_up"]) + np.log(w_nodes)
-    terms = []
+    preds = []
     for j in range(Q):
         q = np.full(len(m_nodes), j / Q)
-        pred = synth.forward_mags(pack_d, par, m_nodes, q, np.zeros(len(m_nodes), int), pop=pop)      # [nodes, nf]
-        terms.append(pred)
+        preds.append(synth.forward_mags(pack_d, par, m_nodes, q, np.zeros(len(m_nodes), int), pop=pop))      # [nodes, nf]
+    terms = np.empty((n, Q * len(m_nodes)))
     for i in range(n):
         acc = []
-        for pred in terms:
+        for pred in preds:
             g = np.where(used[i], -0.5 * (np.log(2 * np.pi * var[i]) + (pred - cl["obs"][i]) ** 2 / var[i]), 0.0).sum(axis=1)
             acc.append(lpm + g)
-        out[i] = logsumexp(np.concatenate(acc))
+        terms[i] = np.concatenate(acc)
+    return terms, np.tile(m_nodes, Q), np.repeat(np.arange(Q) / Q, len(m_nodes))
+
+
+def marg_perstar(pack_d, cl, par, K, Q, pop=0):
+    """Brute-force numpy statement of the marginalised per-star log-likelihood of MS/RGB-stage stars
+    (WD-stage stars: marg_perstar_wd): log sum over primary nodes (K sub-steps per EEP interval, left endpoints) and mass
+    ratios j/Q of  prior(M1) * dM/Q * prod_f N(obs_f | combined_f, sigma_f^2).  Independent of the C oracle."""
+    terms, _, _ = marg_terms(pack_d, cl, par, K, Q, pop)
+    out = np.full(len(terms), -np.inf)
+    for i in range(len(terms)):
+        out[i] = logsumexp(terms[i])
     return out
 
 
-def marg_perstar_wd(pack_d, cl, par, K, pop=0):
-    """The same for the catalogue's WD-stage stars (DESIGN.md section 2): M1 over (AGB tip, M_wd_up] in 8 K equal steps
-    (right endpoints tip + j dM, j = 1 .. 8 K), single stars, each through the WD branch of synth.forward_mags with the
-    star's own DA / DB flag:  log sum_j prior(M1_j) dM prod_f N(obs_f | wd_f(M1_j), sigma_f^2).  Entries of other stars: NaN."""
+def marg_terms_wd(pack_d, cl, par, K, pop=0, n_nodes=None):
+    """The terms of marg_perstar_wd's sum, kept:  (terms[star, node], mass[node]),  node j - 1 at M1 = tip + j dM,
+    j = 1 .. 8 K (or 1 .. n_nodes, the grid of b9_sample_wd_mass), each star through the WD branch with its own DA / DB
+    flag; mass ratio 0.  Rows of other stars: NaN.  (None, None) where the AGB tip is not below M_wd_up."""
     first, imass, imags = synth.derive_isochrone(pack_d, par[abi.P_LOGAGE], par[abi.P_FEH], par[abi.P_Y2 if pop else abi.P_Y])
-    tip, steps = imass[-1], 8 * K
+    tip, steps = imass[-1], n_nodes or 8 * K
     dM = (pack_d["m_wd_up"] - tip) / steps
-    n = len(cl["mass1"])
-    out = np.full(n, np.nan)
     if not dM > 0:
-        out[np.asarray(cl["stage"]) == abi.STAGE_WD] = -np.inf
-        return out
+        return None, None
+    n = len(cl["mass1"])
     m_nodes = tip + dM * np.arange(1, steps + 1)
     lpm = log_prior_mass(m_nodes, pack_d["m_wd_up"]) + np.log(dM)
     sig = np.asarray(cl["sigma"]); used = sig > 0
     var = np.where(used, sig ** 2, 1.0)
+    terms = np.full((n, steps), np.nan)
     pred_by_type = {}
     for i in np.nonzero(np.asarray(cl["stage"]) == abi.STAGE_WD)[0]:
         ty = int(cl["wd_type"][i])
@@ -122,8 +132,22 @@ def marg_perstar_wd(pack_d, cl, par, K, pop=0):
             pred_by_type[ty] = synth.forward_mags(pack_d, par, m_nodes, np.zeros(steps), np.full(steps, ty, int), pop=pop)
         pred = pred_by_type[ty]
         g = np.where(used[i], -0.5 * (np.log(2 * np.pi * var[i]) + (pred - cl["obs"][i]) ** 2 / var[i]), 0.0).sum(axis=1)
-        t = lpm + g
-        t = t[np.isfinite(t)]
+        terms[i] = lpm + g
+    return terms, m_nodes
+
+
+def marg_perstar_wd(pack_d, cl, par, K, pop=0):
+    """The same for the catalogue's WD-stage stars (DESIGN.md section 2): M1 over (AGB tip, M_wd_up] in 8 K equal steps
+    (right endpoints tip + j dM, j = 1 .. 8 K), single stars, each through the WD branch of synth.forward_mags with the
+    star's own DA / DB flag:  log sum_j prior(M1_j) dM prod_f N(obs_f | wd_f(M1_j), sigma_f^2).  Entries of other stars: NaN."""
+    terms, _ = marg_terms_wd(pack_d, cl, par, K, pop)
+    wd = np.asarray(cl["stage"]) == abi.STAGE_WD
+    out = np.full(len(cl["mass1"]), np.nan)
+    if terms is None:
+        out[wd] = -np.inf
+        return out
+    for i in np.nonzero(wd)[0]:
+        t = terms[i][np.isfinite(terms[i])]
         out[i] = logsumexp(t) if len(t) else -np.inf
     return out
 

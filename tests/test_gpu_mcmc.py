@@ -60,7 +60,7 @@ def test_walker_sampler_on_device_recovers_truth():
     {"B9_TREE_DEPTH": "1", "B9_TILES_PER_BLOCK": "2", "B9_DERIVE_PARTS": "3", "B9_DERIVE_ORDER": "-1"},  # derivation workgroups trail the grid
     {"B9_TREE_DEPTH": "1", "B9_TILES_PER_BLOCK": "5", "B9_CONTIGUOUS_TILES": "1"},                      # consecutive tiles, ragged last group
     {"B9_TREE_DEPTH": "1", "B9_TILES_PER_BLOCK": "7"},                                                  # strided tiles, groups without a last tile
-    {"B9_TWO_LAUNCH_STEPS": "1"},                                                 # the two-launch step (what marginalised mode runs)
+    {"B9_TWO_LAUNCH_STEPS": "1"},                                                 # the two-launch step (marginalised mode's fall-back where k_marg_step does not fit)
     {"B9_TREE_DEPTH": "1", "B9_DERIVE_ORDER": "0", "B9_HEAVY_PARTS": "3"},                               # heavy-star workgroups lead the grid; few, long heavy lists
     {"B9_TREE_DEPTH": "1", "B9_DERIVE_ORDER": "1", "B9_HEAVY_PARTS": "16", "B9_DERIVE_PARTS": "2"},      # (default order) many heavy parts, most of them idle
     # the tree-speculative launch (k_mcmc_tree): 2 / 3 steps per launch, blocks that are not a multiple of the depth
