@@ -2,6 +2,7 @@
 
   base_amd/csrc/libbase9hip.so   the HIP kernels + C ABI (gfx950 only)
   base_amd/host/...              the C++ host programs (added by build_host)
+  build/probes/libb9prims.so     test-only probe of the device primitives (tests/probes/, build_probe)
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the dev container; the built
 .so travels to the GPU box with the tree.
@@ -80,8 +81,28 @@ def source_hash() -> str:
     return h.hexdigest()
 
 
+PROBE_SRC = os.path.join(ROOT, "tests", "probes", "b9_prims_probe.hip")
+PROBE_LIB = os.path.join(ROOT, "build", "probes", "libb9prims.so")
+
+
+def probe_sources() -> List[str]:
+    """What the probe library is made of: its own translation unit and every header it includes from csrc/."""
+    return [PROBE_SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(ROOT, "include", "base9_hip.h")]
+
+
+def build_probe(force: bool = False) -> str:
+    """The test-only probe of the shared device primitives (tests/prims_probe.py): the shipped headers, unchanged, under
+    exactly HIP_FLAGS.  A library of its own -- not linked into libbase9hip.so, not in the ABI, not under csrc/ (source_hash)."""
+    if not force and _newer(PROBE_LIB, probe_sources()):
+        return PROBE_LIB
+    os.makedirs(os.path.dirname(PROBE_LIB), exist_ok=True)
+    _run([HIPCC] + HIP_FLAGS + ["-shared", "-o", PROBE_LIB, "-x", "hip", PROBE_SRC])
+    return PROBE_LIB
+
+
 def build_all(force: bool = False) -> None:
     build_hip(force)
+    build_probe(force)
     try:
         from . import host_build  # noqa: WPS433  (optional until the host programs exist)
     except ImportError:

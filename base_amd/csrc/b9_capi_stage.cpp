@@ -109,6 +109,8 @@ int build_stars(b9_ctx *ctx)
         c0[i] = h.mass1[s] > 0.0 ? std::log(pm) + (log_prior_mass(ctx->pk.log_mass_norm, h.mass1[s]) + g) : -INFINITY;
         la[i] = std::log1p(-pm) + log_fs;
         ea[i] = std::exp(la[i]);
+        // (mix_add's domain: A is 0 or a NORMAL double -- a subnormal factor loses bits in the running product)
+        if (ea[i] != 0.0 && ea[i] < 2.2250738585072014e-308) return fail(ctx, B9_ERR_INVALID, "a star's field-star constant (1 - prior) / prod(filter ranges) is subnormal");
         flags[i] = (h.wd_type[s] > 0 ? 1 : 0) | (h.stage[s] << 8);
         permp[i] = s;
     }

@@ -206,7 +206,10 @@ __device__ __forceinline__ void philox4x32(unsigned c0, unsigned c1, unsigned c2
 __device__ __forceinline__ double u01(unsigned hi, unsigned lo)
 {
     const unsigned long long x = ((unsigned long long)(hi >> 5) << 26) + (unsigned long long)(lo >> 6);
-    return ((double)x + 0.5) * (1.0 / 9007199254740992.0);
+    // (x + 0.5 is exact below 2^52 and a tie above; the one tie that matters: x = 2^53 - 1 rounds to 2^53, i.e. u = 1 -- whose
+    //  -log(-log u) is +inf in gumbel() -- so the top is held at the largest double below 1; every other value keeps its bits)
+    const double u = ((double)x + 0.5) * (1.0 / 9007199254740992.0);
+    return u < 1.0 ? u : 0x1.fffffffffffffp-1;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -113,7 +113,7 @@ __device__ __forceinline__ double hot_star(const DevPack &pk, const IsoView<NFP>
 // multiply; the running product is kept as (mantissa in [0.5,1), binary exponent) so it can neither
 // overflow nor underflow, and ONE log per wave turns it back into a sum.  Stars with A_i = 0
 // (certain members) or l_i > 600 (e^{l} would overflow; A_i is then negligible) contribute l_i
-// additively instead.
+// additively instead.  Domain: A_i is 0 or a normal double (b9_load_stars rejects a subnormal one).
 struct MixAcc {
     double mant;    // product of factors, renormalised
     int expo;       // its binary exponent

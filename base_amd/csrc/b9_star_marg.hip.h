@@ -133,7 +133,7 @@ __device__ __forceinline__ double box_bound32(b9_cbox box, const b9_f4 *sf, int 
 #ifndef B9_BOX_NB
 #define B9_BOX_NB 2
 #endif
-    constexpr int NB = B9_BOX_NB;
+    constexpr int NB = B9_BOX_NB < NFP / 2 ? B9_BOX_NB : NFP / 2;      // (never more pairs in a batch than the star has: two filters are ONE pair)
     const unsigned a0 = (unsigned)(size_t)(const __attribute__((address_space(3))) b9_f4 *)sf + (unsigned)lane * 16u;
     b9_f2 acc = {0.0f, 0.0f};
 #pragma unroll
@@ -142,7 +142,8 @@ __device__ __forceinline__ double box_bound32(b9_cbox box, const b9_f4 *sf, int 
 #pragma unroll
         for (int k = 0; k < NB; ++k) asm volatile("ds_read_b128 %0, %1" : "=v"(s4[k]) : "v"(a0 + (unsigned)(p0 + k) * 1024u));
         if constexpr (NB == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(s4[0]), "+v"(s4[1]), "+v"(s4[2]), "+v"(s4[3]));
-        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(s4[0]), "+v"(s4[1]));
+        else if constexpr (NB == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(s4[0]), "+v"(s4[1]));
+        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(s4[0]));
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
             const int p = p0 + k;

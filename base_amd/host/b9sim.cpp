@@ -104,7 +104,8 @@ void philox4x32(const uint32_t ctr[4], uint32_t k0, uint32_t k1, uint32_t out[4]
 double u01(uint32_t hi, uint32_t lo)
 {
     const uint64_t x = (uint64_t)(hi >> 5) * (uint64_t)(1u << 26) + (uint64_t)(lo >> 6);
-    return ((double)x + 0.5) * (1.0 / 9007199254740992.0);
+    const double u = ((double)x + 0.5) * (1.0 / 9007199254740992.0);
+    return u < 1.0 ? u : 0x1.fffffffffffffp-1;      // (x = 2^53 - 1 rounds to 1: held below 1, as the device's u01)
 }
 
 void sim_draw_systems(const SimConfig &c, double lambda, const double tip[2], int64_t i0, int64_t n,

@@ -68,7 +68,8 @@ def philox4x32(c0, c1, c2, c3, k0, k1):
 def _u01(hi, lo):
     """(0,1) double from two uint32: 53 random bits, never 0 or 1."""
     x = (hi.astype(np.uint64) >> np.uint64(5)) * np.uint64(1 << 26) + (lo.astype(np.uint64) >> np.uint64(6))
-    return (x.astype(np.float64) + 0.5) * (1.0 / 9007199254740992.0)
+    u = (x.astype(np.float64) + 0.5) * (1.0 / 9007199254740992.0)
+    return np.minimum(u, np.nextafter(1.0, 0.0))      # (x = 2^53 - 1 rounds to 1: held below 1, as the device's u01)
 
 
 def draws(seed: int, step: int, walkers: np.ndarray, d: int):

@@ -506,6 +506,7 @@ static double gumbel(uint64_t seed, uint64_t row, uint32_t star, uint64_t node, 
                (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32) ^ (uint32_t)(row >> 32), r);
     uint64_t x = ((uint64_t)(r[0] >> 5) << 26) + (uint64_t)(r[1] >> 6);
     double u = ((double)x + 0.5) * (1.0 / 9007199254740992.0);
+    if (!(u < 1.0)) u = 0x1.fffffffffffffp-1;      /* x = 2^53 - 1 rounds to u = 1: held below 1, as the device's u01 */
     return -log(-log(u));
 }
 
