@@ -1,64 +1,180 @@
 // b9_capi_blocks.cpp -- the sampler's device-resident Metropolis blocks (the caller of the hot path):
-// fused one-launch steps (k_mcmc_step), tree-speculative launches (k_mcmc_tree), two-launch steps (marginalised mode);
-// b9_mcmc_run_block enqueues one, b9_mcmc_wait collects it.
+// three runners -- fused one-launch steps (k_mcmc_step / k_marg_step), tree-speculative launches (k_mcmc_tree), two-launch
+// steps -- around one block frame (open_block / close_block / collect_block); b9_mcmc_run_block enqueues a block,
+// b9_mcmc_wait collects it.
 #include "b9_ctx.h"
 
 using namespace b9i;
 
 namespace {
 
-/* Device-resident Metropolis block, given-mass mode: ONE launch per step (StepDev in b9_device.h).
- * Launch sequence for S steps:  D0  K(0) K(1) ... K(S-1)  F
- *   D0   = k_derive_iso: draws step 0's proposal from the starting state and derives its isochrones
- *   K(t) = k_mcmc_step: decision of step t-1, star likelihood of step t's proposal, and -- on a few
- *          extra workgroups -- both candidate isochrone sets of step t+1
- *   F    = k_mcmc_finish: decision of step S-1. */
+using McmcSlot = b9_ctx::McmcSlot;
+
+// ---- the three block layouts (in doubles; BlockLayout in b9_ctx.h).  L.n_samp / n_lps / n_rows / n_int are filled in already.
+
+// Fused block: one device allocation, laid out so that the block needs ONE upload and ONE download (each small pageable copy
+// costs 10-20 us of host time, a block used to make six + four of them):
+//   [cur0][lp0][chol][origin][decided][free, ids][n_acc][state 0] | [state 1][rows][lps][samples]
+//   upload   = cur0 .. state 0        (starting state, proposal factor, moment origin, RNG streams, cleared counters)
+//   download = n_acc .. lps (.. samples when the caller wants the chain)   (acceptance count, both state parities,
+//              summary rows, log-posterior record, chain record)
+void layout_fused(BlockLayout &L, size_t W, size_t d, size_t)
+{
+    const size_t n_state = W * B9_STATE_STRIDE;
+    L.o_cur0 = 0; L.o_lp0 = L.o_cur0 + W * B9_NPARAM; L.o_chol = L.o_lp0 + W; L.o_org = L.o_chol + d * d; L.o_dec = L.o_org + d;
+    L.o_int = L.o_dec + W; L.o_nacc = L.o_int + L.n_int; L.o_st[0] = L.o_nacc + 1; L.o_st[1] = L.o_st[0] + n_state;
+    L.o_rows = L.o_st[1] + n_state; L.o_lps = L.o_rows + L.n_rows; L.o_samp = L.o_lps + L.n_lps; L.n_total = L.o_samp + L.n_samp;
+}
+
+// Tree block:   [chol][origin][free, ids][state 0][state 1] | [rows][lps][samples][step table]        upload = chol .. state 1
+//   download = state 0 .. lps (.. samples when the caller wants the chain)
+void layout_tree(BlockLayout &L, size_t W, size_t d, size_t S)
+{
+    const size_t n_state = W * B9_TREE_STATE_STRIDE, n_tab = W * (S + B9_TREE_MAX_DEPTH) * B9_TREE_TAB_ROW;
+    L.o_chol = 0; L.o_org = L.o_chol + d * d; L.o_int = L.o_org + d; L.o_st[0] = L.o_int + L.n_int; L.o_st[1] = L.o_st[0] + n_state;
+    L.o_rows = L.o_st[1] + n_state; L.o_lps = L.o_rows + L.n_rows; L.o_samp = L.o_lps + L.n_lps; L.o_tab = L.o_samp + L.n_samp;
+    L.n_total = L.o_tab + n_tab;
+}
+
+// Two-launch block:   [chol][origin][free, ids][n_acc][cur: two halves][lp: two halves][rows][lps][samples]
+//   upload = chol .. first half of lp's start state;  download = n_acc .. lps (.. samples when the caller wants the chain)
+void layout_two_launch(BlockLayout &L, size_t W, size_t d, size_t)
+{
+    L.o_chol = 0; L.o_org = L.o_chol + d * d; L.o_int = L.o_org + d; L.o_nacc = L.o_int + L.n_int; L.o_cur = L.o_nacc + 1;
+    L.o_lp = L.o_cur + 2 * W * B9_NPARAM; L.o_rows = L.o_lp + 2 * W; L.o_lps = L.o_rows + L.n_rows; L.o_samp = L.o_lps + L.n_lps;
+    L.n_total = L.o_samp + L.n_samp;
+}
+
+// where a block's final state sits in its device block and mirror: the final parity's state rows, or -- two-launch -- the
+// final half of [cur] (and of [lp])
+size_t final_off(const McmcSlot &sl)
+{
+    return sl.kind == BlockKind::TwoLaunch ? sl.lay.o_cur + (size_t)sl.final_parity * sl.W * B9_NPARAM : sl.lay.o_st[sl.final_parity];
+}
+size_t final_lp_off(const McmcSlot &sl) { return sl.lay.o_lp + (size_t)sl.final_parity * sl.W; }
+
+// ---- the block contract every runner shares: open_block ... the runner's launch sequence ... close_block; collect_block
+
 // Collect an enqueued block: wait for its download, unpack the pinned mirror into the caller's arrays.
-int collect_block(b9_ctx *ctx, b9_ctx::McmcSlot &sl, b9_mcmc_block *blk)
+int collect_block(b9_ctx *ctx, McmcSlot &sl, b9_mcmc_block *blk)
 {
     HIPCHK(ctx, hipEventSynchronize(sl.done));
     sl.in_flight = false;
-    const double *stage = static_cast<const double *>(sl.h);
-    if (sl.kind == 1) {             // two-launch block: [cur][lp] of the final half, n_acc as a 64-bit count
-        std::memcpy(blk->params, stage + sl.o_cur, sizeof(double) * (size_t)sl.W * B9_NPARAM);
-        std::memcpy(blk->logpost, stage + sl.o_lp, sizeof(double) * (size_t)sl.W);
-        if (sl.n_samp && sl.host_samples && blk->samples) std::memcpy(blk->samples, stage + sl.o_samp, sl.n_samp * 8);
-        if (sl.n_rows && blk->rows) std::memcpy(blk->rows, stage + sl.o_rows, sl.n_rows * 8);
-        if (sl.n_lps && blk->lps) std::memcpy(blk->lps, stage + sl.o_lps, sl.n_lps * 8);
+    const BlockLayout &L = sl.lay;
+    const double *stage = static_cast<const double *>(sl.h), *fin = stage + final_off(sl);
+    if (sl.kind == BlockKind::TwoLaunch) {       // [cur][lp] of the final half, n_acc as a 64-bit count
+        std::memcpy(blk->params, fin, sizeof(double) * (size_t)sl.W * B9_NPARAM);
+        std::memcpy(blk->logpost, stage + final_lp_off(sl), sizeof(double) * (size_t)sl.W);
         unsigned long long n_acc = 0;
-        std::memcpy(&n_acc, stage + sl.o_nacc, sizeof n_acc);
+        std::memcpy(&n_acc, stage + L.o_nacc, sizeof n_acc);
         blk->n_accept = (int64_t)n_acc;
-        return B9_OK;
-    }
-    const double *fin = stage + (sl.final_parity ? sl.o_st1 : sl.o_st0);
-    if (sl.kind == 2) {             // tree-speculative block: tree state rows
+    } else {                                     // state rows, the per-walker accepted counts carried in them
+        const bool tree = sl.kind == BlockKind::Tree;
+        const size_t stride = tree ? B9_TREE_STATE_STRIDE : B9_STATE_STRIDE;
+        const int o_cur = tree ? B9_TS_CUR : B9_ST_CUR, o_lp = tree ? B9_TS_LP : B9_ST_LP, o_nacc = tree ? B9_TS_NACC : B9_ST_NACC;
         double n_acc = 0.0;
         for (int w = 0; w < sl.W; ++w) {
-            const double *row = fin + (size_t)w * B9_TREE_STATE_STRIDE;
-            std::memcpy(blk->params + (size_t)w * B9_NPARAM, row + B9_TS_CUR, sizeof(double) * B9_NPARAM);
-            blk->logpost[w] = row[B9_TS_LP];
-            n_acc += row[B9_TS_NACC];
+            const double *row = fin + (size_t)w * stride;
+            std::memcpy(blk->params + (size_t)w * B9_NPARAM, row + o_cur, sizeof(double) * B9_NPARAM);
+            blk->logpost[w] = row[o_lp];
+            n_acc += row[o_nacc];
         }
-        if (sl.n_samp && sl.host_samples && blk->samples) std::memcpy(blk->samples, stage + sl.o_samp, sl.n_samp * 8);
-        if (sl.n_rows && blk->rows) std::memcpy(blk->rows, stage + sl.o_rows, sl.n_rows * 8);
-        if (sl.n_lps && blk->lps) std::memcpy(blk->lps, stage + sl.o_lps, sl.n_lps * 8);
         blk->n_accept = (int64_t)n_acc;
-        return B9_OK;
     }
-    for (int w = 0; w < sl.W; ++w) {
-        std::memcpy(blk->params + (size_t)w * B9_NPARAM, fin + (size_t)w * B9_STATE_STRIDE + B9_ST_CUR, sizeof(double) * B9_NPARAM);
-        blk->logpost[w] = fin[(size_t)w * B9_STATE_STRIDE + B9_ST_LP];
-    }
-    if (sl.n_samp && sl.host_samples && blk->samples) std::memcpy(blk->samples, stage + sl.o_samp, sl.n_samp * 8);
-    if (sl.n_rows && blk->rows) std::memcpy(blk->rows, stage + sl.o_rows, sl.n_rows * 8);
-    if (sl.n_lps && blk->lps) std::memcpy(blk->lps, stage + sl.o_lps, sl.n_lps * 8);
-    double n_acc = 0.0;                              // per-walker counts carried in the state rows
-    for (int w = 0; w < sl.W; ++w) n_acc += fin[(size_t)w * B9_STATE_STRIDE + B9_ST_NACC];
-    blk->n_accept = (int64_t)n_acc;
+    if (L.n_samp && sl.host_samples && blk->samples) std::memcpy(blk->samples, stage + L.o_samp, L.n_samp * 8);
+    if (L.n_rows && blk->rows) std::memcpy(blk->rows, stage + L.o_rows, L.n_rows * 8);
+    if (L.n_lps && blk->lps) std::memcpy(blk->lps, stage + L.o_lps, L.n_lps * 8);
     return B9_OK;
 }
 
-/* The marginalised mode runs the same block with k_marg_step in K(t)'s place (b9_marg_step.hip.h: the candidates are node
+struct BlockFrame {             // an opened block: what a runner's launch sequence works with
+    McmcSlot *sl;
+    const BlockLayout *L;       // &sl->lay
+    double *dev, *stage, *mirror;      // the device block; the pinned mirror as the host and as the device see it
+    bool cont, want_rows;
+    const double *prev_final, *prev_final_lp;   // continuing: the previous block's final state on the device (final_off / final_lp_off)
+};
+
+// Opening: two slots (device block + pinned mirror + events) alternate, so that a block can be enqueued while its predecessor
+// is still running or waiting to be collected.  Takes the next slot, lays the block out, grows the slot's memory, stages the
+// upload words every kind has (proposal factor, moment origin, RNG streams) in the mirror.
+int open_block(b9_ctx *ctx, const b9_mcmc_block *blk, BlockKind kind, void (*layout)(BlockLayout &, size_t, size_t, size_t), BlockFrame *f)
+{
+    const size_t W = blk->n_walkers, d = blk->n_free, S = blk->n_steps;
+    McmcSlot &sl = ctx->slot[ctx->next_slot];
+    f->cont = (blk->flags & B9_BLOCK_CONTINUE) != 0;
+    f->want_rows = blk->row_origin != nullptr;
+    if (sl.in_flight) return fail(ctx, B9_ERR_STATE, "two blocks are already outstanding: collect one with b9_mcmc_wait first");
+    const McmcSlot *pv = ctx->last_slot >= 0 ? &ctx->slot[ctx->last_slot] : nullptr;
+    if (f->cont && (!pv || pv->W != (int)W || pv->kind != kind))
+        return fail(ctx, B9_ERR_STATE, "B9_BLOCK_CONTINUE needs a previous block of this context with the same n_walkers and mode");
+    BlockLayout &L = sl.lay;
+    L = BlockLayout{};
+    L.n_samp = (blk->samples || f->want_rows) ? S * W * d : 0;
+    L.n_lps = blk->lps ? S * W : 0;
+    L.n_rows = f->want_rows ? W * B9_ROW_LEN(d) : 0;
+    L.n_int = (d + W + 1) / 2;                                            // ints, in units of 8 bytes
+    layout(L, W, d, S);
+    if (L.n_total * 8 > sl.cap) {
+        // (a CONTINUE block reads the OTHER slot's final state, never this slot's old contents)
+        if (sl.d) (void)hipFree(sl.d);
+        sl.d = nullptr; sl.cap = 0;
+        HIPCHK(ctx, hipMalloc(&sl.d, L.n_total * 8));
+        sl.cap = L.n_total * 8;
+    }
+    if (L.n_total * 8 > sl.hcap) {
+        if (sl.h) (void)hipHostFree(sl.h);
+        sl.h = nullptr; sl.hcap = 0;
+        HIPCHK(ctx, hipHostMalloc(&sl.h, L.n_total * 8, hipHostMallocMapped));     // pinned staging mirror, mapped into the device
+        HIPCHK(ctx, hipHostGetDevicePointer(&sl.h_dev, sl.h, 0));
+        sl.hcap = L.n_total * 8;
+    }
+    if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    if (!sl.rows_ready) HIPCHK(ctx, hipEventCreateWithFlags(&sl.rows_ready, hipEventDisableTiming));
+    f->sl = &sl; f->L = &L;
+    f->dev = static_cast<double *>(sl.d); f->stage = static_cast<double *>(sl.h); f->mirror = static_cast<double *>(sl.h_dev);
+    std::memcpy(f->stage + L.o_chol, blk->chol, d * d * 8);
+    if (f->want_rows) std::memcpy(f->stage + L.o_org, blk->row_origin, d * 8); else std::memset(f->stage + L.o_org, 0, d * 8);
+    int *hi = reinterpret_cast<int *>(f->stage + L.o_int);
+    std::memcpy(hi, blk->free_idx, d * sizeof(int));
+    std::memcpy(hi + d, blk->walker_ids, W * sizeof(int));
+    // continuing: the previous block's final state, stream-ordered behind its last launch
+    f->prev_final = f->cont ? static_cast<const double *>(pv->d) + final_off(*pv) : nullptr;
+    f->prev_final_lp = (f->cont && kind == BlockKind::TwoLaunch) ? static_cast<const double *>(pv->d) + final_lp_off(*pv) : nullptr;
+    sl.kind = kind; sl.W = (int)W;           // (this slot is never last_slot: nothing reads it before close_block puts it in flight)
+    return B9_OK;
+}
+
+// Closing, behind the block's last kernel: rows_ready when the caller asked for it, the download of [down_from, lps or samples]
+// unless the last kernel wrote the mirror itself (zero_copy), done; then the slot is in flight and the next block gets the other one.
+int close_block(b9_ctx *ctx, b9_mcmc_block *blk, const BlockFrame &f, int final_parity, size_t down_from, bool zero_copy)
+{
+    McmcSlot &sl = *f.sl;
+    const BlockLayout &L = *f.L;
+    hipStream_t s = ctx->stream;
+    const bool rows_event = f.want_rows && (blk->flags & B9_BLOCK_ROWS_EVENT) != 0;
+    if (rows_event) HIPCHK(ctx, hipEventRecord(sl.rows_ready, s));
+    blk->d_rows = f.want_rows ? (void *)(f.dev + L.o_rows) : nullptr;
+    blk->rows_ready = rows_event ? (void *)sl.rows_ready : nullptr;
+    const size_t down_end = L.o_samp + (blk->samples ? L.n_samp : 0);
+    if (!zero_copy) HIPCHK(ctx, hipMemcpyAsync(f.stage + down_from, f.dev + down_from, (down_end - down_from) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipEventRecord(sl.done, s));
+    sl.final_parity = final_parity;
+    sl.host_samples = blk->samples != nullptr;
+    sl.in_flight = true; sl.owner = blk;
+    ctx->last_slot = ctx->next_slot;
+    ctx->next_slot ^= 1;
+    return (blk->flags & B9_BLOCK_ASYNC) ? B9_OK : collect_block(ctx, sl, blk);
+}
+
+/* Device-resident Metropolis block, given-mass mode: ONE launch per step (StepDev in b9_device.h).
+ * Launch sequence for S steps:  D0  K(0) K(1) ... K(S-1)  F
+ *   D0   = k_mcmc_begin (the upload from the mapped mirror) + k_derive_iso: draws step 0's proposal from the starting state
+ *          and derives its isochrones
+ *   K(t) = k_mcmc_step: decision of step t-1, star likelihood of step t's proposal, and -- on a few
+ *          extra workgroups -- both candidate isochrone sets of step t+1
+ *   F    = k_mcmc_finish: decision of step S-1.
+ * The marginalised mode runs the same block with k_marg_step in K(t)'s place (b9_marg_step.hip.h: the candidates are node
  * tables, built inside the launch; no isochrone is materialised) and, for the block's first proposal, k_marg_table behind D0. */
 struct MargBlock {             // what the marginalised flavour adds to a fused block
     int K = 1, Q = 1;
@@ -74,7 +190,6 @@ bool marg_fused_ok(const b9_ctx *ctx) { return b9k_marg_step_lds(ctx->pk.nfp, ct
 int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
 {
     const int W = blk->n_walkers, d = blk->n_free, S = blk->n_steps, n_pops = ctx->opt.n_pops;
-    const bool cont = (blk->flags & B9_BLOCK_CONTINUE) != 0, async = (blk->flags & B9_BLOCK_ASYNC) != 0;
     StepPlan sp{};
     MargBlock mb;
     if (marg) {
@@ -95,80 +210,37 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
     }
     const B9Groups &plan = sp.plan;
     const int derive_parts = sp.derive_parts;
-    // two slots (device block + pinned mirror + event) alternate, so that a block can be enqueued while its
-    // predecessor is still running or waiting to be collected
-    b9_ctx::McmcSlot &sl = ctx->slot[ctx->next_slot];
-    if (sl.in_flight) return fail(ctx, B9_ERR_STATE, "two blocks are already outstanding: collect one with b9_mcmc_wait first");
-    if (cont && (ctx->last_slot < 0 || ctx->slot[ctx->last_slot].W != W || ctx->slot[ctx->last_slot].kind != 0))
-        return fail(ctx, B9_ERR_STATE, "B9_BLOCK_CONTINUE needs a previous block of this context with the same n_walkers and mode");
-    const bool want_rows = blk->row_origin != nullptr;
-    const size_t n_state = (size_t)W * B9_STATE_STRIDE, n_cur = (size_t)W * B9_NPARAM,
-                 n_samp = (blk->samples || want_rows) ? (size_t)S * W * d : 0, n_lps = blk->lps ? (size_t)S * W : 0,
-                 n_rows = want_rows ? (size_t)W * B9_ROW_LEN(d) : 0;
-    // One device allocation, laid out so that the block needs ONE upload and ONE download (each small
-    // pageable copy costs 10-20 us of host time, a block used to make six + four of them):
-    //   [cur0][lp0][chol][origin][decided][free, ids][n_acc][state 0] | [state 1][rows][lps][samples]
-    //   upload   = cur0 .. state 0        (starting state, proposal factor, moment origin, RNG streams, cleared counters)
-    //   download = n_acc .. lps (.. samples when the caller wants the chain)   (acceptance count, both state parities,
-    //              summary rows, log-posterior record, chain record)
-    const size_t n_int = ((size_t)(d + W) + 1) / 2;                       // ints, in units of 8 bytes
-    const size_t o_cur0 = 0, o_lp0 = o_cur0 + n_cur, o_chol = o_lp0 + W, o_org = o_chol + (size_t)d * d, o_dec = o_org + d,
-                 o_int = o_dec + W, o_nacc = o_int + n_int, o_st0 = o_nacc + 1, o_st1 = o_st0 + n_state,
-                 o_rows = o_st1 + n_state, o_lps = o_rows + n_rows, o_samp = o_lps + n_lps, n_total = o_samp + n_samp;
-    const size_t up_words = o_st1, down_words = (blk->samples ? n_total : o_samp) - o_nacc;
-    if (n_total * 8 > sl.cap) {
-        // (a CONTINUE block reads the OTHER slot's final state, never this slot's old contents)
-        if (sl.d) (void)hipFree(sl.d);
-        sl.d = nullptr; sl.cap = 0;
-        HIPCHK(ctx, hipMalloc(&sl.d, n_total * 8));
-        sl.cap = n_total * 8;
-    }
-    if (n_total * 8 > sl.hcap) {
-        if (sl.h) (void)hipHostFree(sl.h);
-        sl.h = nullptr; sl.hcap = 0;
-        HIPCHK(ctx, hipHostMalloc(&sl.h, n_total * 8, hipHostMallocMapped));     // pinned staging mirror, mapped into the device
-        HIPCHK(ctx, hipHostGetDevicePointer(&sl.h_dev, sl.h, 0));
-        sl.hcap = n_total * 8;
-    }
-    if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    if (!sl.rows_ready) HIPCHK(ctx, hipEventCreateWithFlags(&sl.rows_ready, hipEventDisableTiming));
-    double *const dev = static_cast<double *>(sl.d), *const stage = static_cast<double *>(sl.h);
-    double *d_state = dev + o_st0;                   // [2][W][stride]; the block's first launch has parity 1 and reads parity 0
-    double *d_cur0 = dev + o_cur0, *d_lp0 = dev + o_lp0, *d_chol = dev + o_chol;
-    unsigned long long *d_decided = reinterpret_cast<unsigned long long *>(dev + o_dec);
-    int *d_free = reinterpret_cast<int *>(dev + o_int), *d_ids = d_free + d;
-    unsigned long long *d_nacc = reinterpret_cast<unsigned long long *>(dev + o_nacc);
-    double *d_samples = n_samp ? dev + o_samp : nullptr, *d_lps = n_lps ? dev + o_lps : nullptr;
+    BlockFrame f;
+    int rc = open_block(ctx, blk, BlockKind::Fused, layout_fused, &f);
+    if (rc) return rc;
+    const BlockLayout &L = *f.L;
+    double *const dev = f.dev, *const stage = f.stage;
+    const size_t n_state = (size_t)W * B9_STATE_STRIDE, n_cur = (size_t)W * B9_NPARAM;
+    double *d_state = dev + L.o_st[0];               // [2][W][stride]; the block's first launch has parity 1 and reads parity 0
+    double *d_cur0 = dev + L.o_cur0, *d_lp0 = dev + L.o_lp0, *d_chol = dev + L.o_chol;
+    unsigned long long *d_decided = reinterpret_cast<unsigned long long *>(dev + L.o_dec);
+    int *d_free = reinterpret_cast<int *>(dev + L.o_int), *d_ids = d_free + d;
+    unsigned long long *d_nacc = reinterpret_cast<unsigned long long *>(dev + L.o_nacc);
     hipStream_t s = ctx->stream;
     {
-        std::memset(stage + o_cur0, 0, (n_cur + W) * 8);
-        if (!cont) {
-            std::memcpy(stage + o_cur0, blk->params, n_cur * 8);
-            std::memcpy(stage + o_lp0, blk->logpost, (size_t)W * 8);
+        std::memset(stage + L.o_cur0, 0, (n_cur + W) * 8);
+        if (!f.cont) {
+            std::memcpy(stage + L.o_cur0, blk->params, n_cur * 8);
+            std::memcpy(stage + L.o_lp0, blk->logpost, (size_t)W * 8);
         }
-        std::memcpy(stage + o_chol, blk->chol, (size_t)d * d * 8);
-        if (want_rows) std::memcpy(stage + o_org, blk->row_origin, (size_t)d * 8); else std::memset(stage + o_org, 0, (size_t)d * 8);
-        std::memset(stage + o_dec, 0xFF, (size_t)W * 8);                 // no step published yet
-        int *hi = reinterpret_cast<int *>(stage + o_int);
-        std::memcpy(hi, blk->free_idx, d * sizeof(int));
-        std::memcpy(hi + d, blk->walker_ids, W * sizeof(int));
-        std::memset(stage + o_nacc, 0, 8);
-        double *st0 = stage + o_st0;                                      // starting state -> parity 0, which K(0) (parity 1) reads
+        std::memset(stage + L.o_dec, 0xFF, (size_t)W * 8);               // no step published yet
+        std::memset(stage + L.o_nacc, 0, 8);
+        double *st0 = stage + L.o_st[0];                                  // starting state -> parity 0, which K(0) (parity 1) reads
         std::memset(st0, 0, n_state * 8);
-        if (!cont)
+        if (!f.cont)
             for (int w = 0; w < W; ++w) {
                 std::memcpy(st0 + (size_t)w * B9_STATE_STRIDE + B9_ST_CUR, blk->params + (size_t)w * B9_NPARAM, sizeof(double) * B9_NPARAM);
                 st0[(size_t)w * B9_STATE_STRIDE + B9_ST_LP] = blk->logpost[w];
                 st0[(size_t)w * B9_STATE_STRIDE + B9_ST_LPRIOR] = -INFINITY;
             }
-        // one launch: the upload, read by the device from the mapped mirror, and -- continuing -- the previous block's final
-        // state (stream-ordered behind its last launch) in place of the starting state
-        const double *prev_final = nullptr;
-        if (cont) {
-            const b9_ctx::McmcSlot &pv = ctx->slot[ctx->last_slot];
-            prev_final = static_cast<const double *>(pv.d) + (pv.final_parity ? pv.o_st1 : pv.o_st0);
-        }
-        HIPCHK(ctx, b9k_mcmc_begin(static_cast<const double *>(sl.h_dev), dev, (int)up_words, prev_final, d_cur0, d_lp0, d_state, W, s));
+        // one launch: the upload (cur0 .. state 0), read by the device from the mapped mirror, and -- continuing -- the previous
+        // block's final state in place of the starting state
+        HIPCHK(ctx, b9k_mcmc_begin(f.mirror, dev, (int)L.o_st[1], f.prev_final, d_cur0, d_lp0, d_state, W, s));
     }
     StepDev sd{};
     sd.d = d; sd.n_walkers = W; sd.n_pops = n_pops;
@@ -178,8 +250,8 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
     sd.state = d_state; sd.partial = marg ? mb.partial : ctx->d_partial;
     sd.cand_par = ctx->d_params; sd.cand_hdr = ctx->d_hdr; sd.cand_iso = ctx->d_iso;
     sd.chol = d_chol; sd.free_idx = d_free; sd.walker_ids = d_ids;
-    sd.samples = d_samples; sd.lps = d_lps; sd.n_acc = d_nacc; sd.decided = d_decided;
-    sd.rows = nullptr; sd.row_origin = dev + o_org; sd.n_steps = S;
+    sd.samples = L.n_samp ? dev + L.o_samp : nullptr; sd.lps = L.n_lps ? dev + L.o_lps : nullptr; sd.n_acc = d_nacc; sd.decided = d_decided;
+    sd.rows = nullptr; sd.row_origin = dev + L.o_org; sd.n_steps = S;
     // (a parity's row: the hot waves' partials + one set of heavy-star partials per candidate)
     if (2 * ((long long)sd.n_partial + sd.heavy_parts) > sd.partial_stride) return fail(ctx, B9_ERR_CAPACITY, "partial buffer too small for two parities");
     {   // D0: proposal of step 0 and its isochrones -> candidate 0 of parity 1 (K(t) has parity (t + 1) & 1)
@@ -196,55 +268,31 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
                                         sd.cand_par + c10 * W * B9_NPARAM, W, n_pops, mb.K, mb.Q, ctx->d_marg_tab + c10 * rows * mb.tab_doubles,
                                         ctx->st.n_wd > 0 ? ctx->d_marg_wd_tab + c10 * mb.wd_stride : nullptr, s));
     }
-    long t_slot = -1;
-    int t_covered = 0;
+    TimingBracket tb;
     for (int t = 0; t < S; ++t) {
         sd.set = (t + 1) & 1; sd.has_prev = t > 0; sd.derive_next = t + 1 < S; sd.row = t - 1;
         sd.step = (unsigned long long)(blk->step0 + t);
-        // Timing: every ctx->timing-th launch opens an event bracket that spans timing_group consecutive launches of
-        // this kernel (never past the block's last one), so the two event records cost 1/group of what a bracket
-        // around a single launch adds; the bracket's time / its launch count is the kernel's launch period.
-        if (t_slot < 0) {
-            int rc = timing_begin(ctx, s, &t_slot);
-            if (rc) return rc;
-            t_covered = 0;
-        } else if (ctx->timing > 0) ctx->launch_no++;
+        rc = bracket_before(ctx, s, tb);
+        if (rc) return rc;
         if (marg)
             HIPCHK(ctx, b9k_marg_step(ctx->pk, ctx->st, sd, ctx->pr, mb.K, mb.Q, ctx->marg_prune, ctx->d_marg_tab, ctx->d_marg_wd_tab, mb.wd_stride,
                                       ctx->d_marg_shares, s));
         else
             HIPCHK(ctx, b9k_mcmc_step(ctx->pk, ctx->st, sd, ctx->pr, plan, ctx->heavy_parts, derive_parts, ctx->derive_order, s));
-        if (t_slot >= 0 && (++t_covered >= ctx->timing_group || t == S - 1)) {
-            ctx->ev_count[t_slot] = t_covered;
-            int rc = timing_end(ctx, s, t_slot);
-            if (rc) return rc;
-            t_slot = -1;
-        }
+        rc = bracket_after(ctx, s, tb, t == S - 1);
+        if (rc) return rc;
     }
-    sd.set = (S + 1) & 1; sd.has_prev = 1; sd.derive_next = 0; sd.row = S - 1;
+    const int fin = (S + 1) & 1;
+    sd.set = fin; sd.has_prev = 1; sd.derive_next = 0; sd.row = S - 1;
     sd.step = (unsigned long long)(blk->step0 + S);
-    sd.rows = want_rows ? dev + o_rows : nullptr;
+    sd.rows = f.want_rows ? dev + L.o_rows : nullptr;
     // a block whose chain record stays on the device needs no download: its last launch writes what the host reads (final
     // state, accepted counts, summary rows) into the mapped mirror as well
     const bool zero_copy = !blk->samples && !blk->lps;
-    double *const mirror = static_cast<double *>(sl.h_dev);
-    sd.host_state = zero_copy ? mirror + (((S + 1) & 1) ? o_st1 : o_st0) : nullptr;
-    sd.host_rows = (zero_copy && want_rows) ? mirror + o_rows : nullptr;
+    sd.host_state = zero_copy ? f.mirror + L.o_st[fin] : nullptr;
+    sd.host_rows = (zero_copy && f.want_rows) ? f.mirror + L.o_rows : nullptr;
     HIPCHK(ctx, b9k_mcmc_finish(ctx->pk, sd, ctx->pr, s));
-    const bool rows_event = want_rows && (blk->flags & B9_BLOCK_ROWS_EVENT) != 0;
-    if (rows_event) HIPCHK(ctx, hipEventRecord(sl.rows_ready, s));
-    blk->d_rows = want_rows ? (void *)(dev + o_rows) : nullptr;
-    blk->rows_ready = rows_event ? (void *)sl.rows_ready : nullptr;
-    if (!zero_copy) HIPCHK(ctx, hipMemcpyAsync(stage + o_nacc, dev + o_nacc, down_words * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipEventRecord(sl.done, s));
-    sl.kind = 0;
-    sl.W = W; sl.final_parity = (S + 1) & 1;
-    sl.o_nacc = o_nacc; sl.o_st0 = o_st0; sl.o_st1 = o_st1; sl.o_samp = o_samp; sl.o_lps = o_lps; sl.n_samp = n_samp; sl.n_lps = n_lps;
-    sl.o_rows = o_rows; sl.n_rows = n_rows; sl.host_samples = blk->samples != nullptr;
-    sl.in_flight = true; sl.owner = blk;
-    ctx->last_slot = ctx->next_slot;
-    ctx->next_slot ^= 1;
-    return async ? B9_OK : collect_block(ctx, sl, blk);
+    return close_block(ctx, blk, f, fin, L.o_nacc, zero_copy);
 }
 
 /* Device-resident Metropolis block, given-mass mode, tree-speculative launches (TreeDev in b9_device.h): `depth` steps per launch.
@@ -258,60 +306,24 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
 int run_block_tree(b9_ctx *ctx, b9_mcmc_block *blk, const TreePlan &tp)
 {
     const int W = blk->n_walkers, d = blk->n_free, S = blk->n_steps, n_pops = ctx->opt.n_pops, depth = tp.depth;
-    const bool cont = (blk->flags & B9_BLOCK_CONTINUE) != 0, async = (blk->flags & B9_BLOCK_ASYNC) != 0;
     int rc = ensure_tree_buffers(ctx, W, n_pops, tp);
     if (rc) return rc;
-    b9_ctx::McmcSlot &sl = ctx->slot[ctx->next_slot];
-    if (sl.in_flight) return fail(ctx, B9_ERR_STATE, "two blocks are already outstanding: collect one with b9_mcmc_wait first");
-    if (cont && (ctx->last_slot < 0 || ctx->slot[ctx->last_slot].W != W || ctx->slot[ctx->last_slot].kind != 2))
-        return fail(ctx, B9_ERR_STATE, "B9_BLOCK_CONTINUE needs a previous block of this context with the same n_walkers and mode");
-    const bool want_rows = blk->row_origin != nullptr;
-    const size_t n_state = (size_t)W * B9_TREE_STATE_STRIDE,
-                 n_samp = (blk->samples || want_rows) ? (size_t)S * W * d : 0, n_lps = blk->lps ? (size_t)S * W : 0,
-                 n_rows = want_rows ? (size_t)W * B9_ROW_LEN(d) : 0;
-    //   [chol][origin][free, ids][state 0][state 1] | [rows][lps][samples][step table]        upload = chol .. state 1
-    const size_t n_int = ((size_t)(d + W) + 1) / 2;
-    const size_t tab_steps = (size_t)S + B9_TREE_MAX_DEPTH, n_tab = (size_t)W * tab_steps * B9_TREE_TAB_ROW;
-    const size_t o_chol = 0, o_org = o_chol + (size_t)d * d, o_int = o_org + d, o_st0 = o_int + n_int, o_st1 = o_st0 + n_state,
-                 o_rows = o_st1 + n_state, o_lps = o_rows + n_rows, o_samp = o_lps + n_lps, o_tab = o_samp + n_samp, n_total = o_tab + n_tab;
-    const size_t up_words = o_rows;
-    if (n_total * 8 > sl.cap) {
-        if (sl.d) (void)hipFree(sl.d);
-        sl.d = nullptr; sl.cap = 0;
-        HIPCHK(ctx, hipMalloc(&sl.d, n_total * 8));
-        sl.cap = n_total * 8;
-    }
-    if (n_total * 8 > sl.hcap) {
-        if (sl.h) (void)hipHostFree(sl.h);
-        sl.h = nullptr; sl.hcap = 0;
-        HIPCHK(ctx, hipHostMalloc(&sl.h, n_total * 8, hipHostMallocMapped));
-        HIPCHK(ctx, hipHostGetDevicePointer(&sl.h_dev, sl.h, 0));
-        sl.hcap = n_total * 8;
-    }
-    if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    if (!sl.rows_ready) HIPCHK(ctx, hipEventCreateWithFlags(&sl.rows_ready, hipEventDisableTiming));
-    double *const dev = static_cast<double *>(sl.d), *const stage = static_cast<double *>(sl.h);
+    BlockFrame f;
+    rc = open_block(ctx, blk, BlockKind::Tree, layout_tree, &f);
+    if (rc) return rc;
+    const BlockLayout &L = *f.L;
+    double *const dev = f.dev, *const stage = f.stage;
     hipStream_t s = ctx->stream;
-    {
-        std::memcpy(stage + o_chol, blk->chol, (size_t)d * d * 8);
-        if (want_rows) std::memcpy(stage + o_org, blk->row_origin, (size_t)d * 8); else std::memset(stage + o_org, 0, (size_t)d * 8);
-        int *hi = reinterpret_cast<int *>(stage + o_int);
-        std::memcpy(hi, blk->free_idx, d * sizeof(int));
-        std::memcpy(hi + d, blk->walker_ids, W * sizeof(int));
-        std::memset(stage + o_st0, 0, 2 * n_state * 8);
-        if (!cont)
+    {   // B
+        std::memset(stage + L.o_st[0], 0, (L.o_rows - L.o_st[0]) * 8);
+        if (!f.cont)
             for (int p = 0; p < 2; ++p)
                 for (int w = 0; w < W; ++w) {
-                    double *row = stage + (p ? o_st1 : o_st0) + (size_t)w * B9_TREE_STATE_STRIDE;
+                    double *row = stage + L.o_st[p] + (size_t)w * B9_TREE_STATE_STRIDE;
                     std::memcpy(row + B9_TS_CUR, blk->params + (size_t)w * B9_NPARAM, sizeof(double) * B9_NPARAM);
                     row[B9_TS_LP] = blk->logpost[w];
                 }
-        const double *prev_final = nullptr;
-        if (cont) {
-            const b9_ctx::McmcSlot &pv = ctx->slot[ctx->last_slot];
-            prev_final = static_cast<const double *>(pv.d) + (pv.final_parity ? pv.o_st1 : pv.o_st0);
-        }
-        HIPCHK(ctx, b9k_tree_begin(static_cast<const double *>(sl.h_dev), dev, (int)up_words, prev_final, dev + o_st0, W, s));
+        HIPCHK(ctx, b9k_tree_begin(f.mirror, dev, (int)L.o_rows, f.prev_final, dev + L.o_st[0], W, s));
     }
     TreeDev td{};
     td.d = d; td.n_walkers = W; td.n_pops = n_pops; td.depth = depth;
@@ -319,21 +331,19 @@ int run_block_tree(b9_ctx *ctx, b9_mcmc_block *blk, const TreePlan &tp)
     td.part_stride = (int)(((size_t)tp.n_groups * 4 + ctx->heavy_parts + 1) & ~(size_t)1);
     td.k0 = (unsigned)(blk->seed & 0xFFFFFFFFull); td.k1 = (unsigned)(blk->seed >> 32);
     td.iso_stride = ctx->iso_stride;
-    td.state = dev + o_st0; td.partial = ctx->d_tree_partial;
+    td.state = dev + L.o_st[0]; td.partial = ctx->d_tree_partial;
     td.cand_par = ctx->d_tree_par; td.cand_hdr = ctx->d_tree_hdr; td.cand_iso = ctx->d_tree_iso;
-    td.chol = dev + o_chol; td.free_idx = reinterpret_cast<int *>(dev + o_int); td.walker_ids = td.free_idx + d;
-    td.samples = n_samp ? dev + o_samp : nullptr; td.lps = n_lps ? dev + o_lps : nullptr;
-    td.row_origin = dev + o_org; td.n_steps = S;
-    td.step_tab = dev + o_tab; td.tab_steps = (int)tab_steps; td.block_step0 = (unsigned long long)blk->step0;
-    const int tiles_arg = tp.group_tiles;
+    td.chol = dev + L.o_chol; td.free_idx = reinterpret_cast<int *>(dev + L.o_int); td.walker_ids = td.free_idx + d;
+    td.samples = L.n_samp ? dev + L.o_samp : nullptr; td.lps = L.n_lps ? dev + L.o_lps : nullptr;
+    td.row_origin = dev + L.o_org; td.n_steps = S;
+    td.step_tab = dev + L.o_tab; td.tab_steps = S + B9_TREE_MAX_DEPTH; td.block_step0 = (unsigned long long)blk->step0;
     const int M = (S + depth - 1) / depth;
     {   // P: the block's first tree from the starting state -> candidates of parity 0, outcome slot 0
         td.set = 1; td.levels_prev = 0; td.levels = 0; td.derive_mode = 2; td.row = 0;
         td.step = (unsigned long long)blk->step0; td.next_step = (unsigned long long)blk->step0;
-        HIPCHK(ctx, b9k_mcmc_tree(ctx->pk, ctx->st, td, ctx->pr, tiles_arg, tp.derive_parts, s));
+        HIPCHK(ctx, b9k_mcmc_tree(ctx->pk, ctx->st, td, ctx->pr, tp.group_tiles, tp.derive_parts, s));
     }
-    long t_slot = -1;
-    int t_covered = 0;
+    TimingBracket tb;
     for (int m = 0; m < M; ++m) {
         td.set = m & 1;
         td.levels_prev = m > 0 ? depth : 0;
@@ -342,45 +352,25 @@ int run_block_tree(b9_ctx *ctx, b9_mcmc_block *blk, const TreePlan &tp)
         td.row = (m - 1) * depth;
         td.step = (unsigned long long)(blk->step0 + (long long)m * depth);
         td.next_step = td.step + (unsigned)depth;
-        if (t_slot < 0) {
-            rc = timing_begin(ctx, s, &t_slot);
-            if (rc) return rc;
-            t_covered = 0;
-        } else if (ctx->timing > 0) ctx->launch_no++;
-        HIPCHK(ctx, b9k_mcmc_tree(ctx->pk, ctx->st, td, ctx->pr, tiles_arg, tp.derive_parts, s));
-        if (t_slot >= 0 && (++t_covered >= ctx->timing_group || m == M - 1)) {
-            ctx->ev_count[t_slot] = t_covered;
-            rc = timing_end(ctx, s, t_slot);
-            if (rc) return rc;
-            t_slot = -1;
-        }
+        rc = bracket_before(ctx, s, tb);
+        if (rc) return rc;
+        HIPCHK(ctx, b9k_mcmc_tree(ctx->pk, ctx->st, td, ctx->pr, tp.group_tiles, tp.derive_parts, s));
+        rc = bracket_after(ctx, s, tb, m == M - 1);
+        if (rc) return rc;
     }
-    {   // F
-        td.set = M & 1;
-        td.levels_prev = std::min(depth, S - (M - 1) * depth);
-        td.levels = 0; td.derive_mode = 0;
-        td.row = (M - 1) * depth;
-        td.step = (unsigned long long)(blk->step0 + S); td.next_step = td.step;
-        td.rows = want_rows ? dev + o_rows : nullptr;
-        const bool zero_copy = !blk->samples && !blk->lps;
-        double *const mirror = static_cast<double *>(sl.h_dev);
-        td.host_state = zero_copy ? mirror + ((M & 1) ? o_st1 : o_st0) : nullptr;
-        td.host_rows = (zero_copy && want_rows) ? mirror + o_rows : nullptr;
-        HIPCHK(ctx, b9k_tree_finish(td, ctx->pr, s));
-        const bool rows_event = want_rows && (blk->flags & B9_BLOCK_ROWS_EVENT) != 0;
-        if (rows_event) HIPCHK(ctx, hipEventRecord(sl.rows_ready, s));
-        blk->d_rows = want_rows ? (void *)(dev + o_rows) : nullptr;
-        blk->rows_ready = rows_event ? (void *)sl.rows_ready : nullptr;
-        if (!zero_copy) HIPCHK(ctx, hipMemcpyAsync(stage + o_st0, dev + o_st0, ((blk->samples ? o_tab : o_samp) - o_st0) * 8, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(ctx, hipEventRecord(sl.done, s));
-    sl.kind = 2; sl.W = W; sl.final_parity = M & 1;
-    sl.o_st0 = o_st0; sl.o_st1 = o_st1; sl.o_samp = o_samp; sl.o_lps = o_lps; sl.n_samp = n_samp; sl.n_lps = n_lps;
-    sl.o_rows = o_rows; sl.n_rows = n_rows; sl.host_samples = blk->samples != nullptr;
-    sl.in_flight = true; sl.owner = blk;
-    ctx->last_slot = ctx->next_slot;
-    ctx->next_slot ^= 1;
-    return async ? B9_OK : collect_block(ctx, sl, blk);
+    // F
+    const int fin = M & 1;
+    td.set = fin;
+    td.levels_prev = std::min(depth, S - (M - 1) * depth);
+    td.levels = 0; td.derive_mode = 0;
+    td.row = (M - 1) * depth;
+    td.step = (unsigned long long)(blk->step0 + S); td.next_step = td.step;
+    td.rows = f.want_rows ? dev + L.o_rows : nullptr;
+    const bool zero_copy = !blk->samples && !blk->lps;      // (as in run_block_fused: the finish writes the mirror itself)
+    td.host_state = zero_copy ? f.mirror + L.o_st[fin] : nullptr;
+    td.host_rows = (zero_copy && f.want_rows) ? f.mirror + L.o_rows : nullptr;
+    HIPCHK(ctx, b9k_tree_finish(td, ctx->pr, s));
+    return close_block(ctx, blk, f, fin, L.o_st[0], zero_copy);
 }
 
 /* Device-resident Metropolis block with TWO launches per step (marginalised mode; b9_tuning.two_launch_steps):
@@ -394,63 +384,32 @@ int run_block_tree(b9_ctx *ctx, b9_mcmc_block *blk, const TreePlan &tp)
 int run_block_two_launch(b9_ctx *ctx, b9_mcmc_block *blk, const B9Groups &plan)
 {
     const int W = blk->n_walkers, d = blk->n_free, S = blk->n_steps, n_pops = ctx->opt.n_pops;
-    const bool cont = (blk->flags & B9_BLOCK_CONTINUE) != 0, async = (blk->flags & B9_BLOCK_ASYNC) != 0;
-    b9_ctx::McmcSlot &sl = ctx->slot[ctx->next_slot];
-    if (sl.in_flight) return fail(ctx, B9_ERR_STATE, "two blocks are already outstanding: collect one with b9_mcmc_wait first");
-    if (cont && (ctx->last_slot < 0 || ctx->slot[ctx->last_slot].W != W || ctx->slot[ctx->last_slot].kind != 1))
-        return fail(ctx, B9_ERR_STATE, "B9_BLOCK_CONTINUE needs a previous block of this context with the same n_walkers and mode");
-    const bool want_rows = blk->row_origin != nullptr;
-    const size_t n_cur = (size_t)W * B9_NPARAM, n_samp = (blk->samples || want_rows) ? (size_t)S * W * d : 0,
-                 n_lps = blk->lps ? (size_t)S * W : 0, n_rows = want_rows ? (size_t)W * B9_ROW_LEN(d) : 0;
-    // [chol][origin][free, ids][n_acc][cur: two halves][lp: two halves][rows][lps][samples]
-    //  upload = chol .. first half of lp's start state;  download = n_acc .. lps (.. samples when the caller wants the chain)
-    const size_t n_int = ((size_t)(d + W) + 1) / 2;
-    const size_t o_chol = 0, o_org = o_chol + (size_t)d * d, o_int = o_org + d, o_nacc = o_int + n_int, o_cur = o_nacc + 1,
-                 o_lp = o_cur + 2 * n_cur, o_rows = o_lp + 2 * (size_t)W, o_lps = o_rows + n_rows, o_samp = o_lps + n_lps,
-                 n_total = o_samp + n_samp;
-    if (n_total * 8 > sl.cap) {
-        if (sl.d) (void)hipFree(sl.d);
-        sl.d = nullptr; sl.cap = 0;
-        HIPCHK(ctx, hipMalloc(&sl.d, n_total * 8));
-        sl.cap = n_total * 8;
-    }
-    if (n_total * 8 > sl.hcap) {
-        if (sl.h) (void)hipHostFree(sl.h);
-        sl.h = nullptr; sl.hcap = 0;
-        HIPCHK(ctx, hipHostMalloc(&sl.h, n_total * 8, hipHostMallocMapped));
-        HIPCHK(ctx, hipHostGetDevicePointer(&sl.h_dev, sl.h, 0));
-        sl.hcap = n_total * 8;
-    }
-    if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    if (!sl.rows_ready) HIPCHK(ctx, hipEventCreateWithFlags(&sl.rows_ready, hipEventDisableTiming));
-    double *const dev = static_cast<double *>(sl.d), *const stage = static_cast<double *>(sl.h);
+    BlockFrame f;
+    int rc = open_block(ctx, blk, BlockKind::TwoLaunch, layout_two_launch, &f);
+    if (rc) return rc;
+    const BlockLayout &L = *f.L;
+    double *const dev = f.dev, *const stage = f.stage;
+    const size_t n_cur = (size_t)W * B9_NPARAM;
     hipStream_t s = ctx->stream;
     // upload: proposal factor, moment origin, RNG streams, cleared counter and (unless continuing) the starting state
-    std::memcpy(stage + o_chol, blk->chol, (size_t)d * d * 8);
-    if (want_rows) std::memcpy(stage + o_org, blk->row_origin, (size_t)d * 8); else std::memset(stage + o_org, 0, (size_t)d * 8);
-    int *hi = reinterpret_cast<int *>(stage + o_int);
-    std::memcpy(hi, blk->free_idx, d * sizeof(int));
-    std::memcpy(hi + d, blk->walker_ids, W * sizeof(int));
-    std::memset(stage + o_nacc, 0, 8);
-    HIPCHK(ctx, hipMemcpyAsync(dev + o_chol, stage + o_chol, (o_cur - o_chol) * 8, hipMemcpyHostToDevice, s));
-    if (!cont) {
-        std::memcpy(stage + o_cur, blk->params, n_cur * 8);
-        std::memcpy(stage + o_lp, blk->logpost, (size_t)W * 8);
-        HIPCHK(ctx, hipMemcpyAsync(dev + o_cur, stage + o_cur, n_cur * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(dev + o_lp, stage + o_lp, (size_t)W * 8, hipMemcpyHostToDevice, s));
-    } else {      // the previous block's final half (stream-ordered behind its last launch) -> this block's half 0
-        const b9_ctx::McmcSlot &pv = ctx->slot[ctx->last_slot];
-        const double *pd = static_cast<const double *>(pv.d);
-        HIPCHK(ctx, hipMemcpyAsync(dev + o_cur, pd + pv.o_cur, n_cur * 8, hipMemcpyDeviceToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(dev + o_lp, pd + pv.o_lp, (size_t)W * 8, hipMemcpyDeviceToDevice, s));
+    std::memset(stage + L.o_nacc, 0, 8);
+    HIPCHK(ctx, hipMemcpyAsync(dev + L.o_chol, stage + L.o_chol, (L.o_cur - L.o_chol) * 8, hipMemcpyHostToDevice, s));
+    if (!f.cont) {
+        std::memcpy(stage + L.o_cur, blk->params, n_cur * 8);
+        std::memcpy(stage + L.o_lp, blk->logpost, (size_t)W * 8);
+        HIPCHK(ctx, hipMemcpyAsync(dev + L.o_cur, stage + L.o_cur, n_cur * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(dev + L.o_lp, stage + L.o_lp, (size_t)W * 8, hipMemcpyHostToDevice, s));
+    } else {      // the previous block's final half -> this block's half 0
+        HIPCHK(ctx, hipMemcpyAsync(dev + L.o_cur, f.prev_final, n_cur * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(dev + L.o_lp, f.prev_final_lp, (size_t)W * 8, hipMemcpyDeviceToDevice, s));
     }
     McmcDev mc{};
     mc.enabled = 1; mc.d = d; mc.n_walkers = W;
-    mc.cur = dev + o_cur; mc.lp_cur = dev + o_lp;
-    mc.chol = dev + o_chol;
-    mc.free_idx = reinterpret_cast<int *>(dev + o_int); mc.walker_ids = mc.free_idx + d;
-    mc.samples = n_samp ? dev + o_samp : nullptr; mc.lps = n_lps ? dev + o_lps : nullptr;
-    mc.n_acc = reinterpret_cast<unsigned long long *>(dev + o_nacc);
+    mc.cur = dev + L.o_cur; mc.lp_cur = dev + L.o_lp;
+    mc.chol = dev + L.o_chol;
+    mc.free_idx = reinterpret_cast<int *>(dev + L.o_int); mc.walker_ids = mc.free_idx + d;
+    mc.samples = L.n_samp ? dev + L.o_samp : nullptr; mc.lps = L.n_lps ? dev + L.o_lps : nullptr;
+    mc.n_acc = reinterpret_cast<unsigned long long *>(dev + L.o_nacc);
     mc.k0 = (unsigned)(blk->seed & 0xFFFFFFFFull); mc.k1 = (unsigned)(blk->seed >> 32);
     const int n_part = partial_count(ctx, plan);
     for (int t = 0; t < S; ++t) {
@@ -462,7 +421,7 @@ int run_block_two_launch(b9_ctx *ctx, b9_mcmc_block *blk, const B9Groups &plan)
         const B9Prev prev{ctx->d_partial, n_part, partial_stride(ctx), bp.hdr, bp.params};
         HIPCHK(ctx, b9k_derive_iso(ctx->pk, bf.params, W, n_pops, bf.hdr, bf.iso, ctx->iso_stride, ctx->mass_cap,
                                    mc, ctx->pr, prev, s));
-        const int rc = launch_stars(ctx, bf, W, nullptr, plan, s);
+        rc = launch_stars(ctx, bf, W, nullptr, plan, s);
         if (rc) return rc;
     }
     {   // finish the last step
@@ -476,41 +435,27 @@ int run_block_two_launch(b9_ctx *ctx, b9_mcmc_block *blk, const B9Groups &plan)
                                  ctx->d_logpost, nullptr, ctx->st.n, mc, s));
     }
     const int fin = mc.pin ^ 1;                             // half that holds the final state
-    const size_t o_cur_fin = o_cur + (size_t)fin * n_cur, o_lp_fin = o_lp + (size_t)fin * W;
-    if (want_rows) {
+    if (f.want_rows) {
         StepDev sd{};
         sd.d = d; sd.n_walkers = W; sd.n_steps = S; sd.samples = mc.samples; sd.free_idx = mc.free_idx;
-        sd.row_origin = dev + o_org; sd.rows = dev + o_rows; sd.host_rows = nullptr;
-        HIPCHK(ctx, b9k_chain_rows(sd, dev + o_cur_fin, dev + o_lp_fin, s));
+        sd.row_origin = dev + L.o_org; sd.rows = dev + L.o_rows; sd.host_rows = nullptr;
+        HIPCHK(ctx, b9k_chain_rows(sd, dev + L.o_cur + (size_t)fin * n_cur, dev + L.o_lp + (size_t)fin * W, s));
     }
-    const bool rows_event = want_rows && (blk->flags & B9_BLOCK_ROWS_EVENT) != 0;
-    if (rows_event) HIPCHK(ctx, hipEventRecord(sl.rows_ready, s));
-    blk->d_rows = want_rows ? (void *)(dev + o_rows) : nullptr;
-    blk->rows_ready = rows_event ? (void *)sl.rows_ready : nullptr;
-    const size_t down_end = blk->samples ? n_total : o_samp;
-    HIPCHK(ctx, hipMemcpyAsync(stage + o_nacc, dev + o_nacc, (down_end - o_nacc) * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipEventRecord(sl.done, s));
-    sl.kind = 1; sl.W = W; sl.final_parity = fin;
-    sl.o_nacc = o_nacc; sl.o_cur = o_cur_fin; sl.o_lp = o_lp_fin; sl.o_samp = o_samp; sl.o_lps = o_lps; sl.o_rows = o_rows;
-    sl.n_samp = n_samp; sl.n_lps = n_lps; sl.n_rows = n_rows; sl.host_samples = blk->samples != nullptr;
-    sl.in_flight = true; sl.owner = blk;
-    ctx->last_slot = ctx->next_slot;
-    ctx->next_slot ^= 1;
-    return async ? B9_OK : collect_block(ctx, sl, blk);
+    return close_block(ctx, blk, f, fin, L.o_nacc, false);
 }
-
 
 }  // namespace
 
 extern "C" {
 
-/* Device-resident Metropolis block (the caller of the hot path).  Given-mass mode
- * runs the fused one-launch step (run_block_fused above); what follows is the two-launch step of the
- * marginalised mode.
- * Launch sequence for S steps:  D(0) L(0)  D(1) L(1)  ...  D(S-1) L(S-1)  F
- *   D(t) = k_derive_iso: finishes step t-1 (sum + prior + accept; t > 0), proposes step t, derives
- *   L(t) = star likelihood of step t's proposals;   F = k_finalize: finishes the last step.
- * Two launches per step; buffers and walker state ping-pong between two halves. */
+/* Device-resident Metropolis block (the caller of the hot path): validates the block, sizes the work buffers
+ * for its walkers and hands it to one of the three runners above --
+ *   given-mass mode:     run_block_tree when the tree plan's depth is >= 2 (b9_tuning.tree_depth, or automatic: few walkers),
+ *                        else run_block_fused (k_mcmc_step, one launch per step);
+ *   marginalised mode:   run_block_fused with k_marg_step while the table builders' LDS fits beside the star role (marg_fused_ok);
+ *   either mode:         run_block_two_launch when b9_tuning.two_launch_steps is set, and for the marginalised isochrones too
+ *                        long for the fused step.
+ * All three keep the same block contract (open_block / close_block / collect_block). */
 int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk)
 {
     if (!ctx || !blk || blk->n_walkers < 1 || blk->n_steps < 0 || blk->n_free < 1 || blk->n_free > 11 ||

@@ -33,24 +33,13 @@ int launch_stars(b9_ctx *ctx, const Bufs &bf, int32_t n_walkers, double *d_perst
                         hipStream_t stream)
 {
     const int n_pops = ctx->opt.n_pops;
-    size_t slot = 0;
-    const bool timed = ctx->timing > 0 && (ctx->launch_no++ % (unsigned)ctx->timing) == 0;
-    if (timed) {
-        if (ctx->ev_used == ctx->ev_start.size()) {
-            hipEvent_t a, b;
-            HIPCHK(ctx, hipEventCreate(&a));
-            HIPCHK(ctx, hipEventCreate(&b));
-            ctx->ev_start.push_back(a); ctx->ev_stop.push_back(b);
-        }
-        slot = ctx->ev_used++;
-        if (ctx->ev_count.size() < ctx->ev_used) ctx->ev_count.resize(ctx->ev_used, 1);
-        ctx->ev_count[slot] = 1;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_start[slot], stream));
-    }
+    TimingBracket tb;
+    int rc = bracket_before(ctx, stream, tb);
+    if (rc) return rc;
     if (ctx->opt.mode == B9_MODE_MARGINALISED) {
         const int K = ctx->opt.marg_iso_increm > 0 ? ctx->opt.marg_iso_increm : 1;
         const int Q = ctx->opt.marg_n_q > 0 ? ctx->opt.marg_n_q : 1;
-        const int rc = ensure_marg_table(ctx, n_walkers, n_pops, K, Q);
+        rc = ensure_marg_table(ctx, n_walkers, n_pops, K, Q);
         if (rc) return rc;
         HIPCHK(ctx, b9k_star_marg(ctx->pk, ctx->st, bf.hdr, bf.iso, ctx->iso_stride, ctx->mass_cap, bf.params,
                                   n_walkers, n_pops, ctx->d_partial, partial_stride(ctx), d_perstar, K, Q, nullptr, ctx->marg_prune, ctx->d_marg_tab, ctx->d_marg_wd_tab, ctx->d_marg_shares, stream));
@@ -58,8 +47,7 @@ int launch_stars(b9_ctx *ctx, const Bufs &bf, int32_t n_walkers, double *d_perst
         HIPCHK(ctx, b9k_star_like(ctx->pk, ctx->st, bf.hdr, bf.iso, ctx->iso_stride, ctx->mass_cap, bf.params,
                                   n_walkers, n_pops, ctx->d_partial, partial_stride(ctx), d_perstar, plan, ctx->heavy_parts, stream));
     }
-    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev_stop[slot], stream));
-    return B9_OK;
+    return bracket_after(ctx, stream, tb, true);
 }
 
 }  // namespace b9i
@@ -114,8 +102,6 @@ int b9_logpost(b9_ctx *ctx, const double *params, int32_t n_walkers, double *out
     if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
     int rc = check_ready(ctx);
     if (rc) return rc;
-    const B9Groups plan = make_plan(ctx, n_walkers, ctx->opt.n_pops);
-    (void)plan;
     rc = ensure_capacity(ctx, n_walkers, ctx->opt.n_pops, (size_t)partial_stride(ctx) * n_walkers, out_perstar != nullptr);
     if (rc) return rc;
     // The per-step call of a host-driven sampler (the reference's logPostStep) is latency: for up

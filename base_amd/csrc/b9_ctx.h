@@ -29,6 +29,21 @@ struct HostStars {
     double min_mass1 = 0.0;
 };
 
+// Which runner of b9_capi_blocks.cpp enqueued a sampler block.
+enum class BlockKind { Fused, TwoLaunch, Tree };
+
+// Where a sampler block's pieces sit in its device block and in the pinned mirror, in doubles.  One of the three layout
+// functions of b9_capi_blocks.cpp fills it (there are the layouts themselves); a field another kind does not have stays 0.
+struct BlockLayout {
+    size_t n_samp = 0, n_lps = 0, n_rows = 0, n_int = 0;      // chain record, log-posterior record, summary rows, [free_idx, walker_ids]
+    size_t o_chol = 0, o_org = 0, o_int = 0, o_rows = 0, o_lps = 0, o_samp = 0, n_total = 0;     // every kind
+    size_t o_nacc = 0;                                        // fused, two-launch: the accepted count (64 bits)
+    size_t o_st[2] = {0, 0};                                  // fused, tree: the two parities' state rows
+    size_t o_cur0 = 0, o_lp0 = 0, o_dec = 0;                  // fused: starting state as D0 reads it, decision words
+    size_t o_tab = 0;                                         // tree: step table
+    size_t o_cur = 0, o_lp = 0;                               // two-launch: [cur] and [lp], two halves each
+};
+
 }  // namespace b9i
 
 struct b9_ctx {
@@ -72,18 +87,19 @@ struct b9_ctx {
     const int *marg_order_spread = nullptr;   // the load-time order (photometric spread), owned by star_allocs
     std::vector<double> marg_cost;            // measured cost per star chunk (units; empty: not measured)
     std::vector<double> h_log_age, h_feh, h_y;   // host copies of the pack's grid axes (the plan's reference row is clamped into them)
-    struct McmcSlot {                // fused step: one enqueued block (device block, pinned mirror, completion event)
+    struct McmcSlot {                // one enqueued sampler block of any runner: device block, pinned mirror, events, and what
+                                     // b9_mcmc_wait and a B9_BLOCK_CONTINUE successor need to find its results
         void *d = nullptr, *h = nullptr, *h_dev = nullptr;   // h_dev: the pinned mirror as the device sees it (mapped)
         size_t cap = 0, hcap = 0;
-        hipEvent_t done = nullptr;
+        hipEvent_t done = nullptr;         // recorded behind the block's last command (the download, unless the block is zero-copy)
+        hipEvent_t rows_ready = nullptr;   // recorded right after the block's last kernel: the summary rows are in HBM
         bool in_flight = false;
         const void *owner = nullptr; // the b9_mcmc_block it was enqueued for
-        int W = 0, final_parity = 0;
-        size_t o_nacc = 0, o_st0 = 0, o_st1 = 0, o_samp = 0, o_lps = 0, o_rows = 0, n_samp = 0, n_lps = 0, n_rows = 0;
-        bool host_samples = false; // the caller asked for the chain record (else it only exists on the device, for the rows)
-        hipEvent_t rows_ready = nullptr;   // recorded right after the block's last kernel: the summary rows are in HBM
-        int kind = 0;                      // 0: fused one-launch steps; 1: two-launch steps (marginalised mode)
-        size_t o_cur = 0, o_lp = 0;        // two-launch blocks: where the final state half sits in the block
+        b9i::BlockKind kind = b9i::BlockKind::Fused;   // the runner that enqueued it: it decides how the final state is read
+        int W = 0;
+        int final_parity = 0;        // which of lay.o_st[] (two-launch blocks: which half of [cur] / [lp]) holds the final state
+        b9i::BlockLayout lay;        // where everything sits in d and h
+        bool host_samples = false;   // the caller asked for the chain record (else it only exists on the device, for the rows)
     } slot[2];
     int next_slot = 0, last_slot = -1;
     double *h_lp = nullptr, *h_lp_dev = nullptr;   // b9_logpost: 8 log-posteriors + 8 completion words in mapped pinned host memory (host / device view)
@@ -176,6 +192,26 @@ int ensure_marg_table(b9_ctx *ctx, int n_walkers, int n_pops, int K, int Q);
 int check_ready(b9_ctx *ctx);
 int timing_begin(b9_ctx *ctx, hipStream_t stream, long *slot);
 int timing_end(b9_ctx *ctx, hipStream_t stream, long slot);
+
+// Timing of the dominant kernel: every ctx->timing-th launch opens an event bracket that spans up to ctx->timing_group
+// consecutive launches of that kernel (never past `last`), so the two event records cost 1/group of what a bracket around a
+// single launch adds; the bracket's time / its launch count is the kernel's launch period.  bracket_before / bracket_after go
+// around every launch of a loop; a lone launch passes last = true.
+struct TimingBracket { long slot = -1; int covered = 0; };
+inline int bracket_before(b9_ctx *ctx, hipStream_t stream, TimingBracket &b)
+{
+    if (b.slot >= 0) { ctx->launch_no++; return B9_OK; }      // inside an open bracket
+    b.covered = 0;
+    return timing_begin(ctx, stream, &b.slot);
+}
+inline int bracket_after(b9_ctx *ctx, hipStream_t stream, TimingBracket &b, bool last)
+{
+    if (b.slot < 0 || (++b.covered < ctx->timing_group && !last)) return B9_OK;
+    ctx->ev_count[b.slot] = b.covered;
+    const int rc = timing_end(ctx, stream, b.slot);
+    b.slot = -1;
+    return rc;
+}
 
 // ---- b9_capi_margplan.cpp
 int ensure_marg_plan(b9_ctx *ctx);

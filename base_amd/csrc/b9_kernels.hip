@@ -100,6 +100,39 @@ __global__ __launch_bounds__(256) void k_finalize(const IsoHdr *__restrict__ hdr
 // ------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------
+#include <type_traits>
+
+// Opt a kernel in to `lds` bytes of dynamic LDS: above 64 KB a launch needs the attribute, above the CU's 160 KB nothing helps.
+template <class K>
+static hipError_t lds_opt_in(K *kern, size_t lds)
+{
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+// a kernel, its dynamic LDS, and what opting in to that said: derived once for an occupancy query and for the launch
+template <class K> struct LdsKernel { K *kern; size_t lds; hipError_t err; };
+template <class K> static LdsKernel<K> with_lds(K *kern, size_t lds) { return {kern, lds, lds_opt_in(kern, lds)}; }
+
+// Runtime (pk.nfp, n_pops) -> the instantiated <NFP, NPOPS> of {4, 8, 16} x {1, 2}: f gets them as integral constants.
+template <int N> using Int = std::integral_constant<int, N>;
+template <class F>
+static hipError_t dispatch_nfp(int nfp, F &&f)
+{
+    switch (nfp) {
+    case 4:  return f(Int<4>{});
+    case 8:  return f(Int<8>{});
+    case 16: return f(Int<16>{});
+    default: return hipErrorInvalidValue;
+    }
+}
+template <class F>
+static hipError_t dispatch(int nfp, int n_pops, F &&f)
+{
+    return dispatch_nfp(nfp, [&](auto nfp_c) { return n_pops == 2 ? f(nfp_c, Int<2>{}) : f(nfp_c, Int<1>{}); });
+}
+
 hipError_t b9k_derive_iso(const DevPack &pk, double *d_params, int n_walkers, int n_pops,
                           IsoHdr *hdr, double *iso_data, long long iso_stride, int mass_cap,
                           const McmcDev &mc, const DevPriors &pr, const B9Prev &prev, hipStream_t stream)
@@ -135,50 +168,24 @@ static size_t heavy_lds_doubles(const DevPack &pk, int n_pops, int n_cand, int m
     return 8 + (size_t)pk.hc_len + tips + (size_t)n_pops * n_cand * mass_cap + (size_t)n_cand * B9_NPARAM + 8;
 }
 
-template <int NFP, int NPOPS>
-static hipError_t launch_star_like(const DevPack &pk, const DevStars &st, const IsoHdr *hdr,
-                                   const double *iso_data, long long iso_stride, int mass_cap,
-                                   const double *d_params, int n_walkers, double *partial, long long partial_stride,
-                                   double *perstar, const B9Groups &gr, int heavy_parts, hipStream_t stream)
-{
-    // + 8: find_bracket's last stage may read up to 6 entries past a column's end (masked out)
-    const size_t lds = sizeof(double) * std::max((size_t)NPOPS * mass_cap + 8, heavy_lds_doubles(pk, NPOPS, 1, mass_cap));
-    auto kern = k_star_like<NFP, NPOPS>;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    const int hot = 8 * ((gr.n_blocks * NPOPS + 7) / 8) * n_walkers;     // padded so every XCD sees whole walker sets (two populations: a workgroup per half tile)
-    const int heavy = (n_walkers * heavy_parts + 7) / 8 * 8;     // heavy-star workgroups lead the grid
-    hipLaunchKernelGGL(kern, dim3(heavy + hot), dim3(256), lds, stream, pk, st, hdr, iso_data,
-                       iso_stride, mass_cap, d_params, n_walkers, partial, partial_stride, gr.n_groups, gr.group_tiles,
-                       gr.groups_per_block, gr.n_blocks, perstar, heavy, heavy_parts);
-    return hipGetLastError();
-}
-
-#define B9_SWITCH_NFP(CALL2, CALL1)                 \
-    switch (pk.nfp) {                               \
-    case 4:  if (n_pops == 2) { return CALL2(4); } else { return CALL1(4); }   \
-    case 8:  if (n_pops == 2) { return CALL2(8); } else { return CALL1(8); }   \
-    case 16: if (n_pops == 2) { return CALL2(16); } else { return CALL1(16); } \
-    default: return hipErrorInvalidValue;           \
-    }
-
 hipError_t b9k_star_like(const DevPack &pk, const DevStars &st, const IsoHdr *hdr,
                          const double *iso_data, long long iso_stride, int mass_cap,
                          const double *d_params, int n_walkers, int n_pops,
                          double *partial, long long partial_stride, double *perstar, const B9Groups &gr,
                          int heavy_parts, hipStream_t stream)
 {
-#define SL_ARGS pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, partial, partial_stride, perstar, gr, heavy_parts, stream
-#define SL2(NFP) launch_star_like<NFP, 2>(SL_ARGS)
-#define SL1(NFP) launch_star_like<NFP, 1>(SL_ARGS)
-    B9_SWITCH_NFP(SL2, SL1)
-#undef SL1
-#undef SL2
-#undef SL_ARGS
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        // + 8: find_bracket's last stage may read up to 6 entries past a column's end (masked out)
+        const auto k = with_lds(k_star_like<NFP, NPOPS>, sizeof(double) * std::max((size_t)NPOPS * mass_cap + 8, heavy_lds_doubles(pk, NPOPS, 1, mass_cap)));
+        if (k.err != hipSuccess) return k.err;
+        const int hot = 8 * ((gr.n_blocks * NPOPS + 7) / 8) * n_walkers;     // padded so every XCD sees whole walker sets (two populations: a workgroup per half tile)
+        const int heavy = (n_walkers * heavy_parts + 7) / 8 * 8;     // heavy-star workgroups lead the grid
+        hipLaunchKernelGGL(k.kern, dim3(heavy + hot), dim3(256), k.lds, stream, pk, st, hdr, iso_data,
+                           iso_stride, mass_cap, d_params, n_walkers, partial, partial_stride, gr.n_groups, gr.group_tiles,
+                           gr.groups_per_block, gr.n_blocks, perstar, heavy, heavy_parts);
+        return hipGetLastError();
+    });
 }
 
 hipError_t b9k_finalize(const IsoHdr *hdr, const double *partial, int n_partial, long long partial_stride,
@@ -190,71 +197,43 @@ hipError_t b9k_finalize(const IsoHdr *hdr, const double *partial, int n_partial,
     return hipGetLastError();
 }
 
-template <int NFP>
-static hipError_t launch_predict_mags(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                                      int n_pops, const double *d_params, long long n, const double *mass1, const double *mass_ratio,
-                                      const int *wd_type, const int *pop, double *out_mags, int *out_stage, int n_wgs, hipStream_t stream)
-{
-    const size_t lds = sizeof(double) * (size_t)n_pops * mass_cap * (NFP + 1);
-    auto kern = k_predict_mags<NFP>;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    const long long need = (n + 255) / 256;
-    hipLaunchKernelGGL(kern, dim3((unsigned)std::max(1ll, std::min<long long>(need, n_wgs))), dim3(256), lds, stream, pk, hdr, iso_data,
-                       iso_stride, mass_cap, n_pops, d_params, n, mass1, mass_ratio, wd_type, pop, out_mags, out_stage);
-    return hipGetLastError();
-}
-
 size_t b9k_predict_lds(int nfp, int mass_cap, int n_pops) { return sizeof(double) * (size_t)n_pops * mass_cap * (nfp + 1); }
 
 hipError_t b9k_predict_mags(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap, int n_pops,
                             const double *d_params, long long n, const double *mass1, const double *mass_ratio, const int *wd_type,
                             const int *pop, double *out_mags, int *out_stage, int n_wgs, hipStream_t stream)
 {
-#define PM_ARGS pk, hdr, iso_data, iso_stride, mass_cap, n_pops, d_params, n, mass1, mass_ratio, wd_type, pop, out_mags, out_stage, n_wgs, stream
-    switch (pk.nfp) {
-    case 4:  return launch_predict_mags<4>(PM_ARGS);
-    case 8:  return launch_predict_mags<8>(PM_ARGS);
-    case 16: return launch_predict_mags<16>(PM_ARGS);
-    default: return hipErrorInvalidValue;
-    }
-#undef PM_ARGS
+    return dispatch_nfp(pk.nfp, [&](auto nfp_c) {
+        constexpr int NFP = decltype(nfp_c)::value;
+        const auto k = with_lds(k_predict_mags<NFP>, b9k_predict_lds(NFP, mass_cap, n_pops));
+        if (k.err != hipSuccess) return k.err;
+        const long long need = (n + 255) / 256;
+        hipLaunchKernelGGL(k.kern, dim3((unsigned)std::max(1ll, std::min<long long>(need, n_wgs))), dim3(256), k.lds, stream, pk, hdr, iso_data,
+                           iso_stride, mass_cap, n_pops, d_params, n, mass1, mass_ratio, wd_type, pop, out_mags, out_stage);
+        return hipGetLastError();
+    });
 }
 
 // ---- b9_sample_wd_mass: the node table of a chunk of rows, then the WD-stage stars against it -----------------------------
 long long b9k_wd_table_doubles(int nfp, long long n_nodes) { return n_nodes * B9_WDS_NODE_DOUBLES(nfp); }       // per (row, population)
 
-template <int NFP, int NPOPS>
-static hipError_t launch_wd_sample(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride,
-                                   int mass_cap, const double *d_params, int n_rows, int n_nodes, double *tab, const B9WdSample &smp,
-                                   hipStream_t stream)
-{
-    if (!tab || n_rows < 1 || n_nodes < 1 || st.n_wd < 1 || n_rows * NPOPS > 65535) return hipErrorInvalidValue;
-    const int n_wp = n_rows * NPOPS;
-    hipLaunchKernelGGL((k_wd_node_table<NFP>), dim3((n_nodes + 63) / 64, n_wp), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride, mass_cap,
-                       NPOPS, d_params, n_nodes, tab, n_wp);
-    WdSampleOut out{};
-    out.zams = smp.zams; out.member = smp.member; out.pop = smp.pop; out.wd_rank = smp.wd_rank;
-    out.der[0] = smp.wd_mass; out.der[1] = smp.prec_log_age; out.der[2] = smp.log_cool_age; out.der[3] = smp.log_teff; out.der[4] = smp.logg;
-    out.k0 = smp.k0; out.k1 = smp.k1; out.row0 = smp.row0;
-    hipLaunchKernelGGL((k_wd_sample<NFP, NPOPS>), dim3((st.n_wd + 63) / 64, n_rows), dim3(64), 0, stream, pk, st, hdr, d_params, n_nodes,
-                       (const double *)tab, n_wp, out);
-    return hipGetLastError();
-}
-
 hipError_t b9k_wd_sample(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
                          const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const B9WdSample &smp, hipStream_t stream)
 {
-#define WS_ARGS pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, n_nodes, tab, smp, stream
-#define WS2(NFP) launch_wd_sample<NFP, 2>(WS_ARGS)
-#define WS1(NFP) launch_wd_sample<NFP, 1>(WS_ARGS)
-    B9_SWITCH_NFP(WS2, WS1)
-#undef WS1
-#undef WS2
-#undef WS_ARGS
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        if (!tab || n_rows < 1 || n_nodes < 1 || st.n_wd < 1 || n_rows * NPOPS > 65535) return hipErrorInvalidValue;
+        const int n_wp = n_rows * NPOPS;
+        hipLaunchKernelGGL((k_wd_node_table<NFP>), dim3((n_nodes + 63) / 64, n_wp), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride, mass_cap,
+                           NPOPS, d_params, n_nodes, tab, n_wp);
+        WdSampleOut out{};
+        out.zams = smp.zams; out.member = smp.member; out.pop = smp.pop; out.wd_rank = smp.wd_rank;
+        out.der[0] = smp.wd_mass; out.der[1] = smp.prec_log_age; out.der[2] = smp.log_cool_age; out.der[3] = smp.log_teff; out.der[4] = smp.logg;
+        out.k0 = smp.k0; out.k1 = smp.k1; out.row0 = smp.row0;
+        hipLaunchKernelGGL((k_wd_sample<NFP, NPOPS>), dim3((st.n_wd + 63) / 64, n_rows), dim3(64), 0, stream, pk, st, hdr, d_params, n_nodes,
+                           (const double *)tab, n_wp, out);
+        return hipGetLastError();
+    });
 }
 
 // doubles of one (walker, population)'s node table (MargLayout, b9_device.h)
@@ -280,343 +259,245 @@ static bool marg_sparse(long long wgs)
     return wgs * 4 <= (long long)5 * n_cu * 4;
 }
 
-template <int NFP, int NPOPS, bool SAMPLE>
-static hipError_t launch_star_marg_t(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data,
-                                     long long iso_stride, int mass_cap, const double *d_params, int n_walkers,
-                                     double *partial, long long partial_stride, double *perstar, int K, int Q, const B9MargSample *smp, bool prune,
-                                     double *tab, double *wd_tab, double *shares, hipStream_t stream)
+// The node tables of n_walkers x n_pops derived isochrones: one workgroup per (walker-population, 64-node chunk).  Returns what
+// the LDS opt-in said; the caller collects the launch's own error.
+template <int NFP>
+static hipError_t launch_marg_table(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                                    const double *d_params, int n_walkers, int n_pops, int K, int Q, double *tab, hipStream_t stream)
 {
-    MargSample ms{};
-    if (SAMPLE) { ms.mass = smp->mass; ms.ratio = smp->ratio; ms.member = smp->member; ms.pop = smp->pop; ms.k0 = smp->k0; ms.k1 = smp->k1; ms.row0 = smp->row0; }
-    if (!tab) return hipErrorInvalidValue;
     const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
-    // the call's node table: one workgroup per (walker-population, 64-node chunk)
-    const size_t lds = sizeof(double) * ((size_t)mass_cap + 8 + 8 * NFP);
-    if (lds > 64 * 1024) {
-        if (lds > 160 * 1024) return hipErrorInvalidValue;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_marg_table<NFP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((k_marg_table<NFP>), dim3(n_walkers * NPOPS, L.n_chunks), dim3(256), lds, stream, pk, hdr, iso_data,
-                       iso_stride, mass_cap, NPOPS, d_params, K, Q, tab, L);
-    // the stars: one workgroup (four waves sharing the node table's sub-chunks) per (64-star chunk, walker), dispatched in DevStars::marg_order
-    // XCD placement (k_star_marg's head): two walker groups x four star-chunk groups.  Each XCD's L2 fetches its group's node
-    // tables and its share of the stars once: 8 x (tables / wsplit) + wsplit x (star copy) bytes in all -- 50k stars x 8
-    // walkers, 4 x 4 grid: 42.5 MB per launch at wsplit 1, 35.2 at 2, 41.3 at 4 (rocprofv3 FETCH_SIZE; the launch time is the
-    // same for all three: 164 us -- the kernel is VALU-bound, the placement only decides how much crosses the fabric)
-    const int wsplit = n_walkers % 2 == 0 ? 2 : 1;
-    const int csplit = 8 / wsplit, n_chunks = st.mg_pad / 64;
-    // SPLIT: a small catalogue's launch lasts as long as its heaviest star chunk (giants: 100 us where the median chunk takes
-    // 40) while most of the chip idles, so several workgroups share a chunk's window (DevStars::mg_piece; k_marg_merge).  A
-    // function of the CATALOGUE only -- it decides how a star's sum rounds, and a walker's chain must not depend on how many
-    // walkers share the GPU.  The sampleMass draws keep one workgroup per chunk.
-    const bool split = !SAMPLE && st.mg_n_pieces > 0;
-    if (split && !shares) return hipErrorInvalidValue;
-    const int per_xcd = (((split ? st.mg_n_pieces : n_chunks) + csplit - 1) / csplit) * (n_walkers / wsplit);
-    const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
-    // rows through LDS tiles or through scalar registers (star_marg_body, TILE): measured per instance -- 8 (4) filters x one
-    // population, unsplit, is the one shape the scalar path still wins in this kernel (2.20 against 2.17e9 star-evals/s)
-    const bool sparse = !SAMPLE && split && marg_sparse((long long)st.mg_n_pieces * n_walkers);
-    const bool tiled = !SAMPLE && (split || NPOPS == 2 || NFP >= 16);
-    const size_t tile_lds = sizeof(double) * 4 * B9_TILE_DOUBLES(NFP);
-    if (sparse)
-        hipLaunchKernelGGL((k_star_marg<NFP, NPOPS, SAMPLE, !SAMPLE, false, SAMPLE ? 0 : 2>), dim3(8 * per_xcd), dim3(256), tile_lds, stream, pk, st, hdr, iso_data, iso_stride,
-                           mass_cap, d_params, partial, partial_stride, perstar, K, Q, ms, tab, L, n_walkers, cut2, wsplit, shares);
-    else if (split)
-        hipLaunchKernelGGL((k_star_marg<NFP, NPOPS, SAMPLE, !SAMPLE, false, SAMPLE ? 0 : 1>), dim3(8 * per_xcd), dim3(256), tile_lds, stream, pk, st, hdr, iso_data, iso_stride,
-                           mass_cap, d_params, partial, partial_stride, perstar, K, Q, ms, tab, L, n_walkers, cut2, wsplit, shares);
-    else if (tiled)
-        hipLaunchKernelGGL((k_star_marg<NFP, NPOPS, SAMPLE, false, false, SAMPLE ? 0 : 1>), dim3(8 * per_xcd), dim3(256), tile_lds, stream, pk, st, hdr, iso_data, iso_stride,
-                           mass_cap, d_params, partial, partial_stride, perstar, K, Q, ms, tab, L, n_walkers, cut2, wsplit, shares);
-    else
-        hipLaunchKernelGGL((k_star_marg<NFP, NPOPS, SAMPLE, false>), dim3(8 * per_xcd), dim3(256), 0, stream, pk, st, hdr, iso_data, iso_stride,
-                           mass_cap, d_params, partial, partial_stride, perstar, K, Q, ms, tab, L, n_walkers, cut2, wsplit, shares);
-    if (split)
-        hipLaunchKernelGGL((k_marg_merge<NPOPS>), dim3(n_chunks, n_walkers), dim3(64), 0, stream, st, hdr, d_params, partial, partial_stride,
-                           perstar, shares);
-    if (st.n_wd > 0) {        // the catalogue's WD-stage stars: their node table (2 x 8 K WD chains per walker and population), then a wave per star
-        if (!wd_tab) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_marg_wd_table<NFP>), dim3(n_walkers * NPOPS, (8 * K + 63) / 64), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride,
-                           mass_cap, NPOPS, d_params, K, wd_tab, n_walkers * NPOPS);
-        hipLaunchKernelGGL((k_star_marg_wd<NFP, NPOPS, SAMPLE>), dim3((st.n_wd + 3) / 4, n_walkers), dim3(256), 0, stream, pk, st, hdr,
-                           iso_data, iso_stride, mass_cap, d_params, partial, partial_stride, perstar, K, ms, wd_tab);
-    }
-    return hipGetLastError();
+    const auto k = with_lds(k_marg_table<NFP>, sizeof(double) * ((size_t)mass_cap + 8 + 8 * NFP));
+    if (k.err != hipSuccess) return k.err;
+    hipLaunchKernelGGL(k.kern, dim3(n_walkers * n_pops, L.n_chunks), dim3(256), k.lds, stream, pk, hdr, iso_data,
+                       iso_stride, mass_cap, n_pops, d_params, K, Q, tab, L);
+    return hipSuccess;
 }
-
-// The catalogue plan's counting pass: the unsplit star kernel on ONE row (the reference row), every wave leaving the number of
-// (16 nodes x one mass ratio) units it evaluated in cost[star chunk][4].
-template <int NFP, int NPOPS>
-static hipError_t launch_star_marg_cost(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, int mass_cap, const double *d_params,
-                                        double *partial, long long partial_stride, int K, int Q, bool prune, const double *tab, unsigned *cost, hipStream_t stream)
+// ... and the WD-stage stars' node table (2 x 8 K WD chains per walker and population)
+template <int NFP>
+static void launch_marg_wd_table(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                                 const double *d_params, int n_walkers, int n_pops, int K, double *wd_tab, hipStream_t stream)
 {
-    MargSample ms{};
-    ms.cost = cost;
-    const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
-    const int n_chunks = st.mg_pad / 64;
-    const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
-    hipLaunchKernelGGL((k_star_marg<NFP, NPOPS, false, false, true>), dim3(8 * ((n_chunks + 7) / 8)), dim3(256), 0, stream, pk, st, hdr, (const double *)nullptr, 0ll,
-                       mass_cap, d_params, partial, partial_stride, (double *)nullptr, K, Q, ms, tab, L, 1, cut2, 1, (double *)nullptr);
-    return hipGetLastError();
+    hipLaunchKernelGGL((k_marg_wd_table<NFP>), dim3(n_walkers * n_pops, (8 * K + 63) / 64), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride,
+                       mass_cap, n_pops, d_params, K, wd_tab, n_walkers * n_pops);
 }
 
-hipError_t b9k_star_marg_cost(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, int mass_cap, const double *d_params, int n_pops,
-                              double *partial, long long partial_stride, int K, int Q, bool prune, const double *tab, unsigned *cost, hipStream_t stream)
+// The marginalised star grid: one workgroup (four waves sharing the node table's sub-chunks) per (64-star chunk or piece, walker),
+// dispatched in DevStars::marg_order.
+// XCD placement (k_star_marg's head): two walker groups x four star-chunk groups.  Each XCD's L2 fetches its group's node
+// tables and its share of the stars once: 8 x (tables / wsplit) + wsplit x (star copy) bytes in all -- 50k stars x 8
+// walkers, 4 x 4 grid: 42.5 MB per launch at wsplit 1, 35.2 at 2, 41.3 at 4 (rocprofv3 FETCH_SIZE; the launch time is the
+// same for all three: 164 us -- the kernel is VALU-bound, the placement only decides how much crosses the fabric)
+struct MargGrid { int wsplit, csplit, per_xcd; };      // walker groups, star-chunk groups, star workgroups per XCD
+static MargGrid marg_star_grid(const DevStars &st, int n_walkers, bool split)
 {
-#define CS_ARGS pk, st, hdr, mass_cap, d_params, partial, partial_stride, K, Q, prune, tab, cost, stream
-#define CS2(NFP) launch_star_marg_cost<NFP, 2>(CS_ARGS)
-#define CS1(NFP) launch_star_marg_cost<NFP, 1>(CS_ARGS)
-    B9_SWITCH_NFP(CS2, CS1)
-#undef CS1
-#undef CS2
-#undef CS_ARGS
+    MargGrid g;
+    g.wsplit = n_walkers % 2 == 0 ? 2 : 1;
+    g.csplit = 8 / g.wsplit;
+    g.per_xcd = (((split ? st.mg_n_pieces : st.mg_pad / 64) + g.csplit - 1) / g.csplit) * (n_walkers / g.wsplit);
+    return g;
 }
 
-template <int NFP, int NPOPS>
-static hipError_t launch_star_marg(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data,
-                                   long long iso_stride, int mass_cap, const double *d_params, int n_walkers,
-                                   double *partial, long long partial_stride, double *perstar, int K, int Q, const B9MargSample *smp, bool prune, double *tab, double *wd_tab, double *shares, hipStream_t stream)
-{
-    return smp ? launch_star_marg_t<NFP, NPOPS, true>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, partial, partial_stride, perstar, K, Q, smp, prune, tab, wd_tab, shares, stream)
-               : launch_star_marg_t<NFP, NPOPS, false>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, partial, partial_stride, perstar, K, Q, smp, prune, tab, wd_tab, shares, stream);
-}
-
+// smp == nullptr: the plain marginal likelihood; else every star also draws one (mass, ratio[, population]) node
 hipError_t b9k_star_marg(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data,
                          long long iso_stride, int mass_cap, const double *d_params, int n_walkers, int n_pops,
                          double *partial, long long partial_stride, double *perstar, int K, int Q, const B9MargSample *smp, bool prune, double *tab, double *wd_tab, double *shares, hipStream_t stream)
 {
-#define SM_ARGS pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, partial, partial_stride, perstar, K, Q, smp, prune, tab, wd_tab, shares, stream
-#define SM2(NFP) launch_star_marg<NFP, 2>(SM_ARGS)
-#define SM1(NFP) launch_star_marg<NFP, 1>(SM_ARGS)
-    B9_SWITCH_NFP(SM2, SM1)
-#undef SM1
-#undef SM2
-#undef SM_ARGS
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        const auto launch = [&](auto sample_c) {
+            constexpr bool SAMPLE = decltype(sample_c)::value;
+            MargSample ms{};
+            if (SAMPLE) { ms.mass = smp->mass; ms.ratio = smp->ratio; ms.member = smp->member; ms.pop = smp->pop; ms.k0 = smp->k0; ms.k1 = smp->k1; ms.row0 = smp->row0; }
+            if (!tab) return hipErrorInvalidValue;
+            const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
+            const hipError_t e = launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, NPOPS, K, Q, tab, stream);      // the call's node table
+            if (e != hipSuccess) return e;
+            // SPLIT: a small catalogue's launch lasts as long as its heaviest star chunk (giants: 100 us where the median chunk takes
+            // 40) while most of the chip idles, so several workgroups share a chunk's window (DevStars::mg_piece; k_marg_merge).  A
+            // function of the CATALOGUE only -- it decides how a star's sum rounds, and a walker's chain must not depend on how many
+            // walkers share the GPU.  The sampleMass draws keep one workgroup per chunk.
+            const bool split = !SAMPLE && st.mg_n_pieces > 0;
+            if (split && !shares) return hipErrorInvalidValue;
+            const MargGrid g = marg_star_grid(st, n_walkers, split);
+            const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
+            // rows through LDS tiles or through scalar registers (star_marg_body, TILE): measured per instance -- 8 (4) filters x one
+            // population, unsplit, is the one shape the scalar path still wins in this kernel (2.20 against 2.17e9 star-evals/s)
+            const bool sparse = !SAMPLE && split && marg_sparse((long long)st.mg_n_pieces * n_walkers);
+            const bool tiled = !SAMPLE && (split || NPOPS == 2 || NFP >= 16);
+            const auto kern = sparse ? k_star_marg<NFP, NPOPS, SAMPLE, !SAMPLE, false, SAMPLE ? 0 : 2>
+                            : split  ? k_star_marg<NFP, NPOPS, SAMPLE, !SAMPLE, false, SAMPLE ? 0 : 1>
+                            : tiled  ? k_star_marg<NFP, NPOPS, SAMPLE, false, false, SAMPLE ? 0 : 1>
+                                     : k_star_marg<NFP, NPOPS, SAMPLE, false>;
+            const size_t tile_lds = tiled ? sizeof(double) * 4 * B9_TILE_DOUBLES(NFP) : 0;
+            hipLaunchKernelGGL(kern, dim3(8 * g.per_xcd), dim3(256), tile_lds, stream, pk, st, hdr, iso_data, iso_stride,
+                               mass_cap, d_params, partial, partial_stride, perstar, K, Q, ms, tab, L, n_walkers, cut2, g.wsplit, shares);
+            if (split)
+                hipLaunchKernelGGL((k_marg_merge<NPOPS>), dim3(st.mg_pad / 64, n_walkers), dim3(64), 0, stream, st, hdr, d_params, partial, partial_stride,
+                                   perstar, shares);
+            if (st.n_wd > 0) {        // the catalogue's WD-stage stars: their node table, then a wave per star
+                if (!wd_tab) return hipErrorInvalidValue;
+                launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, NPOPS, K, wd_tab, stream);
+                hipLaunchKernelGGL((k_star_marg_wd<NFP, NPOPS, SAMPLE>), dim3((st.n_wd + 3) / 4, n_walkers), dim3(256), 0, stream, pk, st, hdr,
+                                   iso_data, iso_stride, mass_cap, d_params, partial, partial_stride, perstar, K, ms, wd_tab);
+            }
+            return hipGetLastError();
+        };
+        return smp ? launch(std::true_type{}) : launch(std::false_type{});
+    });
+}
+
+// The catalogue plan's counting pass: the unsplit star kernel on ONE row (the reference row), every wave leaving the number of
+// (16 nodes x one mass ratio) units it evaluated in cost[star chunk][4].
+hipError_t b9k_star_marg_cost(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, int mass_cap, const double *d_params, int n_pops,
+                              double *partial, long long partial_stride, int K, int Q, bool prune, const double *tab, unsigned *cost, hipStream_t stream)
+{
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        MargSample ms{};
+        ms.cost = cost;
+        const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
+        const int n_chunks = st.mg_pad / 64;
+        const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
+        hipLaunchKernelGGL((k_star_marg<NFP, NPOPS, false, false, true>), dim3(8 * ((n_chunks + 7) / 8)), dim3(256), 0, stream, pk, st, hdr, (const double *)nullptr, 0ll,
+                           mass_cap, d_params, partial, partial_stride, (double *)nullptr, K, Q, ms, tab, L, 1, cut2, 1, (double *)nullptr);
+        return hipGetLastError();
+    });
 }
 
 // ---- the marginalised mode's fused sampler step (k_marg_step) -----------------------------------------------------------
 // The node tables of a set of derived isochrones WITHOUT the star launch: the prologue of a fused block (its first
 // proposal comes from k_derive_iso; every later one is built inside k_marg_step).
-template <int NFP>
-static hipError_t launch_marg_tables(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                                     const double *d_params, int n_walkers, int n_pops, int K, int Q, double *tab, double *wd_tab, hipStream_t stream)
-{
-    const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
-    const size_t lds = sizeof(double) * ((size_t)mass_cap + 8 + 8 * NFP);
-    if (lds > 64 * 1024) {
-        if (lds > 160 * 1024) return hipErrorInvalidValue;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_marg_table<NFP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((k_marg_table<NFP>), dim3(n_walkers * n_pops, L.n_chunks), dim3(256), lds, stream, pk, hdr, iso_data,
-                       iso_stride, mass_cap, n_pops, d_params, K, Q, tab, L);
-    if (wd_tab)
-        hipLaunchKernelGGL((k_marg_wd_table<NFP>), dim3(n_walkers * n_pops, (8 * K + 63) / 64), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride,
-                           mass_cap, n_pops, d_params, K, wd_tab, n_walkers * n_pops);
-    return hipGetLastError();
-}
-
 hipError_t b9k_marg_tables(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
                            const double *d_params, int n_walkers, int n_pops, int K, int Q, double *tab, double *wd_tab, hipStream_t stream)
 {
-    switch (pk.nfp) {
-    case 4:  return launch_marg_tables<4>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, n_pops, K, Q, tab, wd_tab, stream);
-    case 8:  return launch_marg_tables<8>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, n_pops, K, Q, tab, wd_tab, stream);
-    case 16: return launch_marg_tables<16>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, n_pops, K, Q, tab, wd_tab, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_nfp(pk.nfp, [&](auto nfp_c) {
+        constexpr int NFP = decltype(nfp_c)::value;
+        const hipError_t e = launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, n_pops, K, Q, tab, stream);
+        if (e != hipSuccess) return e;
+        if (wd_tab) launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, n_pops, K, wd_tab, stream);
+        return hipGetLastError();
+    });
 }
 
 // Dynamic LDS of k_marg_step (its table builders' tiles; every workgroup of the launch gets it): the fused step runs only while it
 // leaves the star role its workgroups per CU (B9_MSTEP_LDS_MAX: 160 KB / 7 less the kernel's static arrays, with 8 filters)
 size_t b9k_marg_step_lds(int nfp, int mass_cap) { return sizeof(double) * B9_MSTEP_LDS_DOUBLES(nfp, mass_cap); }
 
-template <int NFP, int NPOPS>
-static hipError_t launch_marg_step(const DevPack &pk, const DevStars &st, const StepDev &sd, const DevPriors &pr, int K, int Q, bool prune,
-                                   double *tab, double *wd_tab, long long wd_stride, double *shares, hipStream_t stream)
-{
-    const int W = sd.n_walkers;
-    MargStep mx{};
-    mx.K = K; mx.Q = Q; mx.L = marg_layout(NFP, sd.mass_cap, K, Q);
-    mx.n_chunks_cap = mx.L.n_chunks;
-    mx.n_wd_blocks = st.n_wd > 0 ? (8 * K + 127) / 128 : 0;
-    mx.wsplit = W % 2 == 0 ? 2 : 1;
-    const int csplit = 8 / mx.wsplit, n_chunks = st.mg_pad / 64;
-    const bool split = st.mg_n_pieces > 0;
-    if (split && !shares) return hipErrorInvalidValue;
-    if (st.n_wd > 0 && !wd_tab) return hipErrorInvalidValue;
-    mx.cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
-    mx.tab = tab; mx.wd_tab = wd_tab; mx.wd_stride = wd_stride; mx.shares = shares;
-    const int front = (W + W * 2 * NPOPS * (mx.n_chunks_cap + mx.n_wd_blocks) + 7) / 8 * 8;
-    const int stars = 8 * ((((split ? st.mg_n_pieces : n_chunks) + csplit - 1) / csplit) * (W / mx.wsplit));
-    const int wd = st.n_wd > 0 ? ((st.n_wd + 3) / 4) * W : 0;
-    const size_t lds = b9k_marg_step_lds(NFP, sd.mass_cap);
-    if (lds > B9_MSTEP_LDS_MAX(NFP)) return hipErrorInvalidValue;
-    // this parity's two candidates, as the star roles read them (see MargStepSel)
-    const size_t rows = (size_t)W * NPOPS, c0 = (size_t)sd.set * 2;
-    const IsoHdr *hdr_rd = sd.cand_hdr + c0 * rows;
-    const double *par_rd = sd.cand_par + c0 * W * B9_NPARAM, *tab_rd = tab + c0 * rows * mx.L.total, *wd_rd = wd_tab ? wd_tab + c0 * wd_stride : nullptr;
-    static_assert(B9_MSTEP_LDS_DOUBLES(NFP, 2) >= 4 * B9_TILE_DOUBLES(NFP), "the star role's row tiles borrow the builders' dynamic LDS");
-    if (split) {
-        if (marg_sparse((long long)st.mg_n_pieces * W))
-            hipLaunchKernelGGL((k_marg_step<NFP, NPOPS, true, 2>), dim3(front + stars + wd), dim3(256), lds, stream, pk, st, sd, pr, mx, front, stars,
-                               hdr_rd, par_rd, tab_rd, wd_rd);
-        else
-            hipLaunchKernelGGL((k_marg_step<NFP, NPOPS, true>), dim3(front + stars + wd), dim3(256), lds, stream, pk, st, sd, pr, mx, front, stars,
-                               hdr_rd, par_rd, tab_rd, wd_rd);
-        hipLaunchKernelGGL((k_marg_step_merge<NPOPS>), dim3(n_chunks, W), dim3(64), 0, stream, st, sd, mx);
-    } else {
-        hipLaunchKernelGGL((k_marg_step<NFP, NPOPS, false>), dim3(front + stars + wd), dim3(256), lds, stream, pk, st, sd, pr, mx, front, stars,
-                           hdr_rd, par_rd, tab_rd, wd_rd);
-    }
-    return hipGetLastError();
-}
-
 hipError_t b9k_marg_step(const DevPack &pk, const DevStars &st, const StepDev &sd, const DevPriors &pr, int K, int Q, bool prune,
                          double *tab, double *wd_tab, long long wd_stride, double *shares, hipStream_t stream)
 {
-    const int n_pops = sd.n_pops;
-#define GS_ARGS pk, st, sd, pr, K, Q, prune, tab, wd_tab, wd_stride, shares, stream
-#define GS2(NFP) launch_marg_step<NFP, 2>(GS_ARGS)
-#define GS1(NFP) launch_marg_step<NFP, 1>(GS_ARGS)
-    B9_SWITCH_NFP(GS2, GS1)
-#undef GS1
-#undef GS2
-#undef GS_ARGS
+    return dispatch(pk.nfp, sd.n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        const int W = sd.n_walkers;
+        const bool split = st.mg_n_pieces > 0;
+        const MargGrid g = marg_star_grid(st, W, split);
+        MargStep mx{};
+        mx.K = K; mx.Q = Q; mx.L = marg_layout(NFP, sd.mass_cap, K, Q);
+        mx.n_chunks_cap = mx.L.n_chunks;
+        mx.n_wd_blocks = st.n_wd > 0 ? (8 * K + 127) / 128 : 0;
+        mx.wsplit = g.wsplit;
+        if (split && !shares) return hipErrorInvalidValue;
+        if (st.n_wd > 0 && !wd_tab) return hipErrorInvalidValue;
+        mx.cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
+        mx.tab = tab; mx.wd_tab = wd_tab; mx.wd_stride = wd_stride; mx.shares = shares;
+        const int front = (W + W * 2 * NPOPS * (mx.n_chunks_cap + mx.n_wd_blocks) + 7) / 8 * 8;
+        const int stars = 8 * g.per_xcd;
+        const int wd = st.n_wd > 0 ? ((st.n_wd + 3) / 4) * W : 0;
+        const size_t lds = b9k_marg_step_lds(NFP, sd.mass_cap);
+        if (lds > B9_MSTEP_LDS_MAX(NFP)) return hipErrorInvalidValue;
+        // this parity's two candidates, as the star roles read them (see MargStepSel)
+        const size_t rows = (size_t)W * NPOPS, c0 = (size_t)sd.set * 2;
+        const IsoHdr *hdr_rd = sd.cand_hdr + c0 * rows;
+        const double *par_rd = sd.cand_par + c0 * W * B9_NPARAM, *tab_rd = tab + c0 * rows * mx.L.total, *wd_rd = wd_tab ? wd_tab + c0 * wd_stride : nullptr;
+        static_assert(B9_MSTEP_LDS_DOUBLES(NFP, 2) >= 4 * B9_TILE_DOUBLES(NFP), "the star role's row tiles borrow the builders' dynamic LDS");
+        const auto kern = !split ? k_marg_step<NFP, NPOPS, false>
+                        : marg_sparse((long long)st.mg_n_pieces * W) ? k_marg_step<NFP, NPOPS, true, 2> : k_marg_step<NFP, NPOPS, true>;
+        hipLaunchKernelGGL(kern, dim3(front + stars + wd), dim3(256), lds, stream, pk, st, sd, pr, mx, front, stars, hdr_rd, par_rd, tab_rd, wd_rd);
+        if (split) hipLaunchKernelGGL((k_marg_step_merge<NPOPS>), dim3(st.mg_pad / 64, W), dim3(64), 0, stream, st, sd, mx);
+        return hipGetLastError();
+    });
 }
 
-// dynamic LDS of k_mcmc_step: the hot role's mass columns of both candidates (+ 8: find_bracket's masked over-read), or
-// the heavy role's axes, whichever is larger
+// ---- the fused sampler step (k_mcmc_step) ------------------------------------------------------------------------
+// k_mcmc_step's instance and its dynamic LDS: the hot role's mass columns of both candidates (+ 8: find_bracket's masked
+// over-read), or the heavy role's axes, whichever is larger
 template <int NFP, int NPOPS>
-static size_t mcmc_step_lds(const DevPack &pk, int mass_cap)
+static auto mcmc_step_kernel(const DevPack &pk, int mass_cap)
 {
-    return sizeof(double) * std::max((size_t)2 * NPOPS * mass_cap + 8, heavy_lds_doubles(pk, NPOPS, 2, mass_cap));
-}
-
-template <int NFP, int NPOPS>
-static hipError_t mcmc_step_occupancy(const DevPack &pk, int mass_cap, int *blocks_per_cu)
-{
-    const size_t lds = mcmc_step_lds<NFP, NPOPS>(pk, mass_cap);
-    auto kern = k_mcmc_step<NFP, NPOPS>;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, reinterpret_cast<const void *>(kern), 256, lds);
+    return with_lds(k_mcmc_step<NFP, NPOPS>, sizeof(double) * std::max((size_t)2 * NPOPS * mass_cap + 8, heavy_lds_doubles(pk, NPOPS, 2, mass_cap)));
 }
 
 // Workgroups of the fused step that one CU holds at once for the loaded pack (registers, LDS, wave slots of THIS
 // instantiation): the launch plan sizes its single occupancy round from it instead of assuming a machine.
 hipError_t b9k_mcmc_step_occupancy(const DevPack &pk, int n_pops, int mass_cap, int *blocks_per_cu)
 {
-#define OC2(NFP) mcmc_step_occupancy<NFP, 2>(pk, mass_cap, blocks_per_cu)
-#define OC1(NFP) mcmc_step_occupancy<NFP, 1>(pk, mass_cap, blocks_per_cu)
-    B9_SWITCH_NFP(OC2, OC1)
-#undef OC1
-#undef OC2
-}
-
-template <int NFP, int NPOPS>
-static hipError_t launch_mcmc_step(const DevPack &pk, const DevStars &st, const StepDev &sd, const DevPriors &pr,
-                                   const B9Groups &gr, int heavy_parts, int derive_parts, int derive_order, hipStream_t stream)
-{
-    const size_t lds = mcmc_step_lds<NFP, NPOPS>(pk, sd.mass_cap);
-    auto kern = k_mcmc_step<NFP, NPOPS>;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    const int W = sd.n_walkers;
-    const int hot = 8 * ((gr.n_blocks * NPOPS + 7) / 8) * W;
-    const int derive_first = derive_order >= 0 ? (derive_order == 1 ? 2 : 1) : 0;
-    const int n_derive = W * 2 * NPOPS * derive_parts;
-    const int front = (W * heavy_parts + W + (derive_first ? n_derive : 0) + 7) / 8 * 8;     // heavy, writers, (derivation), pad
-    const int back = (!derive_first && sd.derive_next) ? n_derive : 0;
-    hipLaunchKernelGGL(kern, dim3(front + hot + back), dim3(256), lds, stream, pk, st, sd, pr, gr.group_tiles, gr.n_groups,
-                       gr.groups_per_block, gr.n_blocks, front, hot, heavy_parts, derive_parts, derive_first);
-    return hipGetLastError();
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        const auto k = mcmc_step_kernel<decltype(nfp_c)::value, decltype(npops_c)::value>(pk, mass_cap);
+        if (k.err != hipSuccess) return k.err;
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, reinterpret_cast<const void *>(k.kern), 256, k.lds);
+    });
 }
 
 hipError_t b9k_mcmc_step(const DevPack &pk, const DevStars &st, const StepDev &sd, const DevPriors &pr,
                          const B9Groups &gr, int heavy_parts, int derive_parts, int derive_order, hipStream_t stream)
 {
-    const int n_pops = sd.n_pops;
-#define MS_ARGS pk, st, sd, pr, gr, heavy_parts, derive_parts, derive_order, stream
-#define MS2(NFP) launch_mcmc_step<NFP, 2>(MS_ARGS)
-#define MS1(NFP) launch_mcmc_step<NFP, 1>(MS_ARGS)
-    B9_SWITCH_NFP(MS2, MS1)
-#undef MS1
-#undef MS2
-#undef MS_ARGS
+    return dispatch(pk.nfp, sd.n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        const auto k = mcmc_step_kernel<NFP, NPOPS>(pk, sd.mass_cap);
+        if (k.err != hipSuccess) return k.err;
+        const int W = sd.n_walkers;
+        const int hot = 8 * ((gr.n_blocks * NPOPS + 7) / 8) * W;
+        const int derive_first = derive_order >= 0 ? (derive_order == 1 ? 2 : 1) : 0;
+        const int n_derive = W * 2 * NPOPS * derive_parts;
+        const int front = (W * heavy_parts + W + (derive_first ? n_derive : 0) + 7) / 8 * 8;     // heavy, writers, (derivation), pad
+        const int back = (!derive_first && sd.derive_next) ? n_derive : 0;
+        hipLaunchKernelGGL(k.kern, dim3(front + hot + back), dim3(256), k.lds, stream, pk, st, sd, pr, gr.group_tiles, gr.n_groups,
+                           gr.groups_per_block, gr.n_blocks, front, hot, heavy_parts, derive_parts, derive_first);
+        return hipGetLastError();
+    });
 }
 
 // ---- tree-speculative step (k_mcmc_tree) -------------------------------------------------------------------------
-template <int NFP, int NPOPS>
-static size_t mcmc_tree_lds(const DevPack &pk, int mass_cap)
-{
-    return sizeof(double) * std::max((size_t)NPOPS * mass_cap + 8, heavy_lds_doubles(pk, NPOPS, 1, mass_cap));
-}
+// which of the two builds of b9_mcmc_tree.hip.h a catalogue of n_groups canonical groups uses
+static bool tree_large(int n_groups) { return n_groups > 16 * B9_TREE_KD_SMALL; }
 
 template <int NFP, int NPOPS>
-static hipError_t mcmc_tree_occupancy(const DevPack &pk, int mass_cap, int n_groups, int *blocks_per_cu)
+static auto mcmc_tree_kernel(const DevPack &pk, int mass_cap, int n_groups)
 {
-    const size_t lds = mcmc_tree_lds<NFP, NPOPS>(pk, mass_cap);
-    auto kern = n_groups > 16 * B9_TREE_KD_SMALL ? tree_kd5::k_mcmc_tree<NFP, NPOPS> : tree_kd3::k_mcmc_tree<NFP, NPOPS>;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, reinterpret_cast<const void *>(kern), 256, lds);
+    return with_lds(tree_large(n_groups) ? tree_kd5::k_mcmc_tree<NFP, NPOPS> : tree_kd3::k_mcmc_tree<NFP, NPOPS>,
+                    sizeof(double) * std::max((size_t)NPOPS * mass_cap + 8, heavy_lds_doubles(pk, NPOPS, 1, mass_cap)));
 }
 
 hipError_t b9k_mcmc_tree_occupancy(const DevPack &pk, int n_pops, int mass_cap, int n_groups, int *blocks_per_cu)
 {
-#define OC2(NFP) mcmc_tree_occupancy<NFP, 2>(pk, mass_cap, n_groups, blocks_per_cu)
-#define OC1(NFP) mcmc_tree_occupancy<NFP, 1>(pk, mass_cap, n_groups, blocks_per_cu)
-    B9_SWITCH_NFP(OC2, OC1)
-#undef OC1
-#undef OC2
-}
-
-template <int NFP, int NPOPS>
-static hipError_t launch_mcmc_tree(const DevPack &pk, const DevStars &st, const TreeDev &td, const DevPriors &pr, int group_tiles,
-                                   int derive_parts, hipStream_t stream)
-{
-    const size_t lds = mcmc_tree_lds<NFP, NPOPS>(pk, td.mass_cap);
-    auto kern = td.n_groups > 16 * B9_TREE_KD_SMALL ? tree_kd5::k_mcmc_tree<NFP, NPOPS> : tree_kd3::k_mcmc_tree<NFP, NPOPS>;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    const int W = td.n_walkers, NN = (1 << td.depth) - 1, NO = td.derive_mode == 2 ? 1 : (1 << td.depth);
-    const int writers = W;                                   // (prologue: the step-table workgroups)
-    const int n_derive = td.derive_mode == 0 ? 0 : W * NO * NN * NPOPS * derive_parts;
-    const int heavy = td.levels > 0 ? W * NN * td.heavy_parts : 0;
-    const int front = (writers + n_derive + heavy + 7) / 8 * 8;
-    const int hot = td.levels > 0 ? 8 * ((td.n_groups * NPOPS + 7) / 8) * W * NN : 0;
-    hipLaunchKernelGGL(kern, dim3(front + hot), dim3(256), lds, stream, pk, st, td, pr, group_tiles, front, derive_parts);
-    return hipGetLastError();
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        const auto k = mcmc_tree_kernel<decltype(nfp_c)::value, decltype(npops_c)::value>(pk, mass_cap, n_groups);
+        if (k.err != hipSuccess) return k.err;
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, reinterpret_cast<const void *>(k.kern), 256, k.lds);
+    });
 }
 
 hipError_t b9k_mcmc_tree(const DevPack &pk, const DevStars &st, const TreeDev &td, const DevPriors &pr, int group_tiles,
                          int derive_parts, hipStream_t stream)
 {
-    const int n_pops = td.n_pops;
-#define MT2(NFP) launch_mcmc_tree<NFP, 2>(pk, st, td, pr, group_tiles, derive_parts, stream)
-#define MT1(NFP) launch_mcmc_tree<NFP, 1>(pk, st, td, pr, group_tiles, derive_parts, stream)
-    B9_SWITCH_NFP(MT2, MT1)
-#undef MT1
-#undef MT2
+    return dispatch(pk.nfp, td.n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        const auto k = mcmc_tree_kernel<NFP, NPOPS>(pk, td.mass_cap, td.n_groups);
+        if (k.err != hipSuccess) return k.err;
+        const int W = td.n_walkers, NN = (1 << td.depth) - 1, NO = td.derive_mode == 2 ? 1 : (1 << td.depth);
+        const int writers = W;                                   // (prologue: the step-table workgroups)
+        const int n_derive = td.derive_mode == 0 ? 0 : W * NO * NN * NPOPS * derive_parts;
+        const int heavy = td.levels > 0 ? W * NN * td.heavy_parts : 0;
+        const int front = (writers + n_derive + heavy + 7) / 8 * 8;
+        const int hot = td.levels > 0 ? 8 * ((td.n_groups * NPOPS + 7) / 8) * W * NN : 0;
+        hipLaunchKernelGGL(k.kern, dim3(front + hot), dim3(256), k.lds, stream, pk, st, td, pr, group_tiles, front, derive_parts);
+        return hipGetLastError();
+    });
 }
 
 hipError_t b9k_tree_finish(const TreeDev &td, const DevPriors &pr, hipStream_t stream)
 {
-    if (td.n_groups > 16 * B9_TREE_KD_SMALL) hipLaunchKernelGGL(tree_kd5::k_tree_finish, dim3(td.n_walkers), dim3(256), 0, stream, td, pr);
-    else hipLaunchKernelGGL(tree_kd3::k_tree_finish, dim3(td.n_walkers), dim3(256), 0, stream, td, pr);
+    hipLaunchKernelGGL(tree_large(td.n_groups) ? tree_kd5::k_tree_finish : tree_kd3::k_tree_finish, dim3(td.n_walkers), dim3(256), 0, stream, td, pr);
     return hipGetLastError();
 }
 

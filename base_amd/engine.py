@@ -123,11 +123,12 @@ class Engine:
                                                   cont=False, asynchronous=False))
 
     def mcmc_submit(self, params, logpost, walker_ids, free, chol, seed, step0, n_steps, record=True, cont=False,
-                    asynchronous=True, row_origin=None):
+                    asynchronous=True, row_origin=None, rows_event=False):
         """Enqueue a block (B9_BLOCK_ASYNC) -- with cont=True from the state the previous block left on the device
         (B9_BLOCK_CONTINUE; params / logpost then only give the shapes).  Returns a handle for mcmc_collect; at
         most two handles may be outstanding and they are collected in submission order.  With `row_origin` the
-        handle's "rows" receive the block's per-walker summary rows (b9_mcmc_block::rows)."""
+        handle's "rows" receive the block's per-walker summary rows (b9_mcmc_block::rows); rows_event adds
+        B9_BLOCK_ROWS_EVENT (the block's rows_ready event is recorded behind its last kernel)."""
         params = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, abi.B9_NPARAM).copy()
         W, d = params.shape[0], len(free)
         logpost = np.ascontiguousarray(logpost, dtype=np.float64).copy()
@@ -140,7 +141,7 @@ class Engine:
         blk.chol = keep["chol"].ctypes.data_as(_dp)
         blk.walker_ids = keep["ids"].ctypes.data_as(_ip)
         blk.seed, blk.step0, blk.n_steps = int(seed), int(step0), int(n_steps)
-        blk.flags = (abi.BLOCK_CONTINUE if cont else 0) | (abi.BLOCK_ASYNC if asynchronous else 0)
+        blk.flags = (abi.BLOCK_CONTINUE if cont else 0) | (abi.BLOCK_ASYNC if asynchronous else 0) | (abi.BLOCK_ROWS_EVENT if rows_event else 0)
         blk.params = params.ctypes.data_as(_dp)
         blk.logpost = logpost.ctypes.data_as(_dp)
         blk.samples = keep["samples"].ctypes.data_as(_dp) if record else None

@@ -1,10 +1,10 @@
 """Bit-for-bit comparison of two builds of libbase9hip.so: sampler chains (tree depths 3 / 2 and the one-step launch, one and two
-populations, WD stars) and marginalised per-star values of the shipped library against build/variants/lib_oldsum.so (or any variant
-named in the script) -- used when a change must not move a single bit (e.g. the cross-lane sums on DPP / permlane moves).
-    python tools/build_variant.py oldsum   (on the tree to compare against);   python tools/compare_bits.py   (GPU box)"""
+populations, WD stars) and marginalised per-star values of the shipped library against the variant library named on the command
+line -- used when a change must not move a single bit (e.g. the cross-lane sums on DPP / permlane moves, a host-side refactor).
+    python tools/build_variant.py oldsum   (on the tree to compare against);   python tools/compare_bits.py build/variants/lib_oldsum.so   (GPU box)"""
 import os, sys, subprocess, pickle
 sys.path.insert(0, os.getcwd())
-if len(sys.argv) > 1:
+if len(sys.argv) == 3 and sys.argv[1] == "--dump":      # child: run the cases with the library B9_HIP_LIB selects, pickle the bytes
     import numpy as np
     from base_amd import abi, engine, mcmc, synth
     out = {}
@@ -20,12 +20,15 @@ if len(sys.argv) > 1:
         # marginalised logpost too
         engm = engine.Engine(abi.make_pack(pack_d), abi.make_stars({k: (v[:3000] if hasattr(v, "__len__") and len(v) == ns else v) for k, v in cl.items()}), synth.default_priors(pack_d, truth, npops), abi.make_options(abi.MODE_MARGINALISED, npops, 4, 4))
         out[name + "m"] = engm.logpost(start, perstar=True)[1].tobytes() if True else None
-    pickle.dump(out, open(sys.argv[1], "wb"))
+    pickle.dump(out, open(sys.argv[2], "wb"))
 else:
+    if len(sys.argv) != 2 or not os.path.exists(sys.argv[1]):
+        raise SystemExit("usage: python tools/compare_bits.py <variant libbase9hip.so>")
     env = dict(os.environ)
-    subprocess.check_call([sys.executable, __file__, "/tmp/new.pkl"], env=env)
-    env["B9_HIP_LIB"] = "build/variants/lib_oldsum.so"
-    subprocess.check_call([sys.executable, __file__, "/tmp/old.pkl"], env=env)
+    env.pop("B9_HIP_LIB", None)
+    subprocess.check_call([sys.executable, __file__, "--dump", "/tmp/new.pkl"], env=env)
+    env["B9_HIP_LIB"] = sys.argv[1]
+    subprocess.check_call([sys.executable, __file__, "--dump", "/tmp/old.pkl"], env=env)
     a, b = pickle.load(open("/tmp/new.pkl", "rb")), pickle.load(open("/tmp/old.pkl", "rb"))
     for k in a:
         print(k, "identical" if a[k] == b[k] else "DIFFERENT", a[k][-1] if not k.endswith("m") else "")
