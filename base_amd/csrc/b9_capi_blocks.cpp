@@ -106,6 +106,9 @@ int open_block(b9_ctx *ctx, const b9_mcmc_block *blk, BlockKind kind, void (*lay
     f->want_rows = blk->row_origin != nullptr;
     if (sl.in_flight) return fail(ctx, B9_ERR_STATE, "two blocks are already outstanding: collect one with b9_mcmc_wait first");
     const McmcSlot *pv = ctx->last_slot >= 0 ? &ctx->slot[ctx->last_slot] : nullptr;
+    if (f->cont && !pv && ctx->cont_dropped_by)
+        return fail(ctx, B9_ERR_STATE, std::string("B9_BLOCK_CONTINUE after ") + ctx->cont_dropped_by +
+                    ": the previous block's state belongs to another posterior; start the block from host state");
     if (f->cont && (!pv || pv->W != (int)W || pv->kind != kind))
         return fail(ctx, B9_ERR_STATE, "B9_BLOCK_CONTINUE needs a previous block of this context with the same n_walkers and mode");
     BlockLayout &L = sl.lay;
@@ -163,6 +166,7 @@ int close_block(b9_ctx *ctx, b9_mcmc_block *blk, const BlockFrame &f, int final_
     sl.host_samples = blk->samples != nullptr;
     sl.in_flight = true; sl.owner = blk;
     ctx->last_slot = ctx->next_slot;
+    ctx->cont_dropped_by = nullptr;
     ctx->next_slot ^= 1;
     return (blk->flags & B9_BLOCK_ASYNC) ? B9_OK : collect_block(ctx, sl, blk);
 }
@@ -470,9 +474,9 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk)
     // (the work buffers are sized for the walker count: they must not be re-allocated under an enqueued block)
     for (const auto &sl : ctx->slot)
         if (sl.in_flight && sl.W != W) return fail(ctx, B9_ERR_STATE, "collect the outstanding block(s) before running a block with another number of walkers");
-    const B9Groups plan = make_plan(ctx, W, n_pops);
-    rc = ensure_capacity(ctx, W, n_pops, (size_t)partial_stride(ctx) * W, false);
+    rc = ensure_capacity(ctx, W, n_pops, (size_t)partial_stride(ctx) * W, false);      // (before any plan: the plans key on mass_cap)
     if (rc) return rc;
+    const B9Groups plan = make_plan(ctx, W, n_pops);
     if (ctx->opt.mode == B9_MODE_GIVEN_MASS && !ctx->two_launch_steps) {
         const TreePlan tp = make_tree_plan(ctx, W, n_pops);
         return tp.depth >= 2 ? run_block_tree(ctx, blk, tp) : run_block_fused(ctx, blk, false);

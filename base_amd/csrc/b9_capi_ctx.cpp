@@ -207,6 +207,7 @@ int b9_set_priors(b9_ctx *ctx, const b9_priors *p)
     for (int k = 0; k < 12; ++k) { ctx->pr.mean[k] = p->mean[k]; ctx->pr.var[k] = p->var[k]; }
     ctx->pr.log_age_min = p->log_age_min; ctx->pr.log_age_max = p->log_age_max;
     ctx->marg_plan_ok = false;         // (the marginalised catalogue plan is measured at the prior means)
+    drop_continuation(ctx, "b9_set_priors");
     return B9_OK;
 }
 
@@ -235,6 +236,7 @@ int b9_set_options(b9_ctx *ctx, const b9_options *o)
     if (o->n_pops != 1 && o->n_pops != 2) return fail(ctx, B9_ERR_INVALID, "n_pops must be 1 or 2");
     ctx->opt = *o;
     ctx->marg_plan_ok = false;
+    drop_continuation(ctx, "b9_set_options");
     return B9_OK;
 }
 

@@ -61,9 +61,11 @@ int launch_logpost(b9_ctx *ctx, double *d_params, int32_t n_walkers, double *d_l
                           unsigned long long *done_flag = nullptr, unsigned long long done_seq = 0)
 {
     const int n_pops = ctx->opt.n_pops;
-    const B9Groups plan = make_plan(ctx, n_walkers, n_pops);
+    // (the buffers first: the canonical tile groups key on mass_cap, which ensure_capacity brings up to the loaded pack -- a
+    //  plan made before it would follow whatever pack the context held before, or none)
     int rc = ensure_capacity(ctx, n_walkers, n_pops, (size_t)partial_stride(ctx) * n_walkers, false);
     if (rc) return rc;
+    const B9Groups plan = make_plan(ctx, n_walkers, n_pops);
     Bufs bf = buffer_set(ctx, 0);
     bf.params = d_params;
     const McmcDev off{};

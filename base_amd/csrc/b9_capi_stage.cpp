@@ -378,6 +378,7 @@ int b9_load_pack(b9_ctx *ctx, const b9_pack *p)
     ctx->pk = d;
     ctx->have_pack = true;
     if (ctx->have_stars) ctx->stars_dirty = true;
+    drop_continuation(ctx, "b9_load_pack");
     return B9_OK;
 }
 
@@ -424,6 +425,7 @@ int b9_load_stars(b9_ctx *ctx, const b9_stars *s)
     ctx->n_wd_stage = (int)std::count(h.stage.begin(), h.stage.end(), (int32_t)B9_STAGE_WD);      // (b9_n_wd_stars answers before the stars are staged)
     ctx->have_stars = true;
     ctx->stars_dirty = true;
+    drop_continuation(ctx, "b9_load_stars");
     return B9_OK;
 }
 

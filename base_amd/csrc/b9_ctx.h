@@ -102,6 +102,7 @@ struct b9_ctx {
         bool host_samples = false;   // the caller asked for the chain record (else it only exists on the device, for the rows)
     } slot[2];
     int next_slot = 0, last_slot = -1;
+    const char *cont_dropped_by = nullptr;   // the configuration call that dropped last_slot (drop_continuation); open_block names it
     double *h_lp = nullptr, *h_lp_dev = nullptr;   // b9_logpost: 8 log-posteriors + 8 completion words in mapped pinned host memory (host / device view)
     unsigned long long lp_seq = 0;                 // ... and the number of the call the completion words announce
 
@@ -176,6 +177,14 @@ inline bool block_outstanding(const b9_ctx *ctx)
     return false;
 }
 constexpr const char *kBlockOutstanding = "a sampler block is outstanding: collect it with b9_mcmc_wait first (it owns the context's work buffers)";
+
+// A successful b9_load_pack / b9_load_stars / b9_set_priors / b9_set_options changes the posterior: the previous block's final
+// state carries a log-posterior of the old one, so no B9_BLOCK_CONTINUE block may start from it (include/base9_hip.h)
+inline void drop_continuation(b9_ctx *ctx, const char *call)
+{
+    ctx->last_slot = -1;
+    ctx->cont_dropped_by = call;
+}
 
 inline void free_all(std::vector<void *> &v)
 {

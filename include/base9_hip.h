@@ -203,6 +203,13 @@ void        b9_ctx_destroy(b9_ctx *ctx);
 const char *b9_last_error(const b9_ctx *ctx);   /* ctx may be NULL: last create error      */
 
 /* ---- staging (cold; once per run) ---------------------------------------------------- */
+/* A staging or configuration call that is REFUSED for its arguments (B9_ERR_INVALID, B9_ERR_CAPACITY: a pack of more than
+ * 16 filters, non-finite photometry in a filter in use, n_pops = 3, ...) changes nothing: both loaders validate the whole
+ * table before they touch the context, so the next evaluating call returns the bits of the configuration in force before the
+ * refused call (tests/test_gpu_history.py pins this).  Only a HIP failure in the middle of an upload (B9_ERR_HIP) leaves the
+ * context without a pack; evaluating calls then return B9_ERR_STATE until a valid b9_load_pack.
+ * A pack may be reloaded under loaded stars when it has the same number of filters: the stars are staged again against it
+ * at the next evaluating call.  With another filter count every call that needs the stars is B9_ERR_INVALID until matching stars are loaded. */
 /* Replaces [RECALL] Model construction: copies the pack's tables to HBM.                   */
 int b9_load_pack(b9_ctx *ctx, const b9_pack *pack);
 /* Replaces [RECALL] reading the .phot into vector<StellarSystem>: SoA + staged to HBM.     */
@@ -283,7 +290,11 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk);
  * blocks until it has run and fills params / logpost / samples / lps / n_accept.  B9_BLOCK_CONTINUE: the block
  * starts from the state the PREVIOUS block of this context left on the device (its params / logpost inputs are
  * ignored; n_walkers must match), so it can be enqueued before that block has finished.  At most two blocks
- * may be outstanding; they are collected in the order they were enqueued.  While a block is outstanding it owns the
+ * may be outstanding; they are collected in the order they were enqueued.  A successful b9_load_pack, b9_load_stars,
+ * b9_set_priors or b9_set_options changes the posterior: the previous block's state carries a log-posterior of the old
+ * one, so the next B9_BLOCK_CONTINUE block returns B9_ERR_STATE (the message names the call that intervened) and the chain
+ * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags and b9_sample_wd_mass (buffers of
+ * their own) between continued blocks are allowed.  While a block is outstanding it owns the
  * context's work buffers: b9_logpost / b9_sample_mass / b9_derive_isochrone, the staging calls, b9_set_options and a block
  * with another n_walkers return B9_ERR_STATE until it has been collected.  A driver that adapts the proposal
  * from block b-1 while block b runs keeps the GPU's queue non-empty: enqueue b+1 (CONTINUE | ASYNC), wait(b), ...
