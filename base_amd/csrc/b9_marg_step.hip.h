@@ -74,7 +74,11 @@ __device__ __forceinline__ IsoHdr marg_header(const DevPack &pk, const double *s
 }
 
 // Table builder: chunk c of the node table of (walker w, candidate cand, population pop) of step t+1 -- k_marg_table's
-// rows, boxes and nb, bit for bit.  Chunk 0 also publishes the candidate's header (with the AGB-tip mass) and, for
+// table.  The primary's decomposition and the nb block are k_marg_table's own functions (marg_primary, marg_store_nb); the
+// companion bracket, the row body and the boxes are restated here and must give k_marg_table's bits (min / max are exact, so
+// the two reductions' different spelling is free; tests/test_gpu_marg.py crosses every instance).  They stay restated
+// because this role is compiled inside k_marg_step: each of them, cut into a shared function, changed that kernel's register
+// allocation (docs/LABNOTES.md section 16).  Chunk 0 also publishes the candidate's header (with the AGB-tip mass) and, for
 // population 0, its parameter row.
 //
 // What of the candidate's isochrone a chunk needs is derived into LDS TILES, each value once: the mass column (every
@@ -146,15 +150,10 @@ __device__ __forceinline__ void marg_build_table(const DevPack &pk, const StepDe
     double *out = mx.tab + (cset * rows + wp) * mx.L.total;
     const MargLayout &L = mx.L;
     const int node = c * 64 + lane, sub = lane >> 4, i16 = lane & 15, u = c * 4 + sub;
-    // the primary
-    bool ok = node < n_nodes;
-    const int e = ok ? node / K : e0, s = node - e * K;
-    const double a = s_mass[e], d = s_mass[e + 1] - a;
-    ok = ok && d > 0.0;
-    const double dM = d / K;
-    const double m1 = fma((double)s, dM, a);
-    const double t1 = ok ? (m1 - a) / d : 0.0;
-    const double *const pr0 = s_prim + (size_t)(e - e0) * NFP;           // the primary's two rows
+    const MargPrimary pri = marg_primary(s_mass, node, n_nodes, K, e0);
+    const bool ok = pri.ok;
+    const double m1 = pri.m1, t1 = pri.t1;
+    const double *const pr0 = s_prim + (size_t)(pri.e - e0) * NFP;       // the primary's two rows
     for (int j = jl; j < Q; j += 4) {
         double *row = out + L.o_rows + (((size_t)u * Q + j) * 16 + i16) * NFP;
         int lo2 = 0; double t2 = 0.0;
@@ -214,16 +213,7 @@ __device__ __forceinline__ void marg_build_table(const DevPack &pk, const StepDe
         }
     }
     HSTAMP(4);
-    if (jl == 0) {                // nb = -2 log(prior(m1) dM / Q) of every node, and its minima
-        const double nb = ok ? -2.0 * (log_prior_mass_dev(pk.log_mass_norm, m1) + log_pos(dM / Q)) : __builtin_inf();
-        out[L.o_nb + node] = nb;
-        double mn = nb;
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) mn = __builtin_fmin(mn, __shfl_xor(mn, o, 64));
-        if (i16 == 0) out[L.o_nbmin16 + u] = mn;
-        mn = __builtin_fmin(mn, __shfl_xor(mn, 16, 64)); mn = __builtin_fmin(mn, __shfl_xor(mn, 32, 64));
-        if (lane == 0) out[L.o_nbmin64 + c] = mn;
-    }
+    if (jl == 0) marg_store_nb(pk, out, L, c, lane, Q, ok, m1, pri.dM);
     __syncthreads();
     if (tid < NFP) {
         double lo = s_box[0][0][tid], hi = s_box[0][1][tid];
@@ -235,7 +225,8 @@ __device__ __forceinline__ void marg_build_table(const DevPack &pk, const StepDe
 
 // WD-table builder: k_marg_wd_table's rows for (walker w, candidate cand, population pop), mass steps
 // 1 + (blk * 2 + wave / 2) * 64 + lane, atmosphere type = wave & 1.  The WD chain needs the candidate isochrone's header
-// only (its AGB-tip mass and grid cell): derived here, nothing is read from another workgroup of the launch.
+// only (its AGB-tip mass and grid cell): derived here, nothing is read from another workgroup of the launch.  The node body
+// restates k_marg_wd_table's (as one shared function it changed k_marg_step: docs/LABNOTES.md section 16).
 template <int NFP>
 __device__ __forceinline__ void marg_build_wd_table(const DevPack &pk, const StepDev &sd, const MargStep &mx, int w, int cand, int pop, int blk)
 {
@@ -251,18 +242,12 @@ __device__ __forceinline__ void marg_build_wd_table(const DevPack &pk, const Ste
     const IsoHdr h = marg_header(pk, s_par, pop, sd.mass_cap, cr);
     if (!h.valid) return;
     const int ny = pk.n_y > 1 ? 2 : 1;
-    IsoView<NFP> is;
-    is.n = h.n; is.tip = corner_interp<true>(pk, cr, h, ny, h.n - 1, 0); is.i_feh = h.i_feh; is.i_y = h.i_y; is.t_feh = h.t_feh; is.t_y = h.t_y;
-    is.mass = nullptr; is.mags = nullptr;                               // (every node lies above the tip: the WD branch never reads them)
+    IsoView<NFP> is = iso_view_of<NFP>(h, nullptr, nullptr);           // (every node lies above the tip: the WD branch never reads them)
+    is.tip = corner_interp<true>(pk, cr, h, ny, h.n - 1, 0);
     const int j = 1 + (blk * 2 + (wave >> 1)) * 64 + lane;
     const double dM = (pk.m_wd_up - is.tip) / steps;
     if (!(dM > 0.0) || j > steps) return;
-    WdAxes ax;
-    ax.log_age = pk.log_age;
-    for (int df = 0; df < 2; ++df) for (int dy = 0; dy < 2; ++dy)
-        ax.tips[df * 2 + dy] = pk.tips + (size_t)((is.i_feh + df) * pk.n_y + (is.i_y + (dy < ny ? dy : 0))) * pk.n_age;
-    ax.wc_log_age_lds = nullptr; ax.wc_track = pk.wc_track; ax.wc_mass = pk.wc_mass; ax.wc_carb = pk.wc_carb;
-    ax.at_log_teff = pk.at_log_teff; ax.at_logg = pk.at_logg;
+    const WdAxes ax = wd_axes_global(pk, is.i_feh, is.i_y);
     const double m1 = is.tip + dM * j, mod = s_par[B9_P_MOD], av = s_par[B9_P_ABS];
     double p[NFP];
     star_mags<NFP>(pk, ax, is, s_par, m1, type, p);

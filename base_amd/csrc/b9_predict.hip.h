@@ -5,7 +5,7 @@
 // Predicted apparent magnitudes and stages of n stellar systems at ONE parameter row whose isochrone(s) k_derive_iso_rows
 // has derived (hdr / iso_data: one per population).  One lane per system, a grid-stride loop over the systems; every
 // workgroup first stages the derived isochrones' mass columns and magnitude rows in LDS (the MS/RGB lookup of every lane
-// searches them), the WD branch reads its axes from L2 (WdAxes as k_marg_wd_table sets them up).  A system's magnitudes are
+// searches them), the WD branch reads its axes from L2 (wd_axes_global).  A system's magnitudes are
 // formed by chi2_system's device functions and expressions -- star_mags of the primary, the flux combination with the
 // secondary at q m1 when q > 0, then + (mod + (A_f / A_V - 1) A_V) -- except that a filter in which NEITHER component
 // gives flux stays exactly B9_MAG_NOFLUX.  Nothing depends on the lane, the workgroup or the launch's other systems.
@@ -42,17 +42,8 @@ __global__ __launch_bounds__(256) void k_predict_mags(DevPack pk, const IsoHdr *
             out_stage[i] = B9_STAGE_DNE;
             continue;
         }
-        IsoView<NFP> iso;
-        iso.mass = s_iso + k * per_pop; iso.mags = iso.mass + mass_cap;
-        iso.n = h.n; iso.tip = h.agb_tip;
-        iso.i_feh = h.i_feh; iso.i_y = h.i_y; iso.t_feh = h.t_feh; iso.t_y = h.t_y;
-        WdAxes ax;
-        ax.log_age = pk.log_age;
-        const int ny = pk.n_y > 1 ? 2 : 1;
-        for (int df = 0; df < 2; ++df) for (int dy = 0; dy < 2; ++dy)
-            ax.tips[df * 2 + dy] = pk.tips + (size_t)((h.i_feh + df) * pk.n_y + (h.i_y + (dy < ny ? dy : 0))) * pk.n_age;
-        ax.wc_log_age_lds = nullptr; ax.wc_track = pk.wc_track; ax.wc_mass = pk.wc_mass; ax.wc_carb = pk.wc_carb;
-        ax.at_log_teff = pk.at_log_teff; ax.at_logg = pk.at_logg;
+        const IsoView<NFP> iso = iso_view_of<NFP>(h, s_iso + k * per_pop, s_iso + k * per_pop + mass_cap);
+        const WdAxes ax = wd_axes_global(pk, h.i_feh, h.i_y);
         const double m1 = mass1[i], q = mass_ratio[i];
         const int wt = wd_type ? wd_type[i] : 0;
         double p1[NFP];

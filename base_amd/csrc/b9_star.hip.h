@@ -15,6 +15,16 @@ struct IsoView {
     double t_feh, t_y;
 };
 
+// the view of the isochrone with header h (mass column / magnitude rows wherever the caller keeps them)
+template <int NFP>
+__device__ __forceinline__ IsoView<NFP> iso_view_of(const IsoHdr &h, const double *mass, const double *mags)
+{
+    IsoView<NFP> is;
+    is.n = h.n; is.tip = h.agb_tip; is.i_feh = h.i_feh; is.i_y = h.i_y; is.t_feh = h.t_feh; is.t_y = h.t_y;
+    is.mass = mass; is.mags = mags;
+    return is;
+}
+
 template <int NFP>
 __device__ __forceinline__ void fill(double (&out)[NFP], double v)
 {
@@ -182,6 +192,19 @@ struct WdAxes {
     const double *wc_log_age_lds; // LDS copy of the cooling tracks' concatenated age axes, or null (then pk.wc_log_age, in L2, is searched)
     const double *wc_track;       // per track: (points | first point << 32) packed in the bits of a double (DevPack::wc_track, or its LDS copy)
 };
+
+// the axes where the pack keeps them, in global memory (L2), for the grid cell (i_feh, i_y): the roles without an LDS copy
+__device__ __forceinline__ WdAxes wd_axes_global(const DevPack &pk, int i_feh, int i_y)
+{
+    WdAxes ax;
+    ax.log_age = pk.log_age;
+    const int ny = pk.n_y > 1 ? 2 : 1;
+    for (int df = 0; df < 2; ++df) for (int dy = 0; dy < 2; ++dy)
+        ax.tips[df * 2 + dy] = pk.tips + (size_t)((i_feh + df) * pk.n_y + (i_y + (dy < ny ? dy : 0))) * pk.n_age;
+    ax.wc_log_age_lds = nullptr; ax.wc_track = pk.wc_track; ax.wc_mass = pk.wc_mass; ax.wc_carb = pk.wc_carb;
+    ax.at_log_teff = pk.at_log_teff; ax.at_logg = pk.at_logg;
+    return ax;
+}
 
 __device__ inline double prec_log_age_corner(const DevPack &pk, const double *tips, const double *log_age, double m)
 {

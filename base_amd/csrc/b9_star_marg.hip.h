@@ -401,6 +401,22 @@ struct MargSelPlain {
 #endif
 #define B9_TILE_OCC(NFP, NPOPS, TILE) (((NFP) >= 16 || (TILE) == 2) ? 4 : ((NPOPS) == 2 ? B9_TILE_OCC_P2 : B9_TILE_OCC_DENSE))
 #define B9_TILE_UNROLL(NFP, NPOPS, TILE) (((NFP) >= 16 || (TILE) == 2) ? 4 : ((NPOPS) == 2 ? B9_TILE_UNROLL_P2 : B9_TILE_UNROLL_DENSE))
+
+// ---- finishing a star (every marginalised kernel) ----
+// A star finished from its per-population cluster terms ll (the mass-prior constant included): l = the populations mixed by
+// lambda (par: the walker's parameter row, read for two populations only), v = log(e^la + e^l) with la the field-star term.
+// The one statement of it for every marginalised kernel: k_star_marg's last wave, k_marg_merge, k_star_marg_wd, k_wd_sample.
+struct StarFinish { double l, v; };
+template <int NPOPS>
+__device__ __forceinline__ StarFinish finish_star(const double (&ll)[NPOPS], const double *par, double la)
+{
+    StarFinish s;
+    s.l = ll[0];
+    if (NPOPS == 2) { const double lam = par[B9_P_LAMBDA]; s.l = logaddexp(log(lam) + ll[0], log1p(-lam) + ll[NPOPS - 1]); }
+    s.v = logaddexp(la, s.l);
+    return s;
+}
+
 template <int NFP, int NPOPS, bool SAMPLE, bool SPLIT, bool COST, int TILE, class Select>
 __device__ __forceinline__ void star_marg_body(const DevPack &pk, const DevStars &st, int block_id, double *tile_lds,
                  const double *__restrict__ iso_data, long long iso_stride, int mass_cap,
@@ -648,9 +664,9 @@ __device__ __forceinline__ void star_marg_body(const DevPack &pk, const DevStars
     if (SPLIT) return;
     double v = 0.0;
     if (!dead) {
-        double l = ll[0];
-        if (NPOPS == 2) { const double lam = par[B9_P_LAMBDA]; l = logaddexp(log(lam) + ll[0], log1p(-lam) + ll[NPOPS - 1]); }
-        v = logaddexp(la, l);
+        const StarFinish fin = finish_star<NPOPS>(ll, par, la);
+        const double l = fin.l;
+        v = fin.v;
         if (perstar) perstar[(size_t)w * st.n + orig] = v;
         if (SAMPLE) {
 #pragma unroll
@@ -720,9 +736,7 @@ __device__ __forceinline__ void marg_merge_body(const DevStars &st, const IsoHdr
     }
     double v = 0.0;
     if (orig >= 0) {
-        double l = ll[0];
-        if (NPOPS == 2) { const double lam = params[(size_t)w * B9_NPARAM + B9_P_LAMBDA]; l = logaddexp(log(lam) + ll[0], log1p(-lam) + ll[NPOPS - 1]); }
-        v = logaddexp(la, l);
+        v = finish_star<NPOPS>(ll, params + (size_t)w * B9_NPARAM, la).v;
         if (perstar) perstar[(size_t)w * st.n + orig] = v;
     }
     const double tot = wave_sum(v);
@@ -744,8 +758,40 @@ __global__ __launch_bounds__(64) void k_marg_merge(DevStars st, const IsoHdr *__
 // system's combined magnitude per filter and -- so that the star loop has nothing left to add -- modulus and absorption.
 // Then the boxes: minimum / maximum over the 16 rows of every (sub-chunk, mass ratio) by shuffles inside a 16-lane
 // row, over the chunk through LDS.  Rows of nodes that do not exist (past the isochrone's end, empty EEP interval) hold
-// zeros, carry nb = +inf and are left out of the boxes.
+// zeros, carry nb = +inf and are left out of the boxes.  marg_primary and marg_store_nb are shared with the fused step's
+// builder (marg_build_table, b9_marg_step.hip.h), which writes the same table from rows it interpolates itself.
 // ------------------------------------------------------------------------------------------
+// the primary of `node`: EEP interval e (e_none for a node past the isochrone's end), mass m1, its step dM and its weight t1
+// between the interval's two rows; ok: the node exists and its interval is not empty.  (s_mass: the mass column, in LDS)
+struct MargPrimary { bool ok; int e; double dM, m1, t1; };
+__device__ __forceinline__ MargPrimary marg_primary(const double *s_mass, int node, int n_nodes, int K, int e_none)
+{
+    MargPrimary p;
+    p.ok = node < n_nodes;
+    p.e = p.ok ? node / K : e_none;
+    const int s = node - p.e * K;
+    const double a = s_mass[p.e], d = s_mass[p.e + 1] - a;
+    p.ok = p.ok && d > 0.0;
+    p.dM = d / K;
+    p.m1 = fma((double)s, p.dM, a);
+    p.t1 = p.ok ? (p.m1 - a) / d : 0.0;
+    return p;
+}
+
+// nb = -2 log(prior(m1) dM / Q) of every node of chunk c (one wave: lane = node), and its minima over 16 and 64 nodes
+__device__ __forceinline__ void marg_store_nb(const DevPack &pk, double *out, const MargLayout &L, int c, int lane, int Q, bool ok, double m1, double dM)
+{
+    const int node = c * 64 + lane, u = c * 4 + (lane >> 4);
+    const double nb = ok ? -2.0 * (log_prior_mass_dev(pk.log_mass_norm, m1) + log_pos(dM / Q)) : __builtin_inf();
+    out[L.o_nb + node] = nb;
+    double mn = nb;
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) mn = __builtin_fmin(mn, __shfl_xor(mn, o, 64));
+    if ((lane & 15) == 0) out[L.o_nbmin16 + u] = mn;
+    mn = __builtin_fmin(mn, __shfl_xor(mn, 16, 64)); mn = __builtin_fmin(mn, __shfl_xor(mn, 32, 64));
+    if (lane == 0) out[L.o_nbmin64 + c] = mn;
+}
+
 template <int NFP>
 __global__ __launch_bounds__(256) void k_marg_table(DevPack pk, const IsoHdr *__restrict__ hdr, const double *__restrict__ iso_data, long long iso_stride,
                                                     int mass_cap, int n_pops, const double *__restrict__ params, int K, int Q,
@@ -767,15 +813,10 @@ __global__ __launch_bounds__(256) void k_marg_table(DevPack pk, const IsoHdr *__
     const double mod = par[B9_P_MOD], av = par[B9_P_ABS];
     double *out = tab + (size_t)wp * L.total;
     const int node = c * 64 + lane, sub = lane >> 4, i16 = lane & 15, u = c * 4 + sub;
-    // the primary
-    bool ok = node < n_nodes;
-    const int e = ok ? node / K : 0, s = node - e * K;
-    const double a = s_mass[e], d = s_mass[e + 1] - a;
-    ok = ok && d > 0.0;
-    const double dM = d / K;
-    const double m1 = fma((double)s, dM, a);
-    const double t1 = ok ? (m1 - a) / d : 0.0;
-    const double *r0 = g_mags + (size_t)e * NFP;
+    const MargPrimary pri = marg_primary(s_mass, node, n_nodes, K, 0);
+    const bool ok = pri.ok;
+    const double m1 = pri.m1, t1 = pri.t1;
+    const double *r0 = g_mags + (size_t)pri.e * NFP;
     double p1[NFP];
 #pragma unroll
     for (int f = 0; f < NFP; ++f) p1[f] = lerp(r0[f], r0[NFP + f], t1);
@@ -825,16 +866,7 @@ __global__ __launch_bounds__(256) void k_marg_table(DevPack pk, const IsoHdr *__
         lo = __builtin_fmin(lo, __shfl_xor(lo, 32, 64)); hi = __builtin_fmax(hi, __shfl_xor(hi, 32, 64));
         if (lane == 0) { s_box[(jl * 2 + 0) * NFP + f] = lo; s_box[(jl * 2 + 1) * NFP + f] = hi; }
     }
-    if (jl == 0) {                // nb = -2 log(prior(m1) dM / Q) of every node, and its minima
-        const double nb = ok ? -2.0 * (log_prior_mass_dev(pk.log_mass_norm, m1) + log_pos(dM / Q)) : __builtin_inf();
-        out[L.o_nb + node] = nb;
-        double mn = nb;
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) mn = __builtin_fmin(mn, __shfl_xor(mn, o, 64));
-        if (i16 == 0) out[L.o_nbmin16 + u] = mn;
-        mn = __builtin_fmin(mn, __shfl_xor(mn, 16, 64)); mn = __builtin_fmin(mn, __shfl_xor(mn, 32, 64));
-        if (lane == 0) out[L.o_nbmin64 + c] = mn;
-    }
+    if (jl == 0) marg_store_nb(pk, out, L, c, lane, Q, ok, m1, pri.dM);
     __syncthreads();
     if (tid < NFP) {
         double lo = s_box[tid], hi = s_box[NFP + tid];
@@ -881,19 +913,12 @@ __global__ __launch_bounds__(128) void k_marg_wd_table(DevPack pk, const IsoHdr 
     const int j = 1 + blockIdx.y * 64 + (threadIdx.x & 63);
     const IsoHdr h = hdr[wp];
     if (!h.valid) return;
-    IsoView<NFP> is;
-    is.n = h.n; is.tip = h.agb_tip; is.i_feh = h.i_feh; is.i_y = h.i_y; is.t_feh = h.t_feh; is.t_y = h.t_y;
-    is.mass = iso_data + (size_t)wp * iso_stride; is.mags = is.mass + mass_cap;
+    const double *g = iso_data + (size_t)wp * iso_stride;
+    const IsoView<NFP> is = iso_view_of<NFP>(h, g, g + mass_cap);
     const double *par = params + (size_t)w * B9_NPARAM;
     const double dM = (pk.m_wd_up - is.tip) / steps;
     if (!(dM > 0.0) || j > steps) return;
-    WdAxes ax;
-    ax.log_age = pk.log_age;
-    const int ny = pk.n_y > 1 ? 2 : 1;
-    for (int df = 0; df < 2; ++df) for (int dy = 0; dy < 2; ++dy)
-        ax.tips[df * 2 + dy] = pk.tips + (size_t)((is.i_feh + df) * pk.n_y + (is.i_y + (dy < ny ? dy : 0))) * pk.n_age;
-    ax.wc_log_age_lds = nullptr; ax.wc_track = pk.wc_track; ax.wc_mass = pk.wc_mass; ax.wc_carb = pk.wc_carb;
-    ax.at_log_teff = pk.at_log_teff; ax.at_logg = pk.at_logg;
+    const WdAxes ax = wd_axes_global(pk, is.i_feh, is.i_y);
     const double m1 = is.tip + dM * j, mod = par[B9_P_MOD], av = par[B9_P_ABS];
     double p[NFP];
     star_mags<NFP>(pk, ax, is, par, m1, type, p);
@@ -986,9 +1011,8 @@ __device__ __forceinline__ void star_marg_wd_body(const DevPack &pk, const DevSt
         }
     }
     if (lane == 0) {
-        double l = ll[0];
-        if (NPOPS == 2) { const double lam = par[B9_P_LAMBDA]; l = logaddexp(log(lam) + ll[0], log1p(-lam) + ll[NPOPS - 1]); }
-        const double v = logaddexp(la, l);
+        const StarFinish fin = finish_star<NPOPS>(ll, par, la);
+        const double l = fin.l, v = fin.v;
         v_out = v;
         if (perstar) perstar[(size_t)w * st.n + orig] = v;
         if (SAMPLE) {

@@ -37,13 +37,7 @@ __global__ __launch_bounds__(128) void k_wd_node_table(DevPack pk, const IsoHdr 
     const double *par = params + (size_t)w * B9_NPARAM;
     const double dM = (pk.m_wd_up - h.agb_tip) / n_nodes;
     if (!(dM > 0.0) || j > n_nodes) return;
-    WdAxes ax;
-    ax.log_age = pk.log_age;
-    const int ny = pk.n_y > 1 ? 2 : 1;
-    for (int df = 0; df < 2; ++df) for (int dy = 0; dy < 2; ++dy)
-        ax.tips[df * 2 + dy] = pk.tips + (size_t)((h.i_feh + df) * pk.n_y + (h.i_y + (dy < ny ? dy : 0))) * pk.n_age;
-    ax.wc_log_age_lds = nullptr; ax.wc_track = pk.wc_track; ax.wc_mass = pk.wc_mass; ax.wc_carb = pk.wc_carb;
-    ax.at_log_teff = pk.at_log_teff; ax.at_logg = pk.at_logg;
+    const WdAxes ax = wd_axes_global(pk, h.i_feh, h.i_y);
     const double m1 = h.agb_tip + dM * (double)j, mod = par[B9_P_MOD], av = par[B9_P_ABS];
     const WdTable<double> t = wd_table_view(tab, NFP, n_wp, n_nodes);
     // star_mags' branches: rounding can put the last node a bit above M_wd_up (no flux, as everywhere in this code base) and,
@@ -53,10 +47,8 @@ __global__ __launch_bounds__(128) void k_wd_node_table(DevPack pk, const IsoHdr 
     if (is_wd) c = wd_chain(pk, ax, h.t_feh, h.t_y, par, m1);
     double p[NFP];
     if (!is_wd && m1 <= h.agb_tip) {
-        IsoView<NFP> is;
-        is.n = h.n; is.tip = h.agb_tip; is.i_feh = h.i_feh; is.i_y = h.i_y; is.t_feh = h.t_feh; is.t_y = h.t_y;
-        is.mass = iso_data + (size_t)wp * iso_stride; is.mags = is.mass + mass_cap;
-        msrgb_mags<NFP>(is, m1, p);
+        const double *g = iso_data + (size_t)wp * iso_stride;
+        msrgb_mags<NFP>(iso_view_of<NFP>(h, g, g + mass_cap), m1, p);
     } else if (c.status == 2) {            // the atmosphere lookup wd_mags does, on the same wd_chain values
         wd_atmosphere<NFP>(pk, ax, c, type, p);
     } else {
@@ -157,9 +149,8 @@ __global__ __launch_bounds__(64) void k_wd_sample(DevPack pk, DevStars st, const
         ll[kp] = (acc.mx == NEG_INF) ? NEG_INF : c0m + (acc.mx + log(acc.sm));
     }
     if (!live) return;
-    double l = ll[0];
-    if (NPOPS == 2) { const double lam = par[B9_P_LAMBDA]; l = logaddexp(log(lam) + ll[0], log1p(-lam) + ll[NPOPS - 1]); }
-    const double v = logaddexp(la, l);
+    const StarFinish fin = finish_star<NPOPS>(ll, par, la);
+    const double l = fin.l, v = fin.v;
     const size_t o = (size_t)r * st.n_wd + out.wd_rank[orig];
     const bool any = best_key != NEG_INF;
     out.zams[o] = any ? best_mass : 0.0;

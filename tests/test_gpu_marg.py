@@ -151,19 +151,16 @@ def test_marginalised_mode_is_bit_reproducible(name, walkers):
     eng.close()
 
 
-@pytest.mark.parametrize("n_pops,wd_frac,n_stars,walkers", [(1, 0.0, 9000, 3), (1, 0.08, 2500, 2), (2, 0.05, 3000, 2), (1, 0.0, 40000, 2)])
-def test_fused_marginalised_step_equals_the_two_launch_step(n_pops, wd_frac, n_stars, walkers):
-    """k_marg_step (one launch per step: decision + stars + both candidate node tables of the next step, built by workgroups
-    that derive their isochrone tiles themselves) against the two-launch step it replaced (k_derive_iso, k_marg_table,
-    k_star_marg [, k_marg_merge, k_marg_wd_table, k_star_marg_wd]; b9_tuning.two_launch_steps): the same chain -- same
-    proposals (bit for bit), the same decisions, log-posteriors equal to the rounding of the two decision sums' orders.
-    Covers split catalogues (pieces + merge), WD-stage stars, two populations with a helium axis (eight corner isochrones per
-    table value), an unsplit catalogue, continued blocks, and proposals that leave the grid (a step scale that reaches the
-    grid's edge in log age)."""
+def _fused_against_two_launch(n_filt, n_pops, wd_frac, n_stars, walkers, K, Q, small=False):
+    """One chain of 40 + 25 steps by the fused step and by the two-launch step: the same chain."""
     from base_amd import engine, mcmc
-    pack_d, cl, pack, stars, priors, _ = build_problem("parsec", 8, n_stars=n_stars, wd_frac=wd_frac, n_y=3 if n_pops == 2 else 1,
-                                                       n_pops=n_pops, small=False, seed=21)
-    eng = engine.Engine(pack, stars, priors, abi.make_options(abi.MODE_MARGINALISED, n_pops, 3, 3))
+    pack_d, cl, pack, stars, priors, _ = build_problem("parsec", n_filt, n_stars=n_stars, wd_frac=wd_frac, n_y=3 if n_pops == 2 else 1,
+                                                       n_pops=n_pops, small=small, seed=21)
+    eng = engine.Engine(pack, stars, priors, abi.make_options(abi.MODE_MARGINALISED, n_pops, K, Q))
+    nfp = 4 if n_filt <= 4 else (8 if n_filt <= 8 else 16)
+    # (the fused step is what runs: its builders' tiles fit its LDS budget -- marg_fused_ok, b9_capi_blocks.cpp; a copy of
+    # B9_MSTEP_LDS_DOUBLES with B9_MSTEP_SEC_ROWS = 24, b9_marg_step.hip.h, and of B9_MSTEP_LDS_MAX, b9_launch.h)
+    assert (((eng.max_eep() + 1) & ~1) + 8 + 65 * nfp + 4 * 24 * nfp) * 8 <= (30 if nfp > 8 else 15) * 1024
     free = np.array(list(mcmc.DEFAULT_FREE) + ([abi.P_Y, abi.P_Y2, abi.P_LAMBDA] if n_pops == 2 else []))
     chol = np.diag([3e-4, 2e-3, 8e-4, 8e-4] + ([3e-4, 3e-4, 2e-3] if n_pops == 2 else []))
     chol[0, 0] = 0.4 if n_stars == 2500 else chol[0, 0]                 # (this case: most log-age proposals fall off the grid)
@@ -186,6 +183,28 @@ def test_fused_marginalised_step_equals_the_two_launch_step(n_pops, wd_frac, n_s
         np.testing.assert_array_equal(f[0], t[0])
     assert 0 < fused[0][4] < 40 * walkers
     eng.close()
+
+
+@pytest.mark.parametrize("n_pops,wd_frac,n_stars,walkers", [(1, 0.0, 9000, 3), (1, 0.08, 2500, 2), (2, 0.05, 3000, 2), (1, 0.0, 40000, 2)])
+def test_fused_marginalised_step_equals_the_two_launch_step(n_pops, wd_frac, n_stars, walkers):
+    """k_marg_step (one launch per step: decision + stars + both candidate node tables of the next step, built by workgroups
+    that derive their isochrone tiles themselves) against the two-launch step it replaced (k_derive_iso, k_marg_table,
+    k_star_marg [, k_marg_merge, k_marg_wd_table, k_star_marg_wd]; b9_tuning.two_launch_steps): the same chain -- same
+    proposals (bit for bit), the same decisions, log-posteriors equal to the rounding of the two decision sums' orders.
+    Covers split catalogues (pieces + merge), WD-stage stars, two populations with a helium axis (eight corner isochrones per
+    table value), an unsplit catalogue, continued blocks, and proposals that leave the grid (a step scale that reaches the
+    grid's edge in log age)."""
+    _fused_against_two_launch(8, n_pops, wd_frac, n_stars, walkers, 3, 3)
+
+
+@pytest.mark.parametrize("n_filt,n_pops,wd_frac,K,Q,small", [(4, 1, 0.0, 1, 1, False), (16, 2, 0.05, 5, 2, False), (8, 1, 0.0, 70, 3, True)])
+def test_fused_builders_equal_the_two_launch_builders_at_every_instance(n_filt, n_pops, wd_frac, K, Q, small):
+    """The same comparison at the other builder instances and at both edge forms of the fused builder's primary tile, on 300
+    stars x 2 walkers (a split catalogue: pieces + k_marg_merge / k_marg_step_merge): 4 filters with K = Q = 1 (64 primaries
+    per chunk: the widest tile, 65 rows unless the isochrone's end clips it); 16 filters, two populations with a helium
+    axis, K = 5, Q = 2, 5 % WD-stage stars (both WD-table builders); 8 filters with K = 70 > 64 (a chunk inside ONE EEP
+    interval: a tile of two rows; the small pack keeps the table short).  The proposal scale is the first test's."""
+    _fused_against_two_launch(n_filt, n_pops, wd_frac, 300, 2, K, Q, small=small)
 
 
 def test_catalogue_plan_changes_rounding_only_and_survives_an_off_grid_reference():
