@@ -280,7 +280,7 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
         if (rc) return rc;
         if (marg)
             HIPCHK(ctx, b9k_marg_step(ctx->pk, ctx->st, sd, ctx->pr, mb.K, mb.Q, ctx->marg_prune, ctx->d_marg_tab, ctx->d_marg_wd_tab, mb.wd_stride,
-                                      ctx->d_marg_shares, s));
+                                      ctx->d_marg_shares, ctx->n_cu, s));
         else
             HIPCHK(ctx, b9k_mcmc_step(ctx->pk, ctx->st, sd, ctx->pr, plan, ctx->heavy_parts, derive_parts, ctx->derive_order, s));
         rc = bracket_after(ctx, s, tb, t == S - 1);

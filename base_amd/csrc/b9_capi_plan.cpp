@@ -58,7 +58,15 @@ B9Groups make_plan(b9_ctx *ctx, int n_walkers, int n_pops)
 {
     const Groups gr = make_groups(ctx, n_pops);
     const long long tiles_wanted = std::max<long long>(1, std::min<long long>(8, (long long)(ctx->st.n_pad / 256) * n_walkers / 4096));
-    return with_groups_per_block(gr, (int)(tiles_wanted / gr.group_tiles));
+    const B9Groups plan = with_groups_per_block(gr, (int)(tiles_wanted / gr.group_tiles));
+    const int key = ((ctx->pk.nfp * 4 + n_pops) * 65536 + ctx->mass_cap) * 64 + plan.group_tiles;
+    if (ctx->plan_debug && ctx->opt.mode != B9_MODE_MARGINALISED &&
+        (ctx->logpost_plan_debug_key != key || ctx->logpost_plan_debug_walkers != n_walkers || ctx->logpost_plan_debug_groups != plan.n_groups)) {
+        ctx->logpost_plan_debug_key = key; ctx->logpost_plan_debug_walkers = n_walkers; ctx->logpost_plan_debug_groups = plan.n_groups;
+        std::fprintf(stderr, "b9 logpost plan: %d walkers x %d workgroups (%d groups each); %d canonical groups of %d tiles\n",
+                     n_walkers, plan.n_blocks * n_pops, plan.groups_per_block, plan.n_groups, plan.group_tiles);
+    }
+    return plan;
 }
 
 // Launch plan of the fused sampler step.  The launch has three kinds of workgroups (heavy-star, candidate
@@ -114,7 +122,7 @@ void apply_tuning(b9_ctx *ctx, const b9_tuning &t)
     ctx->tree_depth = std::max(0, std::min(B9_TREE_MAX_DEPTH, t.tree_depth));
     if (ctx->marg_piece_units != std::max(0, t.marg_piece_units)) ctx->marg_plan_ok = false;
     ctx->marg_piece_units = std::max(0, t.marg_piece_units);
-    ctx->step_occ_key = -1; ctx->plan_debug_key = -1; ctx->tree_occ_key = -1;
+    ctx->step_occ_key = -1; ctx->plan_debug_key = -1; ctx->logpost_plan_debug_key = -1; ctx->tree_occ_key = -1;
 }
 
 // The B9_* environment overrides of the same fields (true when any is set).  Parsed once per context, at creation.

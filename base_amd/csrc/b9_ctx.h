@@ -109,6 +109,7 @@ struct b9_ctx {
     // launch plan
     int n_cu = 256;            // compute units of the device (hipDeviceAttributeMultiprocessorCount)
     int plan_debug_key = -1;
+    int logpost_plan_debug_key = -1, logpost_plan_debug_walkers = -1, logpost_plan_debug_groups = -1;      // make_plan's line: once per (configuration, walker count)
     int step_blocks_per_cu = 0, step_occ_key = -1;   // k_mcmc_step workgroups per CU for (nfp, n_pops, mass_cap), and the key it was queried for
     int heavy_parts = 4;       // workgroups per walker for the stars above the AGB tip (sized in check_ready)
     int n_wd_stage = 0;        // stars the catalogue marks as white dwarfs

@@ -247,16 +247,12 @@ int b9k_marg_split(int n_star_chunks, int n_pops) { return n_star_chunks * n_pop
 long long b9k_marg_shares_doubles(int n_pieces, int n_pops) { return (long long)std::max(1, n_pieces) * n_pops * 128; }      // per walker
 long long b9k_marg_wd_table_doubles(int nfp, int K) { return (long long)8 * K * (2 * nfp + 1); }       // per (walker, population)
 
-// Does a launch of `wgs` star workgroups leave the chip nearly empty (at most five waves per SIMD on average)?  Then its waves
-// are latency-bound on the row loop: the SPARSE tile setting (star_marg_body, TILE = 2: same bits, speed only).
-static bool marg_sparse(long long wgs)
+// Does a launch of `wgs` star workgroups leave the chip nearly empty (at most five waves per SIMD on average; n_cu: the compute
+// units of the context's device, as every other plan counts them)?  Then its waves are latency-bound on the row loop: the SPARSE
+// tile setting (star_marg_body, TILE = 2: same bits, speed only -- tests/test_gpu_placement.py crosses the two).
+static bool marg_sparse(long long wgs, int n_cu)
 {
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
-    }
-    return wgs * 4 <= (long long)5 * n_cu * 4;
+    return wgs * 4 <= (long long)5 * std::max(1, n_cu) * 4;
 }
 
 // The node tables of n_walkers x n_pops derived isochrones: one workgroup per (walker-population, 64-node chunk).  Returns what
@@ -300,7 +296,7 @@ static MargGrid marg_star_grid(const DevStars &st, int n_walkers, bool split)
 // smp == nullptr: the plain marginal likelihood; else every star also draws one (mass, ratio[, population]) node
 hipError_t b9k_star_marg(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data,
                          long long iso_stride, int mass_cap, const double *d_params, int n_walkers, int n_pops,
-                         double *partial, long long partial_stride, double *perstar, int K, int Q, const B9MargSample *smp, bool prune, double *tab, double *wd_tab, double *shares, hipStream_t stream)
+                         double *partial, long long partial_stride, double *perstar, int K, int Q, const B9MargSample *smp, bool prune, double *tab, double *wd_tab, double *shares, int n_cu, hipStream_t stream)
 {
     return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
@@ -322,7 +318,7 @@ hipError_t b9k_star_marg(const DevPack &pk, const DevStars &st, const IsoHdr *hd
             const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
             // rows through LDS tiles or through scalar registers (star_marg_body, TILE): measured per instance -- 8 (4) filters x one
             // population, unsplit, is the one shape the scalar path still wins in this kernel (2.20 against 2.17e9 star-evals/s)
-            const bool sparse = !SAMPLE && split && marg_sparse((long long)st.mg_n_pieces * n_walkers);
+            const bool sparse = !SAMPLE && split && marg_sparse((long long)st.mg_n_pieces * n_walkers, n_cu);
             const bool tiled = !SAMPLE && (split || NPOPS == 2 || NFP >= 16);
             const auto kern = sparse ? k_star_marg<NFP, NPOPS, SAMPLE, !SAMPLE, false, SAMPLE ? 0 : 2>
                             : split  ? k_star_marg<NFP, NPOPS, SAMPLE, !SAMPLE, false, SAMPLE ? 0 : 1>
@@ -384,7 +380,7 @@ hipError_t b9k_marg_tables(const DevPack &pk, const IsoHdr *hdr, const double *i
 size_t b9k_marg_step_lds(int nfp, int mass_cap) { return sizeof(double) * B9_MSTEP_LDS_DOUBLES(nfp, mass_cap); }
 
 hipError_t b9k_marg_step(const DevPack &pk, const DevStars &st, const StepDev &sd, const DevPriors &pr, int K, int Q, bool prune,
-                         double *tab, double *wd_tab, long long wd_stride, double *shares, hipStream_t stream)
+                         double *tab, double *wd_tab, long long wd_stride, double *shares, int n_cu, hipStream_t stream)
 {
     return dispatch(pk.nfp, sd.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
@@ -411,7 +407,7 @@ hipError_t b9k_marg_step(const DevPack &pk, const DevStars &st, const StepDev &s
         const double *par_rd = sd.cand_par + c0 * W * B9_NPARAM, *tab_rd = tab + c0 * rows * mx.L.total, *wd_rd = wd_tab ? wd_tab + c0 * wd_stride : nullptr;
         static_assert(B9_MSTEP_LDS_DOUBLES(NFP, 2) >= 4 * B9_TILE_DOUBLES(NFP), "the star role's row tiles borrow the builders' dynamic LDS");
         const auto kern = !split ? k_marg_step<NFP, NPOPS, false>
-                        : marg_sparse((long long)st.mg_n_pieces * W) ? k_marg_step<NFP, NPOPS, true, 2> : k_marg_step<NFP, NPOPS, true>;
+                        : marg_sparse((long long)st.mg_n_pieces * W, n_cu) ? k_marg_step<NFP, NPOPS, true, 2> : k_marg_step<NFP, NPOPS, true>;
         hipLaunchKernelGGL(kern, dim3(front + stars + wd), dim3(256), lds, stream, pk, st, sd, pr, mx, front, stars, hdr_rd, par_rd, tab_rd, wd_rd);
         if (split) hipLaunchKernelGGL((k_marg_step_merge<NPOPS>), dim3(st.mg_pad / 64, W), dim3(64), 0, stream, st, sd, mx);
         return hipGetLastError();

@@ -52,6 +52,7 @@ hipError_t b9k_star_marg(const DevPack &pk, const DevStars &st, const IsoHdr *hd
                          double *tab /* the call's node table: n_walkers * n_pops * b9k_marg_table_doubles(nfp, mass_cap, K, Q) doubles */,
                          double *wd_tab /* the WD-stage stars' node table: n_walkers * n_pops * b9k_marg_wd_table_doubles(nfp, K) doubles (used when the catalogue has WD-stage stars) */,
                          double *shares /* per-star shares of split launches: n_walkers * b9k_marg_shares_doubles(pieces, n_pops) doubles */,
+                         int n_cu /* compute units of the context's device: a split launch of at most 5 workgroups per CU takes the sparse tile setting */,
                          hipStream_t stream);
 int b9k_marg_split(int n_star_chunks, int n_pops);           // 1: the catalogue's star chunks are split into pieces (DevStars::mg_piece)
 long long b9k_marg_shares_doubles(int n_pieces, int n_pops);   // per walker
@@ -66,7 +67,7 @@ long long b9k_marg_wd_table_doubles(int nfp, int K);
 // n_partial = star chunks + WD-stage stars, cand_iso unused.  tab / wd_tab: [2 parities][2 candidates] blocks of n_walkers * n_pops
 // tables (b9k_marg_table_doubles / wd_stride doubles each).
 hipError_t b9k_marg_step(const DevPack &pk, const DevStars &st, const StepDev &sd, const DevPriors &pr, int K, int Q, bool prune,
-                         double *tab, double *wd_tab, long long wd_stride, double *shares, hipStream_t stream);
+                         double *tab, double *wd_tab, long long wd_stride, double *shares, int n_cu /* as b9k_star_marg's */, hipStream_t stream);
 // the tables alone (k_marg_table [+ k_marg_wd_table when wd_tab]) of derived isochrones: the fused block's prologue
 hipError_t b9k_marg_tables(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
                            const double *d_params, int n_walkers, int n_pops, int K, int Q, double *tab, double *wd_tab, hipStream_t stream);

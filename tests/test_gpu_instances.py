@@ -7,14 +7,13 @@ Which instance a shape takes: NFP = 4 for 1-4 filters, 8 for 5-8, 16 for 9-16.  
 chunks (WD-stage stars apart) is SPLIT when n_mc x n_pops < 512 (b9k_marg_split), and a split launch is SPARSE when its
 pieces x walkers <= 5 x CUs (marg_sparse); an unsplit catalogue runs the TILED star kernel at NFP = 16 or with two
 populations, the SCALAR one otherwise (launch_star_marg_t, launch_marg_step).  sampleMass draws never split."""
-import re
-
 import numpy as np
 import pytest
 
 import oracle
 from base_amd import abi, engine, hostlib, mcmc, synth
 from chain_check import oracle_delta
+from placement_check import launch_form as _launch_form, n_cu as _n_cu, plan_pieces as _plan_pieces  # noqa: F401  (shared with tests/test_gpu_placement.py)
 from sim_check import branch_systems, forward_by_pop, isochrone_tips
 import numpy_ref
 
@@ -289,40 +288,6 @@ def test_predict_mags_instances(n_filt, n_pops):
 # ---------------------------------------------------------------------------------------------------------------------------
 # C. catalogue sizes that pick each launch form of the marginalised kernels
 # ---------------------------------------------------------------------------------------------------------------------------
-def _n_cu(capfd):
-    """The CU count the library plans with (marg_sparse reads the same device attribute), from the given-mass step plan it
-    prints under b9_tuning.plan_debug."""
-    _, _, pack, stars, priors = _problem(4, 1, 64, seed=1)
-    capfd.readouterr()
-    eng = engine.Engine(pack, stars, priors, abi.make_options(abi.MODE_GIVEN_MASS, 1))
-    eng.set_tuning(plan_debug=1)
-    eng.step_tiles_per_block(1)
-    eng.close()
-    return int(re.findall(r"b9 step plan: (\d+) CUs", capfd.readouterr().err)[-1])
-
-
-def _plan_pieces(eng, rows, capfd):
-    """Evaluate once with the catalogue plan printed (b9_tuning.plan_debug): its piece count, or None when the catalogue is
-    not split."""
-    capfd.readouterr()
-    eng.set_tuning(plan_debug=1)
-    out = eng.logpost(rows, perstar=True)
-    eng.set_tuning()
-    err = capfd.readouterr().err
-    m = re.findall(r"\[marg plan\] \d+ chunks.*; (\d+) pieces", err)
-    return (int(m[-1]) if m else None), out
-
-
-def _launch_form(eng, rows, W, n_pops, cl, n_cu, capfd):
-    n_mc = max(1, (int((np.asarray(cl["stage"]) != abi.STAGE_WD).sum()) + 63) // 64)
-    pieces, out = _plan_pieces(eng, rows, capfd)
-    if n_mc * n_pops >= 512:
-        assert pieces is None
-        return ("tiled" if (_nfp(eng.n_filt) >= 16 or n_pops == 2) else "scalar"), out
-    assert pieces is not None and pieces >= n_mc
-    return ("sparse" if pieces * W <= 5 * n_cu else "split"), out
-
-
 def _catalogue_case(capfd, n_filt, n_pops, n_stars, W, want_form, seed, steps=6):
     pack_d, cl, pack, stars, priors = _problem(n_filt, n_pops, n_stars, seed=seed, n_feh=3, n_age=5, n_eep=40)
     opt = abi.make_options(abi.MODE_MARGINALISED, n_pops, 2, 2)
