@@ -61,7 +61,7 @@ int collect_block(b9_ctx *ctx, McmcSlot &sl, b9_mcmc_block *blk)
     HIPCHK(ctx, hipEventSynchronize(sl.done));
     sl.in_flight = false;
     const BlockLayout &L = sl.lay;
-    const double *stage = static_cast<const double *>(sl.h), *fin = stage + final_off(sl);
+    const double *stage = sl.h.get(), *fin = stage + final_off(sl);
     if (sl.kind == BlockKind::TwoLaunch) {       // [cur][lp] of the final half, n_acc as a 64-bit count
         std::memcpy(blk->params, fin, sizeof(double) * (size_t)sl.W * B9_NPARAM);
         std::memcpy(blk->logpost, stage + final_lp_off(sl), sizeof(double) * (size_t)sl.W);
@@ -118,32 +118,20 @@ int open_block(b9_ctx *ctx, const b9_mcmc_block *blk, BlockKind kind, void (*lay
     L.n_rows = f->want_rows ? W * B9_ROW_LEN(d) : 0;
     L.n_int = (d + W + 1) / 2;                                            // ints, in units of 8 bytes
     layout(L, W, d, S);
-    if (L.n_total * 8 > sl.cap) {
-        // (a CONTINUE block reads the OTHER slot's final state, never this slot's old contents)
-        if (sl.d) (void)hipFree(sl.d);
-        sl.d = nullptr; sl.cap = 0;
-        HIPCHK(ctx, hipMalloc(&sl.d, L.n_total * 8));
-        sl.cap = L.n_total * 8;
-    }
-    if (L.n_total * 8 > sl.hcap) {
-        if (sl.h) (void)hipHostFree(sl.h);
-        sl.h = nullptr; sl.hcap = 0;
-        HIPCHK(ctx, hipHostMalloc(&sl.h, L.n_total * 8, hipHostMallocMapped));     // pinned staging mirror, mapped into the device
-        HIPCHK(ctx, hipHostGetDevicePointer(&sl.h_dev, sl.h, 0));
-        sl.hcap = L.n_total * 8;
-    }
+    RESERVE(ctx, sl.d, L.n_total);        // (a CONTINUE block reads the OTHER slot's final state, never this slot's old contents)
+    RESERVE(ctx, sl.h, L.n_total);        // pinned staging mirror, mapped into the device
     if (!sl.done) HIPCHK(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     if (!sl.rows_ready) HIPCHK(ctx, hipEventCreateWithFlags(&sl.rows_ready, hipEventDisableTiming));
     f->sl = &sl; f->L = &L;
-    f->dev = static_cast<double *>(sl.d); f->stage = static_cast<double *>(sl.h); f->mirror = static_cast<double *>(sl.h_dev);
+    f->dev = sl.d.get(); f->stage = sl.h.get(); f->mirror = sl.h.dev();
     std::memcpy(f->stage + L.o_chol, blk->chol, d * d * 8);
     if (f->want_rows) std::memcpy(f->stage + L.o_org, blk->row_origin, d * 8); else std::memset(f->stage + L.o_org, 0, d * 8);
     int *hi = reinterpret_cast<int *>(f->stage + L.o_int);
     std::memcpy(hi, blk->free_idx, d * sizeof(int));
     std::memcpy(hi + d, blk->walker_ids, W * sizeof(int));
     // continuing: the previous block's final state, stream-ordered behind its last launch
-    f->prev_final = f->cont ? static_cast<const double *>(pv->d) + final_off(*pv) : nullptr;
-    f->prev_final_lp = (f->cont && kind == BlockKind::TwoLaunch) ? static_cast<const double *>(pv->d) + final_lp_off(*pv) : nullptr;
+    f->prev_final = f->cont ? pv->d.get() + final_off(*pv) : nullptr;
+    f->prev_final_lp = (f->cont && kind == BlockKind::TwoLaunch) ? pv->d.get() + final_lp_off(*pv) : nullptr;
     sl.kind = kind; sl.W = (int)W;           // (this slot is never last_slot: nothing reads it before close_block puts it in flight)
     return B9_OK;
 }
@@ -189,7 +177,7 @@ struct MargBlock {             // what the marginalised flavour adds to a fused 
 
 // can the marginalised mode run fused steps on this context?  (the table builders' mass column must fit beside the star role's
 // workgroups in LDS: isochrones of more than ~600 points at 8 filters keep the two-launch step)
-bool marg_fused_ok(const b9_ctx *ctx) { return b9k_marg_step_lds(ctx->pk.nfp, ctx->mass_cap) <= B9_MSTEP_LDS_MAX(ctx->pk.nfp); }
+bool marg_fused_ok(const b9_ctx *ctx) { return b9k_marg_step_lds(ctx->pk.nfp, ctx->work.mass_cap) <= B9_MSTEP_LDS_MAX(ctx->pk.nfp); }
 
 int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
 {
@@ -197,8 +185,7 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
     StepPlan sp{};
     MargBlock mb;
     if (marg) {
-        mb.K = ctx->opt.marg_iso_increm > 0 ? ctx->opt.marg_iso_increm : 1;
-        mb.Q = ctx->opt.marg_n_q > 0 ? ctx->opt.marg_n_q : 1;
+        mb.K = marg_grid(ctx).K; mb.Q = marg_grid(ctx).Q;
         // four candidate sets (two parities x two candidates) of node tables, WD tables and split shares
         int rc = ensure_marg_table(ctx, 4 * W, n_pops, mb.K, mb.Q);
         if (rc) return rc;
@@ -206,8 +193,8 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
         mb.stride = 2 * (((long long)mb.n_partial + 7) & ~7ll);
         rc = ensure_capacity(ctx, W, n_pops, (size_t)std::max<long long>(mb.stride, partial_stride(ctx)) * W, false);
         if (rc) return rc;
-        mb.partial = ctx->d_partial;
-        mb.tab_doubles = b9k_marg_table_doubles(ctx->pk.nfp, ctx->mass_cap, mb.K, mb.Q);
+        mb.partial = ctx->d_partial.get();
+        mb.tab_doubles = b9k_marg_table_doubles(ctx->pk.nfp, ctx->work.mass_cap, mb.K, mb.Q);
         mb.wd_stride = (long long)W * n_pops * b9k_marg_wd_table_doubles(ctx->pk.nfp, mb.K);
     } else {
         sp = make_step_plan(ctx, W, n_pops);
@@ -248,11 +235,11 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
     }
     StepDev sd{};
     sd.d = d; sd.n_walkers = W; sd.n_pops = n_pops;
-    sd.n_partial = marg ? mb.n_partial : partial_count(ctx, plan); sd.mass_cap = ctx->mass_cap; sd.heavy_parts = marg ? 0 : ctx->heavy_parts;
-    sd.k0 = (unsigned)(blk->seed & 0xFFFFFFFFull); sd.k1 = (unsigned)(blk->seed >> 32);
-    sd.partial_stride = marg ? mb.stride : partial_stride(ctx); sd.iso_stride = ctx->iso_stride;
-    sd.state = d_state; sd.partial = marg ? mb.partial : ctx->d_partial;
-    sd.cand_par = ctx->d_params; sd.cand_hdr = ctx->d_hdr; sd.cand_iso = ctx->d_iso;
+    sd.n_partial = marg ? mb.n_partial : partial_count(ctx, plan); sd.mass_cap = ctx->work.mass_cap; sd.heavy_parts = marg ? 0 : ctx->heavy_parts;
+    split_seed(blk->seed, &sd.k0, &sd.k1);
+    sd.partial_stride = marg ? mb.stride : partial_stride(ctx); sd.iso_stride = ctx->work.iso_stride;
+    sd.state = d_state; sd.partial = marg ? mb.partial : ctx->d_partial.get();
+    sd.cand_par = ctx->work.params.get(); sd.cand_hdr = ctx->work.hdr.get(); sd.cand_iso = ctx->work.iso.get();
     sd.chol = d_chol; sd.free_idx = d_free; sd.walker_ids = d_ids;
     sd.samples = L.n_samp ? dev + L.o_samp : nullptr; sd.lps = L.n_lps ? dev + L.o_lps : nullptr; sd.n_acc = d_nacc; sd.decided = d_decided;
     sd.rows = nullptr; sd.row_origin = dev + L.o_org; sd.n_steps = S;
@@ -265,12 +252,12 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
         mc.k0 = sd.k0; mc.k1 = sd.k1; mc.step = (unsigned long long)blk->step0; mc.n_acc = d_nacc;
         const size_t rows = (size_t)W * n_pops, c10 = 2;     // (parity 1, candidate 0)
         HIPCHK(ctx, b9k_derive_iso(ctx->pk, sd.cand_par + c10 * W * B9_NPARAM, W, n_pops, sd.cand_hdr + c10 * rows,
-                                   sd.cand_iso + c10 * rows * ctx->iso_stride, ctx->iso_stride, ctx->mass_cap,
-                                   mc, ctx->pr, B9Prev{nullptr, 0, 0, nullptr, nullptr}, s));
+                                   sd.cand_iso + c10 * rows * ctx->work.iso_stride, ctx->work.iso_stride, ctx->work.mass_cap,
+                                   mc, ctx->pr, no_prev(), s));
         if (marg)       // ... and its node tables (every later candidate's are built inside k_marg_step)
-            HIPCHK(ctx, b9k_marg_tables(ctx->pk, sd.cand_hdr + c10 * rows, sd.cand_iso + c10 * rows * ctx->iso_stride, ctx->iso_stride, ctx->mass_cap,
-                                        sd.cand_par + c10 * W * B9_NPARAM, W, n_pops, mb.K, mb.Q, ctx->d_marg_tab + c10 * rows * mb.tab_doubles,
-                                        ctx->st.n_wd > 0 ? ctx->d_marg_wd_tab + c10 * mb.wd_stride : nullptr, s));
+            HIPCHK(ctx, b9k_marg_tables(ctx->pk, sd.cand_hdr + c10 * rows, sd.cand_iso + c10 * rows * ctx->work.iso_stride, ctx->work.iso_stride, ctx->work.mass_cap,
+                                        sd.cand_par + c10 * W * B9_NPARAM, W, n_pops, mb.K, mb.Q, ctx->d_marg_tab.get() + c10 * rows * mb.tab_doubles,
+                                        ctx->st.n_wd > 0 ? ctx->d_marg_wd_tab.get() + c10 * mb.wd_stride : nullptr, s));
     }
     TimingBracket tb;
     for (int t = 0; t < S; ++t) {
@@ -279,8 +266,8 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
         rc = bracket_before(ctx, s, tb);
         if (rc) return rc;
         if (marg)
-            HIPCHK(ctx, b9k_marg_step(ctx->pk, ctx->st, sd, ctx->pr, mb.K, mb.Q, ctx->marg_prune, ctx->d_marg_tab, ctx->d_marg_wd_tab, mb.wd_stride,
-                                      ctx->d_marg_shares, ctx->n_cu, s));
+            HIPCHK(ctx, b9k_marg_step(ctx->pk, ctx->st, sd, ctx->pr, mb.K, mb.Q, ctx->marg_prune, ctx->d_marg_tab.get(), ctx->d_marg_wd_tab.get(), mb.wd_stride,
+                                      ctx->d_marg_shares.get(), ctx->n_cu, s));
         else
             HIPCHK(ctx, b9k_mcmc_step(ctx->pk, ctx->st, sd, ctx->pr, plan, ctx->heavy_parts, derive_parts, ctx->derive_order, s));
         rc = bracket_after(ctx, s, tb, t == S - 1);
@@ -331,12 +318,12 @@ int run_block_tree(b9_ctx *ctx, b9_mcmc_block *blk, const TreePlan &tp)
     }
     TreeDev td{};
     td.d = d; td.n_walkers = W; td.n_pops = n_pops; td.depth = depth;
-    td.n_groups = tp.n_groups; td.heavy_parts = ctx->heavy_parts; td.mass_cap = ctx->mass_cap;
-    td.part_stride = (int)(((size_t)tp.n_groups * 4 + ctx->heavy_parts + 1) & ~(size_t)1);
-    td.k0 = (unsigned)(blk->seed & 0xFFFFFFFFull); td.k1 = (unsigned)(blk->seed >> 32);
-    td.iso_stride = ctx->iso_stride;
-    td.state = dev + L.o_st[0]; td.partial = ctx->d_tree_partial;
-    td.cand_par = ctx->d_tree_par; td.cand_hdr = ctx->d_tree_hdr; td.cand_iso = ctx->d_tree_iso;
+    td.n_groups = tp.n_groups; td.heavy_parts = ctx->heavy_parts; td.mass_cap = ctx->work.mass_cap;
+    td.part_stride = (int)tree_part_stride(tp.n_groups, ctx->heavy_parts);
+    split_seed(blk->seed, &td.k0, &td.k1);
+    td.iso_stride = ctx->work.iso_stride;
+    td.state = dev + L.o_st[0]; td.partial = ctx->tree.partial.get();
+    td.cand_par = ctx->tree.par.get(); td.cand_hdr = ctx->tree.hdr.get(); td.cand_iso = ctx->tree.iso.get();
     td.chol = dev + L.o_chol; td.free_idx = reinterpret_cast<int *>(dev + L.o_int); td.walker_ids = td.free_idx + d;
     td.samples = L.n_samp ? dev + L.o_samp : nullptr; td.lps = L.n_lps ? dev + L.o_lps : nullptr;
     td.row_origin = dev + L.o_org; td.n_steps = S;
@@ -414,7 +401,7 @@ int run_block_two_launch(b9_ctx *ctx, b9_mcmc_block *blk, const B9Groups &plan)
     mc.free_idx = reinterpret_cast<int *>(dev + L.o_int); mc.walker_ids = mc.free_idx + d;
     mc.samples = L.n_samp ? dev + L.o_samp : nullptr; mc.lps = L.n_lps ? dev + L.o_lps : nullptr;
     mc.n_acc = reinterpret_cast<unsigned long long *>(dev + L.o_nacc);
-    mc.k0 = (unsigned)(blk->seed & 0xFFFFFFFFull); mc.k1 = (unsigned)(blk->seed >> 32);
+    split_seed(blk->seed, &mc.k0, &mc.k1);
     const int n_part = partial_count(ctx, plan);
     for (int t = 0; t < S; ++t) {
         const Bufs bf = buffer_set(ctx, t & 1), bp = buffer_set(ctx, (t & 1) ^ 1);
@@ -422,8 +409,8 @@ int run_block_two_launch(b9_ctx *ctx, b9_mcmc_block *blk, const B9Groups &plan)
         mc.has_prev = t > 0;
         mc.pin = t > 0 ? (t - 1) & 1 : 0;                   // state half on entry
         mc.row = t - 1;                                     // chain row of the step being finished
-        const B9Prev prev{ctx->d_partial, n_part, partial_stride(ctx), bp.hdr, bp.params};
-        HIPCHK(ctx, b9k_derive_iso(ctx->pk, bf.params, W, n_pops, bf.hdr, bf.iso, ctx->iso_stride, ctx->mass_cap,
+        const B9Prev prev{ctx->d_partial.get(), n_part, partial_stride(ctx), bp.hdr, bp.params};
+        HIPCHK(ctx, b9k_derive_iso(ctx->pk, bf.params, W, n_pops, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap,
                                    mc, ctx->pr, prev, s));
         rc = launch_stars(ctx, bf, W, nullptr, plan, s);
         if (rc) return rc;
@@ -435,8 +422,8 @@ int run_block_two_launch(b9_ctx *ctx, b9_mcmc_block *blk, const B9Groups &plan)
         mc.pin = S > 1 ? (S - 2) & 1 : 0;                   // the half D(S-1) wrote (or the initial half)
         if (S > 1) mc.pin ^= 1;
         mc.row = S - 1;
-        HIPCHK(ctx, b9k_finalize(bf.hdr, ctx->d_partial, n_part, partial_stride(ctx), n_pops, bf.params, ctx->pr, W,
-                                 ctx->d_logpost, nullptr, ctx->st.n, mc, s));
+        HIPCHK(ctx, b9k_finalize(bf.hdr, ctx->d_partial.get(), n_part, partial_stride(ctx), n_pops, bf.params, ctx->pr, W,
+                                 ctx->work.logpost.get(), nullptr, ctx->st.n, mc, s));
     }
     const int fin = mc.pin ^ 1;                             // half that holds the final state
     if (f.want_rows) {

@@ -14,71 +14,21 @@ namespace b9i {
 
 int ensure_capacity(b9_ctx *ctx, int n_walkers, int n_pops, size_t n_partial, bool want_perstar)
 {
-    // (the isochrone rows depend on BOTH the longest isochrone and the padded filter count of the loaded pack: a pack
-    //  reloaded with the same EEP count but more filters needs wider rows)
-    const int want_cap = (ctx->pk.max_eep + 1) & ~1;
-    if (n_walkers > ctx->cap_walkers || n_pops > ctx->cap_pops || ctx->mass_cap != want_cap ||
-        ctx->iso_stride != (long long)want_cap * (ctx->pk.nfp + 1)) {
-        if (ctx->d_hdr) (void)hipFree(ctx->d_hdr);
-        if (ctx->d_iso) (void)hipFree(ctx->d_iso);
-        if (ctx->d_params) (void)hipFree(ctx->d_params);
-        if (ctx->d_logpost) (void)hipFree(ctx->d_logpost);
-        ctx->d_hdr = nullptr; ctx->d_iso = nullptr; ctx->d_params = nullptr; ctx->d_logpost = nullptr;
-        int cw = std::max(n_walkers, ctx->cap_walkers), cp = std::max(n_pops, ctx->cap_pops);
-        ctx->mass_cap = (ctx->pk.max_eep + 1) & ~1;
-        ctx->iso_stride = (long long)ctx->mass_cap * (ctx->pk.nfp + 1);
-        // four sets: the two-launch sampler (marginalised mode) ping-pongs between sets 0 and 1; the fused
-        // sampler step (given-mass mode) keeps two candidates for each of two step parities (StepDev)
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_hdr, sizeof(IsoHdr) * cw * cp * 4));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_iso, sizeof(double) * (size_t)ctx->iso_stride * cw * cp * 4));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_params, sizeof(double) * B9_NPARAM * cw * 4));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_logpost, sizeof(double) * cw));
-        ctx->cap_walkers = cw; ctx->cap_pops = cp;
-    }
-    if (n_partial > ctx->partial_cap) {
-        if (ctx->d_partial) (void)hipFree(ctx->d_partial);
-        ctx->d_partial = nullptr;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_partial, sizeof(double) * n_partial));
-        ctx->partial_cap = n_partial;
-    }
-    if (want_perstar) {
-        size_t need = (size_t)n_walkers * ctx->st.n;
-        if (need > ctx->perstar_cap) {
-            if (ctx->d_perstar) (void)hipFree(ctx->d_perstar);
-            ctx->d_perstar = nullptr;
-            HIPCHK(ctx, hipMalloc((void **)&ctx->d_perstar, sizeof(double) * std::max<size_t>(need, 1)));
-            ctx->perstar_cap = need;
-        }
-    }
+    const Reserved r = ctx->work.ensure(n_walkers, n_pops, ctx->pk.max_eep, ctx->pk.nfp);
+    if (r.err) return alloc_failed(ctx, r);
+    RESERVE(ctx, ctx->d_partial, n_partial);
+    if (want_perstar) RESERVE(ctx, ctx->d_perstar, (size_t)n_walkers * ctx->st.n);
     return B9_OK;
 }
-
 
 // the marginalised mode's per-call node table for n_walkers rows (grown on demand)
 int ensure_marg_table(b9_ctx *ctx, int n_walkers, int n_pops, int K, int Q)
 {
-    const size_t need = (size_t)n_walkers * n_pops * (size_t)b9k_marg_table_doubles(ctx->pk.nfp, ctx->mass_cap, K, Q);
+    const size_t need = (size_t)n_walkers * n_pops * (size_t)b9k_marg_table_doubles(ctx->pk.nfp, ctx->work.mass_cap, K, Q);
     if (need > ((size_t)8 << 30) / sizeof(double)) return fail(ctx, B9_ERR_CAPACITY, "marginalisation grid too fine: the node table would exceed 8 GiB");
-    if (need > ctx->marg_tab_cap) {
-        if (ctx->d_marg_tab) (void)hipFree(ctx->d_marg_tab);
-        ctx->d_marg_tab = nullptr; ctx->marg_tab_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_marg_tab, need * sizeof(double)));
-        ctx->marg_tab_cap = need;
-    }
-    const size_t need_wd = (size_t)n_walkers * n_pops * (size_t)b9k_marg_wd_table_doubles(ctx->pk.nfp, K);
-    if (need_wd > ctx->marg_wd_tab_cap) {
-        if (ctx->d_marg_wd_tab) (void)hipFree(ctx->d_marg_wd_tab);
-        ctx->d_marg_wd_tab = nullptr; ctx->marg_wd_tab_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_marg_wd_tab, need_wd * sizeof(double)));
-        ctx->marg_wd_tab_cap = need_wd;
-    }
-    const size_t need_sh = (size_t)n_walkers * (size_t)b9k_marg_shares_doubles(ctx->st.mg_n_pieces, n_pops);
-    if (need_sh > ctx->marg_shares_cap) {
-        if (ctx->d_marg_shares) (void)hipFree(ctx->d_marg_shares);
-        ctx->d_marg_shares = nullptr; ctx->marg_shares_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_marg_shares, need_sh * sizeof(double)));
-        ctx->marg_shares_cap = need_sh;
-    }
+    RESERVE(ctx, ctx->d_marg_tab, need);
+    RESERVE(ctx, ctx->d_marg_wd_tab, (size_t)n_walkers * n_pops * (size_t)b9k_marg_wd_table_doubles(ctx->pk.nfp, K));
+    RESERVE(ctx, ctx->d_marg_shares, (size_t)n_walkers * (size_t)b9k_marg_shares_doubles(ctx->st.mg_n_pieces, n_pops));
     return B9_OK;
 }
 
@@ -177,25 +127,15 @@ void b9_ctx_destroy(b9_ctx *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    free_all(ctx->pack_allocs);
-    free_all(ctx->star_allocs);
-    free_all(ctx->marg_plan_allocs);
-    void *bufs[] = {ctx->d_hdr, ctx->d_iso, ctx->d_partial, ctx->d_params, ctx->d_logpost, ctx->d_perstar, ctx->d_marg_tab, ctx->d_marg_wd_tab, ctx->d_marg_shares,
-                    ctx->d_tree_hdr, ctx->d_tree_iso, ctx->d_tree_par, ctx->d_tree_partial,
-                    ctx->d_pred_hdr, ctx->d_pred_iso, ctx->d_pred_par, ctx->d_pred_io, ctx->d_wds};
-    for (void *p : bufs) if (p) (void)hipFree(p);
     for (auto &sl : ctx->slot) {
-        if (sl.d) (void)hipFree(sl.d);
-        if (sl.h) (void)hipHostFree(sl.h);
         if (sl.done) (void)hipEventDestroy(sl.done);
         if (sl.rows_ready) (void)hipEventDestroy(sl.rows_ready);
     }
-    if (ctx->h_lp) (void)hipHostFree(ctx->h_lp);
-    if (ctx->d_clock) (void)hipFree(ctx->d_clock);
     for (auto e : ctx->ev_start) (void)hipEventDestroy(e);
     for (auto e : ctx->ev_stop) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    const hipStream_t stream = ctx->stream;
+    delete ctx;                 // (every buffer and upload list frees its own memory)
+    (void)hipStreamDestroy(stream);
 }
 
 const char *b9_last_error(const b9_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
@@ -346,22 +286,22 @@ int b9_clock_stamp(b9_ctx *ctx, int32_t which)
     if (!ctx || (which != 0 && which != 1)) return B9_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t per = (size_t)B9_CLOCK_SLOTS * 2;
-    if (!ctx->d_clock) HIPCHK(ctx, hipMalloc((void **)&ctx->d_clock, sizeof(unsigned long long) * per * 2));
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_clock + per * which, 0, sizeof(unsigned long long) * per, ctx->stream));
-    if (which == 0) HIPCHK(ctx, hipMemsetAsync(ctx->d_clock + per, 0, sizeof(unsigned long long) * per, ctx->stream));
-    HIPCHK(ctx, b9k_clock_stamp(ctx->d_clock + per * which, ctx->stream));
+    RESERVE(ctx, ctx->d_clock, per * 2);
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_clock.get() + per * which, 0, sizeof(unsigned long long) * per, ctx->stream));
+    if (which == 0) HIPCHK(ctx, hipMemsetAsync(ctx->d_clock.get() + per, 0, sizeof(unsigned long long) * per, ctx->stream));
+    HIPCHK(ctx, b9k_clock_stamp(ctx->d_clock.get() + per * which, ctx->stream));
     return B9_OK;
 }
 
 int b9_clock_mhz(b9_ctx *ctx, double *mhz, double *mhz_min, double *mhz_max, double *ref_seconds)
 {
     if (!ctx || !mhz) return B9_ERR_INVALID;
-    if (!ctx->d_clock) return fail(ctx, B9_ERR_STATE, "b9_clock_mhz: no stamps (call b9_clock_stamp(ctx, 0) and (ctx, 1) first)");
+    if (!ctx->d_clock.get()) return fail(ctx, B9_ERR_STATE, "b9_clock_mhz: no stamps (call b9_clock_stamp(ctx, 0) and (ctx, 1) first)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     const size_t per = (size_t)B9_CLOCK_SLOTS * 2;
     std::vector<unsigned long long> h(per * 2);
-    HIPCHK(ctx, hipMemcpy(h.data(), ctx->d_clock, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(h.data(), ctx->d_clock.get(), sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
     std::vector<double> v;
     double ref = 0.0;
     for (int x = 0; x < B9_CLOCK_SLOTS; ++x) {

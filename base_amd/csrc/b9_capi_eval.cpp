@@ -12,9 +12,9 @@ namespace b9i {
 // ping-pong work-buffer set (0 / 1)
 Bufs buffer_set(const b9_ctx *ctx, int set)
 {
-    const size_t rows = (size_t)ctx->cap_walkers * ctx->cap_pops;
-    return Bufs{ctx->d_params + (size_t)set * ctx->cap_walkers * B9_NPARAM, ctx->d_hdr + (size_t)set * rows,
-                ctx->d_iso + (size_t)set * rows * ctx->iso_stride};
+    const size_t rows = (size_t)ctx->work.cap_walkers * ctx->work.cap_pops;
+    return Bufs{ctx->work.params.get() + (size_t)set * ctx->work.cap_walkers * B9_NPARAM, ctx->work.hdr.get() + (size_t)set * rows,
+                ctx->work.iso.get() + (size_t)set * rows * ctx->work.iso_stride};
 }
 
 // number of partial sums one walker gets from the star kernel under the current plan / mode
@@ -37,15 +37,14 @@ int launch_stars(b9_ctx *ctx, const Bufs &bf, int32_t n_walkers, double *d_perst
     int rc = bracket_before(ctx, stream, tb);
     if (rc) return rc;
     if (ctx->opt.mode == B9_MODE_MARGINALISED) {
-        const int K = ctx->opt.marg_iso_increm > 0 ? ctx->opt.marg_iso_increm : 1;
-        const int Q = ctx->opt.marg_n_q > 0 ? ctx->opt.marg_n_q : 1;
+        const int K = marg_grid(ctx).K, Q = marg_grid(ctx).Q;
         rc = ensure_marg_table(ctx, n_walkers, n_pops, K, Q);
         if (rc) return rc;
-        HIPCHK(ctx, b9k_star_marg(ctx->pk, ctx->st, bf.hdr, bf.iso, ctx->iso_stride, ctx->mass_cap, bf.params,
-                                  n_walkers, n_pops, ctx->d_partial, partial_stride(ctx), d_perstar, K, Q, nullptr, ctx->marg_prune, ctx->d_marg_tab, ctx->d_marg_wd_tab, ctx->d_marg_shares, ctx->n_cu, stream));
+        HIPCHK(ctx, b9k_star_marg(ctx->pk, ctx->st, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap, bf.params,
+                                  n_walkers, n_pops, ctx->d_partial.get(), partial_stride(ctx), d_perstar, K, Q, nullptr, ctx->marg_prune, ctx->d_marg_tab.get(), ctx->d_marg_wd_tab.get(), ctx->d_marg_shares.get(), ctx->n_cu, stream));
     } else {
-        HIPCHK(ctx, b9k_star_like(ctx->pk, ctx->st, bf.hdr, bf.iso, ctx->iso_stride, ctx->mass_cap, bf.params,
-                                  n_walkers, n_pops, ctx->d_partial, partial_stride(ctx), d_perstar, plan, ctx->heavy_parts, stream));
+        HIPCHK(ctx, b9k_star_like(ctx->pk, ctx->st, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap, bf.params,
+                                  n_walkers, n_pops, ctx->d_partial.get(), partial_stride(ctx), d_perstar, plan, ctx->heavy_parts, stream));
     }
     return bracket_after(ctx, stream, tb, true);
 }
@@ -69,16 +68,15 @@ int launch_logpost(b9_ctx *ctx, double *d_params, int32_t n_walkers, double *d_l
     Bufs bf = buffer_set(ctx, 0);
     bf.params = d_params;
     const McmcDev off{};
-    const B9Prev none{nullptr, 0, 0, nullptr, nullptr};
     if (host_rows)      // <= 8 rows travel in the kernel arguments: no upload
-        HIPCHK(ctx, b9k_derive_iso_rows(ctx->pk, host_rows, bf.params, n_walkers, n_pops, bf.hdr, bf.iso, ctx->iso_stride,
-                                        ctx->mass_cap, stream));
+        HIPCHK(ctx, b9k_derive_iso_rows(ctx->pk, host_rows, bf.params, n_walkers, n_pops, bf.hdr, bf.iso, ctx->work.iso_stride,
+                                        ctx->work.mass_cap, stream));
     else
-        HIPCHK(ctx, b9k_derive_iso(ctx->pk, bf.params, n_walkers, n_pops, bf.hdr, bf.iso, ctx->iso_stride, ctx->mass_cap,
-                                   off, ctx->pr, none, stream));
+        HIPCHK(ctx, b9k_derive_iso(ctx->pk, bf.params, n_walkers, n_pops, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap,
+                                   off, ctx->pr, no_prev(), stream));
     rc = launch_stars(ctx, bf, n_walkers, d_perstar, plan, stream);
     if (rc) return rc;
-    HIPCHK(ctx, b9k_finalize(bf.hdr, ctx->d_partial, partial_count(ctx, plan), partial_stride(ctx), n_pops, bf.params, ctx->pr,
+    HIPCHK(ctx, b9k_finalize(bf.hdr, ctx->d_partial.get(), partial_count(ctx, plan), partial_stride(ctx), n_pops, bf.params, ctx->pr,
                              n_walkers, d_logpost, d_perstar, ctx->st.n, off, stream, done_flag, done_seq));
     return B9_OK;
 }
@@ -109,29 +107,29 @@ int b9_logpost(b9_ctx *ctx, const double *params, int32_t n_walkers, double *out
     // The per-step call of a host-driven sampler (the reference's logPostStep) is latency: for up
     // to 8 rows the parameters ride in the first launch's kernel arguments and the log-posteriors are written by
     // k_finalize straight into pinned host memory mapped into the device -- no copy command in the stream at all.
-    if (!ctx->h_lp) {
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_lp, sizeof(double) * 16, hipHostMallocMapped));
-        HIPCHK(ctx, hipHostGetDevicePointer((void **)&ctx->h_lp_dev, ctx->h_lp, 0));
-        std::memset(ctx->h_lp, 0, sizeof(double) * 16);
+    {
+        const Reserved r = ctx->h_lp.reserve(16);
+        if (r.err) return alloc_failed(ctx, named(r, "ctx->h_lp"));
+        if (r.fresh) std::memset(ctx->h_lp.get(), 0, sizeof(double) * 16);
     }
     const bool small = n_walkers <= 8;
     // ... and the host does not wait for the stream's completion signal either (a wake-up of several microseconds): the
     // last launch stores a per-call sequence number behind every log-posterior and the host polls those words
-    volatile unsigned long long *const h_done = reinterpret_cast<volatile unsigned long long *>(ctx->h_lp + 8);
+    volatile unsigned long long *const h_done = reinterpret_cast<volatile unsigned long long *>(ctx->h_lp.get() + 8);
     const bool polled = small && !out_perstar;
     const unsigned long long seq = ++ctx->lp_seq;
     if (small) {
-        rc = launch_logpost(ctx, ctx->d_params, n_walkers, ctx->h_lp_dev, out_perstar ? ctx->d_perstar : nullptr, ctx->stream, params,
-                            polled ? reinterpret_cast<unsigned long long *>(ctx->h_lp_dev + 8) : nullptr, seq);
+        rc = launch_logpost(ctx, ctx->work.params.get(), n_walkers, ctx->h_lp.dev(), out_perstar ? ctx->d_perstar.get() : nullptr, ctx->stream, params,
+                            polled ? reinterpret_cast<unsigned long long *>(ctx->h_lp.dev() + 8) : nullptr, seq);
         if (rc) return rc;
     } else {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_params, params, sizeof(double) * B9_NPARAM * n_walkers, hipMemcpyHostToDevice, ctx->stream));
-        rc = b9_logpost_device(ctx, ctx->d_params, n_walkers, ctx->d_logpost, out_perstar ? ctx->d_perstar : nullptr, ctx->stream);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->work.params.get(), params, sizeof(double) * B9_NPARAM * n_walkers, hipMemcpyHostToDevice, ctx->stream));
+        rc = b9_logpost_device(ctx, ctx->work.params.get(), n_walkers, ctx->work.logpost.get(), out_perstar ? ctx->d_perstar.get() : nullptr, ctx->stream);
         if (rc) return rc;
-        HIPCHK(ctx, hipMemcpyAsync(out_logpost, ctx->d_logpost, sizeof(double) * n_walkers, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(out_logpost, ctx->work.logpost.get(), sizeof(double) * n_walkers, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (out_perstar)
-        HIPCHK(ctx, hipMemcpyAsync(out_perstar, ctx->d_perstar, sizeof(double) * (size_t)n_walkers * ctx->st.n,
+        HIPCHK(ctx, hipMemcpyAsync(out_perstar, ctx->d_perstar.get(), sizeof(double) * (size_t)n_walkers * ctx->st.n,
                                    hipMemcpyDeviceToHost, ctx->stream));
     if (polled) {
         // (bounded: a launch that failed never stores its words -- after ~2 ms the stream's own wait takes over and reports)
@@ -146,7 +144,7 @@ int b9_logpost(b9_ctx *ctx, const double *params, int32_t n_walkers, double *out
     } else {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
-    if (small) std::memcpy(out_logpost, ctx->h_lp, sizeof(double) * n_walkers);
+    if (small) std::memcpy(out_logpost, ctx->h_lp.get(), sizeof(double) * n_walkers);
     return B9_OK;
 }
 
@@ -158,44 +156,42 @@ int b9_sample_mass(b9_ctx *ctx, const double *params, int32_t n_rows, uint64_t s
     int rc = check_ready(ctx);
     if (rc) return rc;
     const int n_pops = ctx->opt.n_pops, n = ctx->st.n;
-    const int K = ctx->opt.marg_iso_increm > 0 ? ctx->opt.marg_iso_increm : 1;
-    const int Q = ctx->opt.marg_n_q > 0 ? ctx->opt.marg_n_q : 1;
+    const int K = marg_grid(ctx).K, Q = marg_grid(ctx).Q;
     const int chunk = std::min<int>(n_rows, 32);
     rc = ensure_capacity(ctx, chunk, n_pops, (size_t)partial_stride(ctx) * chunk, false);
     if (rc) return rc;
     rc = ensure_marg_table(ctx, chunk, n_pops, K, Q);
     if (rc) return rc;
-    double *d_out = nullptr;
-    int *d_pop = nullptr;
+    // (allocated per call and released at return: at 50k stars the draws of a chunk are ~45 MB)
     const size_t per = (size_t)chunk * n;
-    HIPCHK(ctx, hipMalloc((void **)&d_out, sizeof(double) * per * 3));
-    if (out_pop && hipMalloc((void **)&d_pop, sizeof(int) * per) != hipSuccess) { (void)hipFree(d_out); return fail(ctx, B9_ERR_HIP, "hipMalloc failed"); }
+    DeviceBuf<double> out;
+    DeviceBuf<int> pop;
+    RESERVE(ctx, out, per * 3);
+    if (out_pop) RESERVE(ctx, pop, per);
+    double *const d_out = out.get();
+    int *const d_pop = pop.get();
     hipStream_t s = ctx->stream;
     const Bufs bf = buffer_set(ctx, 0);
     const McmcDev off{};
-    rc = B9_OK;
-    for (int r0 = 0; r0 < n_rows && rc == B9_OK; r0 += chunk) {
+    for (int r0 = 0; r0 < n_rows; r0 += chunk) {
         const int m = std::min(chunk, n_rows - r0);
-        hipError_t e = hipMemcpyAsync(bf.params, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, sizeof(double) * per * 3, s);     // rows outside the grid write nothing
-        if (e == hipSuccess && d_pop) e = hipMemsetAsync(d_pop, 0, sizeof(int) * per, s);
-        if (e == hipSuccess) e = b9k_derive_iso(ctx->pk, bf.params, m, n_pops, bf.hdr, bf.iso, ctx->iso_stride, ctx->mass_cap, off, ctx->pr,
-                                                B9Prev{nullptr, 0, 0, nullptr, nullptr}, s);
-        B9MargSample smp{d_out, d_out + per, d_out + 2 * per, d_pop, (unsigned)(seed & 0xFFFFFFFFull), (unsigned)(seed >> 32), (long long)(row0 + r0)};
+        HIPCHK(ctx, hipMemcpyAsync(bf.params, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * per * 3, s));     // rows outside the grid write nothing
+        if (d_pop) HIPCHK(ctx, hipMemsetAsync(d_pop, 0, sizeof(int) * per, s));
+        HIPCHK(ctx, b9k_derive_iso(ctx->pk, bf.params, m, n_pops, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap, off, ctx->pr, no_prev(), s));
+        B9MargSample smp{d_out, d_out + per, d_out + 2 * per, d_pop, 0, 0, (long long)(row0 + r0)};
+        split_seed(seed, &smp.k0, &smp.k1);
         // the kernel indexes its outputs [row][n_stars] with the launch's own row count: rows are contiguous for any m
-        if (e == hipSuccess) e = b9k_star_marg(ctx->pk, ctx->st, bf.hdr, bf.iso, ctx->iso_stride, ctx->mass_cap, bf.params, m, n_pops,
-                                               ctx->d_partial, partial_stride(ctx), nullptr, K, Q, &smp, ctx->marg_prune, ctx->d_marg_tab, ctx->d_marg_wd_tab, ctx->d_marg_shares, ctx->n_cu, s);
+        HIPCHK(ctx, b9k_star_marg(ctx->pk, ctx->st, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap, bf.params, m, n_pops,
+                                  ctx->d_partial.get(), partial_stride(ctx), nullptr, K, Q, &smp, ctx->marg_prune, ctx->d_marg_tab.get(), ctx->d_marg_wd_tab.get(), ctx->d_marg_shares.get(), ctx->n_cu, s));
         const size_t cnt = (size_t)m * n, o = (size_t)r0 * n;
-        if (e == hipSuccess) e = hipMemcpyAsync(out_mass + o, d_out, sizeof(double) * cnt, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_ratio + o, d_out + per, sizeof(double) * cnt, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_member + o, d_out + 2 * per, sizeof(double) * cnt, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && d_pop) e = hipMemcpyAsync(out_pop + o, d_pop, sizeof(int) * cnt, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) rc = fail(ctx, B9_ERR_HIP, std::string("b9_sample_mass: ") + hipGetErrorString(e));
+        HIPCHK(ctx, hipMemcpyAsync(out_mass + o, d_out, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(out_ratio + o, d_out + per, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(out_member + o, d_out + 2 * per, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
+        if (d_pop) HIPCHK(ctx, hipMemcpyAsync(out_pop + o, d_pop, sizeof(int) * cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
     }
-    (void)hipFree(d_out);
-    if (d_pop) (void)hipFree(d_pop);
-    return rc;
+    return B9_OK;
 }
 
 int b9_derive_isochrone(b9_ctx *ctx, const double *param_row, int32_t pop, int32_t cap, double *out_mass,
@@ -210,18 +206,18 @@ int b9_derive_isochrone(b9_ctx *ctx, const double *param_row, int32_t pop, int32
     double row[B9_NPARAM];
     std::memcpy(row, param_row, sizeof row);
     if (pop) row[B9_P_Y] = row[B9_P_Y2];
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_params, row, sizeof row, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, b9k_derive_iso(ctx->pk, ctx->d_params, 1, 1, ctx->d_hdr, ctx->d_iso, ctx->iso_stride, ctx->mass_cap, McmcDev{}, ctx->pr, B9Prev{nullptr, 0, 0, nullptr, nullptr}, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->work.params.get(), row, sizeof row, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, b9k_derive_iso(ctx->pk, ctx->work.params.get(), 1, 1, ctx->work.hdr.get(), ctx->work.iso.get(), ctx->work.iso_stride, ctx->work.mass_cap, McmcDev{}, ctx->pr, no_prev(), ctx->stream));
     IsoHdr h;
-    HIPCHK(ctx, hipMemcpyAsync(&h, ctx->d_hdr, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&h, ctx->work.hdr.get(), sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     *out_n = 0; *out_first_eep = 0; *out_agb_tip = 0.0;
     if (!h.valid) return B9_OK;
     if (h.n > cap) return fail(ctx, B9_ERR_CAPACITY, "isochrone longer than the caller's buffers");
     const int nf = ctx->pk.nf, nfp = ctx->pk.nfp;
     std::vector<double> buf((size_t)h.n * nfp);
-    HIPCHK(ctx, hipMemcpy(out_mass, ctx->d_iso, sizeof(double) * h.n, hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(buf.data(), ctx->d_iso + ctx->mass_cap, sizeof(double) * buf.size(), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(out_mass, ctx->work.iso.get(), sizeof(double) * h.n, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(buf.data(), ctx->work.iso.get() + ctx->work.mass_cap, sizeof(double) * buf.size(), hipMemcpyDeviceToHost));
     for (int e = 0; e < h.n; ++e) std::memcpy(&out_mags[(size_t)e * nf], &buf[(size_t)e * nfp], sizeof(double) * nf);
     *out_n = h.n; *out_first_eep = h.first_eep; *out_agb_tip = h.agb_tip;
     return B9_OK;
@@ -243,42 +239,29 @@ int b9_predict_mags(b9_ctx *ctx, const double *param_row, int64_t n, const doubl
     if (n == 0) return B9_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const DevPack &pk = ctx->pk;
-    const int nf = pk.nf, mass_cap = (pk.max_eep + 1) & ~1;
-    const long long iso_stride = (long long)mass_cap * (pk.nfp + 1);
+    const int nf = pk.nf, mass_cap = pack_mass_cap(pk.max_eep);
+    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
     if (b9k_predict_lds(pk.nfp, mass_cap, n_pops) > 160 * 1024)
         return fail(ctx, B9_ERR_CAPACITY, "b9_predict_mags: the derived isochrones do not fit the kernel's LDS");
-    if (!ctx->d_pred_hdr) {
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_pred_hdr, sizeof(IsoHdr) * 2));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_pred_par, sizeof(double) * B9_NPARAM));
-    }
-    if ((size_t)(2 * iso_stride) > ctx->pred_iso_cap) {
-        if (ctx->d_pred_iso) (void)hipFree(ctx->d_pred_iso);
-        ctx->d_pred_iso = nullptr; ctx->pred_iso_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_pred_iso, sizeof(double) * 2 * iso_stride));
-        ctx->pred_iso_cap = (size_t)(2 * iso_stride);
-    }
+    RESERVE(ctx, ctx->d_pred_hdr, 2);
+    RESERVE(ctx, ctx->d_pred_par, B9_NPARAM);
+    RESERVE(ctx, ctx->d_pred_iso, (size_t)(2 * iso_stride));
     // systems in chunks of at most 2^20 (every system's result depends on that system alone, so the chunking is invisible)
     const int64_t chunk = std::min<int64_t>(n, (int64_t)1 << 20);
-    const size_t o_q = sizeof(double) * chunk, o_mags = 2 * o_q, o_wd = o_mags + sizeof(double) * chunk * nf;
-    const size_t o_pop = o_wd + sizeof(int) * chunk, o_stage = o_pop + sizeof(int) * chunk, bytes = o_stage + sizeof(int) * chunk;
-    if (bytes > ctx->pred_io_cap) {
-        if (ctx->d_pred_io) (void)hipFree(ctx->d_pred_io);
-        ctx->d_pred_io = nullptr; ctx->pred_io_cap = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->d_pred_io, bytes));
-        ctx->pred_io_cap = bytes;
-    }
-    char *io = static_cast<char *>(ctx->d_pred_io);
-    double *d_m1 = reinterpret_cast<double *>(io), *d_q = reinterpret_cast<double *>(io + o_q), *d_mags = reinterpret_cast<double *>(io + o_mags);
-    int *d_wd = reinterpret_cast<int *>(io + o_wd), *d_pop = reinterpret_cast<int *>(io + o_pop), *d_stage = reinterpret_cast<int *>(io + o_stage);
+    const PredArena a = pred_arena((size_t)chunk, nf);
+    RESERVE(ctx, ctx->d_pred_io, a.bytes);
+    char *io = ctx->d_pred_io.get();
+    double *d_m1 = part<double>(io, a.o_m1), *d_q = part<double>(io, a.o_q), *d_mags = part<double>(io, a.o_mags);
+    int *d_wd = part<int>(io, a.o_wd), *d_pop = part<int>(io, a.o_pop), *d_stage = part<int>(io, a.o_stage);
     hipStream_t s = ctx->stream;
-    HIPCHK(ctx, b9k_derive_iso_rows(pk, param_row, ctx->d_pred_par, 1, n_pops, ctx->d_pred_hdr, ctx->d_pred_iso, iso_stride, mass_cap, s));
+    HIPCHK(ctx, b9k_derive_iso_rows(pk, param_row, ctx->d_pred_par.get(), 1, n_pops, ctx->d_pred_hdr.get(), ctx->d_pred_iso.get(), iso_stride, mass_cap, s));
     for (int64_t i0 = 0; i0 < n; i0 += chunk) {
         const int64_t m = std::min(chunk, n - i0);
         HIPCHK(ctx, hipMemcpyAsync(d_m1, mass1 + i0, sizeof(double) * m, hipMemcpyHostToDevice, s));
         HIPCHK(ctx, hipMemcpyAsync(d_q, mass_ratio + i0, sizeof(double) * m, hipMemcpyHostToDevice, s));
         if (wd_type) HIPCHK(ctx, hipMemcpyAsync(d_wd, wd_type + i0, sizeof(int) * m, hipMemcpyHostToDevice, s));
         if (pop) HIPCHK(ctx, hipMemcpyAsync(d_pop, pop + i0, sizeof(int) * m, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, b9k_predict_mags(pk, ctx->d_pred_hdr, ctx->d_pred_iso, iso_stride, mass_cap, n_pops, ctx->d_pred_par, m, d_m1, d_q,
+        HIPCHK(ctx, b9k_predict_mags(pk, ctx->d_pred_hdr.get(), ctx->d_pred_iso.get(), iso_stride, mass_cap, n_pops, ctx->d_pred_par.get(), m, d_m1, d_q,
                                      wd_type ? d_wd : nullptr, pop ? d_pop : nullptr, d_mags, d_stage, 4 * ctx->n_cu, s));
         HIPCHK(ctx, hipMemcpyAsync(out_mags + (size_t)i0 * nf, d_mags, sizeof(double) * m * nf, hipMemcpyDeviceToHost, s));
         if (out_stage) HIPCHK(ctx, hipMemcpyAsync(out_stage + i0, d_stage, sizeof(int) * m, hipMemcpyDeviceToHost, s));
@@ -311,28 +294,20 @@ int b9_sample_wd_mass(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t
     const int n_wd = ctx->st.n_wd, n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
     if (n_wd == 0) return B9_OK;
     const DevPack &pk = ctx->pk;
-    const int mass_cap = (pk.max_eep + 1) & ~1;
-    const long long iso_stride = (long long)mass_cap * (pk.nfp + 1);
+    const int mass_cap = pack_mass_cap(pk.max_eep);
+    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
     const size_t tab_row = (size_t)n_pops * (size_t)b9k_wd_table_doubles(pk.nfp, n_nodes);       // doubles per row
     if (tab_row > ((size_t)8 << 30) / sizeof(double)) return fail(ctx, B9_ERR_CAPACITY, "b9_sample_wd_mass: one row's node table would exceed 8 GiB");
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_rows, (size_t)B9_WDS_MAX_ROWS, B9_WDS_TABLE_BYTES / (tab_row * sizeof(double))}));
-    // one allocation: [params][headers][isochrones][table][7 outputs][pop][columns], every part on a 256-byte boundary
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // one allocation: [params][headers][isochrones][table][7 outputs][pop][columns]
     const size_t per = (size_t)chunk * n_wd;
-    const size_t o_hdr = up(sizeof(double) * B9_NPARAM * chunk), o_iso = o_hdr + up(sizeof(IsoHdr) * chunk * n_pops);
-    const size_t o_tab = o_iso + up(sizeof(double) * (size_t)chunk * n_pops * iso_stride), o_out = o_tab + up(sizeof(double) * chunk * tab_row);
-    const size_t o_pop = o_out + up(sizeof(double) * per * 7), o_rank = o_pop + up(sizeof(int) * per), bytes = o_rank + up(sizeof(int) * n);
-    if (bytes > ctx->wds_cap) {
-        if (ctx->d_wds) (void)hipFree(ctx->d_wds);
-        ctx->d_wds = nullptr; ctx->wds_cap = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->d_wds, bytes));
-        ctx->wds_cap = bytes;
-    }
-    char *base = static_cast<char *>(ctx->d_wds);
-    double *d_par = reinterpret_cast<double *>(base), *d_iso = reinterpret_cast<double *>(base + o_iso);
-    double *d_tab = reinterpret_cast<double *>(base + o_tab), *d_out = reinterpret_cast<double *>(base + o_out);
-    IsoHdr *d_hdr = reinterpret_cast<IsoHdr *>(base + o_hdr);
-    int *d_pop = reinterpret_cast<int *>(base + o_pop), *d_rank = reinterpret_cast<int *>(base + o_rank);
+    const WdsArena a = wds_arena((size_t)chunk, n_pops, iso_stride, tab_row, (size_t)n_wd, (size_t)n, sizeof(IsoHdr));
+    RESERVE(ctx, ctx->d_wds, a.bytes);
+    char *base = ctx->d_wds.get();
+    double *d_par = part<double>(base, a.o_par), *d_iso = part<double>(base, a.o_iso);
+    double *d_tab = part<double>(base, a.o_tab), *d_out = part<double>(base, a.o_out);
+    IsoHdr *d_hdr = part<IsoHdr>(base, a.o_hdr);
+    int *d_pop = part<int>(base, a.o_pop), *d_rank = part<int>(base, a.o_rank);
     std::vector<int> rank(n);
     for (int i = 0, k = 0; i < n; ++i) { rank[i] = k; k += ctx->hs.stage[i] == B9_STAGE_WD; }
     hipStream_t s = ctx->stream;
@@ -344,14 +319,14 @@ int b9_sample_wd_mass(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t
         HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
         HIPCHK(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * per * 7, s));        // rows outside the grid write nothing
         HIPCHK(ctx, hipMemsetAsync(d_pop, 0, sizeof(int) * per, s));
-        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, B9Prev{nullptr, 0, 0, nullptr, nullptr}, s));
+        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
         B9WdSample smp{};
         smp.zams = d_out; smp.member = d_out + per;
         smp.wd_mass = out_wd_mass ? d_out + 2 * per : nullptr; smp.prec_log_age = out_prec_log_age ? d_out + 3 * per : nullptr;
         smp.log_cool_age = out_log_cool_age ? d_out + 4 * per : nullptr; smp.log_teff = out_log_teff ? d_out + 5 * per : nullptr;
         smp.logg = out_logg ? d_out + 6 * per : nullptr;
         smp.pop = d_pop; smp.wd_rank = d_rank;
-        smp.k0 = (unsigned)(seed & 0xFFFFFFFFull); smp.k1 = (unsigned)(seed >> 32); smp.row0 = (long long)(row0 + r0);
+        split_seed(seed, &smp.k0, &smp.k1); smp.row0 = (long long)(row0 + r0);
         // the kernel indexes its outputs [row][n_wd] with the launch's own rows: they are contiguous for any m
         HIPCHK(ctx, b9k_wd_sample(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, n_nodes, d_tab, smp, s));
         const size_t cnt = (size_t)m * n_wd, o = (size_t)r0 * n_wd;

@@ -28,16 +28,6 @@ namespace {
 
 constexpr int kMaxPieces = 32;
 
-int upload_ints(b9_ctx *ctx, const std::vector<int> &v, const int **out)
-{
-    void *d = nullptr;
-    HIPCHK(ctx, hipMalloc(&d, sizeof(int) * std::max<size_t>(v.size(), 1)));
-    ctx->marg_plan_allocs.push_back(d);
-    if (!v.empty()) HIPCHK(ctx, hipMemcpy(d, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice));
-    *out = static_cast<const int *>(d);
-    return B9_OK;
-}
-
 // the reference row: the prior means, the three grid coordinates clamped into the pack's axes
 void reference_row(const b9_ctx *ctx, double *row)
 {
@@ -62,21 +52,20 @@ int counting_pass(b9_ctx *ctx, const double *row, int K, int Q, std::vector<unsi
 {
     const int n_pops = ctx->opt.n_pops, n_mc = ctx->st.mg_pad / 64;
     const Bufs bf = buffer_set(ctx, 0);
-    unsigned *d_cost = nullptr;
-    HIPCHK(ctx, hipMalloc((void **)&d_cost, sizeof(unsigned) * 4 * n_mc));
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemsetAsync(d_cost, 0, sizeof(unsigned) * 4 * n_mc, s);
-    if (e == hipSuccess) e = b9k_derive_iso_rows(ctx->pk, row, bf.params, 1, n_pops, bf.hdr, bf.iso, ctx->iso_stride, ctx->mass_cap, s);
-    if (e == hipSuccess) e = b9k_marg_tables(ctx->pk, bf.hdr, bf.iso, ctx->iso_stride, ctx->mass_cap, bf.params, 1, n_pops, K, Q, ctx->d_marg_tab, nullptr, s);
-    if (e == hipSuccess) e = b9k_star_marg_cost(ctx->pk, ctx->st, bf.hdr, ctx->mass_cap, bf.params, n_pops, ctx->d_partial, partial_stride(ctx), K, Q,
-                                                ctx->marg_prune, ctx->d_marg_tab, d_cost, s);
-    h_cost.assign(4 * (size_t)n_mc, 0u);
     std::vector<IsoHdr> h_hdr(n_pops);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_cost.data(), d_cost, sizeof(unsigned) * h_cost.size(), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_hdr.data(), bf.hdr, sizeof(IsoHdr) * n_pops, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_cost);
-    if (e != hipSuccess) return fail(ctx, B9_ERR_HIP, std::string("marginalised catalogue plan: ") + hipGetErrorString(e));
+    DeviceBuf<unsigned> cost;            // (of this call alone: released at return, before the host arrays it is copied into)
+    RESERVE(ctx, cost, (size_t)4 * n_mc);
+    unsigned *const d_cost = cost.get();
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, hipMemsetAsync(d_cost, 0, sizeof(unsigned) * 4 * n_mc, s));
+    HIPCHK(ctx, b9k_derive_iso_rows(ctx->pk, row, bf.params, 1, n_pops, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap, s));
+    HIPCHK(ctx, b9k_marg_tables(ctx->pk, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap, bf.params, 1, n_pops, K, Q, ctx->d_marg_tab.get(), nullptr, s));
+    HIPCHK(ctx, b9k_star_marg_cost(ctx->pk, ctx->st, bf.hdr, ctx->work.mass_cap, bf.params, n_pops, ctx->d_partial.get(), partial_stride(ctx), K, Q,
+                                   ctx->marg_prune, ctx->d_marg_tab.get(), d_cost, s));
+    h_cost.assign(4 * (size_t)n_mc, 0u);
+    HIPCHK(ctx, hipMemcpyAsync(h_cost.data(), d_cost, sizeof(unsigned) * h_cost.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(h_hdr.data(), bf.hdr, sizeof(IsoHdr) * n_pops, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
     valid = true;
     for (int k = 0; k < n_pops; ++k) valid = valid && h_hdr[k].valid;
     return B9_OK;
@@ -91,8 +80,8 @@ int ensure_marg_plan(b9_ctx *ctx)
     if (ctx->opt.mode != B9_MODE_MARGINALISED || ctx->marg_plan_ok) return B9_OK;
     if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
     const int n_pops = ctx->opt.n_pops, n_mc = ctx->st.mg_pad / 64;
-    const int K = ctx->opt.marg_iso_increm > 0 ? ctx->opt.marg_iso_increm : 1, Q = ctx->opt.marg_n_q > 0 ? ctx->opt.marg_n_q : 1;
-    free_all(ctx->marg_plan_allocs);
+    const int K = marg_grid(ctx).K, Q = marg_grid(ctx).Q;
+    ctx->marg_plan_allocs.clear();
     // back to the load-time order (until the plan's own is in place)
     ctx->st.mg_n_pieces = 0; ctx->st.mg_piece = nullptr; ctx->st.mg_share_base = nullptr;
     ctx->st.marg_order = ctx->marg_order_spread;
@@ -122,7 +111,7 @@ int ensure_marg_plan(b9_ctx *ctx)
         ctx->marg_cost = cost;
         std::iota(order.begin(), order.end(), 0);
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-        if ((rc = upload_ints(ctx, order, &ctx->st.marg_order))) return rc;
+        if ((rc = upload(ctx, ctx->marg_plan_allocs, order.data(), order.size(), &ctx->st.marg_order))) return rc;
     } else {
         HIPCHK(ctx, hipMemcpy(order.data(), ctx->marg_order_spread, sizeof(int) * n_mc, hipMemcpyDeviceToHost));
         std::fill(cost.begin(), cost.end(), 1.0);
@@ -156,8 +145,8 @@ int ensure_marg_plan(b9_ctx *ctx)
         if (ctx->plan_debug > 1)
             for (size_t k = 0; k < pieces.size(); ++k)
                 fprintf(stderr, "[marg plan] position %zu: chunk %d piece %d of %d, chunk cost %.0f\n", k, pieces[k] & 0xFFFFF, (pieces[k] >> 20) & 31, (pieces[k] >> 25) & 63, cost[pieces[k] & 0xFFFFF]);
-        if ((rc = upload_ints(ctx, pieces, &ctx->st.mg_piece))) return rc;
-        if ((rc = upload_ints(ctx, base, &ctx->st.mg_share_base))) return rc;
+        if ((rc = upload(ctx, ctx->marg_plan_allocs, pieces.data(), pieces.size(), &ctx->st.mg_piece))) return rc;
+        if ((rc = upload(ctx, ctx->marg_plan_allocs, base.data(), base.size(), &ctx->st.mg_share_base))) return rc;
     }
     ctx->marg_plan_ok = true;
     return B9_OK;

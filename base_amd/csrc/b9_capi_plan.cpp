@@ -7,10 +7,10 @@ namespace b9i {
 // Workgroups of the fused step resident at once for the loaded pack and options (occupancy query of that instantiation, cached)
 int step_slots(b9_ctx *ctx, int n_pops)
 {
-    const int key = (ctx->pk.nfp * 4 + n_pops) * 65536 + ctx->mass_cap;
+    const int key = (ctx->pk.nfp * 4 + n_pops) * 65536 + ctx->work.mass_cap;
     if (ctx->step_occ_key != key) {
         int per_cu = 0;
-        if (b9k_mcmc_step_occupancy(ctx->pk, n_pops, ctx->mass_cap, &per_cu) != hipSuccess || per_cu < 1) per_cu = 1;
+        if (b9k_mcmc_step_occupancy(ctx->pk, n_pops, ctx->work.mass_cap, &per_cu) != hipSuccess || per_cu < 1) per_cu = 1;
         ctx->step_blocks_per_cu = per_cu;
         ctx->step_occ_key = key;
     }
@@ -59,7 +59,7 @@ B9Groups make_plan(b9_ctx *ctx, int n_walkers, int n_pops)
     const Groups gr = make_groups(ctx, n_pops);
     const long long tiles_wanted = std::max<long long>(1, std::min<long long>(8, (long long)(ctx->st.n_pad / 256) * n_walkers / 4096));
     const B9Groups plan = with_groups_per_block(gr, (int)(tiles_wanted / gr.group_tiles));
-    const int key = ((ctx->pk.nfp * 4 + n_pops) * 65536 + ctx->mass_cap) * 64 + plan.group_tiles;
+    const int key = ((ctx->pk.nfp * 4 + n_pops) * 65536 + ctx->work.mass_cap) * 64 + plan.group_tiles;
     if (ctx->plan_debug && ctx->opt.mode != B9_MODE_MARGINALISED &&
         (ctx->logpost_plan_debug_key != key || ctx->logpost_plan_debug_walkers != n_walkers || ctx->logpost_plan_debug_groups != plan.n_groups)) {
         ctx->logpost_plan_debug_key = key; ctx->logpost_plan_debug_walkers = n_walkers; ctx->logpost_plan_debug_groups = plan.n_groups;
@@ -81,8 +81,8 @@ StepPlan make_step_plan(b9_ctx *ctx, int n_walkers, int n_pops)
     StepPlan sp;
     const Groups gr = make_groups(ctx, n_pops);
     const int slots = step_slots(ctx, n_pops);
-    const int key = (ctx->pk.nfp * 4 + n_pops) * 65536 + ctx->mass_cap;
-    const int full_parts = (ctx->mass_cap * (ctx->pk.nfp + 1) + 255) / 256;
+    const int key = (ctx->pk.nfp * 4 + n_pops) * 65536 + ctx->work.mass_cap;
+    const int full_parts = (ctx->work.mass_cap * (ctx->pk.nfp + 1) + 255) / 256;
     const int m_max = std::max(1, 8 / gr.group_tiles);
     int m = 1;
     while (m < m_max && (long long)((gr.n_groups + m - 1) / m) * n_pops * n_walkers > (long long)(hot_fill(n_pops) * slots)) ++m;
@@ -160,16 +160,16 @@ TreePlan make_tree_plan(b9_ctx *ctx, int n_walkers, int n_pops)
     if (ctx->tree_depth == 1) return tp;
     const Groups gr = make_groups(ctx, n_pops);
     if (gr.n_groups > B9_TREE_MAX_GROUPS) return tp;        // more canonical groups than a walk reads: the one-step launch
-    const int key = ((ctx->pk.nfp * 4 + n_pops) * 65536 + ctx->mass_cap) * 2 + (gr.n_groups > 16 * B9_TREE_KD_SMALL ? 1 : 0);
+    const int key = ((ctx->pk.nfp * 4 + n_pops) * 65536 + ctx->work.mass_cap) * 2 + (gr.n_groups > 16 * B9_TREE_KD_SMALL ? 1 : 0);
     if (ctx->tree_occ_key != key) {
         int per_cu = 0;
-        if (b9k_mcmc_tree_occupancy(ctx->pk, n_pops, ctx->mass_cap, gr.n_groups, &per_cu) != hipSuccess || per_cu < 1) per_cu = 1;
+        if (b9k_mcmc_tree_occupancy(ctx->pk, n_pops, ctx->work.mass_cap, gr.n_groups, &per_cu) != hipSuccess || per_cu < 1) per_cu = 1;
         ctx->tree_blocks_per_cu = per_cu;
         ctx->tree_occ_key = key;
     }
     const long long slots = (long long)ctx->n_cu * ctx->tree_blocks_per_cu;
     const int n_tiles = ctx->st.n_pad / 256;
-    const int full_parts = (ctx->mass_cap * (ctx->pk.nfp + 1) + 255) / 256;
+    const int full_parts = (ctx->work.mass_cap * (ctx->pk.nfp + 1) + 255) / 256;
     for (int d = B9_TREE_MAX_DEPTH; d >= 2; --d) {
         if (ctx->tree_depth >= 2 && d != ctx->tree_depth) continue;          // pinned
         const long long NN = (1 << d) - 1, NO = 1 << d;
@@ -211,26 +211,11 @@ TreePlan make_tree_plan(b9_ctx *ctx, int n_walkers, int n_pops)
 
 int ensure_tree_buffers(b9_ctx *ctx, int n_walkers, int n_pops, const TreePlan &tp)
 {
-    const size_t NN = (1u << tp.depth) - 1, NO = 1u << tp.depth;
-    const size_t n_cand = (size_t)2 * n_walkers * NO * NN;
-    if (n_cand * n_pops > ctx->tree_cand_cap || ctx->tree_iso_stride != ctx->iso_stride) {
-        for (void *p : {(void *)ctx->d_tree_hdr, (void *)ctx->d_tree_iso, (void *)ctx->d_tree_par}) if (p) (void)hipFree(p);
-        ctx->d_tree_hdr = nullptr; ctx->d_tree_iso = nullptr; ctx->d_tree_par = nullptr; ctx->tree_cand_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_tree_hdr, sizeof(IsoHdr) * n_cand * n_pops));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_tree_iso, sizeof(double) * (size_t)ctx->iso_stride * n_cand * n_pops));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_tree_par, sizeof(double) * B9_NPARAM * n_cand));
-        HIPCHK(ctx, hipMemset(ctx->d_tree_hdr, 0, sizeof(IsoHdr) * n_cand * n_pops));
-        ctx->tree_cand_cap = n_cand * n_pops; ctx->tree_iso_stride = ctx->iso_stride;
-    }
-    const size_t part_stride = ((size_t)tp.n_groups * 4 + ctx->heavy_parts + 1) & ~(size_t)1;
-    const size_t n_part = (size_t)2 * n_walkers * NN * part_stride;
-    if (n_part > ctx->tree_partial_cap) {
-        if (ctx->d_tree_partial) (void)hipFree(ctx->d_tree_partial);
-        ctx->d_tree_partial = nullptr; ctx->tree_partial_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_tree_partial, sizeof(double) * n_part));
-        HIPCHK(ctx, hipMemset(ctx->d_tree_partial, 0, sizeof(double) * n_part));
-        ctx->tree_partial_cap = n_part;
-    }
+    auto &t = ctx->tree;
+    const Reserved r = t.ensure(n_walkers, n_pops, tp.depth, ctx->work.iso_stride, tp.n_groups, ctx->heavy_parts);
+    if (r.err) return alloc_failed(ctx, r);
+    if (t.hdr_fresh) HIPCHK(ctx, hipMemset(t.hdr.get(), 0, sizeof(IsoHdr) * t.hdr.capacity()));
+    if (t.partial_fresh) HIPCHK(ctx, hipMemset(t.partial.get(), 0, sizeof(double) * t.partial.capacity()));
     return B9_OK;
 }
 

@@ -6,18 +6,6 @@ using namespace b9i;
 
 namespace {
 
-template <class T>
-int upload(b9_ctx *ctx, std::vector<void *> &owner, const T *src, size_t count, const T **out)
-{
-    void *d = nullptr;
-    size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    HIPCHK(ctx, hipMalloc(&d, bytes));
-    owner.push_back(d);
-    if (count) HIPCHK(ctx, hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *out = static_cast<const T *>(d);
-    return B9_OK;
-}
-
 bool ascending(const double *a, int n)
 {
     for (int i = 1; i < n; ++i)
@@ -59,7 +47,7 @@ int build_stars(b9_ctx *ctx)
     const HostStars &h = ctx->hs;
     const int n = h.n, nf = h.nf, nfp = ctx->pk.nfp;
     if (nf != ctx->pk.nf) return fail(ctx, B9_ERR_INVALID, "stars and pack disagree on n_filt");
-    free_all(ctx->star_allocs);
+    ctx->star_allocs.clear();
     std::vector<int> order(n);
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
@@ -240,7 +228,7 @@ int build_stars(b9_ctx *ctx)
     ctx->st = st;
     ctx->marg_order_spread = st.marg_order;
     ctx->marg_plan_ok = false;
-    free_all(ctx->marg_plan_allocs);
+    ctx->marg_plan_allocs.clear();
     ctx->marg_cost.clear();
     ctx->n_wd_stage = 0;
     for (int i = 0; i < n; ++i) ctx->n_wd_stage += h.stage[i] == B9_STAGE_WD;
@@ -296,7 +284,7 @@ int b9_load_pack(b9_ctx *ctx, const b9_pack *p)
         }
     }
 
-    free_all(ctx->pack_allocs);
+    ctx->pack_allocs.clear();
     ctx->have_pack = false;
     DevPack d{};
     d.nf = p->n_filt; d.nfp = padded_filters(p->n_filt);

@@ -6,10 +6,14 @@
 //   b9_capi_margplan.cpp  the marginalised mode's catalogue plan: measured dispatch order, pieces of small catalogues
 //   b9_capi_eval.cpp    b9_logpost / b9_logpost_device / b9_sample_mass / b9_derive_isochrone / b9_predict_mags / b9_sample_wd_mass
 //   b9_capi_blocks.cpp  the sampler's device-resident blocks (fused, tree-speculative, two-launch), b9_mcmc_run_block / b9_mcmc_wait
+// and, shared by all of them,
+//   b9_devbuf.h         who owns the memory: the owning buffer, the upload list, the arena carve, the sizing rules (no HIP in it;
+//                       the two allocation policies below give it hipMalloc and mapped hipHostMalloc)
 #pragma once
 #include "../../include/base9_hip.h"
 #include "b9_device.h"
 #include "b9_launch.h"
+#include "b9_devbuf.h"
 
 #include <algorithm>
 #include <cmath>
@@ -44,6 +48,31 @@ struct BlockLayout {
     size_t o_cur = 0, o_lp = 0;                               // two-launch: [cur] and [lp], two halves each
 };
 
+// b9_devbuf.h's allocation policies: device memory, and pinned host memory mapped into the device
+struct DeviceAlloc {
+    static int alloc(void **p, void **dev, size_t bytes)
+    {
+        const hipError_t e = hipMalloc(p, bytes);
+        *dev = *p = e == hipSuccess ? *p : nullptr;
+        return (int)e;
+    }
+    static void release(void *p) { (void)hipFree(p); }
+    static int copy_in(void *dst, const void *src, size_t bytes) { return (int)hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
+};
+struct MappedAlloc {
+    static int alloc(void **p, void **dev, size_t bytes)
+    {
+        hipError_t e = hipHostMalloc(p, bytes, hipHostMallocMapped);
+        if (e != hipSuccess) { *p = nullptr; return (int)e; }
+        if ((e = hipHostGetDevicePointer(dev, *p, 0)) != hipSuccess) { (void)hipHostFree(*p); *p = nullptr; }
+        return (int)e;
+    }
+    static void release(void *p) { (void)hipHostFree(p); }
+};
+template <class T> using DeviceBuf = Buf<T, DeviceAlloc>;
+template <class T> using PinnedBuf = Buf<T, MappedAlloc>;      // get(): the host's view, dev(): the device's
+using Uploads = UploadList<DeviceAlloc>;
+
 }  // namespace b9i
 
 struct b9_ctx {
@@ -53,44 +82,34 @@ struct b9_ctx {
 
     bool have_pack = false;
     DevPack pk{};
-    std::vector<void *> pack_allocs;
+    b9i::Uploads pack_allocs;
 
     bool have_stars = false, stars_dirty = false;
     b9i::HostStars hs;
     DevStars st{};
-    std::vector<void *> star_allocs;
+    b9i::Uploads star_allocs;
 
     DevPriors pr{};
     b9_options opt{B9_MODE_GIVEN_MASS, 1, 8, 8};
 
-    // per-call work buffers (grown on demand, never shrunk)
-    int cap_walkers = 0, cap_pops = 0;
-    IsoHdr *d_hdr = nullptr;
-    double *d_iso = nullptr;
-    long long iso_stride = 0;
-    int mass_cap = 0;
-    double *d_partial = nullptr;
-    size_t partial_cap = 0;
-    double *d_params = nullptr, *d_logpost = nullptr, *d_perstar = nullptr;
-    size_t perstar_cap = 0;
-    double *d_marg_tab = nullptr;    // marginalised mode: the companions' flux table of the current call (k_marg_table)
-    size_t marg_tab_cap = 0;
-    double *d_marg_wd_tab = nullptr; // ... and the WD-stage stars' node table (k_marg_wd_table)
-    size_t marg_wd_tab_cap = 0;
-    double *d_marg_shares = nullptr; // ... and the per-star shares of a split k_star_marg launch (small catalogues)
-    size_t marg_shares_cap = 0;
+    // per-call work buffers (grown on demand, never shrunk; every buffer carries its own capacity)
+    b9i::WorkBufs<IsoHdr, b9i::DeviceAlloc> work;   // isochrone headers, isochrones, parameter rows, log-posteriors: four sets, one key
+    b9i::DeviceBuf<double> d_partial, d_perstar;
+    b9i::DeviceBuf<double> d_marg_tab;       // marginalised mode: the companions' flux table of the current call (k_marg_table)
+    b9i::DeviceBuf<double> d_marg_wd_tab;    // ... and the WD-stage stars' node table (k_marg_wd_table)
+    b9i::DeviceBuf<double> d_marg_shares;    // ... and the per-star shares of a split k_star_marg launch (small catalogues)
     // the marginalised mode's catalogue plan (b9_capi_margplan.cpp): measured dispatch order and pieces; remade after the stars,
     // the pack, the priors or the options change
     bool marg_plan_ok = false;
     int marg_piece_units = 0;                 // b9_tuning.marg_piece_units: 0 = default
-    std::vector<void *> marg_plan_allocs;
+    b9i::Uploads marg_plan_allocs;
     const int *marg_order_spread = nullptr;   // the load-time order (photometric spread), owned by star_allocs
     std::vector<double> marg_cost;            // measured cost per star chunk (units; empty: not measured)
     std::vector<double> h_log_age, h_feh, h_y;   // host copies of the pack's grid axes (the plan's reference row is clamped into them)
     struct McmcSlot {                // one enqueued sampler block of any runner: device block, pinned mirror, events, and what
                                      // b9_mcmc_wait and a B9_BLOCK_CONTINUE successor need to find its results
-        void *d = nullptr, *h = nullptr, *h_dev = nullptr;   // h_dev: the pinned mirror as the device sees it (mapped)
-        size_t cap = 0, hcap = 0;
+        b9i::DeviceBuf<double> d;
+        b9i::PinnedBuf<double> h;          // the pinned mirror (mapped: h.dev() is the device's view of it)
         hipEvent_t done = nullptr;         // recorded behind the block's last command (the download, unless the block is zero-copy)
         hipEvent_t rows_ready = nullptr;   // recorded right after the block's last kernel: the summary rows are in HBM
         bool in_flight = false;
@@ -103,7 +122,7 @@ struct b9_ctx {
     } slot[2];
     int next_slot = 0, last_slot = -1;
     const char *cont_dropped_by = nullptr;   // the configuration call that dropped last_slot (drop_continuation); open_block names it
-    double *h_lp = nullptr, *h_lp_dev = nullptr;   // b9_logpost: 8 log-posteriors + 8 completion words in mapped pinned host memory (host / device view)
+    b9i::PinnedBuf<double> h_lp;                   // b9_logpost: 8 log-posteriors + 8 completion words in mapped pinned host memory
     unsigned long long lp_seq = 0;                 // ... and the number of the call the completion words announce
 
     // launch plan
@@ -125,24 +144,18 @@ struct b9_ctx {
     int tree_depth = 0;              // b9_tuning.tree_depth: 0 = automatic
     int tree_blocks_per_cu = 0, tree_occ_key = -1;   // k_mcmc_tree workgroups per CU, and the key it was queried for
     // candidate buffers of the tree-speculative step (grown on demand): [2 parities][W][outcomes][nodes]([pops])
-    IsoHdr *d_tree_hdr = nullptr;
-    double *d_tree_iso = nullptr, *d_tree_par = nullptr, *d_tree_partial = nullptr;
-    size_t tree_cand_cap = 0, tree_partial_cap = 0;
-    long long tree_iso_stride = 0;
+    b9i::TreeBufs<IsoHdr, b9i::DeviceAlloc> tree;
 
     // b9_predict_mags: buffers of its own (grown on demand, never shrunk), so that a call leaves everything a sampler block
     // keeps on the device -- work buffers, candidate isochrones, final state -- untouched
-    IsoHdr *d_pred_hdr = nullptr;    // [2] one per population
-    double *d_pred_iso = nullptr;    // [2][iso_stride]
-    double *d_pred_par = nullptr;    // [B9_NPARAM]
-    size_t pred_iso_cap = 0;         // doubles of d_pred_iso
-    void *d_pred_io = nullptr;       // one chunk of systems: mass1, mass ratio, magnitudes, then wd_type, pop, stage
-    size_t pred_io_cap = 0;          // bytes
+    b9i::DeviceBuf<IsoHdr> d_pred_hdr;    // [2] one per population
+    b9i::DeviceBuf<double> d_pred_iso;    // [2][iso_stride]
+    b9i::DeviceBuf<double> d_pred_par;    // [B9_NPARAM]
+    b9i::DeviceBuf<char> d_pred_io;       // one chunk of systems (pred_arena): mass1, mass ratio, magnitudes, then wd_type, pop, stage
 
     // b9_sample_wd_mass: one allocation of its own (grown on demand, never shrunk), for the same reason: a chunk of rows'
-    // parameters, headers, derived isochrones and node table, the chunk's outputs, the stars' columns
-    void *d_wds = nullptr;
-    size_t wds_cap = 0;              // bytes
+    // parameters, headers, derived isochrones and node table, the chunk's outputs, the stars' columns (wds_arena)
+    b9i::DeviceBuf<char> d_wds;
 
     // timing of the dominant kernel
     int timing = 0;            // 0 off, n > 0: bracket every n-th launch of the dominant kernel with events
@@ -153,7 +166,7 @@ struct b9_ctx {
     int timing_group = 8;            // fused step: a bracket spans this many consecutive launches (B9_TIMING_GROUP)
     double ms_accum = 0.0;
     int launches = 0;
-    unsigned long long *d_clock = nullptr;   // b9_clock_stamp: [2 stamps][B9_CLOCK_SLOTS]{s_memtime, s_memrealtime}
+    b9i::DeviceBuf<unsigned long long> d_clock;   // b9_clock_stamp: [2 stamps][B9_CLOCK_SLOTS]{s_memtime, s_memrealtime}
 };
 
 namespace b9i {
@@ -187,11 +200,33 @@ inline void drop_continuation(b9_ctx *ctx, const char *call)
     ctx->cont_dropped_by = call;
 }
 
-inline void free_all(std::vector<void *> &v)
+// a failed reservation or upload as the call's error: names the buffer and the bytes asked for
+inline int alloc_failed(b9_ctx *ctx, const Reserved &r)
 {
-    for (void *p : v) (void)hipFree(p);
-    v.clear();
+    return fail(ctx, B9_ERR_HIP, std::string(r.what) + ": allocating " + std::to_string(r.bytes) + " bytes: " + hipGetErrorString((hipError_t)r.err));
 }
+#define RESERVE(ctx, buf, count)                                                              \
+    do {                                                                                      \
+        if (const Reserved r_ = (buf).reserve(count); r_.err) return alloc_failed(ctx, named(r_, #buf)); \
+    } while (0)
+
+template <class T>
+int upload(b9_ctx *ctx, Uploads &owner, const T *src, size_t count, const T **out)
+{
+    const Reserved r = b9i::upload<T, DeviceAlloc>(owner, src, count, out);
+    return r.err ? alloc_failed(ctx, r) : B9_OK;
+}
+
+// the marginalisation grid in force: nodes per EEP interval, mass ratios (an option left at 0 counts as 1)
+struct MargGrid { int K, Q; };
+inline MargGrid marg_grid(const b9_ctx *ctx)
+{
+    return MargGrid{ctx->opt.marg_iso_increm > 0 ? ctx->opt.marg_iso_increm : 1, ctx->opt.marg_n_q > 0 ? ctx->opt.marg_n_q : 1};
+}
+// k_derive_iso with no previous step to finish
+inline B9Prev no_prev() { return B9Prev{nullptr, 0, 0, nullptr, nullptr}; }
+// a 64-bit seed as the RNG's two key words
+inline void split_seed(uint64_t seed, unsigned *k0, unsigned *k1) { *k0 = (unsigned)(seed & 0xFFFFFFFFull); *k1 = (unsigned)(seed >> 32); }
 
 // ---- b9_capi_stage.cpp
 int build_stars(b9_ctx *ctx);

@@ -88,7 +88,7 @@ struct DevStars {
     // (the prior means), counted once per (catalogue, pack, priors, options) by a pass of the kernel itself
     // (b9_capi_margplan.cpp); before that pass, and when the reference row lies outside the grid: photometric spread.
     const int *marg_order;           // [mg_pad / 64]
-    // Small catalogues (fewer star chunks than the chip has workgroup slots): a chunk's window is shared by 1 .. 16 workgroups
+    // Small catalogues (fewer star chunks than the chip has workgroup slots): a chunk's window is shared by 1 .. 32 workgroups
     // ("pieces": piece s of n takes the node chunks s, s + n, ...), as many as its measured cost asks for, so that the pieces
     // cost about the same and the launch does not last as long as its heaviest chunk of giants.  mg_piece: dispatch order
     // (most expensive piece first) of (chunk | piece << 20 | pieces of the chunk << 25); mg_share_base[c]: first piece id of
