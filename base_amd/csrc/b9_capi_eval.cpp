@@ -1,6 +1,7 @@
 // b9_capi_eval.cpp -- one log-posterior evaluation through the C ABI: derive -> stars -> finalize (b9_logpost,
 // b9_logpost_device), the per-star mass draws (b9_sample_mass), the isochrone dump (b9_derive_isochrone) and the forward
-// model alone (b9_predict_mags) and the WD-stage stars' posterior draws (b9_sample_wd_mass).
+// model alone (b9_predict_mags) the WD-stage stars' posterior draws (b9_sample_wd_mass) and the
+// per-star posterior moments (b9_star_moments).
 #include "b9_ctx.h"
 #include <algorithm>
 #include <atomic>
@@ -335,6 +336,53 @@ int b9_sample_wd_mass(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t
         if (out_pop) HIPCHK(ctx, hipMemcpyAsync(out_pop + o, d_pop, sizeof(int) * cnt, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipStreamSynchronize(s));      // (the next chunk reuses the same device buffers)
     }
+    return B9_OK;
+}
+
+// Rows are worked in chunks of at most B9_MOM_MAX_ROWS, and of as few rows as keep the chunk's increments within B9_MOM_SCRATCH_BYTES.
+#define B9_MOM_SCRATCH_BYTES ((size_t)64 << 20)
+#define B9_MOM_MAX_ROWS 32
+
+int b9_star_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags, double *acc)
+{
+    if (!ctx || !params || !acc || n_rows < 1) return B9_ERR_INVALID;
+    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
+    if (!ctx->have_pack || !ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
+    const int n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
+    const int K = marg_grid(ctx).K, Q = marg_grid(ctx).Q;
+    if (n == 0) return B9_OK;
+    const DevPack &pk = ctx->pk;
+    const int mass_cap = pack_mass_cap(pk.max_eep);
+    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
+    const size_t tab_row = (size_t)n_pops * (size_t)b9k_marg_table_doubles(pk.nfp, mass_cap, K, Q);
+    const size_t wd_row = ctx->st.n_wd > 0 ? (size_t)n_pops * (size_t)b9k_marg_wd_table_doubles(pk.nfp, K) : 0;
+    const size_t chunk = mom_chunk_rows((size_t)n_rows, (size_t)n, B9_MOM_N, B9_MOM_MAX_ROWS, B9_MOM_SCRATCH_BYTES);
+    if (chunk * (tab_row + wd_row) > ((size_t)8 << 30) / sizeof(double))
+        return fail(ctx, B9_ERR_CAPACITY, "b9_star_moments: marginalisation grid too fine: the node tables would exceed 8 GiB");
+    // one allocation: [params][headers][isochrones][table][WD table][increments][accumulators]
+    const MomArena a = mom_arena(chunk, n_pops, iso_stride, tab_row, wd_row, (size_t)n, B9_MOM_N, sizeof(IsoHdr));
+    RESERVE(ctx, ctx->d_mom, a.bytes);
+    char *base = ctx->d_mom.get();
+    double *d_par = part<double>(base, a.o_par), *d_iso = part<double>(base, a.o_iso), *d_tab = part<double>(base, a.o_tab);
+    double *d_wd = wd_row ? part<double>(base, a.o_wd) : nullptr, *d_scratch = part<double>(base, a.o_scratch), *d_acc = part<double>(base, a.o_acc);
+    IsoHdr *d_hdr = part<IsoHdr>(base, a.o_hdr);
+    const size_t acc_bytes = sizeof(double) * (size_t)n * B9_MOM_N;
+    hipStream_t s = ctx->stream;
+    if (flags & B9_MOM_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_acc, acc, acc_bytes, hipMemcpyHostToDevice, s));
+    else HIPCHK(ctx, hipMemsetAsync(d_acc, 0, acc_bytes, s));
+    const McmcDev off{};
+    for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
+        const int m = std::min((int)chunk, n_rows - r0);
+        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
+        // every (row, star) of the chunk writes its eight increments (zeros where it contributes nothing): no clearing
+        HIPCHK(ctx, b9k_star_moments(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, K, Q, ctx->marg_prune, d_tab, d_wd,
+                                     d_scratch, d_acc, s));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(acc, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
     return B9_OK;
 }
 

@@ -109,6 +109,24 @@ inline WdsArena wds_arena(size_t chunk, int n_pops, long long iso_stride, size_t
     return a;
 }
 
+// b9_star_moments' chunk of rows: [params][headers][isochrones][node table][WD node table][per-(row, star) increments], then the
+// accumulators (tab_row / wd_row: doubles of one row's two tables, all populations; n_mom: increments per star)
+struct MomArena { size_t o_par, o_hdr, o_iso, o_tab, o_wd, o_scratch, o_acc, bytes; };
+inline MomArena mom_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t wd_row, size_t n_stars, size_t n_mom, size_t hdr_bytes)
+{
+    Carve c;
+    MomArena a{c.take(8 * B9_NPARAM * chunk), c.take(hdr_bytes * chunk * n_pops), c.take(8 * chunk * n_pops * (size_t)iso_stride), c.take(8 * chunk * tab_row),
+               c.take(8 * chunk * wd_row), c.take(8 * chunk * n_stars * n_mom), c.take(8 * n_stars * n_mom), 0};
+    a.bytes = c.total;
+    return a;
+}
+// rows of a chunk: at most max_rows, and as few as keep the scratch [rows][n_stars][n_mom] within scratch_bytes (never less than one)
+inline size_t mom_chunk_rows(size_t n_rows, size_t n_stars, size_t n_mom, size_t max_rows, size_t scratch_bytes)
+{
+    const size_t per_row = std::max<size_t>(1, 8 * n_stars * n_mom);
+    return std::max<size_t>(1, std::min({n_rows, max_rows, scratch_bytes / per_row}));
+}
+
 // ---- sizing rules
 
 // rows of a derived isochrone: the pack's longest one, rounded up to even; and its doubles: a mass column + nfp magnitude columns

@@ -27,6 +27,8 @@
 //                                     one lane per system, predicted apparent magnitudes + stage
 //   k_wd_node_table / k_wd_sample      b9_sample_wd_mass: the WD chain once per node of the call's own grid with its
 //                                     derived values kept, then one lane per WD-stage star against the table
+//   k_star_moments / _wd / k_moments_accumulate   b9_star_moments: exact per-star posterior moments over the marginalisation
+//                                     grid (one lane per star, four waves sharing the node table), summed over the rows
 //
 // The kernels live in the *.hip.h files included below (one translation unit); this file holds
 // k_finalize and the host-callable launch wrappers.
@@ -67,6 +69,7 @@ namespace tree_kd5 {
 #include "b9_marg_step.hip.h"
 #include "b9_predict.hip.h"
 #include "b9_wd_sample.hip.h"
+#include "b9_star_moments.hip.h"
 
 // ------------------------------------------------------------------------------------------
 // k_finalize: one workgroup per walker: fixed-order sum of the partials + prior -> logpost[w]
@@ -275,6 +278,31 @@ static void launch_marg_wd_table(const DevPack &pk, const IsoHdr *hdr, const dou
 {
     hipLaunchKernelGGL((k_marg_wd_table<NFP>), dim3(n_walkers * n_pops, (8 * K + 63) / 64), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride,
                        mass_cap, n_pops, d_params, K, wd_tab, n_walkers * n_pops);
+}
+
+// ---- b9_star_moments: the node tables of a chunk of rows into the call's own buffers, the stars' increments, the accumulation -----
+hipError_t b9k_star_moments(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                            const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, double *tab, double *wd_tab,
+                            double *scratch, double *acc, hipStream_t stream)
+{
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        if (!tab || !scratch || !acc || n_rows < 1 || n_rows > 65535 || (st.n_wd > 0 && !wd_tab)) return hipErrorInvalidValue;
+        const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
+        const hipError_t e = launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, tab, stream);
+        if (e != hipSuccess) return e;
+        const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
+        hipLaunchKernelGGL((k_star_moments<NFP, NPOPS>), dim3(st.mg_pad / 64, n_rows), dim3(256), 0, stream, st, hdr, iso_data, iso_stride, mass_cap,
+                           d_params, K, Q, (const double *)tab, L, cut2, scratch);
+        if (st.n_wd > 0) {
+            launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, wd_tab, stream);
+            hipLaunchKernelGGL((k_star_moments_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, hdr, d_params, K,
+                               (const double *)wd_tab, scratch);
+        }
+        const long long n_words = (long long)st.n * B9_MOM_N;
+        hipLaunchKernelGGL(k_moments_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
+        return hipGetLastError();
+    });
 }
 
 // The marginalised star grid: one workgroup (four waves sharing the node table's sub-chunks) per (64-star chunk or piece, walker),

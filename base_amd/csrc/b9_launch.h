@@ -119,6 +119,13 @@ hipError_t b9k_wd_sample(const DevPack &pk, const DevStars &st, const IsoHdr *hd
                          const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const B9WdSample &smp, hipStream_t stream);
 long long b9k_wd_table_doubles(int nfp, long long n_nodes);      // per (row, population)
 
+// b9_star_moments: k_marg_table [+ k_marg_wd_table] of n_rows derived rows into tab / wd_tab (b9k_marg_table_doubles /
+// b9k_marg_wd_table_doubles per (row, population)), every star's eight increments into scratch [n_rows][st.n][B9_MOM_N], then
+// acc [st.n][B9_MOM_N] += the rows in ascending order.  Device pointers, all the caller's own.
+hipError_t b9k_star_moments(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                            const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, double *tab, double *wd_tab,
+                            double *scratch, double *acc, hipStream_t stream);
+
 hipError_t b9k_noop(hipStream_t stream);
 hipError_t b9k_spin(double microseconds, hipStream_t stream);
 constexpr int B9_CLOCK_SLOTS = 8 * 256;      // (XCD, HW_ID[15:8]) -> one slot per compute unit

@@ -199,6 +199,17 @@ class Engine:
         res["star_index"] = self.wd_index.copy()
         return res
 
+    def star_moments(self, rows: np.ndarray, acc: Optional[np.ndarray] = None) -> np.ndarray:
+        """b9_star_moments: the per-star posterior moments [n_stars, abi.MOM_N] summed over `rows`, exactly (no draws).
+        acc=None starts from zeros; else the call continues `acc` (B9_MOM_CONTINUE) and returns a new array."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        if acc is None:
+            out, flags = np.zeros((self.n_stars, abi.MOM_N)), 0
+        else:
+            out, flags = np.array(acc, dtype=np.float64, order="C").reshape(self.n_stars, abi.MOM_N), abi.MOM_CONTINUE
+        self._check(self.lib.b9_star_moments(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], flags, out.ctypes.data_as(_dp)))
+        return out
+
     def derive_isochrone(self, param_row: np.ndarray, pop: int = 0, cap: int = 4096) -> Tuple[int, np.ndarray, np.ndarray, float]:
         row = np.ascontiguousarray(param_row, dtype=np.float64)
         mass = np.empty(cap)
@@ -289,3 +300,10 @@ def make_problem(pack_dict: Dict, cluster: Dict, n_pops: int = 1, mode: int = ab
     priors = synth.default_priors(pack_dict, cluster["truth"], n_pops)
     options = abi.make_options(mode, n_pops, marg_iso_increm, marg_n_q)
     return pack, stars, priors, options
+
+
+def star_table(acc: np.ndarray) -> np.ndarray:
+    """The derived columns of b9_star_moments' accumulators (hostlib.STAR_TABLE_COLUMNS: rows, member, mass, massSd,
+    massRatio, massRatioSd, pBinary, pPop2), [n_stars, 8] -- host arithmetic (b9h_star_table)."""
+    from . import hostlib
+    return hostlib.star_table(acc)

@@ -477,6 +477,45 @@ void ResultWriter::row(const std::vector<double> &values, double logpost, int st
     std::fprintf(f, "%14.6f %5d\n", logpost, stage);
 }
 
+// ---------------------------------------------------------------------------------------------
+// starSummary
+// ---------------------------------------------------------------------------------------------
+void star_table(const double *acc, long n_stars, double *table)
+{
+    for (long i = 0; i < n_stars; ++i) {
+        const double *a = acc + (size_t)i * B9_MOM_N;
+        double *t = table + (size_t)i * kStarTableCols;
+        for (int c = 0; c < kStarTableCols; ++c) t[c] = 0.0;
+        t[0] = a[B9_MOM_ROWS];
+        if (a[B9_MOM_ROWS] > 0.0) t[1] = a[B9_MOM_MEMBER] / a[B9_MOM_ROWS];
+        if (!(a[B9_MOM_MEMBER] > 0.0)) continue;             // no membership weight: every derived value is 0
+        const double w = a[B9_MOM_MEMBER];
+        t[2] = a[B9_MOM_M1] / w;
+        t[3] = std::sqrt(std::max(0.0, a[B9_MOM_M1SQ] / w - t[2] * t[2]));
+        t[4] = a[B9_MOM_Q] / w;
+        t[5] = std::sqrt(std::max(0.0, a[B9_MOM_QSQ] / w - t[4] * t[4]));
+        t[6] = a[B9_MOM_BINARY] / w;
+        t[7] = a[B9_MOM_POP1] / w;
+    }
+}
+
+void write_star_summary(const std::string &path, const std::vector<std::string> &ids, const double *acc, int n_pops)
+{
+    const long n = (long)ids.size();
+    std::vector<double> table((size_t)n * kStarTableCols);
+    star_table(acc, n, table.data());
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) fail("cannot write " + path);
+    std::fprintf(f, "id rows member mass massSd massRatio massRatioSd pBinary%s\n", n_pops == 2 ? " pPop2" : "");
+    for (long i = 0; i < n; ++i) {
+        const double *t = table.data() + (size_t)i * kStarTableCols;
+        std::fprintf(f, "%s %.0f %.6f %.6f %.6f %.6f %.6f %.6f", ids[i].c_str(), t[0], t[1], t[2], t[3], t[4], t[5], t[6]);
+        if (n_pops == 2) std::fprintf(f, " %.6f", t[7]);
+        std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) fail("cannot write " + path);
+}
+
 const char *param_name(int idx)
 {
     static const char *n[B9_NPARAM] = {"logAge", "Y", "FeH", "modulus", "absorption", "carbonicity",

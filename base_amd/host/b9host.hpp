@@ -85,6 +85,18 @@ class ResultWriter {
     void *fp;
 };
 
+// ---- starSummary -----------------------------------------------------------------------------------
+// b9_star_moments' accumulators [n_stars][B9_MOM_N] -> the derived columns [n_stars][kStarTableCols]:
+//   rows = acc0, member = acc1 / acc0, mass = acc2 / acc1, massSd = sqrt(max(0, acc3 / acc1 - mass^2)), ratio and ratioSd
+//   likewise from acc4, acc5, pBinary = acc6 / acc1, pPop2 = acc7 / acc1; with acc1 == 0 every derived value is 0.
+// (Raw second moments in fp64 lose about 2^-52 mass^2 / var relatively: a one-node posterior comes out a few 1e-17 negative,
+// hence the clamp.)  Host arithmetic only.
+constexpr int kStarTableCols = 8;
+void star_table(const double *acc, long n_stars, double *table);
+// <base>.starSummary (docs/FORMATS.md): a header line, then one line per star in the order of `ids`:
+// id rows member mass massSd massRatio massRatioSd pBinary [pPop2 -- two populations only]
+void write_star_summary(const std::string &path, const std::vector<std::string> &ids, const double *acc, int n_pops);
+
 const char *param_name(int idx);          // "logAge", "Y", "FeH", "modulus", "absorption", ...
 
 }  // namespace b9h

@@ -143,6 +143,22 @@ int b9h_read_res_rows(const char *path, const double *start_row, int stage, doub
     });
 }
 
+int b9h_star_table(const double *acc, long n_stars, double *table)
+{
+    return guard([&] {
+        if (n_stars < 0 || (n_stars > 0 && (!acc || !table))) throw std::runtime_error("b9h_star_table: NULL argument");
+        b9h::star_table(acc, n_stars, table);
+    });
+}
+
+int b9h_write_star_summary(const char *path, const char *const *ids, long n_stars, const double *acc, int n_pops)
+{
+    return guard([&] {
+        if (!path || n_stars < 0 || (n_stars > 0 && (!ids || !acc))) throw std::runtime_error("b9h_write_star_summary: NULL argument");
+        b9h::write_star_summary(path, std::vector<std::string>(ids, ids + n_stars), acc, n_pops);
+    });
+}
+
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part)
 {
     return guard([&] { b9h::merge_result_parts(final_path, world, walkers_per_rank, rows_per_part); });

@@ -36,6 +36,7 @@ HOST_SYMBOLS = [
     "b9h_sampler_n_local", "b9h_sampler_state", "b9h_summary_rows",
     "b9h_load_pack", "b9h_free_pack", "b9h_read_phot", "b9h_free_phot", "b9h_settings_dump", "b9h_merge_parts",
     "b9h_sim_draw_systems", "b9h_sim_field_mags", "b9h_scatter", "b9h_sim_settings", "b9h_read_res_rows",
+    "b9h_star_table", "b9h_write_star_summary",
 ]
 
 _lib = None
@@ -83,6 +84,8 @@ def load() -> C.CDLL:
     lib.b9h_settings_dump.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     lib.b9h_merge_parts.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_long]
     lib.b9h_read_res_rows.argtypes = [C.c_char_p, _dp, C.c_int, _dp, C.c_long, C.POINTER(C.c_long)]
+    lib.b9h_star_table.argtypes = [_dp, C.c_long, _dp]
+    lib.b9h_write_star_summary.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int]
     lib.b9h_sim_draw_systems.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_int, C.c_double, _dp, _dp, _dp, _ip, _ip]
     lib.b9h_sim_field_mags.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int, _dp, _dp, _dp]
@@ -296,6 +299,44 @@ def read_res_rows(path: str, start_row, stage: int = 3) -> np.ndarray:
     if n.value:
         _check(load().b9h_read_res_rows(path.encode(), start.ctypes.data_as(_dp), int(stage), rows.ctypes.data_as(_dp), n.value, C.byref(n)))
     return rows
+
+
+STAR_TABLE_COLUMNS = ("rows", "member", "mass", "massSd", "massRatio", "massRatioSd", "pBinary", "pPop2")
+
+
+def star_table(acc) -> np.ndarray:
+    """b9h_star_table: b9_star_moments' accumulators [n_stars, 8] -> the derived columns [n_stars, 8] (STAR_TABLE_COLUMNS)."""
+    acc = np.ascontiguousarray(acc, dtype=np.float64).reshape(-1, 8)
+    out = np.empty_like(acc)
+    _check(load().b9h_star_table(acc.ctypes.data_as(_dp), acc.shape[0], out.ctypes.data_as(_dp)))
+    return out
+
+
+def write_star_summary(path: str, ids, acc, n_pops: int = 1) -> None:
+    """b9h_write_star_summary: the .starSummary file of the accumulators `acc` [len(ids), 8]."""
+    acc = np.ascontiguousarray(acc, dtype=np.float64).reshape(-1, 8)
+    if acc.shape[0] != len(ids):
+        raise ValueError("one id per star")
+    arr = (C.c_char_p * len(ids))(*[str(i).encode() for i in ids])
+    _check(load().b9h_write_star_summary(path.encode(), arr, len(ids), acc.ctypes.data_as(_dp), int(n_pops)))
+
+
+def read_star_summary(path: str):
+    """(ids, columns, table [n_stars, len(columns)]) of a .starSummary file."""
+    with open(path) as f:
+        header = f.readline().split()
+        if header[:1] != ["id"]:
+            raise HostError(path + ": not a .starSummary file")
+        ids, rows = [], []
+        for line in f:
+            t = line.split()
+            if not t:
+                continue
+            if len(t) != len(header):
+                raise HostError(path + ": a line does not hold one value per column")
+            ids.append(t[0])
+            rows.append([float(x) for x in t[1:]])
+    return ids, header[1:], np.array(rows, dtype=np.float64).reshape(len(ids), len(header) - 1)
 
 
 # ------------------------------------------------------------------------------------------

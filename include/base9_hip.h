@@ -293,8 +293,8 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk);
  * may be outstanding; they are collected in the order they were enqueued.  A successful b9_load_pack, b9_load_stars,
  * b9_set_priors or b9_set_options changes the posterior: the previous block's state carries a log-posterior of the old
  * one, so the next B9_BLOCK_CONTINUE block returns B9_ERR_STATE (the message names the call that intervened) and the chain
- * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags and b9_sample_wd_mass (buffers of
- * their own) between continued blocks are allowed.  While a block is outstanding it owns the
+ * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags, b9_sample_wd_mass and b9_star_moments
+ * (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
  * context's work buffers: b9_logpost / b9_sample_mass / b9_derive_isochrone, the staging calls, b9_set_options and a block
  * with another n_walkers return B9_ERR_STATE until it has been collected.  A driver that adapts the proposal
  * from block b-1 while block b runs keeps the GPU's queue non-empty: enqueue b+1 (CONTINUE | ASYNC), wait(b), ...
@@ -399,6 +399,43 @@ int b9_sample_wd_mass(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t
                       double *out_zams, double *out_wd_mass, double *out_prec_log_age,
                       double *out_log_cool_age, double *out_log_teff, double *out_logg,
                       double *out_member, int32_t *out_pop /* nullable */);
+
+/*
+ * Exact per-star posterior moments over a saved chain (the starSummary counterpart).  Added in ABI 6 without a version
+ * change, as b9_predict_mags was: purely additive.  Where b9_sample_mass DRAWS one node per (row, star), this call forms the
+ * conditional expectations over all of them and keeps only their sum over the rows: no random numbers, n_stars * B9_MOM_N
+ * doubles back instead of 3 per (row, star), and a result that is a deterministic function of the chain.
+ *
+ * Definition.  The grid is b9_sample_mass's (marg_iso_increm sub-steps per EEP interval x marg_n_q mass ratios; WD-stage
+ * stars: 8 * marg_iso_increm steps above the AGB tip, mass ratio 0); n_pops is honoured, mode ignored.  For row r and star
+ * i let t_(k,n) = log( prior(M1) dM / n_q * like_i(M1, q) ) [+ log lambda_k] over every node n of population k --
+ * b9_sample_mass's key without the Gumbel term; terms that are not finite do not take part --  L = logsumexp t,
+ * w = exp(t - L), and p = p_i e^L / (p_i e^L + (1 - p_i) fieldLike) the membership as b9_sample_mass forms it.  The row adds
+ *     acc[i][B9_MOM_ROWS]   += 1                  acc[i][B9_MOM_MEMBER] += p
+ *     acc[i][B9_MOM_M1]     += p sum w M1         acc[i][B9_MOM_M1SQ]   += p sum w M1^2       (M1: the node's primary ZAMS mass,
+ *     acc[i][B9_MOM_Q]      += p sum w q          acc[i][B9_MOM_QSQ]    += p sum w q^2         b9_sample_mass's out_mass)
+ *     acc[i][B9_MOM_BINARY] += p sum_{q > 0} w    acc[i][B9_MOM_POP1]   += p sum_{k = 1} w    (0 with one population)
+ * A (row, star) for which b9_sample_mass reports all zeros -- a row outside the grid, a star with no live node -- adds
+ * nothing, not even to B9_MOM_ROWS.  The sums are weighted by membership: acc[M1] / acc[MEMBER] is E[M1 | data, member]
+ * under the chain -- what a membership-weighted average of b9_sample_mass draws estimates.  Terms more than 40 e-folds
+ * below a lower bound of the star's largest term may be dropped (b9_tuning.marg_no_pruning: none are): below
+ * N_nodes e^-40 of the sums.
+ *
+ * acc (host, [n_stars][B9_MOM_N], the caller's star order) is in/out: flags = 0 starts from zeros, B9_MOM_CONTINUE from the
+ * caller's values (doubles round-trip exactly).  Every accumulator is updated as acc + x_r, one plain add per row in ascending
+ * row order: the result is the same bits for any split of the rows over successive continued calls, and for the call's own
+ * chunking (at most 32 rows at a time, fewer while the chunk's per-(row, star) scratch would exceed 64 MiB).  A (row, star)
+ * increment depends on that row and star alone.  Synchronous; host pointers.  B9_ERR_STATE while a sampler block is
+ * outstanding, B9_ERR_INVALID for n_rows < 1 or NULL pointers.  The call uses buffers of its own (isochrones, node tables,
+ * scratch, accumulators): a B9_BLOCK_CONTINUE block enqueued after it gives the same bits as one enqueued without it.
+ */
+enum b9_moment {
+    B9_MOM_ROWS = 0, B9_MOM_MEMBER = 1, B9_MOM_M1 = 2, B9_MOM_M1SQ = 3, B9_MOM_Q = 4, B9_MOM_QSQ = 5, B9_MOM_BINARY = 6, B9_MOM_POP1 = 7,
+    B9_MOM_N = 8
+};
+#define B9_MOM_CONTINUE 1
+int b9_star_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags,
+                    double *acc /* host, [n_stars][B9_MOM_N], in/out */);
 
 /* ---- introspection (used by bench/tests; no compute) --------------------------------- */
 int b9_max_eep(const b9_ctx *ctx);           /* longest isochrone in the loaded pack        */

@@ -101,6 +101,13 @@ int b9h_sim_settings(int program, int argc, char **argv, char *out, int cap);
  * and sampleWDMass read; exposed for tests): start_row [B9_NPARAM] with the file's sampled columns written over it.  *n_rows
  * receives their number; rows (nullable: count only) receives the first min(*n_rows, cap_rows) of them, [row][B9_NPARAM] */
 int b9h_read_res_rows(const char *path, const double *start_row, int stage, double *rows, long cap_rows, long *n_rows);
+/* starSummary.  b9h_star_table: b9_star_moments' accumulators [n_stars][B9_MOM_N] -> the derived columns [n_stars][8]:
+ * rows = acc0, member = acc1 / acc0, mass = acc2 / acc1, massSd = sqrt(max(0, acc3 / acc1 - mass^2)), massRatio and massRatioSd
+ * likewise from acc4 and acc5, pBinary = acc6 / acc1, pPop2 = acc7 / acc1; with acc1 == 0 every derived value is 0.
+ * b9h_write_star_summary: the file <base>.starSummary (docs/FORMATS.md) -- one header line, then per star
+ * "id rows member mass massSd massRatio massRatioSd pBinary [pPop2]" (the last column with n_pops == 2 only), in the order of ids. */
+int b9h_star_table(const double *acc, long n_stars, double *table);
+int b9h_write_star_summary(const char *path, const char *const *ids, long n_stars, const double *acc, int n_pops);
 /* rank 0's merge of <final_path>.part<r> into <final_path> after a --gpus N run (b9h::merge_result_parts; exposed for tests) */
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part);
 
