@@ -13,7 +13,7 @@ import numpy as np
 
 from base_amd import build
 
-M1 = dict(log_ge1=0, log_pos=1, exp_fast=2, log1pexp=3)
+M1 = dict(log_ge1=0, log_pos=1, exp_fast=2, log1pexp=3, exp10=4, log10=5)      # 4, 5: the library's, as wd_chain calls them
 M2 = dict(logaddexp=0, fdiv=1, mix_value=2)
 SEARCH = dict(bracket=0, bracket8=1, bracket8_desc=2, find_bracket=3)
 WAVE1 = dict(wave_sum=0, wave_max_all=1, wave_bcast0=2, wave_uniform=3)

@@ -144,7 +144,7 @@ void b9p_set_mutant(int m) { g_mutant = m; }
 
 int b9p_map1(int op, const double *x, double *y, long long n)
 {
-    for (long long i = 0; i < n; ++i) y[i] = op == 0 || op == 1 ? log_ge1(x[i]) : op == 2 ? exp_fast(x[i]) : log1pexp(x[i]);
+    for (long long i = 0; i < n; ++i) y[i] = op == 0 || op == 1 ? log_ge1(x[i]) : op == 2 ? exp_fast(x[i]) : op == 3 ? log1pexp(x[i]) : op == 4 ? pow(10.0, x[i]) : log10(x[i]);
     return 0;
 }
 int b9p_map2(int op, const double *a, const double *b, double *y, long long n)

@@ -60,14 +60,15 @@ inline int blocks(long long n) { return (int)((n + 255) / 256); }
 // ---------------------------------------------------------------------------------------------------------------------
 // element-wise maps
 // ---------------------------------------------------------------------------------------------------------------------
-enum { M1_LOG_GE1 = 0, M1_LOG_POS = 1, M1_EXP_FAST = 2, M1_LOG1PEXP = 3 };
+enum { M1_LOG_GE1 = 0, M1_LOG_POS = 1, M1_EXP_FAST = 2, M1_LOG1PEXP = 3, M1_EXP10 = 4, M1_LOG10 = 5 };   // 4, 5: the library calls of wd_chain
 template <int OP>
 __global__ void k_map1(const double *__restrict__ x, double *__restrict__ y, long long n)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double v = x[i];
-    y[i] = OP == M1_LOG_GE1 ? log_ge1(v) : OP == M1_LOG_POS ? log_pos(v) : OP == M1_EXP_FAST ? exp_fast(v) : log1pexp(v);
+    y[i] = OP == M1_LOG_GE1 ? log_ge1(v) : OP == M1_LOG_POS ? log_pos(v) : OP == M1_EXP_FAST ? exp_fast(v) : OP == M1_LOG1PEXP ? log1pexp(v)
+         : OP == M1_EXP10 ? exp10(v) : log10(v);
 }
 
 enum { M2_LOGADDEXP = 0, M2_FDIV = 1, M2_MIX_VALUE = 2 };
@@ -357,6 +358,8 @@ int b9p_map1(int op, const double *x, double *y, long long n)
     case M1_LOG_POS: return run_map1<M1_LOG_POS>(x, y, n);
     case M1_EXP_FAST: return run_map1<M1_EXP_FAST>(x, y, n);
     case M1_LOG1PEXP: return run_map1<M1_LOG1PEXP>(x, y, n);
+    case M1_EXP10: return run_map1<M1_EXP10>(x, y, n);
+    case M1_LOG10: return run_map1<M1_LOG10>(x, y, n);
     default: return (int)hipErrorInvalidValue;
     }
 }
