@@ -1,9 +1,10 @@
 // b9_capi_eval.cpp -- one log-posterior evaluation through the C ABI: derive -> stars -> finalize (b9_logpost,
 // b9_logpost_device), the per-star mass draws (b9_sample_mass), the isochrone dump (b9_derive_isochrone) and the forward
-// model alone (b9_predict_mags) the WD-stage stars' posterior draws (b9_sample_wd_mass) and the
-// per-star posterior moments (b9_star_moments).
+// model alone (b9_predict_mags) the WD-stage stars' posterior draws (b9_sample_wd_mass), the
+// per-star posterior moments (b9_star_moments) and the binned mass posteriors (b9_mass_hist).
 #include "b9_ctx.h"
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 
 using namespace b9i;
@@ -382,6 +383,67 @@ int b9_star_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t f
                                      d_scratch, d_acc, s));
     }
     HIPCHK(ctx, hipMemcpyAsync(acc, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return B9_OK;
+}
+
+// Rows are worked in chunks of at most B9_HIST_MAX_ROWS, and of as few rows as keep the chunk's increments within B9_HIST_SCRATCH_BYTES.
+#define B9_HIST_SCRATCH_BYTES ((size_t)64 << 20)
+#define B9_HIST_MAX_ROWS 32
+
+int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quantity, const double *edges, int32_t n_bins, int32_t flags,
+                 double *star_hist, double *row_hist)
+{
+    if (!ctx || !params || !edges || n_rows < 1 || (!star_hist && !row_hist)) return B9_ERR_INVALID;
+    if (quantity != B9_HQ_PRIMARY && quantity != B9_HQ_SECONDARY && quantity != B9_HQ_SYSTEM) return fail(ctx, B9_ERR_INVALID, "b9_mass_hist: unknown quantity");
+    if (n_bins < 1 || n_bins > B9_HIST_MAX_BINS) return fail(ctx, B9_ERR_INVALID, "b9_mass_hist: n_bins must lie in 1 .. B9_HIST_MAX_BINS");
+    for (int b = 0; b <= n_bins; ++b)
+        if (!std::isfinite(edges[b]) || (b > 0 && !(edges[b] > edges[b - 1])))
+            return fail(ctx, B9_ERR_INVALID, "b9_mass_hist: the edges must be finite and strictly ascending");
+    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
+    if (!ctx->have_pack || !ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
+    const int n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
+    const int K = marg_grid(ctx).K, Q = marg_grid(ctx).Q;
+    const size_t ncol = (size_t)n_bins + 1;
+    if (n == 0) {
+        if (row_hist) std::fill(row_hist, row_hist + (size_t)n_rows * ncol, 0.0);
+        return B9_OK;
+    }
+    const DevPack &pk = ctx->pk;
+    const int mass_cap = pack_mass_cap(pk.max_eep);
+    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
+    const size_t tab_row = (size_t)n_pops * (size_t)b9k_marg_table_doubles(pk.nfp, mass_cap, K, Q);
+    const size_t wd_row = ctx->st.n_wd > 0 ? (size_t)n_pops * (size_t)b9k_marg_wd_table_doubles(pk.nfp, K) : 0;
+    const size_t chunk = mom_chunk_rows((size_t)n_rows, (size_t)n, ncol, B9_HIST_MAX_ROWS, B9_HIST_SCRATCH_BYTES);
+    if (chunk * (tab_row + wd_row) > ((size_t)8 << 30) / sizeof(double))
+        return fail(ctx, B9_ERR_CAPACITY, "b9_mass_hist: marginalisation grid too fine: the node tables would exceed 8 GiB");
+    // one allocation: [params][headers][isochrones][table][WD table][increments][accumulators][the chunk's row sums]
+    const HistArena a = hist_arena(chunk, n_pops, iso_stride, tab_row, wd_row, (size_t)n, ncol, sizeof(IsoHdr));
+    RESERVE(ctx, ctx->d_hist, a.bytes);
+    char *base = ctx->d_hist.get();
+    double *d_par = part<double>(base, a.m.o_par), *d_iso = part<double>(base, a.m.o_iso), *d_tab = part<double>(base, a.m.o_tab);
+    double *d_wd = wd_row ? part<double>(base, a.m.o_wd) : nullptr, *d_scratch = part<double>(base, a.m.o_scratch);
+    double *d_acc = star_hist ? part<double>(base, a.m.o_acc) : nullptr, *d_rows = row_hist ? part<double>(base, a.o_rows) : nullptr;
+    IsoHdr *d_hdr = part<IsoHdr>(base, a.m.o_hdr);
+    const size_t acc_bytes = sizeof(double) * (size_t)n * ncol;
+    hipStream_t s = ctx->stream;
+    if (d_acc) {
+        if (flags & B9_HIST_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_acc, star_hist, acc_bytes, hipMemcpyHostToDevice, s));
+        else HIPCHK(ctx, hipMemsetAsync(d_acc, 0, acc_bytes, s));
+    }
+    const McmcDev off{};
+    for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
+        const int m = std::min((int)chunk, n_rows - r0);
+        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
+        // every (row, star) of the chunk writes all its columns (zeros where it contributes nothing): no clearing
+        HIPCHK(ctx, b9k_mass_hist(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, K, Q, ctx->marg_prune, quantity, edges, n_bins,
+                                  d_tab, d_wd, d_scratch, d_acc, d_rows, s));
+        if (d_rows) HIPCHK(ctx, hipMemcpyAsync(row_hist + (size_t)r0 * ncol, d_rows, sizeof(double) * m * ncol, hipMemcpyDeviceToHost, s));
+    }
+    if (d_acc) HIPCHK(ctx, hipMemcpyAsync(star_hist, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return B9_OK;
 }

@@ -127,6 +127,18 @@ inline size_t mom_chunk_rows(size_t n_rows, size_t n_stars, size_t n_mom, size_t
     return std::max<size_t>(1, std::min({n_rows, max_rows, scratch_bytes / per_row}));
 }
 
+// b9_mass_hist's chunk of rows: mom_arena with n_col = n_bins + 1 columns per star, then the chunk's per-row sums [chunk][n_col]
+struct HistArena { MomArena m; size_t o_rows, bytes; };
+inline HistArena hist_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t wd_row, size_t n_stars, size_t n_col, size_t hdr_bytes)
+{
+    HistArena a{mom_arena(chunk, n_pops, iso_stride, tab_row, wd_row, n_stars, n_col, hdr_bytes), 0, 0};
+    Carve c;
+    c.take(a.m.bytes);
+    a.o_rows = c.take(8 * chunk * n_col);
+    a.bytes = c.total;
+    return a;
+}
+
 // ---- sizing rules
 
 // rows of a derived isochrone: the pack's longest one, rounded up to even; and its doubles: a mass column + nfp magnitude columns

@@ -29,6 +29,8 @@
 //                                     derived values kept, then one lane per WD-stage star against the table
 //   k_star_moments / _wd / k_moments_accumulate   b9_star_moments: exact per-star posterior moments over the marginalisation
 //                                     grid (one lane per star, four waves sharing the node table), summed over the rows
+//   k_star_hist / _wd / k_hist_accumulate / k_hist_rows   b9_mass_hist: exact binned mass posteriors over the same grid (a
+//                                     per-wave LDS histogram per lane, bins worked in tiles), summed over the rows and the stars
 //
 // The kernels live in the *.hip.h files included below (one translation unit); this file holds
 // k_finalize and the host-callable launch wrappers.
@@ -70,6 +72,7 @@ namespace tree_kd5 {
 #include "b9_predict.hip.h"
 #include "b9_wd_sample.hip.h"
 #include "b9_star_moments.hip.h"
+#include "b9_mass_hist.hip.h"
 
 // ------------------------------------------------------------------------------------------
 // k_finalize: one workgroup per walker: fixed-order sum of the partials + prior -> logpost[w]
@@ -301,6 +304,43 @@ hipError_t b9k_star_moments(const DevPack &pk, const DevStars &st, const IsoHdr 
         }
         const long long n_words = (long long)st.n * B9_MOM_N;
         hipLaunchKernelGGL(k_moments_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
+        return hipGetLastError();
+    });
+}
+
+// ---- b9_mass_hist: the node tables of a chunk of rows, the stars' binned increments, the accumulation, the rows' sums -----------
+hipError_t b9k_mass_hist(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                         const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, int quantity, const double *edges, int n_bins,
+                         double *tab, double *wd_tab, double *scratch, double *acc, double *rows, hipStream_t stream)
+{
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        if (!tab || !scratch || !edges || n_bins < 1 || n_bins > B9_HIST_MAX_BINS || n_rows < 1 || n_rows > 65535 || (st.n_wd > 0 && !wd_tab))
+            return hipErrorInvalidValue;
+        HistEdges ed{};
+        for (int b = 0; b <= n_bins; ++b) ed.e[b] = edges[b];
+        ed.n_bins = n_bins; ed.quantity = quantity;
+        const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
+        const hipError_t e = launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, tab, stream);
+        if (e != hipSuccess) return e;
+        const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
+        // a tile of bins: one histogram [bins][64] per wave
+        const int tb = std::min(n_bins, B9_HIST_TILE), n_tiles = (n_bins + B9_HIST_TILE - 1) / B9_HIST_TILE;
+        const auto k = with_lds(k_star_hist<NFP, NPOPS>, sizeof(double) * 64 * (NPOPS * 4 + 4 * 2 + 4 * (size_t)tb));   // seeds, states, histograms
+        if (k.err != hipSuccess) return k.err;
+        hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows, n_tiles), dim3(256), k.lds, stream, st, hdr, iso_data, iso_stride, mass_cap,
+                           d_params, K, Q, (const double *)tab, L, cut2, ed, tb, scratch);
+        if (st.n_wd > 0) {
+            launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, wd_tab, stream);
+            hipLaunchKernelGGL((k_star_hist_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, hdr, d_params, K,
+                               (const double *)wd_tab, ed, scratch);
+        }
+        const int ncol = n_bins + 1;
+        const long long n_words = (long long)st.n * ncol;
+        if (acc)
+            hipLaunchKernelGGL(k_hist_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
+        if (rows)
+            hipLaunchKernelGGL(k_hist_rows, dim3((unsigned)((n_rows * ncol + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, st.n, ncol, rows);
         return hipGetLastError();
     });
 }

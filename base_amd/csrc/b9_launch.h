@@ -126,6 +126,14 @@ hipError_t b9k_star_moments(const DevPack &pk, const DevStars &st, const IsoHdr 
                             const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, double *tab, double *wd_tab,
                             double *scratch, double *acc, hipStream_t stream);
 
+// b9_mass_hist: the node tables as b9k_star_moments builds them, every star's binned increments into scratch
+// [n_rows][st.n][n_bins + 1], then acc [st.n][n_bins + 1] += the rows in ascending order (acc may be null) and
+// rows [n_rows][n_bins + 1] = the stars' sum in ascending order (may be null).  edges: HOST, [n_bins + 1], validated by the
+// caller; they travel as kernel arguments.  Device pointers otherwise, all the caller's own.
+hipError_t b9k_mass_hist(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                         const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, int quantity, const double *edges, int n_bins,
+                         double *tab, double *wd_tab, double *scratch, double *acc, double *rows, hipStream_t stream);
+
 hipError_t b9k_noop(hipStream_t stream);
 hipError_t b9k_spin(double microseconds, hipStream_t stream);
 constexpr int B9_CLOCK_SLOTS = 8 * 256;      // (XCD, HW_ID[15:8]) -> one slot per compute unit

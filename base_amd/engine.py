@@ -210,6 +210,29 @@ class Engine:
         self._check(self.lib.b9_star_moments(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], flags, out.ctypes.data_as(_dp)))
         return out
 
+    def mass_hist(self, rows: np.ndarray, edges: np.ndarray, quantity: int = abi.HQ_PRIMARY, star_hist: Optional[np.ndarray] = None,
+                  want_star: bool = True, want_rows: bool = True) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+        """b9_mass_hist: the exact binned mass posteriors over `rows` for the bins `edges` [n_bins + 1] of `quantity`
+        (abi.HQ_*): (star_hist [n_stars, n_bins + 1] summed over the rows, row_hist [n_rows, n_bins + 1] summed over the
+        stars); the last column is the total (membership).  star_hist=None starts from zeros; else the call continues it
+        (B9_HIST_CONTINUE) and returns a new array.  want_star / want_rows = False passes NULL for that output (None back)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        n_bins = len(edges) - 1
+        flags = 0
+        sh = rh = None
+        if want_star:
+            if star_hist is None:
+                sh = np.zeros((self.n_stars, n_bins + 1))
+            else:
+                sh, flags = np.array(star_hist, dtype=np.float64, order="C").reshape(self.n_stars, n_bins + 1), abi.HIST_CONTINUE
+        if want_rows:
+            rh = np.zeros((rows.shape[0], n_bins + 1))
+        ptr = lambda a: a.ctypes.data_as(_dp) if a is not None else None      # noqa: E731
+        self._check(self.lib.b9_mass_hist(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], int(quantity), edges.ctypes.data_as(_dp), n_bins, flags,
+                                          ptr(sh), ptr(rh)))
+        return sh, rh
+
     def derive_isochrone(self, param_row: np.ndarray, pop: int = 0, cap: int = 4096) -> Tuple[int, np.ndarray, np.ndarray, float]:
         row = np.ascontiguousarray(param_row, dtype=np.float64)
         mass = np.empty(cap)

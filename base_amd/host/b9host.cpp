@@ -2,6 +2,7 @@
 #include "b9host.hpp"
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -126,6 +127,8 @@ const std::map<std::string, std::string> &Settings::flag_map()
         {"resComment", "gpu.resComment"},
         {"margIsoIncrem", "sampleMass.margIsoIncrem"}, {"nMassRatios", "sampleMass.nMassRatios"},
         {"nMassNodes", "sampleWDMass.nMassNodes"},
+        {"nBins", "massFunction.nBins"}, {"massFunctionMinMass", "massFunction.minMass"}, {"massFunctionMaxMass", "massFunction.maxMass"},
+        {"linearBins", "massFunction.linearBins"}, {"quantity", "massFunction.quantity"}, {"perStar", "massFunction.perStar"},
         {"nStars", "simCluster.nStars"}, {"percentBinary", "simCluster.percentBinary"}, {"percentDB", "simCluster.percentDB"},
         {"nFieldStars", "simCluster.nFieldStars"}, {"minMass", "simCluster.minMass"}, {"maxMass", "simCluster.maxMass"},
         {"minMassRatio", "simCluster.minMassRatio"}, {"memberPrior", "simCluster.memberPrior"}, {"nPops", "simCluster.nPops"},
@@ -146,7 +149,7 @@ void Settings::parse_args(int argc, char **argv)
         std::string value;
         size_t eq = a.find('=');
         if (eq != std::string::npos) { value = a.substr(eq + 1); a = a.substr(0, eq); }
-        else if (a == "verbose" || a == "marginalise" || a == "forceRanks" || a == "resComment") value = "1";
+        else if (a == "verbose" || a == "marginalise" || a == "forceRanks" || a == "resComment" || a == "linearBins" || a == "perStar") value = "1";
         else { if (i + 1 >= argc) fail("flag --" + a + " needs a value"); value = argv[++i]; }
         if (a == "config") { load_yaml(value); continue; }
         auto it = flag_map().find(a);
@@ -514,6 +517,126 @@ void write_star_summary(const std::string &path, const std::vector<std::string> 
         std::fprintf(f, "\n");
     }
     if (std::fclose(f) != 0) fail("cannot write " + path);
+}
+
+// ---------------------------------------------------------------------------------------------
+// massFunction
+// ---------------------------------------------------------------------------------------------
+namespace {
+// numpy's default percentile of an ascending sample: linear interpolation between the order statistics around (n - 1) q
+double percentile_sorted(const std::vector<double> &v, double q)
+{
+    const double pos = (double)(v.size() - 1) * q;
+    const size_t lo = (size_t)std::floor(pos), hi = std::min(lo + 1, v.size() - 1);
+    const double t = pos - (double)lo;
+    return v[lo] + (v[hi] - v[lo]) * t;
+}
+}  // namespace
+
+void mass_function_table(const double *row_hist, long n_rows, const double *edges, int n_bins, double *table)
+{
+    const size_t ncol = (size_t)n_bins + 1;
+    std::vector<long> use;
+    for (long r = 0; r < n_rows; ++r)
+        if (row_hist[(size_t)r * ncol + n_bins] > 0.0) use.push_back(r);
+    std::vector<double> v(use.size());
+    for (int b = 0; b < n_bins; ++b) {
+        double *t = table + (size_t)b * kMassFunctionCols;
+        for (int c = 0; c < kMassFunctionCols; ++c) t[c] = 0.0;
+        t[0] = edges[b]; t[1] = edges[b + 1];
+        if (use.empty()) continue;
+        double sum = 0.0;
+        for (size_t k = 0; k < use.size(); ++k) { v[k] = row_hist[(size_t)use[k] * ncol + b]; sum += v[k]; }
+        const double mean = sum / (double)use.size();
+        double ss = 0.0;
+        for (double x : v) ss += (x - mean) * (x - mean);
+        std::sort(v.begin(), v.end());
+        t[2] = mean;
+        t[3] = std::sqrt(ss / (double)use.size());
+        t[4] = percentile_sorted(v, 0.16); t[5] = percentile_sorted(v, 0.50); t[6] = percentile_sorted(v, 0.84);
+        if (edges[b] > 0.0) t[7] = mean / std::log10(edges[b + 1] / edges[b]);
+    }
+}
+
+void write_mass_function(const std::string &path, const double *table, int n_bins)
+{
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) fail("cannot write " + path);
+    std::fprintf(f, "lo hi mean sd p16 p50 p84 dNdlogM\n");
+    for (int b = 0; b < n_bins; ++b) {
+        const double *t = table + (size_t)b * kMassFunctionCols;
+        std::fprintf(f, "%.6f %.6f %.6f %.6f %.6f %.6f %.6f %.6f\n", t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7]);
+    }
+    if (std::fclose(f) != 0) fail("cannot write " + path);
+}
+
+void write_star_mass_hist(const std::string &path, const std::vector<std::string> &ids, const double *star_hist, int n_bins, long n_rows)
+{
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) fail("cannot write " + path);
+    std::fprintf(f, "id rows member");
+    for (int b = 0; b < n_bins; ++b) std::fprintf(f, " bin%d", b);
+    std::fprintf(f, "\n");
+    const size_t ncol = (size_t)n_bins + 1;
+    for (size_t i = 0; i < ids.size(); ++i) {
+        const double *a = star_hist + i * ncol, tot = a[n_bins];
+        std::fprintf(f, "%s %ld %.6f", ids[i].c_str(), n_rows, n_rows > 0 ? tot / (double)n_rows : 0.0);
+        for (int b = 0; b < n_bins; ++b) std::fprintf(f, " %.6f", tot > 0.0 ? a[b] / tot : 0.0);
+        std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) fail("cannot write " + path);
+}
+
+std::vector<double> MassFunctionConfig::edges() const
+{
+    std::vector<double> e((size_t)n_bins + 1);
+    for (int b = 0; b <= n_bins; ++b) {
+        const double t = (double)b / (double)n_bins;
+        e[b] = linear ? min_mass + (max_mass - min_mass) * t : min_mass * std::pow(max_mass / min_mass, t);
+    }
+    e[0] = min_mass; e[n_bins] = max_mass;
+    for (int b = 0; b < n_bins; ++b)
+        if (!(e[b + 1] > e[b])) fail("massFunction: the bins are too narrow to tell their edges apart");
+    return e;
+}
+
+MassFunctionConfig mass_function_config(const Settings &st, double m_wd_up)
+{
+    MassFunctionConfig c;
+    c.n_bins = (int)st.integer("massFunction.nBins", 24);
+    c.min_mass = st.num("massFunction.minMass", 0.1);
+    c.max_mass = st.num("massFunction.maxMass", m_wd_up);
+    c.linear = st.integer("massFunction.linearBins", 0) != 0;
+    c.per_star = st.integer("massFunction.perStar", 0) != 0;
+    const std::string q = st.str("massFunction.quantity", "primary");
+    if (q == "primary") c.quantity = B9_HQ_PRIMARY;
+    else if (q == "secondary") c.quantity = B9_HQ_SECONDARY;
+    else if (q == "system") c.quantity = B9_HQ_SYSTEM;
+    else fail("massFunction.quantity must be primary, secondary or system, not '" + q + "'");
+    c.K = (int)st.integer("massFunction.margIsoIncrem", st.integer("sampleMass.margIsoIncrem", 4));
+    c.Q = (int)st.integer("massFunction.nMassRatios", st.integer("sampleMass.nMassRatios", 4));
+    c.n_pops = (int)st.integer("massFunction.nPops", 1);
+    if (c.n_bins < 1 || c.n_bins > B9_HIST_MAX_BINS) fail("massFunction.nBins must lie in 1 .. " + std::to_string(B9_HIST_MAX_BINS));
+    if (!std::isfinite(c.min_mass) || !std::isfinite(c.max_mass) || !(c.max_mass > c.min_mass)) fail("massFunction: maxMass must exceed minMass");
+    if (!c.linear && !(c.min_mass > 0.0)) fail("massFunction: log-spaced bins need minMass > 0 (or --linearBins)");
+    if (c.K < 1 || c.Q < 1) fail("margIsoIncrem and nMassRatios must be positive");
+    if (c.n_pops != 1 && c.n_pops != 2) fail("massFunction.nPops must be 1 or 2");
+    return c;
+}
+
+std::vector<std::string> mass_function_args(int argc, char **argv)
+{
+    std::vector<std::string> out;
+    for (int i = 0; i < argc; ++i) {
+        std::string a = argv[i];
+        for (const char *name : {"minMass", "maxMass"}) {
+            const std::string flag = std::string("--") + name;
+            if (a == flag || a.rfind(flag + "=", 0) == 0)
+                a = std::string("--massFunction") + (char)std::toupper(name[0]) + (name + 1) + a.substr(flag.size());
+        }
+        out.push_back(a);
+    }
+    return out;
 }
 
 const char *param_name(int idx)

@@ -97,6 +97,33 @@ void star_table(const double *acc, long n_stars, double *table);
 // id rows member mass massSd massRatio massRatioSd pBinary [pPop2 -- two populations only]
 void write_star_summary(const std::string &path, const std::vector<std::string> &ids, const double *acc, int n_pops);
 
+// ---- massFunction ----------------------------------------------------------------------------------
+// b9_mass_hist's row_hist [n_rows][n_bins + 1] -> the per-bin table [n_bins][kMassFunctionCols]:
+//   lo, hi, then over the rows whose member column (the last) is > 0 the mean, the population standard deviation and the 16th,
+//   50th and 84th percentiles of the bin's expected count (linear interpolation between order statistics at (n - 1) q, numpy's
+//   default), and dN/dlog10 m = mean / log10(hi / lo) (0 where lo <= 0).  No such row: every statistic is 0.  Host arithmetic only.
+constexpr int kMassFunctionCols = 8;
+void mass_function_table(const double *row_hist, long n_rows, const double *edges, int n_bins, double *table);
+// <base>.massFunction (docs/FORMATS.md): "lo hi mean sd p16 p50 p84 dNdlogM", one line per bin
+void write_mass_function(const std::string &path, const double *table, int n_bins);
+// <base>.starMassHist: "id rows member bin0 .. bin<n-1>", per star its id, the rows counted, the mean membership
+// acc[total] / rows and the posterior probabilities acc[b] / acc[total] (zeros without membership weight)
+void write_star_mass_hist(const std::string &path, const std::vector<std::string> &ids, const double *star_hist, int n_bins, long n_rows);
+
+// massFunction's own settings: massFunction.{nBins, minMass, maxMass, linearBins, quantity, perStar, margIsoIncrem, nMassRatios,
+// nPops} (flags --nBins --minMass --maxMass --linearBins --quantity --perStar; --margIsoIncrem / --nMassRatios as sampleMass).
+// Default: 24 log-spaced bins over [0.1, M_wd_up] of the primary mass.
+struct MassFunctionConfig {
+    int n_bins, quantity, K, Q, n_pops;
+    double min_mass, max_mass;
+    bool linear, per_star;
+    std::vector<double> edges() const;       // n_bins + 1, strictly ascending; the end points are min_mass and max_mass exactly
+};
+MassFunctionConfig mass_function_config(const Settings &st, double m_wd_up);
+// --minMass / --maxMass belong to simCluster in the shared flag table: massFunction's command line has them renamed to the
+// flags of its own keys (--massFunctionMinMass / --massFunctionMaxMass) before Settings::parse_args sees it
+std::vector<std::string> mass_function_args(int argc, char **argv);
+
 const char *param_name(int idx);          // "logAge", "Y", "FeH", "modulus", "absorption", ...
 
 }  // namespace b9h

@@ -159,6 +159,50 @@ int b9h_write_star_summary(const char *path, const char *const *ids, long n_star
     });
 }
 
+int b9h_mass_function_table(const double *row_hist, long n_rows, const double *edges, int n_bins, double *table)
+{
+    return guard([&] {
+        if (n_rows < 0 || n_bins < 1 || !edges || !table || (n_rows > 0 && !row_hist)) throw std::runtime_error("b9h_mass_function_table: invalid argument");
+        b9h::mass_function_table(row_hist, n_rows, edges, n_bins, table);
+    });
+}
+
+int b9h_write_mass_function(const char *path, const double *table, int n_bins)
+{
+    return guard([&] {
+        if (!path || !table || n_bins < 1) throw std::runtime_error("b9h_write_mass_function: invalid argument");
+        b9h::write_mass_function(path, table, n_bins);
+    });
+}
+
+int b9h_write_star_mass_hist(const char *path, const char *const *ids, long n_stars, const double *star_hist, int n_bins, long n_rows)
+{
+    return guard([&] {
+        if (!path || n_stars < 0 || n_bins < 1 || (n_stars > 0 && (!ids || !star_hist))) throw std::runtime_error("b9h_write_star_mass_hist: invalid argument");
+        b9h::write_star_mass_hist(path, std::vector<std::string>(ids, ids + n_stars), star_hist, n_bins, n_rows);
+    });
+}
+
+int b9h_mass_function_settings(int argc, char **argv, double m_wd_up, char *out, int cap, double *edges /* [B9_HIST_MAX_BINS + 1], nullable */)
+{
+    return guard([&] {
+        if (!out) throw std::runtime_error("b9h_mass_function_settings: NULL argument");
+        const std::vector<std::string> args = b9h::mass_function_args(argc, argv);
+        std::vector<char *> av;
+        for (auto &a : args) av.push_back(const_cast<char *>(a.c_str()));
+        b9h::Settings st;
+        st.parse_args((int)av.size(), av.data());
+        const b9h::MassFunctionConfig c = b9h::mass_function_config(st, m_wd_up);
+        const std::string d = "nBins = " + std::to_string(c.n_bins) + "\nminMass = " + g17(c.min_mass) + "\nmaxMass = " + g17(c.max_mass) +
+                              "\nlinearBins = " + std::to_string((int)c.linear) + "\nquantity = " + std::to_string(c.quantity) +
+                              "\nperStar = " + std::to_string((int)c.per_star) + "\nmargIsoIncrem = " + std::to_string(c.K) +
+                              "\nnMassRatios = " + std::to_string(c.Q) + "\nnPops = " + std::to_string(c.n_pops) + "\n";
+        if ((int)d.size() >= cap) throw std::runtime_error("b9h_mass_function_settings: output buffer too small");
+        std::memcpy(out, d.c_str(), d.size() + 1);
+        if (edges) { const std::vector<double> e = c.edges(); std::copy(e.begin(), e.end(), edges); }
+    });
+}
+
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part)
 {
     return guard([&] { b9h::merge_result_parts(final_path, world, walkers_per_rank, rows_per_part); });

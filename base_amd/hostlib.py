@@ -37,6 +37,7 @@ HOST_SYMBOLS = [
     "b9h_load_pack", "b9h_free_pack", "b9h_read_phot", "b9h_free_phot", "b9h_settings_dump", "b9h_merge_parts",
     "b9h_sim_draw_systems", "b9h_sim_field_mags", "b9h_scatter", "b9h_sim_settings", "b9h_read_res_rows",
     "b9h_star_table", "b9h_write_star_summary",
+    "b9h_mass_function_table", "b9h_write_mass_function", "b9h_write_star_mass_hist", "b9h_mass_function_settings",
 ]
 
 _lib = None
@@ -86,6 +87,10 @@ def load() -> C.CDLL:
     lib.b9h_read_res_rows.argtypes = [C.c_char_p, _dp, C.c_int, _dp, C.c_long, C.POINTER(C.c_long)]
     lib.b9h_star_table.argtypes = [_dp, C.c_long, _dp]
     lib.b9h_write_star_summary.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int]
+    lib.b9h_mass_function_table.argtypes = [_dp, C.c_long, _dp, C.c_int, _dp]
+    lib.b9h_write_mass_function.argtypes = [C.c_char_p, _dp, C.c_int]
+    lib.b9h_write_star_mass_hist.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int, C.c_long]
+    lib.b9h_mass_function_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_double, C.c_char_p, C.c_int, _dp]
     lib.b9h_sim_draw_systems.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_int, C.c_double, _dp, _dp, _dp, _ip, _ip]
     lib.b9h_sim_field_mags.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int, _dp, _dp, _dp]
@@ -337,6 +342,66 @@ def read_star_summary(path: str):
             ids.append(t[0])
             rows.append([float(x) for x in t[1:]])
     return ids, header[1:], np.array(rows, dtype=np.float64).reshape(len(ids), len(header) - 1)
+
+
+MASS_FUNCTION_COLUMNS = ("lo", "hi", "mean", "sd", "p16", "p50", "p84", "dNdlogM")
+
+
+def mass_function_table(row_hist, edges) -> np.ndarray:
+    """b9h_mass_function_table: b9_mass_hist's row_hist [n_rows, n_bins + 1] -> the per-bin table [n_bins, 8]
+    (MASS_FUNCTION_COLUMNS)."""
+    edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    n_bins = len(edges) - 1
+    rh = np.ascontiguousarray(row_hist, dtype=np.float64).reshape(-1, n_bins + 1)
+    out = np.empty((n_bins, 8))
+    _check(load().b9h_mass_function_table(rh.ctypes.data_as(_dp), rh.shape[0], edges.ctypes.data_as(_dp), n_bins, out.ctypes.data_as(_dp)))
+    return out
+
+
+def write_mass_function(path: str, table) -> None:
+    """b9h_write_mass_function: the .massFunction file of a per-bin table [n_bins, 8]."""
+    table = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, 8)
+    _check(load().b9h_write_mass_function(path.encode(), table.ctypes.data_as(_dp), table.shape[0]))
+
+
+def write_star_mass_hist(path: str, ids, star_hist, n_rows: int) -> None:
+    """b9h_write_star_mass_hist: the .starMassHist file of b9_mass_hist's star_hist [len(ids), n_bins + 1] over n_rows rows."""
+    sh = np.ascontiguousarray(star_hist, dtype=np.float64).reshape(len(ids), -1)
+    arr = (C.c_char_p * len(ids))(*[str(i).encode() for i in ids])
+    _check(load().b9h_write_star_mass_hist(path.encode(), arr, len(ids), sh.ctypes.data_as(_dp), sh.shape[1] - 1, int(n_rows)))
+
+
+def mass_function_settings(args, m_wd_up: float = 8.0):
+    """massFunction's settings as the program parses `args` (flags, --config file): (dict of its keys, edges [nBins + 1])."""
+    argv = (C.c_char_p * (len(args) + 1))(b"massFunction", *[str(a).encode() for a in args])
+    buf = C.create_string_buffer(4096)
+    edges = np.zeros(65)
+    _check(load().b9h_mass_function_settings(len(args) + 1, argv, float(m_wd_up), buf, 4096, edges.ctypes.data_as(_dp)))
+    d = {}
+    for line in buf.value.decode().splitlines():
+        k, v = line.split(" = ")
+        d[k] = float(v) if k in ("minMass", "maxMass") else int(v)
+    return d, edges[:d["nBins"] + 1].copy()
+
+
+def read_table_file(path: str, first: str):
+    """(labels of the first column, columns, values [lines, len(columns)]) of a whitespace table with one header line;
+    first: the header's first word ("id" for .starMassHist; None: every column is a number, as in .massFunction)."""
+    with open(path) as f:
+        header = f.readline().split()
+        skip = 0 if first is None else 1
+        if first is not None and header[:1] != [first]:
+            raise HostError(path + ": unexpected header")
+        labels, rows = [], []
+        for line in f:
+            t = line.split()
+            if not t:
+                continue
+            if len(t) != len(header):
+                raise HostError(path + ": a line does not hold one value per column")
+            labels.append(t[0])
+            rows.append([float(x) for x in t[skip:]])
+    return labels, header[skip:], np.array(rows, dtype=np.float64).reshape(len(rows), len(header) - skip)
 
 
 # ------------------------------------------------------------------------------------------

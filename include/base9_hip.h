@@ -293,8 +293,8 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk);
  * may be outstanding; they are collected in the order they were enqueued.  A successful b9_load_pack, b9_load_stars,
  * b9_set_priors or b9_set_options changes the posterior: the previous block's state carries a log-posterior of the old
  * one, so the next B9_BLOCK_CONTINUE block returns B9_ERR_STATE (the message names the call that intervened) and the chain
- * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags, b9_sample_wd_mass and b9_star_moments
- * (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
+ * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags, b9_sample_wd_mass, b9_star_moments and
+ * b9_mass_hist (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
  * context's work buffers: b9_logpost / b9_sample_mass / b9_derive_isochrone, the staging calls, b9_set_options and a block
  * with another n_walkers return B9_ERR_STATE until it has been collected.  A driver that adapts the proposal
  * from block b-1 while block b runs keeps the GPU's queue non-empty: enqueue b+1 (CONTINUE | ASYNC), wait(b), ...
@@ -436,6 +436,43 @@ enum b9_moment {
 #define B9_MOM_CONTINUE 1
 int b9_star_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags,
                     double *acc /* host, [n_stars][B9_MOM_N], in/out */);
+
+/*
+ * Exact binned mass posteriors over a saved chain (the massFunction counterpart).  Added in ABI 6 without a version change, as
+ * b9_predict_mags and b9_star_moments were: purely additive.  Where b9_star_moments keeps the first two moments of the
+ * primary mass per star, this call keeps the DISTRIBUTION: per star summed over the rows (star_hist) and per row summed over
+ * the stars (row_hist).
+ *
+ * Definition.  Grid, terms t_(k,n), L = logsumexp t, w = exp(t - L) and the membership p are exactly b9_star_moments':
+ * terms that are not finite do not take part; n_pops is honoured, mode ignored; WD-stage stars use 8 * marg_iso_increm steps
+ * above the AGB tip at mass ratio 0; terms more than 40 e-folds below a data-only lower bound of the star's largest term may be
+ * dropped (b9_tuning.marg_no_pruning: none are).  A node's value v is, by `quantity`,
+ *     B9_HQ_PRIMARY    M1, the node's primary ZAMS mass as b9_sample_mass reports it (MS/RGB: fma(s, dM, a); WD stage: tip + dM j)
+ *     B9_HQ_SECONDARY  m2 = ((double)j / (double)n_q) * M1, for the nodes with j > 0 only (WD-stage stars contribute nothing)
+ *     B9_HQ_SYSTEM     M1 + m2, every operation rounded on its own (j = 0 and WD-stage stars: M1)
+ * edges (host, [n_bins + 1]) must be finite and strictly ascending, 1 <= n_bins <= B9_HIST_MAX_BINS.  Bin b holds
+ * e_b <= v < e_(b+1), decided on the value's own bits; a value below e_0, or at or above the last edge, falls in no bin -- but
+ * still normalises, since w is taken over ALL nodes: a bin's value does not depend on which other bins were asked for, and
+ * calls with disjoint edge sets compose exactly.  Row r adds to star i
+ *     x[b] = p sum_{(k,n): v in bin b} w   (b < n_bins),        x[n_bins] = p   (the total column)
+ * and nothing at all (every entry 0) where b9_star_moments would add nothing: a row outside the grid, a star with no live node.
+ *
+ * star_hist (host, [n_stars][n_bins + 1], the caller's star order, in/out, nullable): acc + x_r, one plain add per row in
+ * ascending row order; flags = 0 starts from zeros, B9_HIST_CONTINUE from the caller's values.  The same bits for the call's
+ * own chunking (at most 32 rows at a time, fewer while the per-(row, star) scratch would exceed 64 MiB) and for any split of the
+ * rows over continued calls.  row_hist (host, [n_rows][n_bins + 1], out, nullable): sum_i x_r[i][c] over the caller's star
+ * order, ascending, one plain add per star; a row's line depends on that row alone; column n_bins is the expected number of
+ * members under that row.  Synchronous; host pointers.  B9_ERR_INVALID (outputs untouched) for bad edges or n_bins, an unknown
+ * quantity, n_rows < 1, NULL params or edges, or both outputs NULL; B9_ERR_STATE while a sampler block is outstanding.  The
+ * call uses buffers of its own: a B9_BLOCK_CONTINUE block enqueued after it gives the same bits as one enqueued without it.
+ */
+enum b9_hist_quantity { B9_HQ_PRIMARY = 0, B9_HQ_SECONDARY = 1, B9_HQ_SYSTEM = 2 };
+#define B9_HIST_MAX_BINS 64
+#define B9_HIST_CONTINUE 1
+int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quantity,
+                 const double *edges /* [n_bins + 1] */, int32_t n_bins, int32_t flags,
+                 double *star_hist /* host [n_stars][n_bins + 1], in/out, may be NULL */,
+                 double *row_hist  /* host [n_rows][n_bins + 1], out,    may be NULL */);
 
 /* ---- introspection (used by bench/tests; no compute) --------------------------------- */
 int b9_max_eep(const b9_ctx *ctx);           /* longest isochrone in the loaded pack        */

@@ -108,6 +108,20 @@ int b9h_read_res_rows(const char *path, const double *start_row, int stage, doub
  * "id rows member mass massSd massRatio massRatioSd pBinary [pPop2]" (the last column with n_pops == 2 only), in the order of ids. */
 int b9h_star_table(const double *acc, long n_stars, double *table);
 int b9h_write_star_summary(const char *path, const char *const *ids, long n_stars, const double *acc, int n_pops);
+/* massFunction.  b9h_mass_function_table: b9_mass_hist's row_hist [n_rows][n_bins + 1] -> the per-bin table [n_bins][8]:
+ * lo, hi, then over the rows whose member column (the last) is > 0 the mean, the population standard deviation, the 16th, 50th
+ * and 84th percentiles of the bin's expected count (linear interpolation between order statistics, numpy's default) and
+ * dN/dlog10 m = mean / log10(hi / lo) (0 where lo <= 0); without such a row every statistic is 0.
+ * b9h_write_mass_function: the file <base>.massFunction (docs/FORMATS.md), "lo hi mean sd p16 p50 p84 dNdlogM" per bin.
+ * b9h_write_star_mass_hist: the file <base>.starMassHist, per star "id rows member bin0 .. bin<n-1>" with member =
+ * star_hist[i][n_bins] / n_rows and bin b = star_hist[i][b] / star_hist[i][n_bins] (0 without membership weight).
+ * b9h_mass_function_settings: massFunction's command line (argv[0] is skipped) and YAML parsed as the program parses them --
+ * "key = value" lines of nBins, minMass, maxMass, linearBins, quantity (0 / 1 / 2), perStar, margIsoIncrem, nMassRatios, nPops
+ * into out, and the nBins + 1 bin edges into edges (nullable); m_wd_up is the default maxMass. */
+int b9h_mass_function_table(const double *row_hist, long n_rows, const double *edges, int n_bins, double *table);
+int b9h_write_mass_function(const char *path, const double *table, int n_bins);
+int b9h_write_star_mass_hist(const char *path, const char *const *ids, long n_stars, const double *star_hist, int n_bins, long n_rows);
+int b9h_mass_function_settings(int argc, char **argv, double m_wd_up, char *out, int cap, double *edges);
 /* rank 0's merge of <final_path>.part<r> into <final_path> after a --gpus N run (b9h::merge_result_parts; exposed for tests) */
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part);
 
