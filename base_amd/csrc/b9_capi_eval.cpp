@@ -1,7 +1,8 @@
 // b9_capi_eval.cpp -- one log-posterior evaluation through the C ABI: derive -> stars -> finalize (b9_logpost,
 // b9_logpost_device), the per-star mass draws (b9_sample_mass), the isochrone dump (b9_derive_isochrone) and the forward
 // model alone (b9_predict_mags) the WD-stage stars' posterior draws (b9_sample_wd_mass), the
-// per-star posterior moments (b9_star_moments) and the binned mass posteriors (b9_mass_hist).
+// per-star posterior moments (b9_star_moments), the binned mass posteriors (b9_mass_hist) and the
+// posterior-predictive residuals (b9_phot_resid).
 #include "b9_ctx.h"
 #include <algorithm>
 #include <cmath>
@@ -444,6 +445,73 @@ int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quan
         if (d_rows) HIPCHK(ctx, hipMemcpyAsync(row_hist + (size_t)r0 * ncol, d_rows, sizeof(double) * m * ncol, hipMemcpyDeviceToHost, s));
     }
     if (d_acc) HIPCHK(ctx, hipMemcpyAsync(star_hist, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return B9_OK;
+}
+
+// Chunks as b9_mass_hist's: at most B9_RESID_MAX_ROWS rows, fewer while the chunk's increments would exceed B9_RESID_SCRATCH_BYTES.
+#define B9_RESID_SCRATCH_BYTES ((size_t)64 << 20)
+#define B9_RESID_MAX_ROWS 32
+
+int b9_phot_resid(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags, double *star_resid, double *row_resid)
+{
+    if (!ctx || !params || n_rows < 1 || (!star_resid && !row_resid)) return B9_ERR_INVALID;
+    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
+    if (!ctx->have_pack || !ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
+    const int n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
+    const int K = marg_grid(ctx).K, Q = marg_grid(ctx).Q;
+    const DevPack &pk = ctx->pk;
+    const size_t nf = (size_t)pk.nf, ncol = 2 + 2 * nf, nrow = 1 + 5 * nf;
+    if (n == 0) {
+        if (row_resid) std::fill(row_resid, row_resid + (size_t)n_rows * nrow, 0.0);
+        return B9_OK;
+    }
+    const int mass_cap = pack_mass_cap(pk.max_eep);
+    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
+    const size_t tab_row = (size_t)n_pops * (size_t)b9k_marg_table_doubles(pk.nfp, mass_cap, K, Q);
+    const size_t wd_row = ctx->st.n_wd > 0 ? (size_t)n_pops * (size_t)b9k_marg_wd_table_doubles(pk.nfp, K) : 0;
+    const size_t chunk = mom_chunk_rows((size_t)n_rows, (size_t)n, ncol, B9_RESID_MAX_ROWS, B9_RESID_SCRATCH_BYTES);
+    if (chunk * (tab_row + wd_row) > ((size_t)8 << 30) / sizeof(double))
+        return fail(ctx, B9_ERR_CAPACITY, "b9_phot_resid: marginalisation grid too fine: the node tables would exceed 8 GiB");
+    // one allocation: [params][headers][isochrones][table][WD table][increments][accumulators][the chunk's row sums][pivots, twice][1 / sigma]
+    const ResidArena a = resid_arena(chunk, n_pops, iso_stride, tab_row, wd_row, (size_t)n, nf, (size_t)pk.nfp, (size_t)ctx->st.mg_pad, sizeof(IsoHdr));
+    RESERVE(ctx, ctx->d_resid, a.bytes);
+    char *base = ctx->d_resid.get();
+    double *d_par = part<double>(base, a.m.o_par), *d_iso = part<double>(base, a.m.o_iso), *d_tab = part<double>(base, a.m.o_tab);
+    double *d_wd = wd_row ? part<double>(base, a.m.o_wd) : nullptr, *d_scratch = part<double>(base, a.m.o_scratch);
+    double *d_acc = star_resid ? part<double>(base, a.m.o_acc) : nullptr, *d_rows = row_resid ? part<double>(base, a.o_rows) : nullptr;
+    double *d_piv_in = part<double>(base, a.o_piv_in), *d_piv_mg = part<double>(base, a.o_piv_mg), *d_isig = part<double>(base, a.o_isig);
+    IsoHdr *d_hdr = part<IsoHdr>(base, a.m.o_hdr);
+    // the pivots (the caller's obs bits where sigma > 0, else 0) and 1 / sigma (0: filter unused), the caller's star order
+    const HostStars &h = ctx->hs;
+    std::vector<double> piv((size_t)n * nf), isig((size_t)n * nf);
+    for (size_t k = 0; k < piv.size(); ++k) {
+        const bool used = h.sigma[k] > 0.0;
+        piv[k] = used ? h.obs[k] : 0.0;
+        isig[k] = used ? 1.0 / h.sigma[k] : 0.0;
+    }
+    const size_t acc_bytes = sizeof(double) * (size_t)n * ncol;
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(d_piv_in, piv.data(), sizeof(double) * piv.size(), hipMemcpyHostToDevice, s));
+    if (d_rows) HIPCHK(ctx, hipMemcpyAsync(d_isig, isig.data(), sizeof(double) * isig.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, b9k_resid_stage(pk, ctx->st, d_piv_in, d_piv_mg, s));
+    if (d_acc) {
+        if (flags & B9_RESID_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_acc, star_resid, acc_bytes, hipMemcpyHostToDevice, s));
+        else HIPCHK(ctx, hipMemsetAsync(d_acc, 0, acc_bytes, s));
+    }
+    const McmcDev off{};
+    for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
+        const int m = std::min((int)chunk, n_rows - r0);
+        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
+        // every (row, star) of the chunk writes all its columns (zeros where it contributes nothing): no clearing
+        HIPCHK(ctx, b9k_phot_resid(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, K, Q, ctx->marg_prune, d_piv_mg, d_isig,
+                                   d_tab, d_wd, d_scratch, d_acc, d_rows, s));
+        if (d_rows) HIPCHK(ctx, hipMemcpyAsync(row_resid + (size_t)r0 * nrow, d_rows, sizeof(double) * m * nrow, hipMemcpyDeviceToHost, s));
+    }
+    if (d_acc) HIPCHK(ctx, hipMemcpyAsync(star_resid, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return B9_OK;
 }

@@ -139,6 +139,23 @@ inline HistArena hist_arena(size_t chunk, int n_pops, long long iso_stride, size
     return a;
 }
 
+// b9_phot_resid's chunk of rows: mom_arena with n_col = 2 + 2 nf columns per star, then the chunk's per-row sums
+// [chunk][1 + 5 nf], the call's pivots in the caller's order [n_stars][nf] and in the mg_* copy's [mg_pad][nfp], and 1 / sigma [n_stars][nf]
+struct ResidArena { MomArena m; size_t o_rows, o_piv_in, o_piv_mg, o_isig, bytes; };
+inline ResidArena resid_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t wd_row, size_t n_stars, size_t nf, size_t nfp,
+                              size_t mg_pad, size_t hdr_bytes)
+{
+    ResidArena a{mom_arena(chunk, n_pops, iso_stride, tab_row, wd_row, n_stars, 2 + 2 * nf, hdr_bytes), 0, 0, 0, 0, 0};
+    Carve c;
+    c.take(a.m.bytes);
+    a.o_rows = c.take(8 * chunk * (1 + 5 * nf));
+    a.o_piv_in = c.take(8 * n_stars * nf);
+    a.o_piv_mg = c.take(8 * mg_pad * nfp);
+    a.o_isig = c.take(8 * n_stars * nf);
+    a.bytes = c.total;
+    return a;
+}
+
 // ---- sizing rules
 
 // rows of a derived isochrone: the pack's longest one, rounded up to even; and its doubles: a mass column + nfp magnitude columns

@@ -31,6 +31,8 @@
 //                                     grid (one lane per star, four waves sharing the node table), summed over the rows
 //   k_star_hist / _wd / k_hist_accumulate / k_hist_rows   b9_mass_hist: exact binned mass posteriors over the same grid (a
 //                                     per-wave LDS histogram per lane, bins worked in tiles), summed over the rows and the stars
+//   k_star_resid / _wd / k_resid_stage / k_resid_accumulate / k_resid_rows   b9_phot_resid: exact posterior-predictive magnitude
+//                                     moments per filter over the same grid, summed over the rows and, standardised, the stars
 //
 // The kernels live in the *.hip.h files included below (one translation unit); this file holds
 // k_finalize and the host-callable launch wrappers.
@@ -73,6 +75,7 @@ namespace tree_kd5 {
 #include "b9_wd_sample.hip.h"
 #include "b9_star_moments.hip.h"
 #include "b9_mass_hist.hip.h"
+#include "b9_phot_resid.hip.h"
 
 // ------------------------------------------------------------------------------------------
 // k_finalize: one workgroup per walker: fixed-order sum of the partials + prior -> logpost[w]
@@ -341,6 +344,50 @@ hipError_t b9k_mass_hist(const DevPack &pk, const DevStars &st, const IsoHdr *hd
             hipLaunchKernelGGL(k_hist_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
         if (rows)
             hipLaunchKernelGGL(k_hist_rows, dim3((unsigned)((n_rows * ncol + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, st.n, ncol, rows);
+        return hipGetLastError();
+    });
+}
+
+// ---- b9_phot_resid: the node tables of a chunk of rows, the stars' residual increments, the accumulation, the rows' sums ----------
+hipError_t b9k_resid_stage(const DevPack &pk, const DevStars &st, const double *piv_in, double *piv_mg, hipStream_t stream)
+{
+    return dispatch_nfp(pk.nfp, [&](auto nfp_c) {
+        constexpr int NFP = decltype(nfp_c)::value;
+        if (!piv_in || !piv_mg) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_resid_stage<NFP>, dim3((unsigned)((st.mg_pad * NFP + 255) / 256)), dim3(256), 0, stream, st, pk.nf, piv_in, piv_mg);
+        return hipGetLastError();
+    });
+}
+
+hipError_t b9k_phot_resid(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                          const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, const double *piv_mg, const double *isig,
+                          double *tab, double *wd_tab, double *scratch, double *acc, double *rows, hipStream_t stream)
+{
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        if (!tab || !scratch || !piv_mg || (rows && !isig) || n_rows < 1 || n_rows > 65535 || (st.n_wd > 0 && !wd_tab)) return hipErrorInvalidValue;
+        const int nf = pk.nf;
+        const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
+        const hipError_t e = launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, tab, stream);
+        if (e != hipSuccess) return e;
+        const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
+        const auto k = with_lds(k_star_resid<NFP, NPOPS>, sizeof(double) * 64 * (NPOPS * 4 + 4 * (2 + 2 * (size_t)NFP)));      // seeds, one population's states
+        if (k.err != hipSuccess) return k.err;
+        hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows), dim3(256), k.lds, stream, st, nf, piv_mg, hdr, iso_data, iso_stride, mass_cap,
+                           d_params, K, Q, (const double *)tab, L, cut2, scratch);
+        if (st.n_wd > 0) {
+            launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, wd_tab, stream);
+            hipLaunchKernelGGL((k_star_resid_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, nf, pk.m_wd_up, hdr, d_params, K,
+                               (const double *)wd_tab, scratch);
+        }
+        const long long n_words = (long long)st.n * (2 + 2 * nf);
+        if (acc)
+            hipLaunchKernelGGL(k_resid_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
+        if (rows) {
+            const auto kr = with_lds(k_resid_rows, sizeof(double) * 2 * B9_RESID_TILE * (2 + 3 * (size_t)nf));      // two tiles of {x, 1 / sigma}
+            if (kr.err != hipSuccess) return kr.err;
+            hipLaunchKernelGGL(kr.kern, dim3(n_rows), dim3(256), kr.lds, stream, (const double *)scratch, isig, st.n, nf, rows);
+        }
         return hipGetLastError();
     });
 }

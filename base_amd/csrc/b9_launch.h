@@ -134,6 +134,16 @@ hipError_t b9k_mass_hist(const DevPack &pk, const DevStars &st, const IsoHdr *hd
                          const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, int quantity, const double *edges, int n_bins,
                          double *tab, double *wd_tab, double *scratch, double *acc, double *rows, hipStream_t stream);
 
+// b9_phot_resid.  b9k_resid_stage: the call's pivots piv_in [st.n][pk.nf] (the caller's star order) into the mg_* copy's order,
+// piv_mg [st.mg_pad / 64][pk.nfp][64].  b9k_phot_resid: the node tables as b9k_star_moments builds them, every star's increments
+// into scratch [n_rows][st.n][2 + 2 nf], then acc [st.n][2 + 2 nf] += the rows in ascending order (acc may be null) and
+// rows [n_rows][1 + 5 nf] = the stars' standardised sums in ascending order (may be null; isig [st.n][nf] = 1 / sigma, 0 for an
+// unused filter, is read for them only).  Device pointers, all the caller's own.
+hipError_t b9k_resid_stage(const DevPack &pk, const DevStars &st, const double *piv_in, double *piv_mg, hipStream_t stream);
+hipError_t b9k_phot_resid(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                          const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, const double *piv_mg, const double *isig,
+                          double *tab, double *wd_tab, double *scratch, double *acc, double *rows, hipStream_t stream);
+
 hipError_t b9k_noop(hipStream_t stream);
 hipError_t b9k_spin(double microseconds, hipStream_t stream);
 constexpr int B9_CLOCK_SLOTS = 8 * 256;      // (XCD, HW_ID[15:8]) -> one slot per compute unit

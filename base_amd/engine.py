@@ -233,6 +233,28 @@ class Engine:
                                           ptr(sh), ptr(rh)))
         return sh, rh
 
+    def phot_resid(self, rows: np.ndarray, star_resid: Optional[np.ndarray] = None, want_star: bool = True,
+                   want_rows: bool = True) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+        """b9_phot_resid: the exact posterior-predictive residuals over `rows`: (star_resid [n_stars, 2 + 2 n_filt] summed over
+        the rows -- ROWS, MEMBER, then per filter p sum w d and p sum w d^2 about the star's pivot --, row_resid
+        [n_rows, 1 + 5 n_filt] -- sum p, then per filter N, R, C, W, D over the stars that have the filter).  star_resid=None
+        starts from zeros; else the call continues it (B9_RESID_CONTINUE) and returns a new array.  want_star / want_rows =
+        False passes NULL for that output (None back)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        nf = self.n_filt
+        flags = 0
+        sr = rr = None
+        if want_star:
+            if star_resid is None:
+                sr = np.zeros((self.n_stars, 2 + 2 * nf))
+            else:
+                sr, flags = np.array(star_resid, dtype=np.float64, order="C").reshape(self.n_stars, 2 + 2 * nf), abi.RESID_CONTINUE
+        if want_rows:
+            rr = np.zeros((rows.shape[0], 1 + 5 * nf))
+        ptr = lambda a: a.ctypes.data_as(_dp) if a is not None else None      # noqa: E731
+        self._check(self.lib.b9_phot_resid(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], flags, ptr(sr), ptr(rr)))
+        return sr, rr
+
     def derive_isochrone(self, param_row: np.ndarray, pop: int = 0, cap: int = 4096) -> Tuple[int, np.ndarray, np.ndarray, float]:
         row = np.ascontiguousarray(param_row, dtype=np.float64)
         mass = np.empty(cap)

@@ -129,6 +129,7 @@ const std::map<std::string, std::string> &Settings::flag_map()
         {"nMassNodes", "sampleWDMass.nMassNodes"},
         {"nBins", "massFunction.nBins"}, {"massFunctionMinMass", "massFunction.minMass"}, {"massFunctionMaxMass", "massFunction.maxMass"},
         {"linearBins", "massFunction.linearBins"}, {"quantity", "massFunction.quantity"}, {"perStar", "massFunction.perStar"},
+        {"photResidualsPerStar", "photResiduals.perStar"}, {"photResidualsNPops", "photResiduals.nPops"},
         {"nStars", "simCluster.nStars"}, {"percentBinary", "simCluster.percentBinary"}, {"percentDB", "simCluster.percentDB"},
         {"nFieldStars", "simCluster.nFieldStars"}, {"minMass", "simCluster.minMass"}, {"maxMass", "simCluster.maxMass"},
         {"minMassRatio", "simCluster.minMassRatio"}, {"memberPrior", "simCluster.memberPrior"}, {"nPops", "simCluster.nPops"},
@@ -637,6 +638,95 @@ std::vector<std::string> mass_function_args(int argc, char **argv)
         out.push_back(a);
     }
     return out;
+}
+
+// ---------------------------------------------------------------------------------------------
+// photResiduals
+// ---------------------------------------------------------------------------------------------
+void resid_table(const double *star_resid, const double *obs, const double *sigma, long n_stars, int nf, double *table)
+{
+    const size_t ncol = 2 + 2 * (size_t)nf, tcol = 2 + 4 * (size_t)nf;
+    for (long i = 0; i < n_stars; ++i) {
+        const double *a = star_resid + (size_t)i * ncol;
+        double *t = table + (size_t)i * tcol;
+        for (size_t c = 0; c < tcol; ++c) t[c] = 0.0;
+        t[0] = a[0];
+        if (a[0] > 0.0) t[1] = a[1] / a[0];
+        if (!(a[1] > 0.0)) continue;                         // no membership weight: every derived value is 0
+        for (int f = 0; f < nf; ++f) {
+            const double sg = sigma[(size_t)i * nf + f], o = obs[(size_t)i * nf + f];
+            const bool used = sg > 0.0;
+            const double m1 = a[2 + 2 * f] / a[1], m2 = a[3 + 2 * f] / a[1];
+            double *tf = t + 2 + 4 * (size_t)f;
+            tf[0] = (used ? o : 0.0) + m1;
+            tf[1] = std::sqrt(std::max(0.0, m2 - m1 * m1));
+            if (used) { tf[2] = o - tf[0]; tf[3] = std::sqrt(m2) / sg; }
+        }
+    }
+}
+
+void filter_resid_table(const double *row_resid, long n_rows, int nf, double *table)
+{
+    const size_t ncol = 1 + 5 * (size_t)nf;
+    std::vector<double> v;
+    for (int f = 0; f < nf; ++f) {
+        double *t = table + (size_t)f * kFilterResidCols;
+        for (int c = 0; c < kFilterResidCols; ++c) t[c] = 0.0;
+        std::vector<long> use;
+        for (long r = 0; r < n_rows; ++r)
+            if (row_resid[(size_t)r * ncol + 1 + 5 * f] > 0.0) use.push_back(r);
+        t[0] = (double)use.size();
+        if (use.empty()) continue;
+        for (int q = 0; q < 3; ++q) {
+            v.resize(use.size());
+            double sum = 0.0;
+            for (size_t k = 0; k < use.size(); ++k) {
+                const double *x = row_resid + (size_t)use[k] * ncol + 1 + 5 * f;          // N, R, C, W, D
+                v[k] = q == 0 ? x[1] / x[0] : q == 1 ? x[2] / x[0] : (x[3] > 0.0 ? x[4] / x[3] : 0.0);
+                sum += v[k];
+            }
+            const double mean = sum / (double)use.size();
+            double ss = 0.0;
+            for (double x : v) ss += (x - mean) * (x - mean);
+            std::sort(v.begin(), v.end());
+            double *tq = t + 1 + 5 * q;
+            tq[0] = mean;
+            tq[1] = std::sqrt(ss / (double)use.size());
+            tq[2] = percentile_sorted(v, 0.16); tq[3] = percentile_sorted(v, 0.50); tq[4] = percentile_sorted(v, 0.84);
+        }
+    }
+}
+
+void write_phot_resid(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &filters, const double *table)
+{
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) fail("cannot write " + path);
+    std::fprintf(f, "id rows member");
+    for (const std::string &n : filters) std::fprintf(f, " %s_predMag %s_predSd %s_resid %s_rmsZ", n.c_str(), n.c_str(), n.c_str(), n.c_str());
+    std::fprintf(f, "\n");
+    const size_t tcol = 2 + 4 * filters.size();
+    for (size_t i = 0; i < ids.size(); ++i) {
+        std::fprintf(f, "%s", ids[i].c_str());
+        for (size_t c = 0; c < tcol; ++c) std::fprintf(f, " %.17g", table[i * tcol + c]);
+        std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) fail("cannot write " + path);
+}
+
+void write_filter_resid(const std::string &path, const std::vector<std::string> &filters, const double *table)
+{
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) fail("cannot write " + path);
+    std::fprintf(f, "filter nRows");
+    for (const char *q : {"meanZ", "chi2", "offset"})
+        for (const char *s : {"mean", "sd", "p16", "p50", "p84"}) std::fprintf(f, " %s_%s", q, s);
+    std::fprintf(f, "\n");
+    for (size_t k = 0; k < filters.size(); ++k) {
+        std::fprintf(f, "%s", filters[k].c_str());
+        for (int c = 0; c < kFilterResidCols; ++c) std::fprintf(f, " %.17g", table[k * kFilterResidCols + c]);
+        std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) fail("cannot write " + path);
 }
 
 const char *param_name(int idx)

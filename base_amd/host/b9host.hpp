@@ -124,6 +124,26 @@ MassFunctionConfig mass_function_config(const Settings &st, double m_wd_up);
 // flags of its own keys (--massFunctionMinMass / --massFunctionMaxMass) before Settings::parse_args sees it
 std::vector<std::string> mass_function_args(int argc, char **argv);
 
+// ---- photResiduals ---------------------------------------------------------------------------------
+// b9_phot_resid's star_resid [n_stars][2 + 2 nf] with the catalogue's obs / sigma [n_stars][nf] -> the per-star table
+// [n_stars][2 + 4 nf]: rows, member (= acc[1] / rows), then per filter
+//   predMag = c + acc[2 + 2f] / acc[1]        (c: obs where sigma > 0, else 0 -- the call's pivot)
+//   predSd  = sqrt(max(0, acc[3 + 2f] / acc[1] - (acc[2 + 2f] / acc[1])^2))
+//   resid   = obs - predMag                   (used filters; 0 for an unused one)
+//   rmsZ    = sqrt(acc[3 + 2f] / acc[1]) / sigma   (likewise)
+// Every derived value is 0 when acc[1] == 0.  Host arithmetic only.
+void resid_table(const double *star_resid, const double *obs, const double *sigma, long n_stars, int nf, double *table);
+// b9_phot_resid's row_resid [n_rows][1 + 5 nf] -> the per-filter table [nf][kFilterResidCols]: the number of rows with N_f > 0,
+// then over those rows the mean, the population standard deviation and the 16th / 50th / 84th percentiles (mass_function_table's
+// rule) of meanZ = R_f / N_f, of chi2 = C_f / N_f and of offset = D_f / W_f.  No such row: every entry 0.
+constexpr int kFilterResidCols = 16;
+void filter_resid_table(const double *row_resid, long n_rows, int nf, double *table);
+// <base>.photResid (docs/FORMATS.md): "id rows member {<filter>_predMag <filter>_predSd <filter>_resid <filter>_rmsZ}", one line
+// per star in the order of ids; <base>.filterResid: "filter nRows {meanZ chi2 offset}_{mean sd p16 p50 p84}", one line per filter.
+// Numbers are written with 17 significant digits: the files read back to the tables' bits.
+void write_phot_resid(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &filters, const double *table);
+void write_filter_resid(const std::string &path, const std::vector<std::string> &filters, const double *table);
+
 const char *param_name(int idx);          // "logAge", "Y", "FeH", "modulus", "absorption", ...
 
 }  // namespace b9h

@@ -203,6 +203,55 @@ int b9h_mass_function_settings(int argc, char **argv, double m_wd_up, char *out,
     });
 }
 
+int b9h_resid_table(const double *star_resid, const double *obs, const double *sigma, long n_stars, int n_filt, double *table)
+{
+    return guard([&] {
+        if (n_stars < 0 || n_filt < 1 || !table || (n_stars > 0 && (!star_resid || !obs || !sigma))) throw std::runtime_error("b9h_resid_table: invalid argument");
+        b9h::resid_table(star_resid, obs, sigma, n_stars, n_filt, table);
+    });
+}
+
+int b9h_filter_resid_table(const double *row_resid, long n_rows, int n_filt, double *table)
+{
+    return guard([&] {
+        if (n_rows < 0 || n_filt < 1 || !table || (n_rows > 0 && !row_resid)) throw std::runtime_error("b9h_filter_resid_table: invalid argument");
+        b9h::filter_resid_table(row_resid, n_rows, n_filt, table);
+    });
+}
+
+int b9h_write_phot_resid(const char *path, const char *const *ids, long n_stars, const char *const *filters, int n_filt, const double *table)
+{
+    return guard([&] {
+        if (!path || n_stars < 0 || n_filt < 1 || !filters || (n_stars > 0 && (!ids || !table))) throw std::runtime_error("b9h_write_phot_resid: invalid argument");
+        b9h::write_phot_resid(path, std::vector<std::string>(ids, ids + n_stars), std::vector<std::string>(filters, filters + n_filt), table);
+    });
+}
+
+int b9h_write_filter_resid(const char *path, const char *const *filters, int n_filt, const double *table)
+{
+    return guard([&] {
+        if (!path || n_filt < 1 || !filters || !table) throw std::runtime_error("b9h_write_filter_resid: invalid argument");
+        b9h::write_filter_resid(path, std::vector<std::string>(filters, filters + n_filt), table);
+    });
+}
+
+int b9h_phot_resid_settings(int argc, char **argv, char *out, int cap)
+{
+    return guard([&] {
+        if (!out) throw std::runtime_error("b9h_phot_resid_settings: NULL argument");
+        const std::vector<std::string> args = b9h::phot_resid_args(argc, argv);
+        std::vector<char *> av;
+        for (auto &a : args) av.push_back(const_cast<char *>(a.c_str()));
+        b9h::Settings st;
+        st.parse_args((int)av.size(), av.data());
+        const b9h::PhotResidConfig c = b9h::phot_resid_config(st);
+        const std::string d = "margIsoIncrem = " + std::to_string(c.K) + "\nnMassRatios = " + std::to_string(c.Q) + "\nnPops = " + std::to_string(c.n_pops) +
+                              "\nperStar = " + std::to_string((int)c.per_star) + "\n";
+        if ((int)d.size() >= cap) throw std::runtime_error("b9h_phot_resid_settings: output buffer too small");
+        std::memcpy(out, d.c_str(), d.size() + 1);
+    });
+}
+
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part)
 {
     return guard([&] { b9h::merge_result_parts(final_path, world, walkers_per_rank, rows_per_part); });

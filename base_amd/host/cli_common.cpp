@@ -433,6 +433,31 @@ std::vector<double> read_res_rows(const std::string &res_path, const std::vector
     return rows;
 }
 
+PhotResidConfig phot_resid_config(const Settings &st)
+{
+    PhotResidConfig c;
+    c.K = (int)st.integer("photResiduals.margIsoIncrem", st.integer("sampleMass.margIsoIncrem", 4));
+    c.Q = (int)st.integer("photResiduals.nMassRatios", st.integer("sampleMass.nMassRatios", 4));
+    c.n_pops = (int)st.integer("photResiduals.nPops", 1);
+    c.per_star = st.integer("photResiduals.perStar", 0) != 0;
+    if (c.K < 1 || c.Q < 1) throw std::runtime_error("margIsoIncrem and nMassRatios must be positive");
+    if (c.n_pops != 1 && c.n_pops != 2) throw std::runtime_error("photResiduals.nPops must be 1 or 2");
+    return c;
+}
+
+std::vector<std::string> phot_resid_args(int argc, char **argv)
+{
+    std::vector<std::string> out;
+    for (int i = 0; i < argc; ++i) {
+        std::string a = argv[i];
+        if (a == "--perStar") a = "--photResidualsPerStar=1";
+        else if (a.rfind("--perStar=", 0) == 0) a = "--photResidualsPerStar" + a.substr(9);
+        else if (a == "--nPops" || a.rfind("--nPops=", 0) == 0) a = "--photResidualsNPops" + a.substr(7);
+        out.push_back(a);
+    }
+    return out;
+}
+
 int report_and_exit_code(const char *prog, const std::exception &e)
 {
     std::fprintf(stderr, "%s: %s\n", prog, e.what());

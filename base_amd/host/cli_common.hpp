@@ -62,6 +62,14 @@ void merge_result_parts(const std::string &final_path, int world, int per, long 
 // What sampleMass and sampleWDMass read (libbase9host exports it as b9h_read_res_rows).
 std::vector<double> read_res_rows(const std::string &res_path, const std::vector<double> &start, int stage);
 
+// photResiduals' own settings: photResiduals.{margIsoIncrem, nMassRatios, nPops, perStar}, the grid defaulting to sampleMass's
+// (4 each; flags --margIsoIncrem / --nMassRatios as sampleMass), one population, no per-star file.
+struct PhotResidConfig { int K, Q, n_pops; bool per_star; };
+PhotResidConfig phot_resid_config(const Settings &st);
+// --perStar and --nPops belong to massFunction and simCluster in the shared flag table: photResiduals' command line has them
+// renamed to the flags of its own keys (--photResidualsPerStar / --photResidualsNPops) before Settings::parse_args sees it
+std::vector<std::string> phot_resid_args(int argc, char **argv);
+
 int report_and_exit_code(const char *prog, const std::exception &e);
 
 }  // namespace b9h

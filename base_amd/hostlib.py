@@ -38,6 +38,7 @@ HOST_SYMBOLS = [
     "b9h_sim_draw_systems", "b9h_sim_field_mags", "b9h_scatter", "b9h_sim_settings", "b9h_read_res_rows",
     "b9h_star_table", "b9h_write_star_summary",
     "b9h_mass_function_table", "b9h_write_mass_function", "b9h_write_star_mass_hist", "b9h_mass_function_settings",
+    "b9h_resid_table", "b9h_filter_resid_table", "b9h_write_phot_resid", "b9h_write_filter_resid", "b9h_phot_resid_settings",
 ]
 
 _lib = None
@@ -91,6 +92,11 @@ def load() -> C.CDLL:
     lib.b9h_write_mass_function.argtypes = [C.c_char_p, _dp, C.c_int]
     lib.b9h_write_star_mass_hist.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int, C.c_long]
     lib.b9h_mass_function_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_double, C.c_char_p, C.c_int, _dp]
+    lib.b9h_resid_table.argtypes = [_dp, _dp, _dp, C.c_long, C.c_int, _dp]
+    lib.b9h_filter_resid_table.argtypes = [_dp, C.c_long, C.c_int, _dp]
+    lib.b9h_write_phot_resid.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, C.POINTER(C.c_char_p), C.c_int, _dp]
+    lib.b9h_write_filter_resid.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, _dp]
+    lib.b9h_phot_resid_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     lib.b9h_sim_draw_systems.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_int, C.c_double, _dp, _dp, _dp, _ip, _ip]
     lib.b9h_sim_field_mags.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int, _dp, _dp, _dp]
@@ -402,6 +408,64 @@ def read_table_file(path: str, first: str):
             labels.append(t[0])
             rows.append([float(x) for x in t[skip:]])
     return labels, header[skip:], np.array(rows, dtype=np.float64).reshape(len(rows), len(header) - skip)
+
+
+RESID_STAR_COLUMNS = ("predMag", "predSd", "resid", "rmsZ")
+FILTER_RESID_COLUMNS = ("nRows",) + tuple(q + "_" + s for q in ("meanZ", "chi2", "offset") for s in ("mean", "sd", "p16", "p50", "p84"))
+
+
+def resid_table(star_resid, obs, sigma) -> np.ndarray:
+    """b9h_resid_table: b9_phot_resid's star_resid [n_stars, 2 + 2 nf] with the catalogue's obs / sigma [n_stars, nf] -> the
+    per-star table [n_stars, 2 + 4 nf]: rows, member, then RESID_STAR_COLUMNS per filter."""
+    obs = np.ascontiguousarray(obs, dtype=np.float64)
+    n, nf = obs.shape
+    sigma = np.ascontiguousarray(sigma, dtype=np.float64).reshape(n, nf)
+    sr = np.ascontiguousarray(star_resid, dtype=np.float64).reshape(n, 2 + 2 * nf)
+    out = np.empty((n, 2 + 4 * nf))
+    _check(load().b9h_resid_table(sr.ctypes.data_as(_dp), obs.ctypes.data_as(_dp), sigma.ctypes.data_as(_dp), n, nf, out.ctypes.data_as(_dp)))
+    return out
+
+
+def filter_resid_table(row_resid, n_filt: int) -> np.ndarray:
+    """b9h_filter_resid_table: b9_phot_resid's row_resid [n_rows, 1 + 5 nf] -> the per-filter table [nf, 16] (FILTER_RESID_COLUMNS)."""
+    rr = np.ascontiguousarray(row_resid, dtype=np.float64).reshape(-1, 1 + 5 * n_filt)
+    out = np.empty((n_filt, 16))
+    _check(load().b9h_filter_resid_table(rr.ctypes.data_as(_dp), rr.shape[0], int(n_filt), out.ctypes.data_as(_dp)))
+    return out
+
+
+def _names(v):
+    return (C.c_char_p * len(v))(*[str(i).encode() for i in v])
+
+
+def write_phot_resid(path: str, ids, filters, table) -> None:
+    """b9h_write_phot_resid: the .photResid file of a per-star table [len(ids), 2 + 4 len(filters)]."""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(len(ids), 2 + 4 * len(filters))
+    _check(load().b9h_write_phot_resid(path.encode(), _names(ids), len(ids), _names(filters), len(filters), t.ctypes.data_as(_dp)))
+
+
+def write_filter_resid(path: str, filters, table) -> None:
+    """b9h_write_filter_resid: the .filterResid file of a per-filter table [len(filters), 16]."""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(len(filters), 16)
+    _check(load().b9h_write_filter_resid(path.encode(), _names(filters), len(filters), t.ctypes.data_as(_dp)))
+
+
+def read_phot_resid(path: str):
+    """(ids, columns, table [n_stars, 2 + 4 nf]) of a .photResid file."""
+    return read_table_file(path, "id")
+
+
+def read_filter_resid(path: str):
+    """(filters, columns, table [nf, 16]) of a .filterResid file."""
+    return read_table_file(path, "filter")
+
+
+def phot_resid_settings(args):
+    """photResiduals' settings as the program parses `args` (flags, --config file): a dict of its four keys."""
+    argv = (C.c_char_p * (len(args) + 1))(b"photResiduals", *[str(a).encode() for a in args])
+    buf = C.create_string_buffer(1024)
+    _check(load().b9h_phot_resid_settings(len(args) + 1, argv, buf, 1024))
+    return {k: int(v) for k, v in (line.split(" = ") for line in buf.value.decode().splitlines())}
 
 
 # ------------------------------------------------------------------------------------------

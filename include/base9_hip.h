@@ -293,8 +293,8 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk);
  * may be outstanding; they are collected in the order they were enqueued.  A successful b9_load_pack, b9_load_stars,
  * b9_set_priors or b9_set_options changes the posterior: the previous block's state carries a log-posterior of the old
  * one, so the next B9_BLOCK_CONTINUE block returns B9_ERR_STATE (the message names the call that intervened) and the chain
- * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags, b9_sample_wd_mass, b9_star_moments and
- * b9_mass_hist (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
+ * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags, b9_sample_wd_mass, b9_star_moments,
+ * b9_mass_hist and b9_phot_resid (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
  * context's work buffers: b9_logpost / b9_sample_mass / b9_derive_isochrone, the staging calls, b9_set_options and a block
  * with another n_walkers return B9_ERR_STATE until it has been collected.  A driver that adapts the proposal
  * from block b-1 while block b runs keeps the GPU's queue non-empty: enqueue b+1 (CONTINUE | ASYNC), wait(b), ...
@@ -473,6 +473,47 @@ int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quan
                  const double *edges /* [n_bins + 1] */, int32_t n_bins, int32_t flags,
                  double *star_hist /* host [n_stars][n_bins + 1], in/out, may be NULL */,
                  double *row_hist  /* host [n_rows][n_bins + 1], out,    may be NULL */);
+
+/*
+ * Exact per-filter posterior-predictive residuals over a saved chain (the photResiduals counterpart).  Added in ABI 6 without a
+ * version change, as b9_star_moments and b9_mass_hist were: purely additive.  Where those calls say what the fit implies for a
+ * star's masses, this one says what it implies for the star's MAGNITUDES, filter by filter, and how far the observed ones lie
+ * from that: per star summed over the rows (star_resid) and, standardised, per row summed over the stars (row_resid).
+ *
+ * Definition.  Grid, terms t_(k,n), L = logsumexp t, w = exp(t - L) and the membership p are exactly b9_star_moments':
+ * terms that are not finite do not take part; n_pops is honoured, mode ignored; WD-stage stars use 8 * marg_iso_increm steps
+ * above the AGB tip at mass ratio 0, through the WD branch with the star's own wd_type; terms more than 40 e-folds below a
+ * data-only lower bound of the star's largest term may be dropped (b9_tuning.marg_no_pruning: none are).  pred_f(k,n) is the
+ * node's combined apparent magnitude in filter f, the value the likelihood compares with obs_f.  The pivot c_if is obs_if, the
+ * caller's bits, where sigma_if > 0, and 0 for an unused filter; d_f = pred_f - c_if, one rounded subtraction.  Row r adds to
+ * star i the 2 + 2 n_filt columns
+ *     x[0] = 1 (ROWS),  x[1] = p (MEMBER),  x[2 + 2f] = p sum w d_f,  x[3 + 2f] = p sum w d_f^2
+ * and nothing at all (every entry 0, ROWS included) where b9_star_moments would add nothing: a row outside the grid, a star
+ * with no live node.  An unused filter still gets its two sums about the pivot 0: the magnitude the posterior predicts in a
+ * band the star was not observed in.  A star with every filter unused is weighted by the prior over the grid.
+ *
+ * star_resid (host, [n_stars][2 + 2 n_filt], the caller's star order, in/out, nullable): acc + x_r, one plain add per row in
+ * ascending row order; flags = 0 starts from zeros, B9_RESID_CONTINUE from the caller's values.  The same bits for the call's
+ * own chunking (at most 32 rows at a time, fewer while the per-(row, star) scratch would exceed 64 MiB) and for any split of the
+ * rows over continued calls.  predMag_f = c_f + acc[2 + 2f] / acc[1]; its variance acc[3 + 2f] / acc[1] - (acc[2 + 2f] / acc[1])^2.
+ *
+ * row_resid (host, [n_rows][1 + 5 n_filt], out, nullable): column 0 is sum_i p_i over all stars.  For filter f, over the stars
+ * with sigma_if > 0 only, with s = 1 / sigma_if (one rounded division) and z = (obs - pred) / sigma (observed minus computed):
+ *     [1 + 5f] N_f = sum p              [2 + 5f] R_f = sum p E_w[z]   = sum -(x[2 + 2f] s)
+ *     [3 + 5f] C_f = sum p E_w[z^2] = sum (x[3 + 2f] s) s             [4 + 5f] W_f = sum (p s) s
+ *     [5 + 5f] D_f = sum -((x[2 + 2f] s) s)
+ * over the caller's star order, ascending, one plain add per star; a row's line depends on that row alone.  R_f / N_f is the
+ * members' mean standardised residual in the band, C_f / N_f its reduced chi^2, D_f / W_f the inverse-variance-weighted
+ * zero-point offset in magnitudes.
+ *
+ * Synchronous; host pointers.  B9_ERR_INVALID (outputs untouched) for n_rows < 1, NULL params or both outputs NULL;
+ * B9_ERR_STATE while a sampler block is outstanding; B9_ERR_CAPACITY as its siblings.  The call uses buffers of its own: a
+ * B9_BLOCK_CONTINUE block enqueued after it gives the same bits as one enqueued without it.
+ */
+#define B9_RESID_CONTINUE 1
+int b9_phot_resid(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags,
+                  double *star_resid /* host [n_stars][2 + 2 n_filt], in/out, may be NULL */,
+                  double *row_resid  /* host [n_rows][1 + 5 n_filt], out,    may be NULL */);
 
 /* ---- introspection (used by bench/tests; no compute) --------------------------------- */
 int b9_max_eep(const b9_ctx *ctx);           /* longest isochrone in the loaded pack        */

@@ -122,6 +122,22 @@ int b9h_mass_function_table(const double *row_hist, long n_rows, const double *e
 int b9h_write_mass_function(const char *path, const double *table, int n_bins);
 int b9h_write_star_mass_hist(const char *path, const char *const *ids, long n_stars, const double *star_hist, int n_bins, long n_rows);
 int b9h_mass_function_settings(int argc, char **argv, double m_wd_up, char *out, int cap, double *edges);
+/* photResiduals.  b9h_resid_table: b9_phot_resid's star_resid [n_stars][2 + 2 n_filt] with the catalogue's obs and sigma
+ * [n_stars][n_filt] (sigma <= 0: filter unused) -> the per-star table [n_stars][2 + 4 n_filt]: rows, member = acc[1] / rows,
+ * then per filter predMag = c + acc[2 + 2f] / acc[1] (c = obs for a used filter, else 0), predSd = sqrt(max(0, acc[3 + 2f] / acc[1]
+ * - (acc[2 + 2f] / acc[1])^2)) and, for used filters (0 otherwise), resid = obs - predMag and rmsZ = sqrt(acc[3 + 2f] / acc[1]) / sigma;
+ * every derived value is 0 when acc[1] == 0.
+ * b9h_filter_resid_table: row_resid [n_rows][1 + 5 n_filt] -> the per-filter table [n_filt][16]: the number of rows with
+ * N_f > 0, then over them the mean, population standard deviation and 16th / 50th / 84th percentiles (b9h_mass_function_table's
+ * rule) of meanZ = R_f / N_f, chi2 = C_f / N_f and offset = D_f / W_f; zeros without such a row.
+ * b9h_write_phot_resid / b9h_write_filter_resid: the files <base>.photResid and <base>.filterResid (docs/FORMATS.md) of those
+ * tables, 17 significant digits.  b9h_phot_resid_settings: photResiduals' command line (argv[0] is skipped) and YAML parsed
+ * as the program parses them -- "key = value" lines of margIsoIncrem, nMassRatios, nPops, perStar into out. */
+int b9h_resid_table(const double *star_resid, const double *obs, const double *sigma, long n_stars, int n_filt, double *table);
+int b9h_filter_resid_table(const double *row_resid, long n_rows, int n_filt, double *table);
+int b9h_write_phot_resid(const char *path, const char *const *ids, long n_stars, const char *const *filters, int n_filt, const double *table);
+int b9h_write_filter_resid(const char *path, const char *const *filters, int n_filt, const double *table);
+int b9h_phot_resid_settings(int argc, char **argv, char *out, int cap);
 /* rank 0's merge of <final_path>.part<r> into <final_path> after a --gpus N run (b9h::merge_result_parts; exposed for tests) */
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part);
 
