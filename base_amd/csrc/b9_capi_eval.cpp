@@ -2,7 +2,7 @@
 // b9_logpost_device), the per-star mass draws (b9_sample_mass), the isochrone dump (b9_derive_isochrone) and the forward
 // model alone (b9_predict_mags) the WD-stage stars' posterior draws (b9_sample_wd_mass), the
 // per-star posterior moments (b9_star_moments), the binned mass posteriors (b9_mass_hist) and the
-// posterior-predictive residuals (b9_phot_resid).
+// posterior-predictive residuals (b9_phot_resid) and the pointwise predictive densities (b9_pointwise).
 #include "b9_ctx.h"
 #include <algorithm>
 #include <cmath>
@@ -512,6 +512,73 @@ int b9_phot_resid(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t fla
         if (d_rows) HIPCHK(ctx, hipMemcpyAsync(row_resid + (size_t)r0 * nrow, d_rows, sizeof(double) * m * nrow, hipMemcpyDeviceToHost, s));
     }
     if (d_acc) HIPCHK(ctx, hipMemcpyAsync(star_resid, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return B9_OK;
+}
+
+// Chunks of at most B9_PW_MAX_ROWS rows (b9_launch.h: the reducers hold a chunk's rows in registers), fewer while the chunk's
+// values [rows][stars] would exceed B9_PW_SCRATCH_BYTES: 32 rows up to 65536 stars.
+#define B9_PW_SCRATCH_BYTES ((size_t)16 << 20)
+
+int b9_pointwise(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags, int32_t tail_len, double *acc, double *tail, double *row_lpd)
+{
+    if (!ctx || !params || n_rows < 1 || (!acc && !row_lpd)) return B9_ERR_INVALID;
+    if (tail_len < 0 || tail_len > B9_PW_MAX_TAIL) return fail(ctx, B9_ERR_INVALID, "b9_pointwise: tail_len must lie in 0 .. B9_PW_MAX_TAIL");
+    if (tail && !acc) return fail(ctx, B9_ERR_INVALID, "b9_pointwise: tail requires acc");
+    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
+    if (!ctx->have_pack || !ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
+    const int n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
+    const int K = marg_grid(ctx).K, Q = marg_grid(ctx).Q;
+    if (n == 0) {
+        if (row_lpd) std::fill(row_lpd, row_lpd + n_rows, 0.0);
+        return B9_OK;
+    }
+    const size_t T = (tail && tail_len > 0) ? (size_t)tail_len : 0;
+    const DevPack &pk = ctx->pk;
+    const int mass_cap = pack_mass_cap(pk.max_eep);
+    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
+    const size_t tab_row = (size_t)n_pops * (size_t)b9k_marg_table_doubles(pk.nfp, mass_cap, K, Q);
+    const size_t wd_row = ctx->st.n_wd > 0 ? (size_t)n_pops * (size_t)b9k_marg_wd_table_doubles(pk.nfp, K) : 0;
+    const size_t chunk = mom_chunk_rows((size_t)n_rows, (size_t)n, 1, B9_PW_MAX_ROWS, B9_PW_SCRATCH_BYTES);
+    if (chunk * (tab_row + wd_row) > ((size_t)8 << 30) / sizeof(double))
+        return fail(ctx, B9_ERR_CAPACITY, "b9_pointwise: marginalisation grid too fine: the node tables would exceed 8 GiB");
+    // one allocation: [params][headers][isochrones][table][WD table][v][row flags][state][the chunk's row sums][tail][tail, the caller's layout]
+    const PwArena a = pw_arena(chunk, n_pops, iso_stride, tab_row, wd_row, (size_t)n, B9_PW_N, T, sizeof(IsoHdr));
+    RESERVE(ctx, ctx->d_pw, a.bytes);
+    char *base = ctx->d_pw.get();
+    double *d_par = part<double>(base, a.o_par), *d_iso = part<double>(base, a.o_iso), *d_tab = part<double>(base, a.o_tab);
+    double *d_wd = wd_row ? part<double>(base, a.o_wd) : nullptr, *d_scratch = part<double>(base, a.o_scratch);
+    double *d_acc = acc ? part<double>(base, a.o_acc) : nullptr, *d_rows = row_lpd ? part<double>(base, a.o_rows) : nullptr;
+    double *d_tail = T ? part<double>(base, a.o_tail) : nullptr, *d_tail_io = T ? part<double>(base, a.o_tail_io) : nullptr;
+    int *d_flag = part<int>(base, a.o_flag);
+    IsoHdr *d_hdr = part<IsoHdr>(base, a.o_hdr);
+    const size_t acc_bytes = sizeof(double) * (size_t)n * B9_PW_N, tail_bytes = sizeof(double) * (size_t)n * T;
+    hipStream_t s = ctx->stream;
+    if (d_acc) {
+        if (flags & B9_PW_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_acc, acc, acc_bytes, hipMemcpyHostToDevice, s));
+        else HIPCHK(ctx, hipMemsetAsync(d_acc, 0, acc_bytes, s));
+    }
+    if (d_tail) {
+        if (flags & B9_PW_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_tail_io, tail, tail_bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, b9k_pw_tail_load((flags & B9_PW_CONTINUE) ? d_tail_io : nullptr, n, (int)T, d_tail, s));
+    }
+    const McmcDev off{};
+    for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
+        const int m = std::min((int)chunk, n_rows - r0);
+        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
+        // every (row, star) of a row inside the grid writes its value, every row its flag: no clearing
+        HIPCHK(ctx, b9k_pointwise(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, K, Q, ctx->marg_prune, d_tab, d_wd,
+                                  d_scratch, d_flag, d_acc, d_tail, (int)T, d_rows, s));
+        if (d_rows) HIPCHK(ctx, hipMemcpyAsync(row_lpd + r0, d_rows, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+    }
+    if (d_acc) HIPCHK(ctx, hipMemcpyAsync(acc, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
+    if (d_tail) {
+        HIPCHK(ctx, b9k_pw_tail_store(d_tail, n, (int)T, d_tail_io, s));
+        HIPCHK(ctx, hipMemcpyAsync(tail, d_tail_io, tail_bytes, hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(ctx, hipStreamSynchronize(s));
     return B9_OK;
 }

@@ -156,6 +156,21 @@ inline ResidArena resid_arena(size_t chunk, int n_pops, long long iso_stride, si
     return a;
 }
 
+// b9_pointwise's chunk of rows: b9_star_moments' leading parts, then v [chunk][n_stars], the rows' inside-the-grid words
+// [chunk], the per-star state [n_stars][n_acc], the chunk's row sums [chunk] and the tail twice: the device's
+// [tail_len][n_stars] and the caller's [n_stars][tail_len] it is transposed from and to
+struct PwArena { size_t o_par, o_hdr, o_iso, o_tab, o_wd, o_scratch, o_flag, o_acc, o_rows, o_tail, o_tail_io, bytes; };
+inline PwArena pw_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t wd_row, size_t n_stars, size_t n_acc, size_t tail_len,
+                        size_t hdr_bytes)
+{
+    Carve c;
+    PwArena a{c.take(8 * B9_NPARAM * chunk), c.take(hdr_bytes * chunk * n_pops), c.take(8 * chunk * n_pops * (size_t)iso_stride), c.take(8 * chunk * tab_row),
+              c.take(8 * chunk * wd_row), c.take(8 * chunk * n_stars), c.take(4 * chunk), c.take(8 * n_stars * n_acc), c.take(8 * chunk),
+              c.take(8 * n_stars * tail_len), c.take(8 * n_stars * tail_len), 0};
+    a.bytes = c.total;
+    return a;
+}
+
 // ---- sizing rules
 
 // rows of a derived isochrone: the pack's longest one, rounded up to even; and its doubles: a mass column + nfp magnitude columns

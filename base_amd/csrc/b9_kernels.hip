@@ -33,6 +33,8 @@
 //                                     per-wave LDS histogram per lane, bins worked in tiles), summed over the rows and the stars
 //   k_star_resid / _wd / k_resid_stage / k_resid_accumulate / k_resid_rows   b9_phot_resid: exact posterior-predictive magnitude
 //                                     moments per filter over the same grid, summed over the rows and, standardised, the stars
+//   k_star_lpd / _wd / k_pw_accumulate / k_pw_tail / k_pw_rows   b9_pointwise: every star's marginal log-likelihood per row over
+//                                     the same grid, reduced over the rows (online log-sum-exps, Welford, largest -v) and the stars
 //
 // The kernels live in the *.hip.h files included below (one translation unit); this file holds
 // k_finalize and the host-callable launch wrappers.
@@ -76,6 +78,7 @@ namespace tree_kd5 {
 #include "b9_star_moments.hip.h"
 #include "b9_mass_hist.hip.h"
 #include "b9_phot_resid.hip.h"
+#include "b9_pointwise.hip.h"
 
 // ------------------------------------------------------------------------------------------
 // k_finalize: one workgroup per walker: fixed-order sum of the partials + prior -> logpost[w]
@@ -388,6 +391,58 @@ hipError_t b9k_phot_resid(const DevPack &pk, const DevStars &st, const IsoHdr *h
             if (kr.err != hipSuccess) return kr.err;
             hipLaunchKernelGGL(kr.kern, dim3(n_rows), dim3(256), kr.lds, stream, (const double *)scratch, isig, st.n, nf, rows);
         }
+        return hipGetLastError();
+    });
+}
+
+// ---- b9_pointwise: the node tables of a chunk of rows, every star's v, the per-star state, the tails, the rows' sums ---------------
+hipError_t b9k_pw_tail_load(const double *tail_io, int n_stars, int tail_len, double *tail, hipStream_t stream)
+{
+    if (!tail || n_stars < 1 || tail_len < 1) return hipErrorInvalidValue;
+    const long long n = (long long)n_stars * tail_len;
+    if (tail_io) hipLaunchKernelGGL(k_pw_transpose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tail_io, n_stars, tail_len, tail);
+    else hipLaunchKernelGGL(k_pw_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tail, n, (double)NEG_INF);
+    return hipGetLastError();
+}
+
+hipError_t b9k_pw_tail_store(const double *tail, int n_stars, int tail_len, double *tail_io, hipStream_t stream)
+{
+    if (!tail || !tail_io || n_stars < 1 || tail_len < 1) return hipErrorInvalidValue;
+    const long long n = (long long)n_stars * tail_len;
+    hipLaunchKernelGGL(k_pw_transpose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tail, tail_len, n_stars, tail_io);
+    return hipGetLastError();
+}
+
+hipError_t b9k_pointwise(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                         const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, double *tab, double *wd_tab,
+                         double *scratch, int *row_in, double *acc, double *tail, int tail_len, double *rows, hipStream_t stream)
+{
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        if (!tab || !scratch || !row_in || n_rows < 1 || n_rows > B9_PW_MAX_ROWS || (st.n_wd > 0 && !wd_tab) || (tail && (!acc || tail_len < 1 || tail_len > B9_PW_MAX_TAIL)))
+            return hipErrorInvalidValue;
+        const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
+        const hipError_t e = launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, tab, stream);
+        if (e != hipSuccess) return e;
+        const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
+        hipLaunchKernelGGL((k_star_lpd<NFP, NPOPS>), dim3(st.mg_pad / 64, n_rows), dim3(256), 0, stream, st, hdr, iso_data, iso_stride, mass_cap,
+                           d_params, K, Q, (const double *)tab, L, cut2, scratch, row_in);
+        if (st.n_wd > 0) {
+            launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, wd_tab, stream);
+            hipLaunchKernelGGL((k_star_lpd_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, hdr, d_params, K,
+                               (const double *)wd_tab, scratch);
+        }
+        const unsigned star_wgs = (unsigned)((st.n + 255) / 256);
+        if (acc)
+            hipLaunchKernelGGL(k_pw_accumulate, dim3(star_wgs), dim3(256), 0, stream, (const double *)scratch, (const int *)row_in, n_rows, st.n, acc);
+        if (tail) {
+            const auto kt = with_lds(k_pw_tail, sizeof(double) * 64 * (size_t)tail_len);          // the wave's 64 lists
+            if (kt.err != hipSuccess) return kt.err;
+            hipLaunchKernelGGL(kt.kern, dim3((unsigned)((st.n + 63) / 64)), dim3(64), kt.lds, stream, (const double *)scratch, (const int *)row_in,
+                               n_rows, st.n, tail_len, tail);
+        }
+        if (rows)
+            hipLaunchKernelGGL(k_pw_rows, dim3((unsigned)n_rows), dim3(64), 0, stream, (const double *)scratch, (const int *)row_in, st.n, rows);
         return hipGetLastError();
     });
 }

@@ -144,6 +144,20 @@ hipError_t b9k_phot_resid(const DevPack &pk, const DevStars &st, const IsoHdr *h
                           const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, const double *piv_mg, const double *isig,
                           double *tab, double *wd_tab, double *scratch, double *acc, double *rows, hipStream_t stream);
 
+// rows of one b9k_pointwise launch: the reducers hold a chunk's rows in registers (k_pw_accumulate, k_pw_tail), and b9_pointwise
+// chunks its rows by the same number
+#define B9_PW_MAX_ROWS 32
+// b9_pointwise: the node tables as b9k_star_moments builds them, every star's v = finish_star().v into scratch [n_rows][st.n]
+// (n_rows <= B9_PW_MAX_ROWS) and row_in [n_rows] (1: the row lies inside the grid; 0: it wrote no value), then -- each optional --
+// acc [st.n][B9_PW_N] through the recurrence, rows ascending; tail [tail_len][st.n] (the DEVICE layout) the largest -v;
+// rows [n_rows] the stars' sum in ascending order.  b9k_pw_tail_load: tail from the caller's layout tail_io [st.n][tail_len],
+// or -inf everywhere when tail_io is null; b9k_pw_tail_store: back to it.  Device pointers, all the caller's own.
+hipError_t b9k_pw_tail_load(const double *tail_io, int n_stars, int tail_len, double *tail, hipStream_t stream);
+hipError_t b9k_pw_tail_store(const double *tail, int n_stars, int tail_len, double *tail_io, hipStream_t stream);
+hipError_t b9k_pointwise(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                         const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, double *tab, double *wd_tab,
+                         double *scratch, int *row_in, double *acc, double *tail, int tail_len, double *rows, hipStream_t stream);
+
 hipError_t b9k_noop(hipStream_t stream);
 hipError_t b9k_spin(double microseconds, hipStream_t stream);
 constexpr int B9_CLOCK_SLOTS = 8 * 256;      // (XCD, HW_ID[15:8]) -> one slot per compute unit

@@ -255,6 +255,30 @@ class Engine:
         self._check(self.lib.b9_phot_resid(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], flags, ptr(sr), ptr(rr)))
         return sr, rr
 
+    def pointwise(self, rows: np.ndarray, tail_len: int = 0, acc: Optional[np.ndarray] = None, tail: Optional[np.ndarray] = None,
+                  want_rows: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+        """b9_pointwise: every star's marginal log-likelihood v over `rows`, reduced: (acc [n_stars, 8] -- abi.PW_ROWS .. PW_M2 --,
+        tail [n_stars, tail_len] -- the largest -v, descending, padded with -inf; None for tail_len = 0 --, row_lpd [n_rows] --
+        the rows' sums over the stars; None for want_rows = False).  acc=None starts from zeros (and the tail from -inf); else the
+        call continues acc and tail (B9_PW_CONTINUE) and returns new arrays."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        flags = 0
+        if acc is None:
+            a = np.zeros((self.n_stars, abi.PW_N))
+            t = np.full((self.n_stars, tail_len), -np.inf) if tail_len > 0 else None
+        else:
+            flags = abi.PW_CONTINUE
+            a = np.array(acc, dtype=np.float64, order="C").reshape(self.n_stars, abi.PW_N)
+            t = None
+            if tail_len > 0:
+                if tail is None:
+                    raise ValueError("continuing with tail_len > 0 needs the tail of the calls before")
+                t = np.array(tail, dtype=np.float64, order="C").reshape(self.n_stars, tail_len)
+        rl = np.zeros(rows.shape[0]) if want_rows else None
+        ptr = lambda x: x.ctypes.data_as(_dp) if x is not None else None      # noqa: E731
+        self._check(self.lib.b9_pointwise(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], flags, int(tail_len), ptr(a), ptr(t), ptr(rl)))
+        return a, t, rl
+
     def derive_isochrone(self, param_row: np.ndarray, pop: int = 0, cap: int = 4096) -> Tuple[int, np.ndarray, np.ndarray, float]:
         row = np.ascontiguousarray(param_row, dtype=np.float64)
         mass = np.empty(cap)

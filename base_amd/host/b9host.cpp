@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <sstream>
 #include <stdexcept>
 
@@ -130,6 +131,7 @@ const std::map<std::string, std::string> &Settings::flag_map()
         {"nBins", "massFunction.nBins"}, {"massFunctionMinMass", "massFunction.minMass"}, {"massFunctionMaxMass", "massFunction.maxMass"},
         {"linearBins", "massFunction.linearBins"}, {"quantity", "massFunction.quantity"}, {"perStar", "massFunction.perStar"},
         {"photResidualsPerStar", "photResiduals.perStar"}, {"photResidualsNPops", "photResiduals.nPops"},
+        {"modelScorePerRow", "modelScore.perRow"}, {"modelScoreNPops", "modelScore.nPops"}, {"compareTo", "modelScore.compareTo"},
         {"nStars", "simCluster.nStars"}, {"percentBinary", "simCluster.percentBinary"}, {"percentDB", "simCluster.percentDB"},
         {"nFieldStars", "simCluster.nFieldStars"}, {"minMass", "simCluster.minMass"}, {"maxMass", "simCluster.maxMass"},
         {"minMassRatio", "simCluster.minMassRatio"}, {"memberPrior", "simCluster.memberPrior"}, {"nPops", "simCluster.nPops"},
@@ -727,6 +729,209 @@ void write_filter_resid(const std::string &path, const std::vector<std::string> 
         std::fprintf(f, "\n");
     }
     if (std::fclose(f) != 0) fail("cannot write " + path);
+}
+
+// ---------------------------------------------------------------------------------------------
+// modelScore
+// ---------------------------------------------------------------------------------------------
+namespace {
+const double kInf = std::numeric_limits<double>::infinity(), kNaN = std::numeric_limits<double>::quiet_NaN();
+
+// PSIS of one star: r[0 .. n_t) the finite tail values, descending (r[0] = RMAX); -> paretoK, elpdLoo (elpd_is where no fit is made)
+void psis_star(const double *r, long n_t, double n_f, double rmax, double sneg, double elpd_is, double &pareto_k, double &elpd_loo)
+{
+    pareto_k = kNaN;
+    elpd_loo = elpd_is;
+    const long M = std::min({(long)std::floor(n_f / 5.0), (long)std::ceil(3.0 * std::sqrt(n_f)), n_t - 1});
+    if (M < 5) return;
+    const long N = M;
+    std::vector<double> rho((size_t)M + 1), x((size_t)M);
+    for (long j = 0; j <= M; ++j) rho[(size_t)j] = r[j] - r[0];
+    const double ec = std::exp(rho[(size_t)M]);
+    for (long j = 0; j < M; ++j) x[(size_t)(M - 1 - j)] = std::exp(rho[(size_t)j]) - ec;          // ascending: rho descends
+    const double x_n = x[(size_t)N - 1], x_star = x[(size_t)std::floor((double)N / 4.0 + 0.5) - 1];
+    if (x_n == 0.0 || !(x_star > 0.0)) return;
+    // Zhang & Stephens' profile fit of the generalised Pareto distribution, with the weakly informative prior on k
+    const long m = 30 + (long)std::floor(std::sqrt((double)N));
+    std::vector<double> theta((size_t)m), ell((size_t)m);
+    auto mean_log1p = [&](double th) { double sum = 0.0; for (long i = 0; i < N; ++i) sum += std::log1p(-th * x[(size_t)i]); return sum / (double)N; };
+    for (long j = 1; j <= m; ++j) {
+        const double th = 1.0 / x_n + (1.0 - std::sqrt((double)m / ((double)j - 0.5))) / (3.0 * x_star);
+        const double k = mean_log1p(th);
+        theta[(size_t)j - 1] = th;
+        ell[(size_t)j - 1] = (double)N * (std::log(-th / k) - k - 1.0);
+    }
+    double theta_hat = 0.0;
+    for (long j = 0; j < m; ++j) {
+        double den = 0.0;
+        for (long l = 0; l < m; ++l) den += std::exp(ell[(size_t)l] - ell[(size_t)j]);
+        theta_hat += theta[(size_t)j] * (1.0 / den);
+    }
+    double k_hat = mean_log1p(theta_hat);
+    const double sigma = -k_hat / theta_hat;
+    k_hat = ((double)N * k_hat + 5.0) / ((double)N + 10.0);
+    // the smoothed weights, paired by rank: the j-th smallest tail value takes the quantile at p_j = (j - 1/2) / M
+    double num = n_f - (double)M, tail_raw = 0.0, tail_smooth = 0.0;
+    for (long j = 1; j <= M; ++j) {
+        const double p = ((double)j - 0.5) / (double)M, lp = std::log1p(-p);
+        const double q = k_hat == 0.0 ? -sigma * lp : sigma * std::expm1(-k_hat * lp) / k_hat;
+        const double w = std::min(1.0, ec + q), rh = rho[(size_t)(M - j)];
+        num += std::exp(std::log(w) - rh);
+        tail_smooth += w;
+        tail_raw += std::exp(rh);
+    }
+    const double den = std::max(0.0, sneg - tail_raw) + tail_smooth;
+    pareto_k = k_hat;
+    elpd_loo = std::log(num) - std::log(den) - rmax;
+}
+
+// sum and sqrt(N var_ddof1) of v
+void sum_se(const std::vector<double> &v, double &sum, double &se)
+{
+    sum = 0.0; se = 0.0;
+    for (double x : v) sum += x;
+    const size_t n = v.size();
+    if (n < 2) return;
+    const double mean = sum / (double)n;
+    double ss = 0.0;
+    for (double x : v) ss += (x - mean) * (x - mean);
+    se = std::sqrt((double)n * (ss / (double)(n - 1)));
+}
+}  // namespace
+
+void pointwise_table(const double *acc, const double *tail, int tail_len, long n_stars, double *table)
+{
+    for (long i = 0; i < n_stars; ++i) {
+        const double *a = acc + (size_t)i * 8;
+        double *t = table + (size_t)i * kPointwiseCols;
+        for (int c = 0; c < kPointwiseCols; ++c) t[c] = 0.0;
+        const double rows = a[0], n_inf = a[1], n_f = rows - n_inf;
+        t[0] = rows; t[1] = n_inf;
+        if (n_inf > 0.0) {                               // a row gives the star no likelihood at all: no finite score
+            t[2] = n_f > 0.0 ? a[2] + std::log(a[3]) - std::log(rows) : -kInf;
+            t[3] = n_f >= 2.0 ? a[7] / (n_f - 1.0) : 0.0;
+            t[4] = t[5] = t[7] = -kInf; t[6] = kInf; t[8] = kInf;
+            continue;
+        }
+        if (!(n_f > 0.0)) continue;
+        const double lppd = a[2] + std::log(a[3]) - std::log(rows);
+        const double p_waic = n_f >= 2.0 ? a[7] / (n_f - 1.0) : 0.0;
+        const double elpd_is = std::log(n_f) - (a[4] + std::log(a[5]));
+        long n_t = 0;
+        const double *r = tail ? tail + (size_t)i * (size_t)tail_len : nullptr;
+        while (r && n_t < tail_len && std::isfinite(r[n_t])) ++n_t;
+        double k, loo;
+        psis_star(r, n_t, n_f, a[4], a[5], elpd_is, k, loo);
+        t[2] = lppd; t[3] = p_waic; t[4] = lppd - p_waic; t[5] = elpd_is; t[6] = k; t[7] = loo; t[8] = lppd - loo;
+    }
+}
+
+void score_totals(const double *table, long n_stars, double *totals)
+{
+    std::vector<double> lppd, waic, loo;
+    double p_waic = 0.0, p_loo = 0.0, n_infs = 0.0, n_high = 0.0, k_max = kNaN;
+    for (long i = 0; i < n_stars; ++i) {
+        const double *t = table + (size_t)i * kPointwiseCols;
+        if (!(t[0] > 0.0)) continue;
+        lppd.push_back(t[2]); waic.push_back(t[4]); loo.push_back(t[7]);
+        p_waic += t[3]; p_loo += t[8];
+        if (t[1] > 0.0) n_infs += 1.0;
+        if (t[6] > 0.7) n_high += 1.0;
+        if (std::isfinite(t[6]) && !(k_max >= t[6])) k_max = t[6];
+    }
+    totals[0] = (double)lppd.size();
+    sum_se(lppd, totals[1], totals[2]);
+    sum_se(waic, totals[3], totals[4]);
+    sum_se(loo, totals[5], totals[6]);
+    totals[7] = p_waic; totals[8] = p_loo; totals[9] = n_infs; totals[10] = n_high; totals[11] = k_max;
+}
+
+void score_compare(const double *table_a, const std::vector<std::string> &ids_a, const double *table_b, const std::vector<std::string> &ids_b,
+                   double *out)
+{
+    if (ids_a.size() != ids_b.size()) fail("modelScore: the two catalogues differ in their number of stars");
+    for (size_t i = 0; i < ids_a.size(); ++i)
+        if (ids_a[i] != ids_b[i]) fail("modelScore: the two catalogues differ at star " + std::to_string(i) + " ('" + ids_a[i] + "' against '" + ids_b[i] + "')");
+    std::vector<double> d_loo, d_waic;
+    double dropped = 0.0;
+    for (size_t i = 0; i < ids_a.size(); ++i) {
+        const double *a = table_a + i * kPointwiseCols, *b = table_b + i * kPointwiseCols;
+        if ((a[0] > 0.0) != (b[0] > 0.0)) dropped += 1.0;                  // scored by one fit only
+        if (!(a[0] > 0.0) || !(b[0] > 0.0)) continue;
+        d_loo.push_back(a[7] - b[7]);
+        d_waic.push_back(a[4] - b[4]);
+    }
+    out[0] = (double)d_loo.size();
+    sum_se(d_loo, out[1], out[2]);
+    sum_se(d_waic, out[3], out[4]);
+    out[5] = dropped;
+}
+
+static const char *const kPointwiseNames[kPointwiseCols] = {"rows", "nInf", "lppd", "pWaic", "elpdWaic", "elpdIs", "paretoK", "elpdLoo", "pLoo"};
+static const char *const kScoreNames[kScoreTotals] = {"nStars", "lppd", "lppdSe", "elpdWaic", "elpdWaicSe", "elpdLoo", "elpdLooSe", "pWaic", "pLoo",
+                                                      "nInfStars", "nHighK", "maxK"};
+static const char *const kCompareNames[kScoreCompare] = {"nStars", "dElpdLoo", "dElpdLooSe", "dElpdWaic", "dElpdWaicSe", "nDropped"};
+
+void write_pointwise(const std::string &path, const std::vector<std::string> &ids, const double *table)
+{
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) fail("cannot write " + path);
+    std::fprintf(f, "id");
+    for (const char *n : kPointwiseNames) std::fprintf(f, " %s", n);
+    std::fprintf(f, "\n");
+    for (size_t i = 0; i < ids.size(); ++i) {
+        std::fprintf(f, "%s", ids[i].c_str());
+        for (int c = 0; c < kPointwiseCols; ++c) std::fprintf(f, " %.17g", table[i * kPointwiseCols + c]);
+        std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) fail("cannot write " + path);
+}
+
+static void write_named(const std::string &path, const char *const *names, int n, const double *v)
+{
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) fail("cannot write " + path);
+    for (int c = 0; c < n; ++c) std::fprintf(f, "%s%s", c ? " " : "", names[c]);
+    std::fprintf(f, "\n");
+    for (int c = 0; c < n; ++c) std::fprintf(f, "%s%.17g", c ? " " : "", v[c]);
+    std::fprintf(f, "\n");
+    if (std::fclose(f) != 0) fail("cannot write " + path);
+}
+void write_model_score(const std::string &path, const double *totals) { write_named(path, kScoreNames, kScoreTotals, totals); }
+void write_model_compare(const std::string &path, const double *cmp) { write_named(path, kCompareNames, kScoreCompare, cmp); }
+
+void write_row_lpd(const std::string &path, const double *row_lpd, long n_rows)
+{
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) fail("cannot write " + path);
+    std::fprintf(f, "row lpd\n");
+    for (long r = 0; r < n_rows; ++r) std::fprintf(f, "%ld %.17g\n", r, row_lpd[r]);
+    if (std::fclose(f) != 0) fail("cannot write " + path);
+}
+
+void read_pointwise(const std::string &path, std::vector<std::string> &ids, std::vector<double> &table)
+{
+    std::ifstream in(path);
+    if (!in) fail("cannot read " + path);
+    std::string line, word;
+    if (!std::getline(in, line)) fail(path + ": empty file");
+    {
+        std::istringstream hs(line);
+        hs >> word;
+        if (word != "id") fail(path + ": not a .pointwise file (the header starts with '" + word + "')");
+        for (const char *n : kPointwiseNames)
+            if (!(hs >> word) || word != n) fail(path + ": column '" + std::string(n) + "' missing from the header");
+    }
+    ids.clear(); table.clear();
+    while (std::getline(in, line)) {
+        std::istringstream ls(line);
+        if (!(ls >> word)) continue;
+        ids.push_back(word);
+        for (int c = 0; c < kPointwiseCols; ++c) {
+            if (!(ls >> word)) fail(path + ": short line for star '" + ids.back() + "'");
+            table.push_back(std::strtod(word.c_str(), nullptr));         // (strtod reads inf / -inf / nan as printf wrote them)
+        }
+    }
 }
 
 const char *param_name(int idx)

@@ -144,6 +144,33 @@ void filter_resid_table(const double *row_resid, long n_rows, int nf, double *ta
 void write_phot_resid(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &filters, const double *table);
 void write_filter_resid(const std::string &path, const std::vector<std::string> &filters, const double *table);
 
+// ---- modelScore ------------------------------------------------------------------------------------
+// b9_pointwise's acc [n_stars][8] and tail [n_stars][tail_len] (may be null: no PSIS fit is made) -> the per-star table
+// [n_stars][kPointwiseCols]: rows, nInf, lppd, pWaic, elpdWaic, elpdIs, paretoK, elpdLoo, pLoo (DESIGN.md section 2 states the
+// arithmetic).  With n_f = rows - nInf: lppd = VMAX + log SPOS - log rows; pWaic = M2 / (n_f - 1) (0 for n_f < 2); elpdWaic =
+// lppd - pWaic; elpdIs = log n_f - (RMAX + log SNEG); paretoK / elpdLoo by Pareto-smoothed importance sampling of the tail
+// (paretoK NaN and elpdLoo = elpdIs where the tail is too short to fit); pLoo = lppd - elpdLoo.  nInf > 0: elpdWaic = elpdIs =
+// elpdLoo = -inf, paretoK = pLoo = +inf.  rows - nInf = 0 otherwise (rows = 0): every value 0.  Host arithmetic only.
+constexpr int kPointwiseCols = 9;
+void pointwise_table(const double *acc, const double *tail, int tail_len, long n_stars, double *table);
+// over the stars with rows > 0 -> totals [kScoreTotals]: their number N, then sum and se = sqrt(N var_ddof1) of lppd, elpdWaic
+// and elpdLoo, sum pWaic, sum pLoo, the stars with nInf > 0, the stars with paretoK > 0.7, the largest finite paretoK (NaN: none)
+constexpr int kScoreTotals = 12;
+void score_totals(const double *table, long n_stars, double *totals);
+// two tables of the SAME catalogue (throws when the ids differ in content or order) -> out [kScoreCompare]: the number N of
+// stars with rows > 0 in both, then sum and se = sqrt(N var_ddof1) of elpdLoo_A - elpdLoo_B, the same pair for elpdWaic, and
+// the number of stars with rows > 0 in exactly one of the two tables (they take no part, and are reported)
+constexpr int kScoreCompare = 6;
+void score_compare(const double *table_a, const std::vector<std::string> &ids_a, const double *table_b, const std::vector<std::string> &ids_b,
+                   double *out);
+// <base>.pointwise ("id rows nInf lppd ... pLoo", one line per star), <base>.modelScore, <base>.modelCompare (one header line,
+// one line of values) and <base>.rowLpd ("row lpd"); docs/FORMATS.md.  17 significant digits; inf / -inf / nan as printf writes them.
+void write_pointwise(const std::string &path, const std::vector<std::string> &ids, const double *table);
+void write_model_score(const std::string &path, const double *totals);
+void write_model_compare(const std::string &path, const double *cmp);
+void write_row_lpd(const std::string &path, const double *row_lpd, long n_rows);
+void read_pointwise(const std::string &path, std::vector<std::string> &ids, std::vector<double> &table);
+
 const char *param_name(int idx);          // "logAge", "Y", "FeH", "modulus", "absorption", ...
 
 }  // namespace b9h

@@ -252,6 +252,64 @@ int b9h_phot_resid_settings(int argc, char **argv, char *out, int cap)
     });
 }
 
+int b9h_pointwise_table(const double *acc, const double *tail, int tail_len, long n_stars, double *table)
+{
+    return guard([&] {
+        if (n_stars < 0 || !table || tail_len < 0 || (n_stars > 0 && !acc)) throw std::runtime_error("b9h_pointwise_table: invalid argument");
+        b9h::pointwise_table(acc, tail_len > 0 ? tail : nullptr, tail_len, n_stars, table);
+    });
+}
+
+int b9h_score_totals(const double *table, long n_stars, double *totals)
+{
+    return guard([&] {
+        if (n_stars < 0 || !totals || (n_stars > 0 && !table)) throw std::runtime_error("b9h_score_totals: invalid argument");
+        b9h::score_totals(table, n_stars, totals);
+    });
+}
+
+int b9h_score_compare(const double *table_a, const char *const *ids_a, long n_a, const double *table_b, const char *const *ids_b, long n_b, double *out)
+{
+    return guard([&] {
+        if (n_a < 0 || n_b < 0 || !out || (n_a > 0 && (!table_a || !ids_a)) || (n_b > 0 && (!table_b || !ids_b)))
+            throw std::runtime_error("b9h_score_compare: invalid argument");
+        b9h::score_compare(table_a, std::vector<std::string>(ids_a, ids_a + n_a), table_b, std::vector<std::string>(ids_b, ids_b + n_b), out);
+    });
+}
+
+int b9h_write_pointwise(const char *path, const char *const *ids, long n_stars, const double *table)
+{
+    return guard([&] {
+        if (!path || n_stars < 0 || (n_stars > 0 && (!ids || !table))) throw std::runtime_error("b9h_write_pointwise: invalid argument");
+        b9h::write_pointwise(path, std::vector<std::string>(ids, ids + n_stars), table);
+    });
+}
+
+int b9h_write_model_score(const char *path, const double *totals)
+{
+    return guard([&] {
+        if (!path || !totals) throw std::runtime_error("b9h_write_model_score: invalid argument");
+        b9h::write_model_score(path, totals);
+    });
+}
+
+int b9h_model_score_settings(int argc, char **argv, char *out, int cap)
+{
+    return guard([&] {
+        if (!out) throw std::runtime_error("b9h_model_score_settings: NULL argument");
+        const std::vector<std::string> args = b9h::model_score_args(argc, argv);
+        std::vector<char *> av;
+        for (auto &a : args) av.push_back(const_cast<char *>(a.c_str()));
+        b9h::Settings st;
+        st.parse_args((int)av.size(), av.data());
+        const b9h::ModelScoreConfig c = b9h::model_score_config(st);
+        const std::string d = "margIsoIncrem = " + std::to_string(c.K) + "\nnMassRatios = " + std::to_string(c.Q) + "\nnPops = " + std::to_string(c.n_pops) +
+                              "\nperRow = " + std::to_string((int)c.per_row) + "\ncompareTo = " + c.compare_to + "\n";
+        if ((int)d.size() >= cap) throw std::runtime_error("b9h_model_score_settings: output buffer too small");
+        std::memcpy(out, d.c_str(), d.size() + 1);
+    });
+}
+
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part)
 {
     return guard([&] { b9h::merge_result_parts(final_path, world, walkers_per_rank, rows_per_part); });

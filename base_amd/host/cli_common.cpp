@@ -458,6 +458,38 @@ std::vector<std::string> phot_resid_args(int argc, char **argv)
     return out;
 }
 
+ModelScoreConfig model_score_config(const Settings &st)
+{
+    ModelScoreConfig c;
+    c.K = (int)st.integer("modelScore.margIsoIncrem", st.integer("sampleMass.margIsoIncrem", 4));
+    c.Q = (int)st.integer("modelScore.nMassRatios", st.integer("sampleMass.nMassRatios", 4));
+    c.n_pops = (int)st.integer("modelScore.nPops", 1);
+    c.per_row = st.integer("modelScore.perRow", 0) != 0;
+    c.compare_to = st.str("modelScore.compareTo", "");
+    if (c.K < 1 || c.Q < 1) throw std::runtime_error("margIsoIncrem and nMassRatios must be positive");
+    if (c.n_pops != 1 && c.n_pops != 2) throw std::runtime_error("modelScore.nPops must be 1 or 2");
+    return c;
+}
+
+std::vector<std::string> model_score_args(int argc, char **argv)
+{
+    std::vector<std::string> out;
+    for (int i = 0; i < argc; ++i) {
+        std::string a = argv[i];
+        if (a == "--perRow") a = "--modelScorePerRow=1";
+        else if (a.rfind("--perRow=", 0) == 0) a = "--modelScorePerRow" + a.substr(8);
+        else if (a == "--nPops" || a.rfind("--nPops=", 0) == 0) a = "--modelScoreNPops" + a.substr(7);
+        out.push_back(a);
+    }
+    return out;
+}
+
+int model_score_tail_len(long n_rows)
+{
+    const double s = (double)n_rows;
+    return (int)std::min(256.0, std::min(std::floor(s / 5.0), std::ceil(3.0 * std::sqrt(s))) + 1.0);
+}
+
 int report_and_exit_code(const char *prog, const std::exception &e)
 {
     std::fprintf(stderr, "%s: %s\n", prog, e.what());

@@ -70,6 +70,16 @@ PhotResidConfig phot_resid_config(const Settings &st);
 // renamed to the flags of its own keys (--photResidualsPerStar / --photResidualsNPops) before Settings::parse_args sees it
 std::vector<std::string> phot_resid_args(int argc, char **argv);
 
+// modelScore's own settings: modelScore.{margIsoIncrem, nMassRatios, nPops, perRow, compareTo}, the grid defaulting to
+// sampleMass's (4 each), one population, no per-row file, no comparison.
+struct ModelScoreConfig { int K, Q, n_pops; bool per_row; std::string compare_to; };
+ModelScoreConfig model_score_config(const Settings &st);
+// --perRow and --nPops are renamed to the flags of modelScore's own keys (--modelScorePerRow / --modelScoreNPops) before
+// Settings::parse_args sees them (--nPops belongs to simCluster in the shared flag table); --margIsoIncrem / --nMassRatios as sampleMass
+std::vector<std::string> model_score_args(int argc, char **argv);
+// the tail kept per star for a chain of n_rows rows: min(256, min(floor(S / 5), ceil(3 sqrt S)) + 1)
+int model_score_tail_len(long n_rows);
+
 int report_and_exit_code(const char *prog, const std::exception &e);
 
 }  // namespace b9h

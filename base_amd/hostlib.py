@@ -39,6 +39,7 @@ HOST_SYMBOLS = [
     "b9h_star_table", "b9h_write_star_summary",
     "b9h_mass_function_table", "b9h_write_mass_function", "b9h_write_star_mass_hist", "b9h_mass_function_settings",
     "b9h_resid_table", "b9h_filter_resid_table", "b9h_write_phot_resid", "b9h_write_filter_resid", "b9h_phot_resid_settings",
+    "b9h_pointwise_table", "b9h_score_totals", "b9h_score_compare", "b9h_write_pointwise", "b9h_write_model_score", "b9h_model_score_settings",
 ]
 
 _lib = None
@@ -97,6 +98,12 @@ def load() -> C.CDLL:
     lib.b9h_write_phot_resid.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, C.POINTER(C.c_char_p), C.c_int, _dp]
     lib.b9h_write_filter_resid.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, _dp]
     lib.b9h_phot_resid_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
+    lib.b9h_pointwise_table.argtypes = [_dp, _dp, C.c_int, C.c_long, _dp]
+    lib.b9h_score_totals.argtypes = [_dp, C.c_long, _dp]
+    lib.b9h_score_compare.argtypes = [_dp, C.POINTER(C.c_char_p), C.c_long, _dp, C.POINTER(C.c_char_p), C.c_long, _dp]
+    lib.b9h_write_pointwise.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp]
+    lib.b9h_write_model_score.argtypes = [C.c_char_p, _dp]
+    lib.b9h_model_score_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     lib.b9h_sim_draw_systems.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_int, C.c_double, _dp, _dp, _dp, _ip, _ip]
     lib.b9h_sim_field_mags.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int, _dp, _dp, _dp]
@@ -466,6 +473,82 @@ def phot_resid_settings(args):
     buf = C.create_string_buffer(1024)
     _check(load().b9h_phot_resid_settings(len(args) + 1, argv, buf, 1024))
     return {k: int(v) for k, v in (line.split(" = ") for line in buf.value.decode().splitlines())}
+
+
+POINTWISE_COLUMNS = ("rows", "nInf", "lppd", "pWaic", "elpdWaic", "elpdIs", "paretoK", "elpdLoo", "pLoo")
+SCORE_TOTALS = ("nStars", "lppd", "lppdSe", "elpdWaic", "elpdWaicSe", "elpdLoo", "elpdLooSe", "pWaic", "pLoo", "nInfStars", "nHighK", "maxK")
+SCORE_COMPARE = ("nStars", "dElpdLoo", "dElpdLooSe", "dElpdWaic", "dElpdWaicSe", "nDropped")
+
+
+def pointwise_table(acc, tail=None) -> np.ndarray:
+    """b9h_pointwise_table: b9_pointwise's acc [n_stars, 8] and tail [n_stars, tail_len] (None: no PSIS fit) -> the per-star
+    table [n_stars, 9] (POINTWISE_COLUMNS)."""
+    a = np.ascontiguousarray(acc, dtype=np.float64).reshape(-1, 8)
+    n = a.shape[0]
+    t = None if tail is None else np.ascontiguousarray(tail, dtype=np.float64).reshape(n, -1)
+    out = np.empty((n, len(POINTWISE_COLUMNS)))
+    _check(load().b9h_pointwise_table(a.ctypes.data_as(_dp), t.ctypes.data_as(_dp) if t is not None else None, 0 if t is None else t.shape[1], n,
+                                      out.ctypes.data_as(_dp)))
+    return out
+
+
+def score_totals(table) -> dict:
+    """b9h_score_totals: the totals of a per-star table over its stars with rows > 0 (SCORE_TOTALS)."""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, len(POINTWISE_COLUMNS))
+    out = np.empty(len(SCORE_TOTALS))
+    _check(load().b9h_score_totals(t.ctypes.data_as(_dp), t.shape[0], out.ctypes.data_as(_dp)))
+    return dict(zip(SCORE_TOTALS, out.tolist()))
+
+
+def score_compare(table_a, ids_a, table_b, ids_b) -> dict:
+    """b9h_score_compare: the paired difference A - B of two per-star tables of the same catalogue (SCORE_COMPARE); HostError
+    when the star ids differ in content or order."""
+    a = np.ascontiguousarray(table_a, dtype=np.float64).reshape(len(ids_a), len(POINTWISE_COLUMNS))
+    b = np.ascontiguousarray(table_b, dtype=np.float64).reshape(len(ids_b), len(POINTWISE_COLUMNS))
+    out = np.empty(len(SCORE_COMPARE))
+    _check(load().b9h_score_compare(a.ctypes.data_as(_dp), _names(ids_a), len(ids_a), b.ctypes.data_as(_dp), _names(ids_b), len(ids_b),
+                                    out.ctypes.data_as(_dp)))
+    return dict(zip(SCORE_COMPARE, out.tolist()))
+
+
+def write_pointwise(path: str, ids, table) -> None:
+    """b9h_write_pointwise: the .pointwise file of a per-star table [len(ids), 9]."""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(len(ids), len(POINTWISE_COLUMNS))
+    _check(load().b9h_write_pointwise(path.encode(), _names(ids), len(ids), t.ctypes.data_as(_dp)))
+
+
+def write_model_score(path: str, totals) -> None:
+    """b9h_write_model_score: the .modelScore file of score_totals' values."""
+    v = np.array([totals[k] for k in SCORE_TOTALS] if isinstance(totals, dict) else totals, dtype=np.float64)
+    _check(load().b9h_write_model_score(path.encode(), v.ctypes.data_as(_dp)))
+
+
+def read_pointwise(path: str):
+    """(ids, columns, table [n_stars, 9]) of a .pointwise file."""
+    return read_table_file(path, "id")
+
+
+def read_named_values(path: str) -> dict:
+    """A .modelScore / .modelCompare file (one header line, one line of values) as a dict."""
+    with open(path) as f:
+        names, values = f.readline().split(), f.readline().split()
+    return dict(zip(names, (float(v) for v in values)))
+
+
+def read_row_lpd(path: str) -> np.ndarray:
+    """The lpd column of a .rowLpd file."""
+    with open(path) as f:
+        assert f.readline().split() == ["row", "lpd"]
+        return np.array([float(line.split()[1]) for line in f if line.strip()])
+
+
+def model_score_settings(args):
+    """modelScore's settings as the program parses `args` (flags, --config file): a dict of its five keys."""
+    argv = (C.c_char_p * (len(args) + 1))(b"modelScore", *[str(a).encode() for a in args])
+    buf = C.create_string_buffer(4096)
+    _check(load().b9h_model_score_settings(len(args) + 1, argv, buf, 4096))
+    d = dict(line.split(" = ") if " = " in line else (line.rstrip(" ="), "") for line in buf.value.decode().splitlines())
+    return {k: (v if k == "compareTo" else int(v)) for k, v in d.items()}
 
 
 # ------------------------------------------------------------------------------------------

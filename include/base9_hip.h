@@ -294,7 +294,7 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk);
  * b9_set_priors or b9_set_options changes the posterior: the previous block's state carries a log-posterior of the old
  * one, so the next B9_BLOCK_CONTINUE block returns B9_ERR_STATE (the message names the call that intervened) and the chain
  * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags, b9_sample_wd_mass, b9_star_moments,
- * b9_mass_hist and b9_phot_resid (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
+ * b9_mass_hist, b9_phot_resid and b9_pointwise (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
  * context's work buffers: b9_logpost / b9_sample_mass / b9_derive_isochrone, the staging calls, b9_set_options and a block
  * with another n_walkers return B9_ERR_STATE until it has been collected.  A driver that adapts the proposal
  * from block b-1 while block b runs keeps the GPU's queue non-empty: enqueue b+1 (CONTINUE | ASYNC), wait(b), ...
@@ -514,6 +514,56 @@ int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quan
 int b9_phot_resid(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags,
                   double *star_resid /* host [n_stars][2 + 2 n_filt], in/out, may be NULL */,
                   double *row_resid  /* host [n_rows][1 + 5 n_filt], out,    may be NULL */);
+
+/*
+ * Exact pointwise predictive densities over a saved chain (the modelScore counterpart): what WAIC, PSIS-LOO and the paired
+ * comparison of two fits need.  Added in ABI 6 without a version change, as its siblings were: purely additive.
+ *
+ * Definition.  Grid, terms and pruning are exactly b9_star_moments': marg_iso_increm x marg_n_q nodes per EEP interval; WD-stage
+ * stars 8 * marg_iso_increm steps above the AGB tip at mass ratio 0; n_pops honoured, mode ignored; terms that are not finite do
+ * not take part; terms more than 40 e-folds below a data-only lower bound may be dropped (b9_tuning.marg_no_pruning: none are).
+ * The value of (row r, star i) is v = logaddexp(la_i, l) with l the lambda-mixed c0m_i + logsumexp(t) and la_i = log(1 - p_i) +
+ * log fs: the per-star value b9_logpost reports in marginalised mode.  A star with no live node under a row has v = la_i, the
+ * field term (-inf at membership prior 1), and -- unlike b9_star_moments -- that (row, star) COUNTS.  A row outside the grid
+ * contributes nothing to any star.
+ *
+ * acc (host, [n_stars][B9_PW_N], the caller's star order, in/out, nullable): updated one row at a time in ascending row order;
+ * with k = the finite rows the star has taken so far and the row's value v:
+ *     B9_PW_ROWS + 1 for every row inside the grid;  B9_PW_NINF + 1 if v = -inf, and such a row touches nothing else;
+ *     k = 0:  (VMAX, SPOS, RMAX, SNEG, MEAN, M2) = (v, 1, -v, 1, v, 0);
+ *     k > 0:  v > VMAX ? (SPOS = fma(SPOS, exp(VMAX - v), 1), VMAX = v) : SPOS += exp(v - VMAX);  the same rule on
+ *             (RMAX, SNEG) with r = -v;  d = v - MEAN, MEAN += d / (k + 1), M2 = fma(d, v - MEAN, M2)      (Welford).
+ * One exp; contractions only where written.  The state is carried whole, so the bits are the same for the call's own chunking
+ * (at most 32 rows at a time) and for any split of the rows over B9_PW_CONTINUE calls; flags = 0 starts from zeros.  A star is
+ * empty when ROWS - NINF = 0.  lppd_i = VMAX + log SPOS - log ROWS;  the variance of v is M2 / (ROWS - NINF - 1).
+ *
+ * tail (host, [n_stars][tail_len], in/out, nullable, 0 <= tail_len <= B9_PW_MAX_TAIL; requires acc): the tail_len largest values
+ * of r = -v among the star's finite rows, descending, padded with -inf: a function of the multiset of values only, so identical
+ * for any row order, chunking or split.  flags = 0 starts from -inf.
+ *
+ * row_lpd (host, [n_rows], out, nullable): sum_i v_ri over the caller's star order, ascending, one plain add per star; -inf for
+ * a row outside the grid; a row's value depends on that row alone.
+ *
+ * Synchronous; host pointers.  B9_ERR_INVALID (outputs untouched) for n_rows < 1, NULL params, both acc and row_lpd NULL,
+ * tail_len outside [0, B9_PW_MAX_TAIL] or tail without acc; B9_ERR_STATE while a sampler block is outstanding; B9_ERR_CAPACITY as
+ * its siblings.  The call uses buffers of its own: a B9_BLOCK_CONTINUE block enqueued after it gives the same bits as one
+ * enqueued without it.
+ */
+#define B9_PW_ROWS 0
+#define B9_PW_NINF 1
+#define B9_PW_VMAX 2
+#define B9_PW_SPOS 3
+#define B9_PW_RMAX 4
+#define B9_PW_SNEG 5
+#define B9_PW_MEAN 6
+#define B9_PW_M2 7
+#define B9_PW_N 8
+#define B9_PW_MAX_TAIL 256
+#define B9_PW_CONTINUE 1
+int b9_pointwise(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags, int32_t tail_len,
+                 double *acc     /* host [n_stars][B9_PW_N],   in/out, may be NULL */,
+                 double *tail    /* host [n_stars][tail_len],  in/out, may be NULL */,
+                 double *row_lpd /* host [n_rows],             out,    may be NULL */);
 
 /* ---- introspection (used by bench/tests; no compute) --------------------------------- */
 int b9_max_eep(const b9_ctx *ctx);           /* longest isochrone in the loaded pack        */

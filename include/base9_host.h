@@ -138,6 +138,26 @@ int b9h_filter_resid_table(const double *row_resid, long n_rows, int n_filt, dou
 int b9h_write_phot_resid(const char *path, const char *const *ids, long n_stars, const char *const *filters, int n_filt, const double *table);
 int b9h_write_filter_resid(const char *path, const char *const *filters, int n_filt, const double *table);
 int b9h_phot_resid_settings(int argc, char **argv, char *out, int cap);
+/* modelScore.  b9h_pointwise_table: b9_pointwise's acc [n_stars][8] and tail [n_stars][tail_len] (NULL or tail_len 0: no PSIS
+ * fit) -> the per-star table [n_stars][9]: rows, nInf, lppd, pWaic, elpdWaic, elpdIs, paretoK, elpdLoo, pLoo.  With n_f = rows -
+ * nInf: lppd = VMAX + log SPOS - log rows, pWaic = M2 / (n_f - 1) (0 for n_f < 2), elpdWaic = lppd - pWaic, elpdIs = log n_f -
+ * (RMAX + log SNEG); paretoK and elpdLoo by Pareto-smoothed importance sampling of the tail (Vehtari, Gelman & Gabry 2017; the
+ * generalised Pareto fit of Zhang & Stephens 2009; DESIGN.md section 2 states every step), paretoK NaN and elpdLoo = elpdIs where
+ * the tail is too short to fit; pLoo = lppd - elpdLoo.  nInf > 0: elpdWaic = elpdIs = elpdLoo = -inf, paretoK = pLoo = +inf.
+ * rows = 0: every value 0.
+ * b9h_score_totals: over the stars with rows > 0 -> totals [12]: their number N, sum and se = sqrt(N var_ddof1) of lppd, of
+ * elpdWaic and of elpdLoo, sum pWaic, sum pLoo, the stars with nInf > 0, the stars with paretoK > 0.7, the largest finite paretoK.
+ * b9h_score_compare: two tables of the same catalogue -> out [6]: the stars with rows > 0 in both, then sum and se of
+ * elpdLoo_A - elpdLoo_B and of elpdWaic_A - elpdWaic_B, then the stars with rows > 0 in exactly one table (left out, reported); fails (-1, b9h_last_error) when the ids differ in content or order.
+ * b9h_write_pointwise / b9h_write_model_score: the files <base>.pointwise and <base>.modelScore (docs/FORMATS.md).
+ * b9h_model_score_settings: modelScore's command line (argv[0] is skipped) and YAML parsed as the program parses them --
+ * "key = value" lines of margIsoIncrem, nMassRatios, nPops, perRow, compareTo into out. */
+int b9h_pointwise_table(const double *acc, const double *tail, int tail_len, long n_stars, double *table);
+int b9h_score_totals(const double *table, long n_stars, double *totals);
+int b9h_score_compare(const double *table_a, const char *const *ids_a, long n_a, const double *table_b, const char *const *ids_b, long n_b, double *out);
+int b9h_write_pointwise(const char *path, const char *const *ids, long n_stars, const double *table);
+int b9h_write_model_score(const char *path, const double *totals);
+int b9h_model_score_settings(int argc, char **argv, char *out, int cap);
 /* rank 0's merge of <final_path>.part<r> into <final_path> after a --gpus N run (b9h::merge_result_parts; exposed for tests) */
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part);
 
