@@ -7,6 +7,9 @@
 #include <algorithm>
 #include <cmath>
 #include <atomic>
+#include <functional>
+#include <string>
+#include <vector>
 
 using namespace b9i;
 
@@ -341,56 +344,114 @@ int b9_sample_wd_mass(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t
     return B9_OK;
 }
 
-// Rows are worked in chunks of at most B9_MOM_MAX_ROWS, and of as few rows as keep the chunk's increments within B9_MOM_SCRATCH_BYTES.
-#define B9_MOM_SCRATCH_BYTES ((size_t)64 << 20)
-#define B9_MOM_MAX_ROWS 32
+}  // extern "C"
 
-int b9_star_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags, double *acc)
+namespace {
+
+// ---- the reductions over a saved chain: b9_star_moments, b9_mass_hist, b9_phot_resid, b9_pointwise --------------------------
+// What one of them is to the driver below.  Rows are worked in chunks of at most max_rows, and of as few rows as keep the chunk's
+// increments [rows][n_stars][n_col] within scratch_bytes.
+struct ChainCall {
+    const char *name;
+    size_t n_col, n_acc, n_rowcol;       // increments per (row, star); accumulator words per star; words of a row's sums
+    size_t max_rows, scratch_bytes;
+    bool cont;                           // the call's CONTINUE flag: acc comes in
+    double *acc, *rows;                  // host: the per-star accumulators [n_stars][n_acc], the per-row sums [n_rows][n_rowcol] (null: not asked for)
+    size_t extra_bytes[kChainExtras];    // the call's own parts of the arena
+};
+// ... and what the call's hooks see: the arena's parts (acc / rows null when the caller did not ask for them; wd without WD-stage stars)
+struct ChainDev {
+    double *par, *iso, *tab, *wd, *scratch, *acc, *rows;
+    IsoHdr *hdr;
+    char *extra[kChainExtras];
+    int n_pops, K, Q, mass_cap;
+    long long iso_stride;
+};
+using ChainHook = std::function<int(const ChainDev &)>;
+using ChainBody = std::function<hipError_t(const ChainDev &, int /* rows of the chunk */)>;
+
+// The shared checks of the context's state, behind each call's own argument validation.
+int chain_ready(b9_ctx *ctx)
 {
-    if (!ctx || !params || !acc || n_rows < 1) return B9_ERR_INVALID;
     if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
     if (!ctx->have_pack || !ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
-    const int n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
-    const int K = marg_grid(ctx).K, Q = marg_grid(ctx).Q;
-    if (n == 0) return B9_OK;
+    return B9_OK;
+}
+
+// The chunked driver (after chain_ready): sizes, one arena in ctx->d_chain, the accumulators in (or cleared), `begin`, then per
+// chunk the parameter rows, their isochrones, `body` -- which writes every (row, star) of the chunk, so nothing is cleared -- and
+// the chunk's row sums out; at last the accumulators out, `end`, and the wait.  An empty catalogue has all-zero row sums.
+int chain_reduce(b9_ctx *ctx, const ChainCall &c, const double *params, int n_rows, const ChainBody &body, const ChainHook &begin = nullptr,
+                 const ChainHook &end = nullptr)
+{
+    const int n = ctx->st.n;
+    if (n == 0) {
+        if (c.rows) std::fill(c.rows, c.rows + (size_t)n_rows * c.n_rowcol, 0.0);
+        return B9_OK;
+    }
     const DevPack &pk = ctx->pk;
-    const int mass_cap = pack_mass_cap(pk.max_eep);
-    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
-    const size_t tab_row = (size_t)n_pops * (size_t)b9k_marg_table_doubles(pk.nfp, mass_cap, K, Q);
-    const size_t wd_row = ctx->st.n_wd > 0 ? (size_t)n_pops * (size_t)b9k_marg_wd_table_doubles(pk.nfp, K) : 0;
-    const size_t chunk = mom_chunk_rows((size_t)n_rows, (size_t)n, B9_MOM_N, B9_MOM_MAX_ROWS, B9_MOM_SCRATCH_BYTES);
+    ChainDev d{};
+    d.n_pops = ctx->opt.n_pops == 2 ? 2 : 1; d.K = marg_grid(ctx).K; d.Q = marg_grid(ctx).Q;
+    d.mass_cap = pack_mass_cap(pk.max_eep); d.iso_stride = pack_iso_stride(d.mass_cap, pk.nfp);
+    const size_t tab_row = (size_t)d.n_pops * (size_t)b9k_marg_table_doubles(pk.nfp, d.mass_cap, d.K, d.Q);
+    const size_t wd_row = ctx->st.n_wd > 0 ? (size_t)d.n_pops * (size_t)b9k_marg_wd_table_doubles(pk.nfp, d.K) : 0;
+    const size_t chunk = mom_chunk_rows((size_t)n_rows, (size_t)n, c.n_col, c.max_rows, c.scratch_bytes);
     if (chunk * (tab_row + wd_row) > ((size_t)8 << 30) / sizeof(double))
-        return fail(ctx, B9_ERR_CAPACITY, "b9_star_moments: marginalisation grid too fine: the node tables would exceed 8 GiB");
-    // one allocation: [params][headers][isochrones][table][WD table][increments][accumulators]
-    const MomArena a = mom_arena(chunk, n_pops, iso_stride, tab_row, wd_row, (size_t)n, B9_MOM_N, sizeof(IsoHdr));
-    RESERVE(ctx, ctx->d_mom, a.bytes);
-    char *base = ctx->d_mom.get();
-    double *d_par = part<double>(base, a.o_par), *d_iso = part<double>(base, a.o_iso), *d_tab = part<double>(base, a.o_tab);
-    double *d_wd = wd_row ? part<double>(base, a.o_wd) : nullptr, *d_scratch = part<double>(base, a.o_scratch), *d_acc = part<double>(base, a.o_acc);
-    IsoHdr *d_hdr = part<IsoHdr>(base, a.o_hdr);
-    const size_t acc_bytes = sizeof(double) * (size_t)n * B9_MOM_N;
+        return fail(ctx, B9_ERR_CAPACITY, std::string(c.name) + ": marginalisation grid too fine: the node tables would exceed 8 GiB");
+    const ChainArena a = chain_arena(chunk, d.n_pops, d.iso_stride, tab_row, wd_row, (size_t)n, c.n_col, c.n_acc, c.rows ? c.n_rowcol : 0, sizeof(IsoHdr),
+                                     c.extra_bytes);
+    RESERVE(ctx, ctx->d_chain, a.bytes);
+    char *base = ctx->d_chain.get();
+    d.par = part<double>(base, a.o_par); d.hdr = part<IsoHdr>(base, a.o_hdr); d.iso = part<double>(base, a.o_iso); d.tab = part<double>(base, a.o_tab);
+    d.wd = wd_row ? part<double>(base, a.o_wd) : nullptr; d.scratch = part<double>(base, a.o_scratch);
+    d.acc = c.acc ? part<double>(base, a.o_acc) : nullptr; d.rows = c.rows ? part<double>(base, a.o_rows) : nullptr;
+    for (int k = 0; k < kChainExtras; ++k) d.extra[k] = base + a.o_extra[k];
+    const size_t acc_bytes = sizeof(double) * (size_t)n * c.n_acc;
     hipStream_t s = ctx->stream;
-    if (flags & B9_MOM_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_acc, acc, acc_bytes, hipMemcpyHostToDevice, s));
-    else HIPCHK(ctx, hipMemsetAsync(d_acc, 0, acc_bytes, s));
+    if (d.acc) {
+        if (c.cont) HIPCHK(ctx, hipMemcpyAsync(d.acc, c.acc, acc_bytes, hipMemcpyHostToDevice, s));
+        else HIPCHK(ctx, hipMemsetAsync(d.acc, 0, acc_bytes, s));
+    }
+    if (begin) { const int rc = begin(d); if (rc) return rc; }
     const McmcDev off{};
     for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
         const int m = std::min((int)chunk, n_rows - r0);
-        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
-        // every (row, star) of the chunk writes its eight increments (zeros where it contributes nothing): no clearing
-        HIPCHK(ctx, b9k_star_moments(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, K, Q, ctx->marg_prune, d_tab, d_wd,
-                                     d_scratch, d_acc, s));
+        HIPCHK(ctx, hipMemcpyAsync(d.par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, b9k_derive_iso(pk, d.par, m, d.n_pops, d.hdr, d.iso, d.iso_stride, d.mass_cap, off, ctx->pr, no_prev(), s));
+        HIPCHK(ctx, body(d, m));
+        if (d.rows) HIPCHK(ctx, hipMemcpyAsync(c.rows + (size_t)r0 * c.n_rowcol, d.rows, sizeof(double) * m * c.n_rowcol, hipMemcpyDeviceToHost, s));
     }
-    HIPCHK(ctx, hipMemcpyAsync(acc, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
+    if (d.acc) HIPCHK(ctx, hipMemcpyAsync(c.acc, d.acc, acc_bytes, hipMemcpyDeviceToHost, s));
+    if (end) { const int rc = end(d); if (rc) return rc; }
     HIPCHK(ctx, hipStreamSynchronize(s));
     return B9_OK;
 }
 
-// Rows are worked in chunks of at most B9_HIST_MAX_ROWS, and of as few rows as keep the chunk's increments within B9_HIST_SCRATCH_BYTES.
+}  // namespace
+
+#define B9_MOM_SCRATCH_BYTES ((size_t)64 << 20)
+#define B9_MOM_MAX_ROWS 32
 #define B9_HIST_SCRATCH_BYTES ((size_t)64 << 20)
 #define B9_HIST_MAX_ROWS 32
+#define B9_RESID_SCRATCH_BYTES ((size_t)64 << 20)
+#define B9_RESID_MAX_ROWS 32
+// (B9_PW_MAX_ROWS: b9_launch.h -- the reducers hold a chunk's rows in registers; 32 rows up to 65536 stars)
+#define B9_PW_SCRATCH_BYTES ((size_t)16 << 20)
+
+extern "C" {
+
+int b9_star_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags, double *acc)
+{
+    if (!ctx || !params || !acc || n_rows < 1) return B9_ERR_INVALID;
+    if (const int rc = chain_ready(ctx)) return rc;
+    const ChainCall c{"b9_star_moments", B9_MOM_N, B9_MOM_N, 0, B9_MOM_MAX_ROWS, B9_MOM_SCRATCH_BYTES, (flags & B9_MOM_CONTINUE) != 0, acc, nullptr, {}};
+    return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
+        return b9k_star_moments(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, d.K, d.Q, ctx->marg_prune, d.tab, d.wd,
+                                d.scratch, d.acc, ctx->stream);
+    });
+}
 
 int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quantity, const double *edges, int32_t n_bins, int32_t flags,
                  double *star_hist, double *row_hist)
@@ -401,186 +462,73 @@ int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quan
     for (int b = 0; b <= n_bins; ++b)
         if (!std::isfinite(edges[b]) || (b > 0 && !(edges[b] > edges[b - 1])))
             return fail(ctx, B9_ERR_INVALID, "b9_mass_hist: the edges must be finite and strictly ascending");
-    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
-    if (!ctx->have_pack || !ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
-    const int n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
-    const int K = marg_grid(ctx).K, Q = marg_grid(ctx).Q;
+    if (const int rc = chain_ready(ctx)) return rc;
     const size_t ncol = (size_t)n_bins + 1;
-    if (n == 0) {
-        if (row_hist) std::fill(row_hist, row_hist + (size_t)n_rows * ncol, 0.0);
-        return B9_OK;
-    }
-    const DevPack &pk = ctx->pk;
-    const int mass_cap = pack_mass_cap(pk.max_eep);
-    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
-    const size_t tab_row = (size_t)n_pops * (size_t)b9k_marg_table_doubles(pk.nfp, mass_cap, K, Q);
-    const size_t wd_row = ctx->st.n_wd > 0 ? (size_t)n_pops * (size_t)b9k_marg_wd_table_doubles(pk.nfp, K) : 0;
-    const size_t chunk = mom_chunk_rows((size_t)n_rows, (size_t)n, ncol, B9_HIST_MAX_ROWS, B9_HIST_SCRATCH_BYTES);
-    if (chunk * (tab_row + wd_row) > ((size_t)8 << 30) / sizeof(double))
-        return fail(ctx, B9_ERR_CAPACITY, "b9_mass_hist: marginalisation grid too fine: the node tables would exceed 8 GiB");
-    // one allocation: [params][headers][isochrones][table][WD table][increments][accumulators][the chunk's row sums]
-    const HistArena a = hist_arena(chunk, n_pops, iso_stride, tab_row, wd_row, (size_t)n, ncol, sizeof(IsoHdr));
-    RESERVE(ctx, ctx->d_hist, a.bytes);
-    char *base = ctx->d_hist.get();
-    double *d_par = part<double>(base, a.m.o_par), *d_iso = part<double>(base, a.m.o_iso), *d_tab = part<double>(base, a.m.o_tab);
-    double *d_wd = wd_row ? part<double>(base, a.m.o_wd) : nullptr, *d_scratch = part<double>(base, a.m.o_scratch);
-    double *d_acc = star_hist ? part<double>(base, a.m.o_acc) : nullptr, *d_rows = row_hist ? part<double>(base, a.o_rows) : nullptr;
-    IsoHdr *d_hdr = part<IsoHdr>(base, a.m.o_hdr);
-    const size_t acc_bytes = sizeof(double) * (size_t)n * ncol;
-    hipStream_t s = ctx->stream;
-    if (d_acc) {
-        if (flags & B9_HIST_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_acc, star_hist, acc_bytes, hipMemcpyHostToDevice, s));
-        else HIPCHK(ctx, hipMemsetAsync(d_acc, 0, acc_bytes, s));
-    }
-    const McmcDev off{};
-    for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
-        const int m = std::min((int)chunk, n_rows - r0);
-        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
-        // every (row, star) of the chunk writes all its columns (zeros where it contributes nothing): no clearing
-        HIPCHK(ctx, b9k_mass_hist(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, K, Q, ctx->marg_prune, quantity, edges, n_bins,
-                                  d_tab, d_wd, d_scratch, d_acc, d_rows, s));
-        if (d_rows) HIPCHK(ctx, hipMemcpyAsync(row_hist + (size_t)r0 * ncol, d_rows, sizeof(double) * m * ncol, hipMemcpyDeviceToHost, s));
-    }
-    if (d_acc) HIPCHK(ctx, hipMemcpyAsync(star_hist, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return B9_OK;
+    const ChainCall c{"b9_mass_hist", ncol, ncol, ncol, B9_HIST_MAX_ROWS, B9_HIST_SCRATCH_BYTES, (flags & B9_HIST_CONTINUE) != 0, star_hist, row_hist, {}};
+    return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
+        return b9k_mass_hist(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, d.K, d.Q, ctx->marg_prune, quantity, edges, n_bins,
+                             d.tab, d.wd, d.scratch, d.acc, d.rows, ctx->stream);
+    });
 }
-
-// Chunks as b9_mass_hist's: at most B9_RESID_MAX_ROWS rows, fewer while the chunk's increments would exceed B9_RESID_SCRATCH_BYTES.
-#define B9_RESID_SCRATCH_BYTES ((size_t)64 << 20)
-#define B9_RESID_MAX_ROWS 32
 
 int b9_phot_resid(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags, double *star_resid, double *row_resid)
 {
     if (!ctx || !params || n_rows < 1 || (!star_resid && !row_resid)) return B9_ERR_INVALID;
-    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
-    if (!ctx->have_pack || !ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
-    const int n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
-    const int K = marg_grid(ctx).K, Q = marg_grid(ctx).Q;
+    if (const int rc = chain_ready(ctx)) return rc;
     const DevPack &pk = ctx->pk;
-    const size_t nf = (size_t)pk.nf, ncol = 2 + 2 * nf, nrow = 1 + 5 * nf;
-    if (n == 0) {
-        if (row_resid) std::fill(row_resid, row_resid + (size_t)n_rows * nrow, 0.0);
-        return B9_OK;
-    }
-    const int mass_cap = pack_mass_cap(pk.max_eep);
-    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
-    const size_t tab_row = (size_t)n_pops * (size_t)b9k_marg_table_doubles(pk.nfp, mass_cap, K, Q);
-    const size_t wd_row = ctx->st.n_wd > 0 ? (size_t)n_pops * (size_t)b9k_marg_wd_table_doubles(pk.nfp, K) : 0;
-    const size_t chunk = mom_chunk_rows((size_t)n_rows, (size_t)n, ncol, B9_RESID_MAX_ROWS, B9_RESID_SCRATCH_BYTES);
-    if (chunk * (tab_row + wd_row) > ((size_t)8 << 30) / sizeof(double))
-        return fail(ctx, B9_ERR_CAPACITY, "b9_phot_resid: marginalisation grid too fine: the node tables would exceed 8 GiB");
-    // one allocation: [params][headers][isochrones][table][WD table][increments][accumulators][the chunk's row sums][pivots, twice][1 / sigma]
-    const ResidArena a = resid_arena(chunk, n_pops, iso_stride, tab_row, wd_row, (size_t)n, nf, (size_t)pk.nfp, (size_t)ctx->st.mg_pad, sizeof(IsoHdr));
-    RESERVE(ctx, ctx->d_resid, a.bytes);
-    char *base = ctx->d_resid.get();
-    double *d_par = part<double>(base, a.m.o_par), *d_iso = part<double>(base, a.m.o_iso), *d_tab = part<double>(base, a.m.o_tab);
-    double *d_wd = wd_row ? part<double>(base, a.m.o_wd) : nullptr, *d_scratch = part<double>(base, a.m.o_scratch);
-    double *d_acc = star_resid ? part<double>(base, a.m.o_acc) : nullptr, *d_rows = row_resid ? part<double>(base, a.o_rows) : nullptr;
-    double *d_piv_in = part<double>(base, a.o_piv_in), *d_piv_mg = part<double>(base, a.o_piv_mg), *d_isig = part<double>(base, a.o_isig);
-    IsoHdr *d_hdr = part<IsoHdr>(base, a.m.o_hdr);
-    // the pivots (the caller's obs bits where sigma > 0, else 0) and 1 / sigma (0: filter unused), the caller's star order
-    const HostStars &h = ctx->hs;
-    std::vector<double> piv((size_t)n * nf), isig((size_t)n * nf);
-    for (size_t k = 0; k < piv.size(); ++k) {
-        const bool used = h.sigma[k] > 0.0;
-        piv[k] = used ? h.obs[k] : 0.0;
-        isig[k] = used ? 1.0 / h.sigma[k] : 0.0;
-    }
-    const size_t acc_bytes = sizeof(double) * (size_t)n * ncol;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(d_piv_in, piv.data(), sizeof(double) * piv.size(), hipMemcpyHostToDevice, s));
-    if (d_rows) HIPCHK(ctx, hipMemcpyAsync(d_isig, isig.data(), sizeof(double) * isig.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, b9k_resid_stage(pk, ctx->st, d_piv_in, d_piv_mg, s));
-    if (d_acc) {
-        if (flags & B9_RESID_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_acc, star_resid, acc_bytes, hipMemcpyHostToDevice, s));
-        else HIPCHK(ctx, hipMemsetAsync(d_acc, 0, acc_bytes, s));
-    }
-    const McmcDev off{};
-    for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
-        const int m = std::min((int)chunk, n_rows - r0);
-        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
-        // every (row, star) of the chunk writes all its columns (zeros where it contributes nothing): no clearing
-        HIPCHK(ctx, b9k_phot_resid(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, K, Q, ctx->marg_prune, d_piv_mg, d_isig,
-                                   d_tab, d_wd, d_scratch, d_acc, d_rows, s));
-        if (d_rows) HIPCHK(ctx, hipMemcpyAsync(row_resid + (size_t)r0 * nrow, d_rows, sizeof(double) * m * nrow, hipMemcpyDeviceToHost, s));
-    }
-    if (d_acc) HIPCHK(ctx, hipMemcpyAsync(star_resid, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return B9_OK;
+    const size_t n = (size_t)ctx->st.n, nf = (size_t)pk.nf, ncol = 2 + 2 * nf;
+    // the call's parts: the pivots in the caller's order [n][nf] and in the mg_* copy's [mg_pad][nfp], and 1 / sigma [n][nf]
+    const ChainCall c{"b9_phot_resid", ncol, ncol, 1 + 5 * nf, B9_RESID_MAX_ROWS, B9_RESID_SCRATCH_BYTES, (flags & B9_RESID_CONTINUE) != 0, star_resid, row_resid,
+                      {8 * n * nf, 8 * (size_t)ctx->st.mg_pad * pk.nfp, 8 * n * nf}};
+    auto piv_mg = [](const ChainDev &d) { return reinterpret_cast<double *>(d.extra[1]); };
+    auto isig = [](const ChainDev &d) { return reinterpret_cast<double *>(d.extra[2]); };
+    std::vector<double> piv, is;         // (the uploads' sources: they live until the driver has waited for the stream)
+    return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
+        return b9k_phot_resid(pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, d.K, d.Q, ctx->marg_prune, piv_mg(d), isig(d),
+                              d.tab, d.wd, d.scratch, d.acc, d.rows, ctx->stream);
+    }, [&](const ChainDev &d) {
+        // the pivots (the caller's obs bits where sigma > 0, else 0) and 1 / sigma (0: filter unused), the caller's star order
+        const HostStars &h = ctx->hs;
+        piv.resize(n * nf); is.resize(n * nf);
+        for (size_t k = 0; k < piv.size(); ++k) {
+            const bool used = h.sigma[k] > 0.0;
+            piv[k] = used ? h.obs[k] : 0.0;
+            is[k] = used ? 1.0 / h.sigma[k] : 0.0;
+        }
+        HIPCHK(ctx, hipMemcpyAsync(d.extra[0], piv.data(), sizeof(double) * piv.size(), hipMemcpyHostToDevice, ctx->stream));
+        if (d.rows) HIPCHK(ctx, hipMemcpyAsync(isig(d), is.data(), sizeof(double) * is.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, b9k_resid_stage(pk, ctx->st, reinterpret_cast<double *>(d.extra[0]), piv_mg(d), ctx->stream));
+        return (int)B9_OK;
+    });
 }
-
-// Chunks of at most B9_PW_MAX_ROWS rows (b9_launch.h: the reducers hold a chunk's rows in registers), fewer while the chunk's
-// values [rows][stars] would exceed B9_PW_SCRATCH_BYTES: 32 rows up to 65536 stars.
-#define B9_PW_SCRATCH_BYTES ((size_t)16 << 20)
 
 int b9_pointwise(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags, int32_t tail_len, double *acc, double *tail, double *row_lpd)
 {
     if (!ctx || !params || n_rows < 1 || (!acc && !row_lpd)) return B9_ERR_INVALID;
     if (tail_len < 0 || tail_len > B9_PW_MAX_TAIL) return fail(ctx, B9_ERR_INVALID, "b9_pointwise: tail_len must lie in 0 .. B9_PW_MAX_TAIL");
     if (tail && !acc) return fail(ctx, B9_ERR_INVALID, "b9_pointwise: tail requires acc");
-    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
-    if (!ctx->have_pack || !ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
-    const int n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
-    const int K = marg_grid(ctx).K, Q = marg_grid(ctx).Q;
-    if (n == 0) {
-        if (row_lpd) std::fill(row_lpd, row_lpd + n_rows, 0.0);
-        return B9_OK;
-    }
-    const size_t T = (tail && tail_len > 0) ? (size_t)tail_len : 0;
-    const DevPack &pk = ctx->pk;
-    const int mass_cap = pack_mass_cap(pk.max_eep);
-    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
-    const size_t tab_row = (size_t)n_pops * (size_t)b9k_marg_table_doubles(pk.nfp, mass_cap, K, Q);
-    const size_t wd_row = ctx->st.n_wd > 0 ? (size_t)n_pops * (size_t)b9k_marg_wd_table_doubles(pk.nfp, K) : 0;
-    const size_t chunk = mom_chunk_rows((size_t)n_rows, (size_t)n, 1, B9_PW_MAX_ROWS, B9_PW_SCRATCH_BYTES);
-    if (chunk * (tab_row + wd_row) > ((size_t)8 << 30) / sizeof(double))
-        return fail(ctx, B9_ERR_CAPACITY, "b9_pointwise: marginalisation grid too fine: the node tables would exceed 8 GiB");
-    // one allocation: [params][headers][isochrones][table][WD table][v][row flags][state][the chunk's row sums][tail][tail, the caller's layout]
-    const PwArena a = pw_arena(chunk, n_pops, iso_stride, tab_row, wd_row, (size_t)n, B9_PW_N, T, sizeof(IsoHdr));
-    RESERVE(ctx, ctx->d_pw, a.bytes);
-    char *base = ctx->d_pw.get();
-    double *d_par = part<double>(base, a.o_par), *d_iso = part<double>(base, a.o_iso), *d_tab = part<double>(base, a.o_tab);
-    double *d_wd = wd_row ? part<double>(base, a.o_wd) : nullptr, *d_scratch = part<double>(base, a.o_scratch);
-    double *d_acc = acc ? part<double>(base, a.o_acc) : nullptr, *d_rows = row_lpd ? part<double>(base, a.o_rows) : nullptr;
-    double *d_tail = T ? part<double>(base, a.o_tail) : nullptr, *d_tail_io = T ? part<double>(base, a.o_tail_io) : nullptr;
-    int *d_flag = part<int>(base, a.o_flag);
-    IsoHdr *d_hdr = part<IsoHdr>(base, a.o_hdr);
-    const size_t acc_bytes = sizeof(double) * (size_t)n * B9_PW_N, tail_bytes = sizeof(double) * (size_t)n * T;
-    hipStream_t s = ctx->stream;
-    if (d_acc) {
-        if (flags & B9_PW_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_acc, acc, acc_bytes, hipMemcpyHostToDevice, s));
-        else HIPCHK(ctx, hipMemsetAsync(d_acc, 0, acc_bytes, s));
-    }
-    if (d_tail) {
-        if (flags & B9_PW_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_tail_io, tail, tail_bytes, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, b9k_pw_tail_load((flags & B9_PW_CONTINUE) ? d_tail_io : nullptr, n, (int)T, d_tail, s));
-    }
-    const McmcDev off{};
-    for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
-        const int m = std::min((int)chunk, n_rows - r0);
-        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
-        // every (row, star) of a row inside the grid writes its value, every row its flag: no clearing
-        HIPCHK(ctx, b9k_pointwise(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, K, Q, ctx->marg_prune, d_tab, d_wd,
-                                  d_scratch, d_flag, d_acc, d_tail, (int)T, d_rows, s));
-        if (d_rows) HIPCHK(ctx, hipMemcpyAsync(row_lpd + r0, d_rows, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-    }
-    if (d_acc) HIPCHK(ctx, hipMemcpyAsync(acc, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
-    if (d_tail) {
-        HIPCHK(ctx, b9k_pw_tail_store(d_tail, n, (int)T, d_tail_io, s));
-        HIPCHK(ctx, hipMemcpyAsync(tail, d_tail_io, tail_bytes, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return B9_OK;
+    if (const int rc = chain_ready(ctx)) return rc;
+    const int n = ctx->st.n, T = (tail && tail_len > 0) ? tail_len : 0;
+    const bool cont = (flags & B9_PW_CONTINUE) != 0;
+    const size_t tail_bytes = sizeof(double) * (size_t)n * T;
+    // the call's parts: the rows' inside-the-grid words, and the tail twice: the device's [tail_len][n] and the caller's [n][tail_len]
+    const ChainCall c{"b9_pointwise", 1, B9_PW_N, 1, B9_PW_MAX_ROWS, B9_PW_SCRATCH_BYTES, cont, acc, row_lpd, {4 * (size_t)B9_PW_MAX_ROWS, tail_bytes, tail_bytes}};
+    auto d_tail = [&](const ChainDev &d) { return T ? reinterpret_cast<double *>(d.extra[1]) : nullptr; };
+    auto d_tail_io = [](const ChainDev &d) { return reinterpret_cast<double *>(d.extra[2]); };
+    return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
+        return b9k_pointwise(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, d.K, d.Q, ctx->marg_prune, d.tab, d.wd,
+                             d.scratch, reinterpret_cast<int *>(d.extra[0]), d.acc, d_tail(d), T, d.rows, ctx->stream);
+    }, [&](const ChainDev &d) {
+        if (!T) return (int)B9_OK;
+        if (cont) HIPCHK(ctx, hipMemcpyAsync(d_tail_io(d), tail, tail_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, b9k_pw_tail_load(cont ? d_tail_io(d) : nullptr, n, T, d_tail(d), ctx->stream));
+        return (int)B9_OK;
+    }, [&](const ChainDev &d) {
+        if (!T) return (int)B9_OK;
+        HIPCHK(ctx, b9k_pw_tail_store(d_tail(d), n, T, d_tail_io(d), ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(tail, d_tail_io(d), tail_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return (int)B9_OK;
+    });
 }
 
 }  // extern "C"

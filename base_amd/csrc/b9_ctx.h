@@ -157,20 +157,11 @@ struct b9_ctx {
     // parameters, headers, derived isochrones and node table, the chunk's outputs, the stars' columns (wds_arena)
     b9i::DeviceBuf<char> d_wds;
 
-    // b9_star_moments: one allocation of its own (grown on demand, never shrunk), for the same reason: a chunk of rows'
-    // parameters, headers, derived isochrones and node tables, the chunk's increments, the accumulators (mom_arena)
-    b9i::DeviceBuf<char> d_mom;
-
-    // b9_mass_hist: likewise one allocation of its own (hist_arena): b9_star_moments' parts with n_bins + 1 columns, and the
-    // chunk's per-row sums
-    b9i::DeviceBuf<char> d_hist;
-
-    // b9_phot_resid: likewise (resid_arena): b9_star_moments' parts with 2 + 2 n_filt columns, the chunk's per-row sums, the
-    // call's pivots and 1 / sigma
-    b9i::DeviceBuf<char> d_resid;
-
-    // b9_pointwise: likewise (pw_arena): one double per (row, star), the rows' flags, the per-star state, the tails
-    b9i::DeviceBuf<char> d_pw;
+    // b9_star_moments, b9_mass_hist, b9_phot_resid, b9_pointwise: one allocation for the four (grown on demand, never shrunk),
+    // for the same reason: a chunk of rows' parameters, headers, derived isochrones and node tables, the chunk's increments,
+    // the accumulators, the chunk's per-row sums and the call's own parts (chain_arena).  The calls are synchronous and keep
+    // nothing on the device between them, so only one of them is using it at any time.
+    b9i::DeviceBuf<char> d_chain;
 
     // timing of the dominant kernel
     int timing = 0;            // 0 off, n > 0: bracket every n-th launch of the dominant kernel with events

@@ -109,14 +109,20 @@ inline WdsArena wds_arena(size_t chunk, int n_pops, long long iso_stride, size_t
     return a;
 }
 
-// b9_star_moments' chunk of rows: [params][headers][isochrones][node table][WD node table][per-(row, star) increments], then the
-// accumulators (tab_row / wd_row: doubles of one row's two tables, all populations; n_mom: increments per star)
-struct MomArena { size_t o_par, o_hdr, o_iso, o_tab, o_wd, o_scratch, o_acc, bytes; };
-inline MomArena mom_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t wd_row, size_t n_stars, size_t n_mom, size_t hdr_bytes)
+// The reductions over a saved chain (b9_star_moments, b9_mass_hist, b9_phot_resid, b9_pointwise), one chunk of rows:
+// [params][headers][isochrones][node table][WD node table][per-(row, star) increments [chunk][n_stars][n_col]], then the
+// accumulators [n_stars][n_acc], the chunk's per-row sums [chunk][n_rowcol], and the call's own extra parts in the order it
+// lists their bytes (at most kChainExtras).  tab_row / wd_row: doubles of one row's two tables, all populations.  A part of 0
+// bytes is empty: it shares its offset with the next one.
+constexpr int kChainExtras = 3;
+struct ChainArena { size_t o_par, o_hdr, o_iso, o_tab, o_wd, o_scratch, o_acc, o_rows, o_extra[kChainExtras], bytes; };
+inline ChainArena chain_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t wd_row, size_t n_stars, size_t n_col, size_t n_acc,
+                              size_t n_rowcol, size_t hdr_bytes, const size_t (&extra_bytes)[kChainExtras])
 {
     Carve c;
-    MomArena a{c.take(8 * B9_NPARAM * chunk), c.take(hdr_bytes * chunk * n_pops), c.take(8 * chunk * n_pops * (size_t)iso_stride), c.take(8 * chunk * tab_row),
-               c.take(8 * chunk * wd_row), c.take(8 * chunk * n_stars * n_mom), c.take(8 * n_stars * n_mom), 0};
+    ChainArena a{c.take(8 * B9_NPARAM * chunk), c.take(hdr_bytes * chunk * n_pops), c.take(8 * chunk * n_pops * (size_t)iso_stride), c.take(8 * chunk * tab_row),
+                 c.take(8 * chunk * wd_row), c.take(8 * chunk * n_stars * n_col), c.take(8 * n_stars * n_acc), c.take(8 * chunk * n_rowcol), {}, 0};
+    for (int k = 0; k < kChainExtras; ++k) a.o_extra[k] = c.take(extra_bytes[k]);
     a.bytes = c.total;
     return a;
 }
@@ -125,50 +131,6 @@ inline size_t mom_chunk_rows(size_t n_rows, size_t n_stars, size_t n_mom, size_t
 {
     const size_t per_row = std::max<size_t>(1, 8 * n_stars * n_mom);
     return std::max<size_t>(1, std::min({n_rows, max_rows, scratch_bytes / per_row}));
-}
-
-// b9_mass_hist's chunk of rows: mom_arena with n_col = n_bins + 1 columns per star, then the chunk's per-row sums [chunk][n_col]
-struct HistArena { MomArena m; size_t o_rows, bytes; };
-inline HistArena hist_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t wd_row, size_t n_stars, size_t n_col, size_t hdr_bytes)
-{
-    HistArena a{mom_arena(chunk, n_pops, iso_stride, tab_row, wd_row, n_stars, n_col, hdr_bytes), 0, 0};
-    Carve c;
-    c.take(a.m.bytes);
-    a.o_rows = c.take(8 * chunk * n_col);
-    a.bytes = c.total;
-    return a;
-}
-
-// b9_phot_resid's chunk of rows: mom_arena with n_col = 2 + 2 nf columns per star, then the chunk's per-row sums
-// [chunk][1 + 5 nf], the call's pivots in the caller's order [n_stars][nf] and in the mg_* copy's [mg_pad][nfp], and 1 / sigma [n_stars][nf]
-struct ResidArena { MomArena m; size_t o_rows, o_piv_in, o_piv_mg, o_isig, bytes; };
-inline ResidArena resid_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t wd_row, size_t n_stars, size_t nf, size_t nfp,
-                              size_t mg_pad, size_t hdr_bytes)
-{
-    ResidArena a{mom_arena(chunk, n_pops, iso_stride, tab_row, wd_row, n_stars, 2 + 2 * nf, hdr_bytes), 0, 0, 0, 0, 0};
-    Carve c;
-    c.take(a.m.bytes);
-    a.o_rows = c.take(8 * chunk * (1 + 5 * nf));
-    a.o_piv_in = c.take(8 * n_stars * nf);
-    a.o_piv_mg = c.take(8 * mg_pad * nfp);
-    a.o_isig = c.take(8 * n_stars * nf);
-    a.bytes = c.total;
-    return a;
-}
-
-// b9_pointwise's chunk of rows: b9_star_moments' leading parts, then v [chunk][n_stars], the rows' inside-the-grid words
-// [chunk], the per-star state [n_stars][n_acc], the chunk's row sums [chunk] and the tail twice: the device's
-// [tail_len][n_stars] and the caller's [n_stars][tail_len] it is transposed from and to
-struct PwArena { size_t o_par, o_hdr, o_iso, o_tab, o_wd, o_scratch, o_flag, o_acc, o_rows, o_tail, o_tail_io, bytes; };
-inline PwArena pw_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t wd_row, size_t n_stars, size_t n_acc, size_t tail_len,
-                        size_t hdr_bytes)
-{
-    Carve c;
-    PwArena a{c.take(8 * B9_NPARAM * chunk), c.take(hdr_bytes * chunk * n_pops), c.take(8 * chunk * n_pops * (size_t)iso_stride), c.take(8 * chunk * tab_row),
-              c.take(8 * chunk * wd_row), c.take(8 * chunk * n_stars), c.take(4 * chunk), c.take(8 * n_stars * n_acc), c.take(8 * chunk),
-              c.take(8 * n_stars * tail_len), c.take(8 * n_stars * tail_len), 0};
-    a.bytes = c.total;
-    return a;
 }
 
 // ---- sizing rules

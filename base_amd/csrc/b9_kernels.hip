@@ -27,11 +27,13 @@
 //                                     one lane per system, predicted apparent magnitudes + stage
 //   k_wd_node_table / k_wd_sample      b9_sample_wd_mass: the WD chain once per node of the call's own grid with its
 //                                     derived values kept, then one lane per WD-stage star against the table
-//   k_star_moments / _wd / k_moments_accumulate   b9_star_moments: exact per-star posterior moments over the marginalisation
+//   k_chain_accumulate               the four reductions over a saved chain below: their shared node walk, star finish and WD
+//                                     steps (b9_chain_walk.hip.h), and the per-star accumulation of a chunk's rows
+//   k_star_moments / _wd              b9_star_moments: exact per-star posterior moments over the marginalisation
 //                                     grid (one lane per star, four waves sharing the node table), summed over the rows
-//   k_star_hist / _wd / k_hist_accumulate / k_hist_rows   b9_mass_hist: exact binned mass posteriors over the same grid (a
+//   k_star_hist / _wd / k_hist_rows   b9_mass_hist: exact binned mass posteriors over the same grid (a
 //                                     per-wave LDS histogram per lane, bins worked in tiles), summed over the rows and the stars
-//   k_star_resid / _wd / k_resid_stage / k_resid_accumulate / k_resid_rows   b9_phot_resid: exact posterior-predictive magnitude
+//   k_star_resid / _wd / k_resid_stage / k_resid_rows   b9_phot_resid: exact posterior-predictive magnitude
 //                                     moments per filter over the same grid, summed over the rows and, standardised, the stars
 //   k_star_lpd / _wd / k_pw_accumulate / k_pw_tail / k_pw_rows   b9_pointwise: every star's marginal log-likelihood per row over
 //                                     the same grid, reduced over the rows (online log-sum-exps, Welford, largest -v) and the stars
@@ -75,6 +77,7 @@ namespace tree_kd5 {
 #include "b9_marg_step.hip.h"
 #include "b9_predict.hip.h"
 #include "b9_wd_sample.hip.h"
+#include "b9_chain_walk.hip.h"
 #include "b9_star_moments.hip.h"
 #include "b9_mass_hist.hip.h"
 #include "b9_phot_resid.hip.h"
@@ -289,6 +292,19 @@ static void launch_marg_wd_table(const DevPack &pk, const IsoHdr *hdr, const dou
                        mass_cap, n_pops, d_params, K, wd_tab, n_walkers * n_pops);
 }
 
+// What the four reductions over a saved chain launch first: the node table of a chunk of rows (k_marg_table, its layout L) into
+// the call's own buffer, with WD-stage stars k_marg_wd_table too, and the pruning width cut2 the star kernels take.
+struct ChainTables { hipError_t err; MargLayout L; double cut2; };
+template <int NFP>
+static ChainTables chain_tables(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                                const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, double *tab, double *wd_tab, hipStream_t stream)
+{
+    const ChainTables t{launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, n_pops, K, Q, tab, stream),
+                        marg_layout(NFP, mass_cap, K, Q), prune ? 2.0 * B9_MARG_CUT : __builtin_inf()};
+    if (t.err == hipSuccess && st.n_wd > 0) launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, n_pops, K, wd_tab, stream);
+    return t;
+}
+
 // ---- b9_star_moments: the node tables of a chunk of rows into the call's own buffers, the stars' increments, the accumulation -----
 hipError_t b9k_star_moments(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
                             const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, double *tab, double *wd_tab,
@@ -297,19 +313,15 @@ hipError_t b9k_star_moments(const DevPack &pk, const DevStars &st, const IsoHdr 
     return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
         if (!tab || !scratch || !acc || n_rows < 1 || n_rows > 65535 || (st.n_wd > 0 && !wd_tab)) return hipErrorInvalidValue;
-        const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
-        const hipError_t e = launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, tab, stream);
-        if (e != hipSuccess) return e;
-        const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
+        const ChainTables t = chain_tables<NFP>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, prune, tab, wd_tab, stream);
+        if (t.err != hipSuccess) return t.err;
         hipLaunchKernelGGL((k_star_moments<NFP, NPOPS>), dim3(st.mg_pad / 64, n_rows), dim3(256), 0, stream, st, hdr, iso_data, iso_stride, mass_cap,
-                           d_params, K, Q, (const double *)tab, L, cut2, scratch);
-        if (st.n_wd > 0) {
-            launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, wd_tab, stream);
+                           d_params, K, Q, (const double *)tab, t.L, t.cut2, scratch);
+        if (st.n_wd > 0)
             hipLaunchKernelGGL((k_star_moments_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, hdr, d_params, K,
                                (const double *)wd_tab, scratch);
-        }
         const long long n_words = (long long)st.n * B9_MOM_N;
-        hipLaunchKernelGGL(k_moments_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
+        hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
         return hipGetLastError();
     });
 }
@@ -326,25 +338,21 @@ hipError_t b9k_mass_hist(const DevPack &pk, const DevStars &st, const IsoHdr *hd
         HistEdges ed{};
         for (int b = 0; b <= n_bins; ++b) ed.e[b] = edges[b];
         ed.n_bins = n_bins; ed.quantity = quantity;
-        const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
-        const hipError_t e = launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, tab, stream);
-        if (e != hipSuccess) return e;
-        const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
+        const ChainTables t = chain_tables<NFP>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, prune, tab, wd_tab, stream);
+        if (t.err != hipSuccess) return t.err;
         // a tile of bins: one histogram [bins][64] per wave
         const int tb = std::min(n_bins, B9_HIST_TILE), n_tiles = (n_bins + B9_HIST_TILE - 1) / B9_HIST_TILE;
         const auto k = with_lds(k_star_hist<NFP, NPOPS>, sizeof(double) * 64 * (NPOPS * 4 + 4 * 2 + 4 * (size_t)tb));   // seeds, states, histograms
         if (k.err != hipSuccess) return k.err;
         hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows, n_tiles), dim3(256), k.lds, stream, st, hdr, iso_data, iso_stride, mass_cap,
-                           d_params, K, Q, (const double *)tab, L, cut2, ed, tb, scratch);
-        if (st.n_wd > 0) {
-            launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, wd_tab, stream);
+                           d_params, K, Q, (const double *)tab, t.L, t.cut2, ed, tb, scratch);
+        if (st.n_wd > 0)
             hipLaunchKernelGGL((k_star_hist_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, hdr, d_params, K,
                                (const double *)wd_tab, ed, scratch);
-        }
         const int ncol = n_bins + 1;
         const long long n_words = (long long)st.n * ncol;
         if (acc)
-            hipLaunchKernelGGL(k_hist_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
+            hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
         if (rows)
             hipLaunchKernelGGL(k_hist_rows, dim3((unsigned)((n_rows * ncol + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, st.n, ncol, rows);
         return hipGetLastError();
@@ -370,22 +378,18 @@ hipError_t b9k_phot_resid(const DevPack &pk, const DevStars &st, const IsoHdr *h
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
         if (!tab || !scratch || !piv_mg || (rows && !isig) || n_rows < 1 || n_rows > 65535 || (st.n_wd > 0 && !wd_tab)) return hipErrorInvalidValue;
         const int nf = pk.nf;
-        const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
-        const hipError_t e = launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, tab, stream);
-        if (e != hipSuccess) return e;
-        const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
+        const ChainTables t = chain_tables<NFP>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, prune, tab, wd_tab, stream);
+        if (t.err != hipSuccess) return t.err;
         const auto k = with_lds(k_star_resid<NFP, NPOPS>, sizeof(double) * 64 * (NPOPS * 4 + 4 * (2 + 2 * (size_t)NFP)));      // seeds, one population's states
         if (k.err != hipSuccess) return k.err;
         hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows), dim3(256), k.lds, stream, st, nf, piv_mg, hdr, iso_data, iso_stride, mass_cap,
-                           d_params, K, Q, (const double *)tab, L, cut2, scratch);
-        if (st.n_wd > 0) {
-            launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, wd_tab, stream);
+                           d_params, K, Q, (const double *)tab, t.L, t.cut2, scratch);
+        if (st.n_wd > 0)
             hipLaunchKernelGGL((k_star_resid_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, nf, pk.m_wd_up, hdr, d_params, K,
                                (const double *)wd_tab, scratch);
-        }
         const long long n_words = (long long)st.n * (2 + 2 * nf);
         if (acc)
-            hipLaunchKernelGGL(k_resid_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
+            hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
         if (rows) {
             const auto kr = with_lds(k_resid_rows, sizeof(double) * 2 * B9_RESID_TILE * (2 + 3 * (size_t)nf));      // two tiles of {x, 1 / sigma}
             if (kr.err != hipSuccess) return kr.err;
@@ -421,17 +425,13 @@ hipError_t b9k_pointwise(const DevPack &pk, const DevStars &st, const IsoHdr *hd
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
         if (!tab || !scratch || !row_in || n_rows < 1 || n_rows > B9_PW_MAX_ROWS || (st.n_wd > 0 && !wd_tab) || (tail && (!acc || tail_len < 1 || tail_len > B9_PW_MAX_TAIL)))
             return hipErrorInvalidValue;
-        const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
-        const hipError_t e = launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, tab, stream);
-        if (e != hipSuccess) return e;
-        const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
+        const ChainTables t = chain_tables<NFP>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, prune, tab, wd_tab, stream);
+        if (t.err != hipSuccess) return t.err;
         hipLaunchKernelGGL((k_star_lpd<NFP, NPOPS>), dim3(st.mg_pad / 64, n_rows), dim3(256), 0, stream, st, hdr, iso_data, iso_stride, mass_cap,
-                           d_params, K, Q, (const double *)tab, L, cut2, scratch, row_in);
-        if (st.n_wd > 0) {
-            launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, wd_tab, stream);
+                           d_params, K, Q, (const double *)tab, t.L, t.cut2, scratch, row_in);
+        if (st.n_wd > 0)
             hipLaunchKernelGGL((k_star_lpd_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, hdr, d_params, K,
                                (const double *)wd_tab, scratch);
-        }
         const unsigned star_wgs = (unsigned)((st.n + 255) / 256);
         if (acc)
             hipLaunchKernelGGL(k_pw_accumulate, dim3(star_wgs), dim3(256), 0, stream, (const double *)scratch, (const int *)row_in, n_rows, st.n, acc);

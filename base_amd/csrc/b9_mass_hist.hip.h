@@ -1,7 +1,6 @@
 // b9_mass_hist.hip.h -- b9_mass_hist (the massFunction counterpart): k_star_hist (MS/RGB-stage stars, one LANE per star),
-// k_star_hist_wd (WD-stage stars, one WAVE per star), k_hist_accumulate (the per-star accumulators) and k_hist_rows (a row's
-// sum over the stars).  Part of the single translation unit b9_kernels.hip (included there, after b9_star_moments.hip.h);
-// gfx950 only.
+// k_star_hist_wd (WD-stage stars, one WAVE per star) and k_hist_rows (a row's sum over the stars).  Part of the single
+// translation unit b9_kernels.hip (included there, after b9_star_moments.hip.h); gfx950 only.
 #pragma once
 
 // ------------------------------------------------------------------------------------------
@@ -9,19 +8,17 @@
 // the weights w = exp(t - logsumexp t) and the membership p are b9_star_moments'; where that call keeps five weighted sums, these
 // kernels keep, for n_bins bins [e_b, e_b+1) of the node value v (primary mass M1, secondary mass (j / Q) M1 of the nodes with
 // j > 0, or the system's M1 + m2), x[b] = p sum_{v in bin b} w and the total column x[n_bins] = p.  They go per (row, star) to
-// a scratch [row][star][n_bins + 1] in the caller's star order; k_hist_accumulate adds the rows to the per-star accumulators
+// a scratch [row][star][n_bins + 1] in the caller's star order; k_chain_accumulate adds the rows to the per-star accumulators
 // in ascending row order and k_hist_rows sums a row over the stars in ascending star order, one plain add each: the same bits
 // for any chunking.  No random numbers, no atomics.
 //
-// k_star_hist: grid (64-star chunk of the mg_* copy, row, bin tile) x 256, k_star_moments' shape: the four waves hold the SAME
-// 64 stars and take the units (16 nodes x one mass ratio) of every 64-node chunk by the diagonal rule; table words are
-// wave-uniform scalar loads through b9_ctab; the seed pass and the box pruning are k_star_moments'.  A node's value and
+// k_star_hist: grid (64-star chunk of the mg_* copy, row, bin tile) x 256, the walk and the pruning of b9_chain_walk.hip.h
+// (walk_nodes calls back for all 64 lanes of a wave that has a live node: the bin search is wave-uniform).  A node's value and
 // therefore its bin are wave-uniform: the bin is kept in scalar registers with its two edges, and searched again (a binary
 // search over the edges in the kernel's arguments) only when a node's value leaves it.  A lane's accumulators live in LDS, one
 // histogram [bins of the tile][64] per wave (a bank per lane pair: conflict-free), S0 and the reference in registers.  The
-// online log-sum-exp is mom_term's: the reference stays while terms lie within 600 e-folds above it; the rare rescale walks
-// the wave's LDS bins.  Per population the four waves' histograms are merged in wave order 0..3 by wave 0 and divided by the
-// merged S0; the populations are mixed with moments_finish's weights and multiplied by p.  A tile holds at most
+// online log-sum-exp is lse_step's; its rare rescale walks the wave's LDS bins.  Per population the four waves' histograms are merged in wave order 0..3 by wave 0 and divided by the
+// merged S0; the populations are mixed with star_finish's weights and multiplied by p.  A tile holds at most
 // B9_HIST_TILE bins (64 KB of LDS); the reference's evolution and the pruning depend on the terms only, never on the bins,
 // so a bin's bits are the same in any tile and among any other bins.
 // ------------------------------------------------------------------------------------------
@@ -55,53 +52,16 @@ __device__ __forceinline__ double uniform_f64(double v)
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
-// one more term t = -X / 2 whose node falls in bin `hb` of the wave's tile (hb < 0: in none of them): mom_term's scheme.
+// one more term t = -X / 2 whose node falls in bin `hb` of the wave's tile (hb < 0: in none of them).
 // h: the lane's column of the wave's LDS histogram, [tb][64].
 __device__ __forceinline__ void hist_term(double t, int hb, int tb, double &ref, double &s0, double *h)
 {
-    const double d = t - ref;
-    double e;
-    if (__ballot(d > 600.0) != 0ull) {
-        const bool up = d > 600.0;
-        const double f = exp_marg(max_vs(up ? -d : d, -700.0));
-        const double scale = up ? f : 1.0;
+    const double e = lse_step(t, ref, [&](double scale) {
         s0 *= scale;
         for (int b = 0; b < tb; ++b) h[b * 64] *= scale;
-        e = up ? 1.0 : f;
-        ref = up ? t : ref;
-    } else {
-        e = exp_marg(max_vs(d, -700.0));
-    }
+    });
     s0 += e;
     if (hb >= 0) h[hb * 64] += e;
-}
-
-// The membership p and the populations' weights wk of a star from its per-population log-sums lg[k] (c0m NOT included; -inf: no
-// live node), as moments_finish forms them.  false: no live node in any population -- the (row, star) contributes nothing.
-template <int NPOPS>
-__device__ __forceinline__ bool hist_finish(const double (&lg)[NPOPS], double c0m, double la, const double *par, double &p, double (&wk)[NPOPS])
-{
-    double a[NPOPS], ll[NPOPS];
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < NPOPS; ++k) {
-        a[k] = lg[k];
-        if (NPOPS == 2) { const double lam = par[B9_P_LAMBDA]; a[k] = (lg[k] == NEG_INF) ? NEG_INF : (k ? log1p(-lam) : log(lam)) + lg[k]; }
-        ll[k] = (lg[k] == NEG_INF) ? NEG_INF : c0m + lg[k];
-        any = any || a[k] != NEG_INF;
-        wk[k] = 0.0;
-    }
-    p = 0.0;
-    if (!any) return false;
-    const StarFinish fin = finish_star<NPOPS>(ll, par, la);
-    p = (fin.l == NEG_INF) ? 0.0 : exp(fin.l - fin.v);
-    wk[0] = 1.0;
-    if (NPOPS == 2) {
-        const double A = logaddexp(a[0], a[NPOPS - 1]);
-#pragma unroll
-        for (int k = 0; k < NPOPS; ++k) wk[k] = (a[k] == NEG_INF) ? 0.0 : exp(a[k] - A);
-    }
-    return true;
 }
 
 template <int NFP, int NPOPS>
@@ -137,88 +97,46 @@ __global__ __launch_bounds__(256) void k_star_hist(DevStars st, const IsoHdr *__
     }
     double *const h_mine = s_hist + (size_t)wave * tb * 64 + lane;
 
-    // ---- the seed pass: this wave's share of every 16th node at mass ratio 0
 #pragma unroll
-    for (int kp = 0; kp < NPOPS; ++kp) {
-        const b9_ctab t_wp = (b9_ctab)(tab + (size_t)(w * NPOPS + kp) * L.total);
-        const int n_units = (((iso[kp].n - 1) * K + 63) >> 6) * 4;
-        double xmin = __builtin_inf();
-        for (int u = wave; u < n_units; u += 4)
-            xmin = __builtin_fmin(xmin, row_x<NFP>(t_wp + L.o_rows + (size_t)u * Q * 16 * NFP, t_wp[L.o_nb + u * 16], so, sw));
-        s_seed[kp][wave][lane] = -0.5 * xmin;
-    }
+    for (int kp = 0; kp < NPOPS; ++kp)
+        s_seed[kp][wave][lane] = walk_seed<NFP>((b9_ctab)(tab + (size_t)(w * NPOPS + kp) * L.total), L, (iso[kp].n - 1) * K, Q, wave, so, sw);
     __syncthreads();
 
     double lg[NPOPS];
 #pragma unroll
     for (int kp = 0; kp < NPOPS; ++kp) {
         const b9_ctab t_wp = (b9_ctab)(tab + (size_t)(w * NPOPS + kp) * L.total);
-        const int n_nodes = (iso[kp].n - 1) * K, n_chunks = (n_nodes + 63) >> 6;
-        // the lower bound every wave starts from, and the lane's running maximum
-        double tmax = __builtin_fmax(__builtin_fmax(s_seed[kp][0][lane], s_seed[kp][1][lane]), __builtin_fmax(s_seed[kp][2][lane], s_seed[kp][3][lane]));
+        double tmax = walk_start(s_seed[kp], lane);
         double ref = tmax, s0 = 0.0;
         for (int b = 0; b < tb; ++b) h_mine[b * 64] = 0.0;
         // the bin the last node fell in, wave-uniform: c_lo <= v < c_hi keeps it (an empty interval to start with)
         double c_lo = __builtin_inf(), c_hi = NEG_INF;
         int c_b = -1;
-        for (int c = 0; c < n_chunks; ++c) {
-            double xcut = dead ? NEG_INF : fma(-2.0, tmax, cut2);                 // a term counts while X < xcut
-            if (__ballot(box_bound64<NFP>(t_wp + L.o_box1 + (size_t)c * 2 * NFP, so, sw) + t_wp[L.o_nbmin64 + c] < xcut) == 0ull) continue;
-            for (int sub = 0; sub < 4; ++sub) {
-                const int u = c * 4 + sub;
-                const double nbm = t_wp[L.o_nbmin16 + u];
-                for (int j = (wave - 2 * sub) & 3; j < Q; j += 4) {
-                    if (__ballot(box_bound64<NFP>(t_wp + L.o_box2 + ((size_t)u * Q + j) * 2 * NFP, so, sw) + nbm < xcut) == 0ull) continue;
-                    const b9_ctab rowp = t_wp + L.o_rows + ((size_t)u * Q + j) * 16 * NFP;
-                    const bool counts = ed.quantity != B9_HQ_SECONDARY || j > 0;
-                    for (int i = 0; i < 16; ++i) {
-                        const int node = u * 16 + i;
-                        const double x = row_x<NFP>(rowp + i * NFP, t_wp[L.o_nb + node], so, sw);
-                        const bool live = x < xcut;
-                        if (__ballot(live) == 0ull) continue;
-                        const double v = uniform_f64(hist_value(ed.quantity, marg_primary(iso[kp].mass, node, n_nodes, K, 0).m1, j, Q));
-                        if (!(v >= c_lo && v < c_hi)) {
-                            c_b = hist_bin(ed, v);
-                            c_lo = c_b >= 0 ? ed.e[c_b] : NEG_INF;
-                            c_hi = c_b < n_bins ? ed.e[c_b + 1] : __builtin_inf();
-                        }
-                        const int hb = (counts && c_b >= b0 && c_b < b0 + tb) ? c_b - b0 : -1;
-                        if (live) {
-                            const double t = -0.5 * x;
-                            hist_term(t, hb, tb, ref, s0, h_mine);
-                            tmax = max_vv(tmax, t);
-                        }
-                    }
-                    xcut = dead ? NEG_INF : fma(-2.0, tmax, cut2);
-                }
+        walk_nodes<NFP>(t_wp, L, (iso[kp].n - 1) * K, Q, wave, dead, cut2, tmax, so, sw, [&](bool live, double x, int node, int j, b9_ctab) {
+            const double v = uniform_f64(hist_value(ed.quantity, marg_primary(iso[kp].mass, node, (iso[kp].n - 1) * K, K, 0).m1, j, Q));
+            if (!(v >= c_lo && v < c_hi)) {
+                c_b = hist_bin(ed, v);
+                c_lo = c_b >= 0 ? ed.e[c_b] : NEG_INF;
+                c_hi = c_b < n_bins ? ed.e[c_b + 1] : __builtin_inf();
             }
-        }
+            const bool counts = ed.quantity != B9_HQ_SECONDARY || j > 0;
+            const int hb = (counts && c_b >= b0 && c_b < b0 + tb) ? c_b - b0 : -1;
+            if (live) hist_term(-0.5 * x, hb, tb, ref, s0, h_mine);
+        });
         s_state[wave][0][lane] = ref;
         s_state[wave][1][lane] = s0;
         __syncthreads();
 
         // ---- wave 0: the four shares merged in wave order.  A population before the last parks its normalised bins in the
-        // output (a lane reads back only what it wrote itself); the last one mixes them with moments_finish's weights
+        // output (a lane reads back only what it wrote itself); the last one mixes them with star_finish's weights
         if (wave == 0 && !dead) {
-            double r = NEG_INF;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) r = (s_state[k][1][lane] > 0.0 && s_state[k][0][lane] > r) ? s_state[k][0][lane] : r;
-            double f[4], S0 = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                f[k] = s_state[k][1][lane] > 0.0 ? exp_fast(s_state[k][0][lane] - r) : 0.0;
-                if (s_state[k][1][lane] > 0.0) S0 += s_state[k][1][lane] * f[k];
-            }
-            lg[kp] = (S0 > 0.0) ? r + log(S0) : NEG_INF;
+            const WaveMerge mg = wave_merge(s_state, lane);
+            lg[kp] = (mg.S0 > 0.0) ? mg.r + log(mg.S0) : NEG_INF;
             double p = 0.0, wk[NPOPS];
             bool any = false;
-            if (kp == NPOPS - 1) any = hist_finish<NPOPS>(lg, st.mg_c0m[slot], st.mg_la[slot], par, p, wk);
+            if (kp == NPOPS - 1) any = star_finish<NPOPS>(lg, st.mg_c0m[slot], st.mg_la[slot], par, p, wk);
             for (int b = 0; b < tb; ++b) {
-                double H = 0.0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (s_state[k][1][lane] > 0.0) H += s_hist[((size_t)k * tb + b) * 64 + lane] * f[k];
-                const double hn = (S0 > 0.0) ? H / S0 : 0.0;
+                const double hn = (mg.S0 > 0.0) ? wave_sum(mg, s_hist + (size_t)b * 64 + lane, (size_t)tb * 64) / mg.S0 : 0.0;
                 if (kp < NPOPS - 1) { out[b0 + b] = hn; continue; }
                 double m = wk[NPOPS - 1] * hn;
                 if (NPOPS == 2) m = wk[0] * out[b0 + b] + m;
@@ -231,69 +149,43 @@ __global__ __launch_bounds__(256) void k_star_hist(DevStars st, const IsoHdr *__
 }
 
 // ------------------------------------------------------------------------------------------
-// k_star_hist_wd: the WD-stage stars, one wavefront per (row, star) as in k_star_moments_wd: lanes stride over the 8 K steps
-// m_j = tip + dM j (j = 1 .. 8 K) of k_marg_wd_table's rows, mass ratio 0.  Here the bin is per lane.  Per population: L first
-// (an online log-sum-exp per lane, merged by the wave's shuffle tree and broadcast), then every step's w = exp(t - L) goes to
-// the lane that owns its bin -- lane b holds bin b -- in ascending step order: a block of 64 steps at a time, the block's lanes
-// read out one after the other.  The order depends on the layout only.  B9_HQ_SECONDARY: no node counts, the total still does.
-// Grid: (ceil(n_wd / 4), rows) x 256.
+// k_star_hist_wd: the WD-stage stars (b9_chain_walk.hip.h).  Here the bin is per lane.  Per population: L first (an online
+// log-sum-exp per lane, merged by the wave's shuffle tree and broadcast), then every step's w = exp(t - L) goes to the lane that
+// owns its bin -- lane b holds bin b -- in ascending step order: a block of 64 steps at a time, the block's lanes read out one
+// after the other.  The order depends on the layout only.  B9_HQ_SECONDARY: no node counts, the total still does.
 // ------------------------------------------------------------------------------------------
 template <int NFP, int NPOPS>
 __global__ __launch_bounds__(256) void k_star_hist_wd(DevStars st, double m_wd_up, const IsoHdr *__restrict__ hdr, const double *__restrict__ params,
                                                       int K, const double *__restrict__ wtab, HistEdges ed, double *__restrict__ scratch)
 {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int k_wd = blockIdx.x * 4 + wave, w = blockIdx.y, n_wp = gridDim.y * NPOPS, steps = 8 * K;
+    const int k_wd = blockIdx.x * 4 + wave, w = blockIdx.y, n_wp = gridDim.y * NPOPS;
     const int n_bins = ed.n_bins, ncol = n_bins + 1;
     if (k_wd >= st.n_wd) return;
-    const int slot = st.wd_slot[k_wd], orig = st.perm[slot];
-    double obs[NFP], wgt[NFP];
-#pragma unroll
-    for (int f = 0; f < NFP; ++f) { obs[f] = st.obs[B9_SIDX(NFP, f, slot)]; wgt[f] = st.w[B9_SIDX(NFP, f, slot)]; }
-    const int wd_type = st.flags[slot] & 1;
-    const double *par = params + (size_t)w * B9_NPARAM;
-    double *__restrict__ const out = scratch + ((size_t)w * st.n + orig) * ncol;
-    bool valid = true;
-#pragma unroll
-    for (int kp = 0; kp < NPOPS; ++kp) valid = valid && hdr[w * NPOPS + kp].valid;
-    if (!valid) {
+    const WdStar<NFP> ws = wd_star<NFP, NPOPS>(st, hdr, params, k_wd, w);
+    double *__restrict__ const out = scratch + ((size_t)w * st.n + ws.orig) * ncol;
+    if (!ws.valid) {
         for (int c = lane; c < ncol; c += 64) out[c] = 0.0;
         return;
     }
     double lg[NPOPS], hk[NPOPS];                         // hk: the lane's bin under population k, normalised
 #pragma unroll
     for (int kp = 0; kp < NPOPS; ++kp) {
-        const int wp = w * NPOPS + kp;
-        const double tip = hdr[wp].agb_tip, dM = (m_wd_up - tip) / steps;
-        const double log_w = dM > 0.0 ? log(dM) : 0.0;
-        const double *__restrict__ const rows = wtab + (((size_t)wp * 2 + wd_type) * steps) * NFP;      // k_marg_wd_table's
-        const double *__restrict__ const lpm = wtab + (size_t)n_wp * 2 * steps * NFP + (size_t)wp * steps;
-        auto term_of = [&](int j) -> double {            // -inf: the step does not take part
-            if (!(dM > 0.0) || j > steps) return NEG_INF;
-            const double *__restrict__ const r = rows + (size_t)(j - 1) * NFP;
-            double chi2 = 0.0;
-#pragma unroll
-            for (int f = 0; f < NFP; ++f) { const double d = r[f] - obs[f]; chi2 = fma(wgt[f] * d, d, chi2); }
-            return isfinite(chi2) ? (lpm[j - 1] - 0.5 * chi2) + log_w : NEG_INF;
-        };
+        const WdSteps<NFP> sp = wd_steps<NFP>(ws, m_wd_up, hdr, K, wtab, w * NPOPS + kp, n_wp);
         Lse acc; acc.mx = NEG_INF; acc.sm = 0.0;
-        for (int j = 1 + lane; j <= steps; j += 64) lse_add(acc, term_of(j));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            Lse b; b.mx = __shfl_down(acc.mx, o, 64); b.sm = __shfl_down(acc.sm, o, 64);
-            acc = lse_merge(acc, b);
-        }
+        for (int j = 1 + lane; j <= sp.steps; j += 64) lse_add(acc, sp.term(ws, j));
+        acc = lse_wave(acc);
         acc.mx = __shfl(acc.mx, 0, 64); acc.sm = __shfl(acc.sm, 0, 64);
         const bool has = acc.mx != NEG_INF;
         const double Lk = has ? acc.mx + log(acc.sm) : NEG_INF;
         lg[kp] = Lk;
         double h = 0.0;
         if (has && ed.quantity != B9_HQ_SECONDARY) {
-            for (int jb = 0; jb < steps; jb += 64) {
+            for (int jb = 0; jb < sp.steps; jb += 64) {
                 const int j = jb + 1 + lane;
-                const double t = term_of(j);
+                const double t = sp.term(ws, j);
                 const double wj = t == NEG_INF ? 0.0 : exp(t - Lk);
-                const int bj = t == NEG_INF ? -1 : hist_bin(ed, tip + dM * j);
+                const int bj = t == NEG_INF ? -1 : hist_bin(ed, sp.m1(j));
                 for (int l = 0; l < 64; ++l) {
                     const double wl = __shfl(wj, l, 64);
                     const int bl = __shfl(bj, l, 64);
@@ -304,21 +196,11 @@ __global__ __launch_bounds__(256) void k_star_hist_wd(DevStars st, double m_wd_u
         hk[kp] = h;
     }
     double p, wk[NPOPS];
-    const bool any = hist_finish<NPOPS>(lg, st.c0m[slot], st.la[slot], par, p, wk);
+    const bool any = star_finish<NPOPS>(lg, st.c0m[ws.slot], st.la[ws.slot], ws.par, p, wk);
     double m = wk[0] * hk[0];
     if (NPOPS == 2) m = m + wk[NPOPS - 1] * hk[NPOPS - 1];
     if (lane < n_bins) out[lane] = any ? p * m : 0.0;
     if (lane == 0) out[n_bins] = any ? p : 0.0;
-}
-
-// k_hist_accumulate: one lane per (star, column): acc += x_r for the chunk's rows r in ascending order, one plain add each
-__global__ __launch_bounds__(256) void k_hist_accumulate(const double *__restrict__ scratch, int n_rows, long long n_words, double *__restrict__ acc)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_words) return;
-    double a = acc[i];
-    for (int r = 0; r < n_rows; ++r) a = a + scratch[(size_t)r * n_words + i];
-    acc[i] = a;
 }
 
 // k_hist_rows: one lane per (row, column): the row's increments summed over the stars in ascending (the caller's) order, one plain

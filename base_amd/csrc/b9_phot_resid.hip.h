@@ -1,7 +1,7 @@
 // b9_phot_resid.hip.h -- b9_phot_resid (the photResiduals counterpart): k_resid_stage (the call's pivots in the mg_* order),
-// k_star_resid (MS/RGB-stage stars, one LANE per star), k_star_resid_wd (WD-stage stars, one WAVE per star), k_resid_accumulate
-// (the per-star accumulators) and k_resid_rows (a row's sums over the stars).  Part of the single translation unit
-// b9_kernels.hip (included there, after b9_mass_hist.hip.h); gfx950 only.
+// k_star_resid (MS/RGB-stage stars, one LANE per star), k_star_resid_wd (WD-stage stars, one WAVE per star) and k_resid_rows (a
+// row's sums over the stars).  Part of the single translation unit b9_kernels.hip (included there, after b9_mass_hist.hip.h);
+// gfx950 only.
 #pragma once
 
 // ------------------------------------------------------------------------------------------
@@ -10,16 +10,13 @@
 // moments of the node's masses, these kernels keep the moments of the node's MAGNITUDES about a per-star pivot c_f (the caller's
 // obs_f where sigma_f > 0, else 0):  d_f = pred_f - c_f, one rounded subtraction of the node table's row word, and
 //     x = {1, p, p sum w d_0, p sum w d_0^2, ..., p sum w d_(nf-1), p sum w d_(nf-1)^2}          (2 + 2 nf columns)
-// per (row, star) in a scratch [row][star][2 + 2 nf] in the caller's star order; k_resid_accumulate adds the rows to the per-star
+// per (row, star) in a scratch [row][star][2 + 2 nf] in the caller's star order; k_chain_accumulate adds the rows to the per-star
 // accumulators in ascending row order and k_resid_rows sums a row over the stars in ascending star order, one plain add each:
 // the same bits for any chunking.  No random numbers, no atomics.
 //
-// k_star_resid: grid (64-star chunk of the mg_* copy, row) x 256, k_star_moments' shape: the four waves hold the SAME 64 stars
-// and take the units (16 nodes x one mass ratio) of every 64-node chunk by the diagonal rule; table words are wave-uniform
-// scalar loads through b9_ctab; the seed pass and the box pruning are k_star_moments'.  Per population a lane keeps an online
-// log-sum-exp reference, S0 and 2 NFP weighted sums in registers (mom_term's scheme: the reference stays while terms lie within
-// 600 e-folds above it; the rare jump rescales all of them).  Which terms enter, and how the reference moves, depends on the
-// terms alone.
+// k_star_resid: grid (64-star chunk of the mg_* copy, row) x 256, the walk and the pruning of b9_chain_walk.hip.h.  Per population
+// a lane keeps an online log-sum-exp reference, S0 and 2 NFP weighted sums in registers (lse_step: the rare jump of the
+// reference rescales all of them).  Which terms enter, and how the reference moves, depends on the terms alone.
 //
 // LDS.  A population's four wave states are [4][2 + 2 NFP][64] doubles: 68 KB at 16 filters, so two populations' states do not
 // fit a static block.  Of the two possible forms (a population at a time through one reused block; filters tiled across
@@ -42,24 +39,15 @@ __global__ __launch_bounds__(256) void k_resid_stage(DevStars st, int nf, const 
     piv_mg[B9_SIDX(NFP, f, slot)] = (orig >= 0 && f < nf) ? piv_in[(size_t)orig * nf + f] : 0.0;
 }
 
-// one more term t = -X / 2 of a node whose row (NFP magnitudes) is wave-uniform: mom_term's scheme.
+// one more term t = -X / 2 of a node whose row (NFP magnitudes) is wave-uniform.
 // s: {S0, then per filter the sums weighted by d and d^2}
 template <int NFP>
 __device__ __forceinline__ void resid_term(double t, b9_ctab row, const double (&piv)[NFP], double &ref, double (&s)[1 + 2 * NFP])
 {
-    const double dt = t - ref;
-    double e;
-    if (__ballot(dt > 600.0) != 0ull) {
-        const bool up = dt > 600.0;
-        const double f = exp_marg(max_vs(up ? -dt : dt, -700.0));
-        const double scale = up ? f : 1.0;
+    const double e = lse_step(t, ref, [&](double scale) {
 #pragma unroll
         for (int c = 0; c < 1 + 2 * NFP; ++c) s[c] *= scale;
-        e = up ? 1.0 : f;
-        ref = up ? t : ref;
-    } else {
-        e = exp_marg(max_vs(dt, -700.0));
-    }
+    });
     s[0] += e;
 #pragma unroll
     for (int f = 0; f < NFP; ++f) {
@@ -99,78 +87,37 @@ __global__ __launch_bounds__(256) void k_star_resid(DevStars st, int nf, const d
         return;
     }
 
-    // ---- the seed pass: this wave's share of every 16th node at mass ratio 0
 #pragma unroll
-    for (int kp = 0; kp < NPOPS; ++kp) {
-        const b9_ctab t_wp = (b9_ctab)(tab + (size_t)(w * NPOPS + kp) * L.total);
-        const int n_units = (((iso[kp].n - 1) * K + 63) >> 6) * 4;
-        double xmin = __builtin_inf();
-        for (int u = wave; u < n_units; u += 4)
-            xmin = __builtin_fmin(xmin, row_x<NFP>(t_wp + L.o_rows + (size_t)u * Q * 16 * NFP, t_wp[L.o_nb + u * 16], so, sw));
-        s_seed[kp][wave][lane] = -0.5 * xmin;
-    }
+    for (int kp = 0; kp < NPOPS; ++kp)
+        s_seed[kp][wave][lane] = walk_seed<NFP>((b9_ctab)(tab + (size_t)(w * NPOPS + kp) * L.total), L, (iso[kp].n - 1) * K, Q, wave, so, sw);
     __syncthreads();
 
     double lg[NPOPS];
 #pragma unroll
     for (int kp = 0; kp < NPOPS; ++kp) {
         const b9_ctab t_wp = (b9_ctab)(tab + (size_t)(w * NPOPS + kp) * L.total);
-        const int n_nodes = (iso[kp].n - 1) * K, n_chunks = (n_nodes + 63) >> 6;
-        // the lower bound every wave starts from, and the lane's running maximum
-        double tmax = __builtin_fmax(__builtin_fmax(s_seed[kp][0][lane], s_seed[kp][1][lane]), __builtin_fmax(s_seed[kp][2][lane], s_seed[kp][3][lane]));
+        double tmax = walk_start(s_seed[kp], lane);
         double ref = tmax, s[NS];
 #pragma unroll
         for (int c = 0; c < NS; ++c) s[c] = 0.0;
-        for (int c = 0; c < n_chunks; ++c) {
-            double xcut = dead ? NEG_INF : fma(-2.0, tmax, cut2);                 // a term counts while X < xcut
-            if (__ballot(box_bound64<NFP>(t_wp + L.o_box1 + (size_t)c * 2 * NFP, so, sw) + t_wp[L.o_nbmin64 + c] < xcut) == 0ull) continue;
-            for (int sub = 0; sub < 4; ++sub) {
-                const int u = c * 4 + sub;
-                const double nbm = t_wp[L.o_nbmin16 + u];
-                for (int j = (wave - 2 * sub) & 3; j < Q; j += 4) {
-                    if (__ballot(box_bound64<NFP>(t_wp + L.o_box2 + ((size_t)u * Q + j) * 2 * NFP, so, sw) + nbm < xcut) == 0ull) continue;
-                    const b9_ctab rowp = t_wp + L.o_rows + ((size_t)u * Q + j) * 16 * NFP;
-                    for (int i = 0; i < 16; ++i) {
-                        const double x = row_x<NFP>(rowp + i * NFP, t_wp[L.o_nb + u * 16 + i], so, sw);
-                        const bool live = x < xcut;
-                        if (__ballot(live) == 0ull) continue;
-                        if (live) {
-                            const double t = -0.5 * x;
-                            resid_term<NFP>(t, rowp + i * NFP, piv, ref, s);
-                            tmax = max_vv(tmax, t);
-                        }
-                    }
-                    xcut = dead ? NEG_INF : fma(-2.0, tmax, cut2);
-                }
-            }
-        }
+        walk_nodes<NFP>(t_wp, L, (iso[kp].n - 1) * K, Q, wave, dead, cut2, tmax, so, sw, [&](bool live, double x, int, int, b9_ctab row) {
+            if (live) resid_term<NFP>(-0.5 * x, row, piv, ref, s);
+        });
         s_state[wave][0][lane] = ref;
 #pragma unroll
         for (int c = 0; c < NS; ++c) s_state[wave][1 + c][lane] = s[c];
         __syncthreads();
 
         // ---- wave 0: the four shares merged in wave order.  A population before the last parks its normalised sums in the
-        // output's columns 2.. (a lane reads back only what it wrote itself); the last one mixes them with moments_finish's weights
+        // output's columns 2.. (a lane reads back only what it wrote itself); the last one mixes them with star_finish's weights
         if (wave == 0 && !dead) {
-            double r = NEG_INF;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) r = (s_state[k][1][lane] > 0.0 && s_state[k][0][lane] > r) ? s_state[k][0][lane] : r;
-            double f[4], S0 = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                f[k] = s_state[k][1][lane] > 0.0 ? exp_fast(s_state[k][0][lane] - r) : 0.0;
-                if (s_state[k][1][lane] > 0.0) S0 += s_state[k][1][lane] * f[k];
-            }
-            lg[kp] = (S0 > 0.0) ? r + log(S0) : NEG_INF;
+            const WaveMerge mg = wave_merge(s_state, lane);
+            lg[kp] = (mg.S0 > 0.0) ? mg.r + log(mg.S0) : NEG_INF;
             double p = 0.0, wk[NPOPS];
             bool any = false;
-            if (kp == NPOPS - 1) any = hist_finish<NPOPS>(lg, st.mg_c0m[slot], st.mg_la[slot], par, p, wk);
+            if (kp == NPOPS - 1) any = star_finish<NPOPS>(lg, st.mg_c0m[slot], st.mg_la[slot], par, p, wk);
             for (int c = 0; c < 2 * nf; ++c) {
-                double M = 0.0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (s_state[k][1][lane] > 0.0) M += s_state[k][2 + c][lane] * f[k];
-                const double mn = (S0 > 0.0) ? M / S0 : 0.0;
+                const double mn = (mg.S0 > 0.0) ? wave_sum(mg, &s_state[0][2 + c][lane], (1 + NS) * 64) / mg.S0 : 0.0;
                 if (kp < NPOPS - 1) { out[2 + c] = mn; continue; }
                 double m = wk[NPOPS - 1] * mn;
                 if (NPOPS == 2) m = wk[0] * out[2 + c] + m;
@@ -183,30 +130,10 @@ __global__ __launch_bounds__(256) void k_star_resid(DevStars st, int nf, const d
 }
 
 // ------------------------------------------------------------------------------------------
-// k_star_resid_wd: the WD-stage stars, one wavefront per (row, star) as in k_star_moments_wd: lanes stride over the 8 K steps
-// m_j = tip + dM j (j = 1 .. 8 K) of k_marg_wd_table's rows (the star's own wd_type), mass ratio 0.  Per lane an online
-// log-sum-exp with S0 and the 2 NFP weighted sums; the lanes' states are merged by the wave's shuffle tree (a fixed order).  The
-// pivot is the slot-order copy's obs word: the caller's bits where sigma > 0, 0 for an unused filter.
-// Grid: (ceil(n_wd / 4), rows) x 256.
+// k_star_resid_wd: the WD-stage stars (b9_chain_walk.hip.h).  Per lane an online log-sum-exp with S0 and the 2 NFP weighted sums;
+// the lanes' states are merged by the wave's shuffle tree (a fixed order).  The pivot is the slot-order copy's obs word: the
+// caller's bits where sigma > 0, 0 for an unused filter.
 // ------------------------------------------------------------------------------------------
-template <int NS>
-__device__ __forceinline__ void lser_merge(double &amx, double (&as)[NS], double bmx, const double (&bs)[NS])
-{
-    if (bmx == NEG_INF) return;
-    if (amx == NEG_INF) {
-        amx = bmx;
-#pragma unroll
-        for (int c = 0; c < NS; ++c) as[c] = bs[c];
-        return;
-    }
-    const bool a_hi = amx >= bmx;
-    const double f = exp_fast(a_hi ? bmx - amx : amx - bmx);
-    const double fa = a_hi ? 1.0 : f, fb = a_hi ? f : 1.0;
-    amx = a_hi ? amx : bmx;
-#pragma unroll
-    for (int c = 0; c < NS; ++c) as[c] = as[c] * fa + bs[c] * fb;
-}
-
 template <int NFP, int NPOPS>
 __global__ __launch_bounds__(256) void k_star_resid_wd(DevStars st, int nf, double m_wd_up, const IsoHdr *__restrict__ hdr,
                                                        const double *__restrict__ params, int K, const double *__restrict__ wtab,
@@ -214,19 +141,11 @@ __global__ __launch_bounds__(256) void k_star_resid_wd(DevStars st, int nf, doub
 {
     constexpr int NS = 1 + 2 * NFP;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int k_wd = blockIdx.x * 4 + wave, w = blockIdx.y, n_wp = gridDim.y * NPOPS, steps = 8 * K, ncol = 2 + 2 * nf;
+    const int k_wd = blockIdx.x * 4 + wave, w = blockIdx.y, n_wp = gridDim.y * NPOPS, ncol = 2 + 2 * nf;
     if (k_wd >= st.n_wd) return;
-    const int slot = st.wd_slot[k_wd], orig = st.perm[slot];
-    double obs[NFP], wgt[NFP];
-#pragma unroll
-    for (int f = 0; f < NFP; ++f) { obs[f] = st.obs[B9_SIDX(NFP, f, slot)]; wgt[f] = st.w[B9_SIDX(NFP, f, slot)]; }
-    const int wd_type = st.flags[slot] & 1;
-    const double *par = params + (size_t)w * B9_NPARAM;
-    double *__restrict__ const out = scratch + ((size_t)w * st.n + orig) * ncol;
-    bool valid = true;
-#pragma unroll
-    for (int kp = 0; kp < NPOPS; ++kp) valid = valid && hdr[w * NPOPS + kp].valid;
-    if (!valid) {
+    const WdStar<NFP> ws = wd_star<NFP, NPOPS>(st, hdr, params, k_wd, w);
+    double *__restrict__ const out = scratch + ((size_t)w * st.n + ws.orig) * ncol;
+    if (!ws.valid) {
         for (int c = lane; c < ncol; c += 64) out[c] = 0.0;
         return;
     }
@@ -234,22 +153,18 @@ __global__ __launch_bounds__(256) void k_star_resid_wd(DevStars st, int nf, doub
     double lg[NPOPS], s[NS];
 #pragma unroll
     for (int kp = 0; kp < NPOPS; ++kp) {
-        const int wp = w * NPOPS + kp;
-        const double tip = hdr[wp].agb_tip, dM = (m_wd_up - tip) / steps;
+        const WdSteps<NFP> sp = wd_steps<NFP>(ws, m_wd_up, hdr, K, wtab, w * NPOPS + kp, n_wp);
         double mx = NEG_INF;
 #pragma unroll
         for (int c = 0; c < NS; ++c) s[c] = 0.0;
-        if (dM > 0.0) {
-            const double log_w = log(dM);
-            const double *__restrict__ const rows = wtab + (((size_t)wp * 2 + wd_type) * steps) * NFP;      // k_marg_wd_table's
-            const double *__restrict__ const lpm = wtab + (size_t)n_wp * 2 * steps * NFP + (size_t)wp * steps;
-            for (int j = 1 + lane; j <= steps; j += 64) {
-                const double *__restrict__ const r = rows + (size_t)(j - 1) * NFP;
+        if (sp.on) {
+            for (int j = 1 + lane; j <= sp.steps; j += 64) {
+                const double *__restrict__ const r = sp.rows + (size_t)(j - 1) * NFP;
                 double d[NFP], chi2 = 0.0;
 #pragma unroll
-                for (int f = 0; f < NFP; ++f) { d[f] = r[f] - obs[f]; chi2 = fma(wgt[f] * d[f], d[f], chi2); }
+                for (int f = 0; f < NFP; ++f) { d[f] = r[f] - ws.obs[f]; chi2 = fma(ws.wgt[f] * d[f], d[f], chi2); }
                 if (isfinite(chi2)) {
-                    const double term = (lpm[j - 1] - 0.5 * chi2) + log_w;
+                    const double term = (sp.lpm[j - 1] - 0.5 * chi2) + sp.log_w;
                     if (term == NEG_INF) continue;
                     double b[NS];
                     b[0] = 1.0;
@@ -279,7 +194,7 @@ __global__ __launch_bounds__(256) void k_star_resid_wd(DevStars st, int nf, doub
     }
     if (lane != 0) return;
     double p, wk[NPOPS];
-    const bool any = hist_finish<NPOPS>(lg, st.c0m[slot], st.la[slot], par, p, wk);
+    const bool any = star_finish<NPOPS>(lg, st.c0m[ws.slot], st.la[ws.slot], ws.par, p, wk);
 #pragma unroll
     for (int c = 0; c < 2 * NFP; ++c)
         if (c < 2 * nf) {
@@ -288,16 +203,6 @@ __global__ __launch_bounds__(256) void k_star_resid_wd(DevStars st, int nf, doub
             out[2 + c] = any ? p * m : 0.0;
         }
     out[0] = any ? 1.0 : 0.0; out[1] = any ? p : 0.0;
-}
-
-// k_resid_accumulate: one lane per (star, column): acc += x_r for the chunk's rows r in ascending order, one plain add each
-__global__ __launch_bounds__(256) void k_resid_accumulate(const double *__restrict__ scratch, int n_rows, long long n_words, double *__restrict__ acc)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_words) return;
-    double a = acc[i];
-    for (int r = 0; r < n_rows; ++r) a = a + scratch[(size_t)r * n_words + i];
-    acc[i] = a;
 }
 
 // k_resid_rows: a row's sums over the stars in ascending (the caller's) order, one plain add each, formed from the scratch values

@@ -15,13 +15,13 @@
 // order: k_pw_accumulate the rows of a star ascending, k_pw_rows the stars of a row ascending; k_pw_tail keeps a function of
 // the multiset of a star's values.  No random numbers, no atomics.
 //
-// k_star_lpd: k_star_moments' frame -- grid (64-star chunk of the mg_* copy, row) x 256, the seed pass, the diagonal unit
-// dealing (2 sub + j) mod 4, b9_ctab scalar loads, box pruning against the seeded lower bound, the merge through LDS in wave
-// order by wave 0 -- with a lane's state cut down to the log-sum-exp pair (ref, S0) per population: no weighted sums, no
-// marg_primary call in the row loop.
+// k_star_lpd: k_star_moments' frame -- grid (64-star chunk of the mg_* copy, row) x 256, the walk and the pruning of
+// b9_chain_walk.hip.h, the merge through LDS in wave order by wave 0 -- with a lane's state cut down to the log-sum-exp pair
+// (ref, S0) per population: no weighted sums, no marg_primary call in the row loop.
 // ------------------------------------------------------------------------------------------
 
-// one more term t = -X / 2: mom_term's scheme on S0 alone (reference fixed while terms stay within 600 e-folds above it)
+// one more term t = -X / 2: lse_step's scheme on S0 alone, written out: at a jump of the reference fma(s0, f, 1.0) rounds once
+// where lse_step's rescale-then-add rounds twice
 __device__ __forceinline__ void lpd_term(double t, double &ref, double &s0)
 {
     const double d = t - ref;
@@ -57,48 +57,19 @@ __global__ __launch_bounds__(256) void k_star_lpd(DevStars st, const IsoHdr *__r
     if (sc == 0 && threadIdx.x == 0) row_in[w] = valid ? 1 : 0;
     if (!valid) return;                                  // a row outside the grid: flagged, no value written
 
-    // ---- the seed pass: this wave's share of every 16th node at mass ratio 0
 #pragma unroll
-    for (int kp = 0; kp < NPOPS; ++kp) {
-        const b9_ctab t_wp = (b9_ctab)(tab + (size_t)(w * NPOPS + kp) * L.total);
-        const int n_units = (((iso[kp].n - 1) * K + 63) >> 6) * 4;
-        double xmin = __builtin_inf();
-        for (int u = wave; u < n_units; u += 4)
-            xmin = __builtin_fmin(xmin, row_x<NFP>(t_wp + L.o_rows + (size_t)u * Q * 16 * NFP, t_wp[L.o_nb + u * 16], so, sw));
-        s_seed[kp][wave][lane] = -0.5 * xmin;
-    }
+    for (int kp = 0; kp < NPOPS; ++kp)
+        s_seed[kp][wave][lane] = walk_seed<NFP>((b9_ctab)(tab + (size_t)(w * NPOPS + kp) * L.total), L, (iso[kp].n - 1) * K, Q, wave, so, sw);
     __syncthreads();
 
 #pragma unroll
     for (int kp = 0; kp < NPOPS; ++kp) {
         const b9_ctab t_wp = (b9_ctab)(tab + (size_t)(w * NPOPS + kp) * L.total);
-        const int n_nodes = (iso[kp].n - 1) * K, n_chunks = (n_nodes + 63) >> 6;
-        // the lower bound every wave starts from, and the lane's running maximum
-        double tmax = __builtin_fmax(__builtin_fmax(s_seed[kp][0][lane], s_seed[kp][1][lane]), __builtin_fmax(s_seed[kp][2][lane], s_seed[kp][3][lane]));
+        double tmax = walk_start(s_seed[kp], lane);
         double ref = tmax, s0 = 0.0;
-        for (int c = 0; c < n_chunks; ++c) {
-            double xcut = dead ? NEG_INF : fma(-2.0, tmax, cut2);                 // a term counts while X < xcut
-            if (__ballot(box_bound64<NFP>(t_wp + L.o_box1 + (size_t)c * 2 * NFP, so, sw) + t_wp[L.o_nbmin64 + c] < xcut) == 0ull) continue;
-            for (int sub = 0; sub < 4; ++sub) {
-                const int u = c * 4 + sub;
-                const double nbm = t_wp[L.o_nbmin16 + u];
-                for (int j = (wave - 2 * sub) & 3; j < Q; j += 4) {
-                    if (__ballot(box_bound64<NFP>(t_wp + L.o_box2 + ((size_t)u * Q + j) * 2 * NFP, so, sw) + nbm < xcut) == 0ull) continue;
-                    const b9_ctab rowp = t_wp + L.o_rows + ((size_t)u * Q + j) * 16 * NFP;
-                    for (int i = 0; i < 16; ++i) {
-                        const double x = row_x<NFP>(rowp + i * NFP, t_wp[L.o_nb + u * 16 + i], so, sw);
-                        const bool live = x < xcut;
-                        if (__ballot(live) == 0ull) continue;
-                        if (live) {
-                            const double t = -0.5 * x;
-                            lpd_term(t, ref, s0);
-                            tmax = max_vv(tmax, t);
-                        }
-                    }
-                    xcut = dead ? NEG_INF : fma(-2.0, tmax, cut2);
-                }
-            }
-        }
+        walk_nodes<NFP>(t_wp, L, (iso[kp].n - 1) * K, Q, wave, dead, cut2, tmax, so, sw, [&](bool live, double x, int, int, b9_ctab) {
+            if (live) lpd_term(-0.5 * x, ref, s0);
+        });
         s_state[kp][wave][0][lane] = ref;
         s_state[kp][wave][1][lane] = s0;
     }
@@ -110,67 +81,44 @@ __global__ __launch_bounds__(256) void k_star_lpd(DevStars st, const IsoHdr *__r
     double ll[NPOPS];
 #pragma unroll
     for (int kp = 0; kp < NPOPS; ++kp) {
-        double r = NEG_INF;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r = (s_state[kp][k][1][lane] > 0.0 && s_state[kp][k][0][lane] > r) ? s_state[kp][k][0][lane] : r;
-        double S = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (s_state[kp][k][1][lane] > 0.0) S += s_state[kp][k][1][lane] * exp_fast(s_state[kp][k][0][lane] - r);
-        ll[kp] = (S > 0.0) ? c0m + (r + log(S)) : NEG_INF;
+        const WaveMerge m = wave_merge(s_state[kp], lane);
+        ll[kp] = (m.S0 > 0.0) ? c0m + (m.r + log(m.S0)) : NEG_INF;
     }
     scratch[(size_t)w * st.n + orig] = finish_star<NPOPS>(ll, par, st.mg_la[slot]).v;
 }
 
 // ------------------------------------------------------------------------------------------
-// k_star_lpd_wd: the WD-stage stars, one wavefront per (row, star) as in k_star_moments_wd: lanes stride over the 8 K steps
-// of k_marg_wd_table's rows with a per-lane online log-sum-exp pair, merged by the wave's shuffle tree (a fixed order).
-// Grid: (ceil(n_wd / 4), rows) x 256.
+// k_star_lpd_wd: the WD-stage stars (b9_chain_walk.hip.h) with a per-lane online log-sum-exp pair, merged by the wave's shuffle
+// tree (a fixed order).
 // ------------------------------------------------------------------------------------------
 template <int NFP, int NPOPS>
 __global__ __launch_bounds__(256) void k_star_lpd_wd(DevStars st, double m_wd_up, const IsoHdr *__restrict__ hdr, const double *__restrict__ params,
                                                      int K, const double *__restrict__ wtab, double *__restrict__ scratch)
 {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int k_wd = blockIdx.x * 4 + wave, w = blockIdx.y, n_wp = gridDim.y * NPOPS, steps = 8 * K;
+    const int k_wd = blockIdx.x * 4 + wave, w = blockIdx.y, n_wp = gridDim.y * NPOPS;
     if (k_wd >= st.n_wd) return;
-    const int slot = st.wd_slot[k_wd], orig = st.perm[slot];
-    double obs[NFP], wgt[NFP];
-#pragma unroll
-    for (int f = 0; f < NFP; ++f) { obs[f] = st.obs[B9_SIDX(NFP, f, slot)]; wgt[f] = st.w[B9_SIDX(NFP, f, slot)]; }
-    const int wd_type = st.flags[slot] & 1;
-    const double *par = params + (size_t)w * B9_NPARAM;
-    bool valid = true;
-#pragma unroll
-    for (int kp = 0; kp < NPOPS; ++kp) valid = valid && hdr[w * NPOPS + kp].valid;
-    if (!valid) return;                                  // (k_star_lpd has flagged the row)
-    const double c0m = st.c0m[slot];
+    const WdStar<NFP> ws = wd_star<NFP, NPOPS>(st, hdr, params, k_wd, w);
+    if (!ws.valid) return;                               // (k_star_lpd has flagged the row)
+    const double c0m = st.c0m[ws.slot];
     double ll[NPOPS];
 #pragma unroll
     for (int kp = 0; kp < NPOPS; ++kp) {
-        const int wp = w * NPOPS + kp;
-        const double tip = hdr[wp].agb_tip, dM = (m_wd_up - tip) / steps;
+        const WdSteps<NFP> sp = wd_steps<NFP>(ws, m_wd_up, hdr, K, wtab, w * NPOPS + kp, n_wp);
         Lse acc; acc.mx = NEG_INF; acc.sm = 0.0;
-        if (dM > 0.0) {
-            const double log_w = log(dM);
-            const double *__restrict__ const rows = wtab + (((size_t)wp * 2 + wd_type) * steps) * NFP;      // k_marg_wd_table's
-            const double *__restrict__ const lpm = wtab + (size_t)n_wp * 2 * steps * NFP + (size_t)wp * steps;
-            for (int j = 1 + lane; j <= steps; j += 64) {
-                const double *__restrict__ const r = rows + (size_t)(j - 1) * NFP;
+        if (sp.on) {
+            for (int j = 1 + lane; j <= sp.steps; j += 64) {
+                const double *__restrict__ const r = sp.rows + (size_t)(j - 1) * NFP;
                 double chi2 = 0.0;
 #pragma unroll
-                for (int f = 0; f < NFP; ++f) { const double d = r[f] - obs[f]; chi2 = fma(wgt[f] * d, d, chi2); }
-                if (isfinite(chi2)) lse_add(acc, (lpm[j - 1] - 0.5 * chi2) + log_w);
+                for (int f = 0; f < NFP; ++f) { const double d = r[f] - ws.obs[f]; chi2 = fma(ws.wgt[f] * d, d, chi2); }
+                if (isfinite(chi2)) lse_add(acc, (sp.lpm[j - 1] - 0.5 * chi2) + sp.log_w);
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            Lse b; b.mx = __shfl_down(acc.mx, o, 64); b.sm = __shfl_down(acc.sm, o, 64);
-            acc = lse_merge(acc, b);
-        }
+        acc = lse_wave(acc);
         ll[kp] = (acc.mx == NEG_INF) ? NEG_INF : c0m + (acc.mx + log(acc.sm));
     }
-    if (lane == 0) scratch[(size_t)w * st.n + orig] = finish_star<NPOPS>(ll, par, st.la[slot]).v;
+    if (lane == 0) scratch[(size_t)w * st.n + ws.orig] = finish_star<NPOPS>(ll, ws.par, st.la[ws.slot]).v;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -297,6 +297,34 @@ void carve_checks()
         const size_t offs[] = {a.o_par, a.o_hdr, a.o_iso, a.o_tab, a.o_out, a.o_pop, a.o_rank, a.bytes};
         for (int k = 0; k < 7; ++k) CHECK(offs[k] % 256 == 0 && offs[k] < offs[k + 1]);
     }
+    // the reductions over a saved chain: the four calls' shapes (moments; hist with row sums; resid with its three extra parts;
+    // pointwise with flags and two tails), a call without WD-stage stars, and one without a tail or row sums.  Every part lies
+    // on an 8-byte (in fact 256-byte) boundary, holds its bytes without reaching the next one, and `bytes` is the end of the
+    // last part; a part of 0 bytes is empty -- it starts where the next one does.
+    struct { size_t chunk; int n_pops; long long stride; size_t tab_row, wd_row, n, n_col, n_acc, n_rowcol, extra[kChainExtras]; } chain[] = {
+        {32, 2, 122 * 9, 40000, 2 * 32 * 17, 1000, 8, 8, 0, {0, 0, 0}},
+        {32, 1, 62 * 5, 1234, 32 * 9, 13, 34, 34, 34, {0, 0, 0}},
+        {7, 2, 122 * 17, 5000, 2 * 32 * 33, 130, 34, 34, 81, {8 * 130 * 16, 8 * 192 * 16, 8 * 130 * 16}},
+        {32, 1, 122 * 9, 40000, 32 * 17, 1000, 1, 8, 1, {4 * 32, 8 * 1000 * 5, 8 * 1000 * 5}},
+        {32, 1, 122 * 9, 40000, 0, 1000, 1, 8, 1, {4 * 32, 8 * 1000 * 5, 8 * 1000 * 5}},       // wd_row = 0
+        {32, 1, 122 * 9, 40000, 32 * 17, 1000, 1, 8, 0, {4 * 32, 0, 0}},                      // tail_len = 0, no row sums
+    };
+    for (const auto &s : chain) {
+        const ChainArena a = chain_arena(s.chunk, s.n_pops, s.stride, s.tab_row, s.wd_row, s.n, s.n_col, s.n_acc, s.n_rowcol, sizeof(Hdr), s.extra);
+        const size_t offs[] = {a.o_par, a.o_hdr, a.o_iso, a.o_tab, a.o_wd, a.o_scratch, a.o_acc, a.o_rows, a.o_extra[0], a.o_extra[1], a.o_extra[2], a.bytes};
+        const size_t sizes[] = {8 * B9_NPARAM * s.chunk, sizeof(Hdr) * s.chunk * s.n_pops, 8 * s.chunk * s.n_pops * (size_t)s.stride, 8 * s.chunk * s.tab_row,
+                                8 * s.chunk * s.wd_row, 8 * s.chunk * s.n * s.n_col, 8 * s.n * s.n_acc, 8 * s.chunk * s.n_rowcol,
+                                s.extra[0], s.extra[1], s.extra[2]};
+        CHECK(a.o_par == 0);
+        for (int k = 0; k < 11; ++k) {
+            CHECK(offs[k] % 8 == 0 && offs[k] % kArenaAlign == 0);
+            CHECK(offs[k] + sizes[k] <= offs[k + 1] && offs[k + 1] == offs[k] + up256(sizes[k]));      // disjoint, in order, no slack beyond the rounding
+            if (sizes[k] == 0) CHECK(offs[k] == offs[k + 1]);                                           // an empty part
+        }
+        CHECK(a.bytes == a.o_extra[2] + up256(s.extra[2]));
+    }
+    CHECK(mom_chunk_rows(33, 130, 8, 32, (size_t)64 << 20) == 32 && mom_chunk_rows(5, 130, 8, 32, (size_t)64 << 20) == 5);
+    CHECK(mom_chunk_rows(33, 1 << 20, 8, 32, (size_t)64 << 20) == 1 && mom_chunk_rows(33, 0, 8, 32, (size_t)64 << 20) == 32);
     // b9_predict_mags: its body laid the six parts back to back (8c, 8c, 8c nf, 4c, 4c, 4c bytes).  Whole chunks of 2^20
     // systems -- every chunk but a catalogue's last -- and any chunk that is a multiple of 64 systems have every part on a
     // 256-byte boundary already: same offsets, same total.  Any other count gains less than 256 bytes of padding per part.

@@ -4,7 +4,9 @@ g++ -fsanitize=address,undefined and run as a child process).  It walks every fa
 non-zero at the first violated line: a failed reserve leaves pointer null AND capacity 0, growth frees the old block once,
 a moved-from buffer frees nothing, nothing is live at the end, the upload list frees the block whose copy failed, the work
 buffers' and the tree buffers' groups hold what the sizing functions ask for after every step, the carve is ordered, disjoint
-and aligned.
+and aligned -- the one arena of the four reductions over a saved chain (chain_arena) included: its parts do not overlap, lie
+on 8-byte boundaries, `bytes` is the end of the last part, and a call without WD-stage stars, row sums or a tail carves empty
+parts.
 
 There is no GPU test of these paths on purpose: allocation failures are not provoked on a device, and the tree-buffer defect
 this header removed wrote out of bounds.  That defect as arithmetic -- the rule the tree buffers were sized by before:
