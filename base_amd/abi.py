@@ -21,6 +21,10 @@ BLOCK_CONTINUE, BLOCK_ASYNC, BLOCK_ROWS_EVENT = 1, 2, 4
 # b9_star_moments: the accumulator's components (enum b9_moment) and its flag
 MOM_ROWS, MOM_MEMBER, MOM_M1, MOM_M1SQ, MOM_Q, MOM_QSQ, MOM_BINARY, MOM_POP1, MOM_N = range(9)
 MOM_CONTINUE = 1
+# b9_wd_moments: the accumulator's components (enum b9_wd_moment) and its flag
+(WDM_ROWS, WDM_MEMBER, WDM_POP1, WDM_COOLED, WDM_M1, WDM_M1SQ, WDM_WDMASS, WDM_WDMASS_SQ, WDM_PREC, WDM_PREC_SQ,
+ WDM_LOGCOOL, WDM_LOGCOOL_SQ, WDM_LOGTEFF, WDM_LOGTEFF_SQ, WDM_LOGG, WDM_LOGG_SQ, WDM_N) = range(17)
+WDM_CONTINUE = 1
 # b9_mass_hist: what is binned (enum b9_hist_quantity), the most bins of a call and its flag
 HQ_PRIMARY, HQ_SECONDARY, HQ_SYSTEM = range(3)
 HIST_MAX_BINS = 64
@@ -207,7 +211,7 @@ ABI_SYMBOLS = [
     "b9_abi_version", "b9_ctx_create", "b9_ctx_destroy", "b9_last_error",
     "b9_load_pack", "b9_load_stars", "b9_set_priors", "b9_set_options", "b9_set_tuning", "b9_get_tuning",
     "b9_logpost", "b9_logpost_device", "b9_mcmc_run_block", "b9_mcmc_wait", "b9_sample_mass", "b9_derive_isochrone",
-    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_star_moments", "b9_mass_hist", "b9_phot_resid", "b9_pointwise", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
+    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_star_moments", "b9_wd_moments", "b9_mass_hist", "b9_phot_resid", "b9_pointwise", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
     "b9_enable_timing", "b9_kernel_time_ms", "b9_calibrate_timing", "b9_clock_stamp", "b9_clock_mhz",
 ]
 
@@ -243,6 +247,7 @@ def load_hip_library(path: Optional[str] = None) -> C.CDLL:
     lib.b9_n_wd_stars.argtypes = [vp]
     lib.b9_sample_wd_mass.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]
     lib.b9_star_moments.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp]
+    lib.b9_wd_moments.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp]
     lib.b9_mass_hist.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, _dp]
     lib.b9_phot_resid.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, _dp]
     lib.b9_pointwise.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]

@@ -344,6 +344,50 @@ int b9_sample_wd_mass(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t
     return B9_OK;
 }
 
+// The rows in b9_sample_wd_mass's chunks (the table has one more double per node); the accumulators go in (or are cleared) before
+// the first chunk and come out after the last, with the one wait: a chunk's buffers are reused in stream order.
+int b9_wd_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_nodes, int32_t flags, double *acc)
+{
+    if (!ctx || !params || !acc || n_rows < 1 || n_nodes < 1) return B9_ERR_INVALID;
+    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
+    if (!ctx->have_pack || !ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
+    const int n_wd = ctx->st.n_wd, n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
+    if (n_wd == 0) return B9_OK;
+    const DevPack &pk = ctx->pk;
+    const int mass_cap = pack_mass_cap(pk.max_eep);
+    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
+    const size_t tab_row = (size_t)n_pops * (size_t)b9k_wd_moments_table_doubles(pk.nfp, n_nodes);       // doubles per row
+    if (tab_row > ((size_t)8 << 30) / sizeof(double)) return fail(ctx, B9_ERR_CAPACITY, "b9_wd_moments: one row's node table would exceed 8 GiB");
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_rows, (size_t)B9_WDS_MAX_ROWS, B9_WDS_TABLE_BYTES / (tab_row * sizeof(double))}));
+    const WdmArena a = wdm_arena((size_t)chunk, n_pops, iso_stride, tab_row, (size_t)n_wd, (size_t)n, B9_WDM_N, sizeof(IsoHdr));
+    RESERVE(ctx, ctx->d_wds, a.bytes);
+    char *base = ctx->d_wds.get();
+    double *d_par = part<double>(base, a.o_par), *d_iso = part<double>(base, a.o_iso), *d_tab = part<double>(base, a.o_tab);
+    double *d_scratch = part<double>(base, a.o_scratch), *d_acc = part<double>(base, a.o_acc);
+    IsoHdr *d_hdr = part<IsoHdr>(base, a.o_hdr);
+    int *d_rank = part<int>(base, a.o_rank);
+    std::vector<int> rank(n);            // (an upload's source: it lives until the wait below)
+    for (int i = 0, k = 0; i < n; ++i) { rank[i] = k; k += ctx->hs.stage[i] == B9_STAGE_WD; }
+    hipStream_t s = ctx->stream;
+    const size_t acc_bytes = sizeof(double) * (size_t)n_wd * B9_WDM_N;
+    HIPCHK(ctx, hipMemcpyAsync(d_rank, rank.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
+    if (flags & B9_WDM_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_acc, acc, acc_bytes, hipMemcpyHostToDevice, s));
+    else HIPCHK(ctx, hipMemsetAsync(d_acc, 0, acc_bytes, s));
+    const McmcDev off{};
+    for (int r0 = 0; r0 < n_rows; r0 += chunk) {
+        const int m = std::min(chunk, n_rows - r0);
+        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
+        // the star kernel writes every (row, WD-stage star) of the chunk, so nothing is cleared
+        HIPCHK(ctx, b9k_wd_moments(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, n_nodes, d_tab, d_rank, d_scratch, d_acc, s));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(acc, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return B9_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -109,6 +109,18 @@ inline WdsArena wds_arena(size_t chunk, int n_pops, long long iso_stride, size_t
     return a;
 }
 
+// b9_wd_moments' chunk of rows, in the same allocation: [params][headers][isochrones][node table with the nodes' status]
+// [per-(row, star) increments [chunk][n_wd][n_col]], then the accumulators [n_wd][n_col] and the stars' columns
+struct WdmArena { size_t o_par, o_hdr, o_iso, o_tab, o_scratch, o_acc, o_rank, bytes; };
+inline WdmArena wdm_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t n_wd, size_t n_stars, size_t n_col, size_t hdr_bytes)
+{
+    Carve c;
+    WdmArena a{c.take(8 * B9_NPARAM * chunk), c.take(hdr_bytes * chunk * n_pops), c.take(8 * chunk * n_pops * (size_t)iso_stride), c.take(8 * chunk * tab_row),
+               c.take(8 * chunk * n_wd * n_col), c.take(8 * n_wd * n_col), c.take(4 * n_stars), 0};
+    a.bytes = c.total;
+    return a;
+}
+
 // The reductions over a saved chain (b9_star_moments, b9_mass_hist, b9_phot_resid, b9_pointwise), one chunk of rows:
 // [params][headers][isochrones][node table][WD node table][per-(row, star) increments [chunk][n_stars][n_col]], then the
 // accumulators [n_stars][n_acc], the chunk's per-row sums [chunk][n_rowcol], and the call's own extra parts in the order it

@@ -29,6 +29,8 @@
 //                                     derived values kept, then one lane per WD-stage star against the table
 //   k_chain_accumulate               the four reductions over a saved chain below: their shared node walk, star finish and WD
 //                                     steps (b9_chain_walk.hip.h), and the per-star accumulation of a chunk's rows
+//   k_wd_node_table_status / k_wd_moments   b9_wd_moments: exact per-WD posterior moments of the ZAMS mass and the five derived
+//                                     values over b9_sample_wd_mass's grid (one lane per WD-stage star), summed over the rows
 //   k_star_moments / _wd              b9_star_moments: exact per-star posterior moments over the marginalisation
 //                                     grid (one lane per star, four waves sharing the node table), summed over the rows
 //   k_star_hist / _wd / k_hist_rows   b9_mass_hist: exact binned mass posteriors over the same grid (a
@@ -79,6 +81,7 @@ namespace tree_kd5 {
 #include "b9_wd_sample.hip.h"
 #include "b9_chain_walk.hip.h"
 #include "b9_star_moments.hip.h"
+#include "b9_wd_moments.hip.h"
 #include "b9_mass_hist.hip.h"
 #include "b9_phot_resid.hip.h"
 #include "b9_pointwise.hip.h"
@@ -247,6 +250,27 @@ hipError_t b9k_wd_sample(const DevPack &pk, const DevStars &st, const IsoHdr *hd
         out.k0 = smp.k0; out.k1 = smp.k1; out.row0 = smp.row0;
         hipLaunchKernelGGL((k_wd_sample<NFP, NPOPS>), dim3((st.n_wd + 63) / 64, n_rows), dim3(64), 0, stream, pk, st, hdr, d_params, n_nodes,
                            (const double *)tab, n_wp, out);
+        return hipGetLastError();
+    });
+}
+
+// ---- b9_wd_moments: the node table with every node's status, the WD-stage stars' increments, the accumulation -----------------
+long long b9k_wd_moments_table_doubles(int nfp, long long n_nodes) { return n_nodes * B9_WDM_NODE_DOUBLES(nfp); }       // per (row, population)
+
+hipError_t b9k_wd_moments(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                          const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const int *wd_rank, double *scratch, double *acc,
+                          hipStream_t stream)
+{
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        if (!tab || !wd_rank || !scratch || !acc || n_rows < 1 || n_nodes < 1 || st.n_wd < 1 || n_rows * NPOPS > 65535) return hipErrorInvalidValue;
+        const int n_wp = n_rows * NPOPS;
+        hipLaunchKernelGGL((k_wd_node_table_status<NFP>), dim3((n_nodes + 63) / 64, n_wp), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride, mass_cap,
+                           NPOPS, d_params, n_nodes, tab, n_wp);
+        hipLaunchKernelGGL((k_wd_moments<NFP, NPOPS>), dim3((st.n_wd + 63) / 64, n_rows), dim3(64), 0, stream, pk, st, hdr, d_params, n_nodes,
+                           (const double *)tab, n_wp, wd_rank, scratch);
+        const long long n_words = (long long)st.n_wd * B9_WDM_N;
+        hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
         return hipGetLastError();
     });
 }

@@ -119,6 +119,15 @@ hipError_t b9k_wd_sample(const DevPack &pk, const DevStars &st, const IsoHdr *hd
                          const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const B9WdSample &smp, hipStream_t stream);
 long long b9k_wd_table_doubles(int nfp, long long n_nodes);      // per (row, population)
 
+// b9_wd_moments: k_wd_node_table_status (k_wd_node_table's table with every node's status; b9k_wd_moments_table_doubles per (row, population)) +
+// k_wd_moments on n_rows derived rows (n_rows * n_pops <= 65535): every WD-stage star's sixteen increments into scratch
+// [n_rows][st.n_wd][B9_WDM_N] (column wd_rank[original index], as B9WdSample's), then acc [st.n_wd][B9_WDM_N] += the rows in
+// ascending order.  Device pointers, all the caller's own.
+hipError_t b9k_wd_moments(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                          const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const int *wd_rank, double *scratch, double *acc,
+                          hipStream_t stream);
+long long b9k_wd_moments_table_doubles(int nfp, long long n_nodes);      // per (row, population)
+
 // b9_star_moments: k_marg_table [+ k_marg_wd_table] of n_rows derived rows into tab / wd_tab (b9k_marg_table_doubles /
 // b9k_marg_wd_table_doubles per (row, population)), every star's eight increments into scratch [n_rows][st.n][B9_MOM_N], then
 // acc [st.n][B9_MOM_N] += the rows in ascending order.  Device pointers, all the caller's own.

@@ -11,6 +11,8 @@
 //   lpm  [wp][n_nodes]              log mass prior of the node
 //   der  [wp][n_nodes][5]           wd_mass, precursor log-age, log cooling age, log Teff, log g: what the row's magnitudes
 //                                   were computed FROM (wd_chain's values, not a second evaluation)
+// and, in the table b9_wd_moments builds (k_wd_node_table_status: the same body with STATUS), behind them
+//   stat [wp][n_nodes]              wd_chain's status of the node, as a double (b9_wd_moments.hip.h)
 // ------------------------------------------------------------------------------------------
 #define B9_WDS_DER 5
 #define B9_WDS_NODE_DOUBLES(nfp) (2 * (nfp) + 1 + B9_WDS_DER)       // table doubles per (row, population, node)
@@ -24,11 +26,11 @@ __host__ __device__ static inline WdTable<T> wd_table_view(T *tab, int nfp, long
     return t;
 }
 
-// grid (ceil(n_nodes / 64), rows * pops) x 128 threads: lane = node, wave = DA / DB
-template <int NFP>
-__global__ __launch_bounds__(128) void k_wd_node_table(DevPack pk, const IsoHdr *__restrict__ hdr, const double *__restrict__ iso_data,
-                                                       long long iso_stride, int mass_cap, int n_pops, const double *__restrict__ params,
-                                                       int n_nodes, double *__restrict__ tab, int n_wp)
+// one node of the table, by one lane of grid (ceil(n_nodes / 64), rows * pops) x 128 threads: lane = node, wave = DA / DB
+template <int NFP, bool STATUS>
+__device__ __forceinline__ void wd_node_table_body(const DevPack &pk, const IsoHdr *__restrict__ hdr, const double *__restrict__ iso_data,
+                                                   long long iso_stride, int mass_cap, int n_pops, const double *__restrict__ params,
+                                                   int n_nodes, double *__restrict__ tab, int n_wp)
 {
     const int wp = blockIdx.y, w = wp / n_pops, type = threadIdx.x >> 6;
     const long long j = 1 + (long long)blockIdx.x * 64 + (threadIdx.x & 63);
@@ -62,7 +64,24 @@ __global__ __launch_bounds__(128) void k_wd_node_table(DevPack pk, const IsoHdr 
         t.lpm[n] = log_prior_mass_dev(pk.log_mass_norm, m1);
         double *d = t.der + n * B9_WDS_DER;
         d[0] = c.wd_mass; d[1] = c.prec; d[2] = c.log_cool; d[3] = c.log_teff; d[4] = c.logg;
+        if (STATUS) t.der[(size_t)n_wp * n_nodes * B9_WDS_DER + n] = (double)c.status;
     }
+}
+
+template <int NFP>
+__global__ __launch_bounds__(128) void k_wd_node_table(DevPack pk, const IsoHdr *__restrict__ hdr, const double *__restrict__ iso_data,
+                                                       long long iso_stride, int mass_cap, int n_pops, const double *__restrict__ params,
+                                                       int n_nodes, double *__restrict__ tab, int n_wp)
+{
+    wd_node_table_body<NFP, false>(pk, hdr, iso_data, iso_stride, mass_cap, n_pops, params, n_nodes, tab, n_wp);
+}
+// ... and its sibling for b9_wd_moments: the same table with every node's status behind it
+template <int NFP>
+__global__ __launch_bounds__(128) void k_wd_node_table_status(DevPack pk, const IsoHdr *__restrict__ hdr, const double *__restrict__ iso_data,
+                                                              long long iso_stride, int mass_cap, int n_pops, const double *__restrict__ params,
+                                                              int n_nodes, double *__restrict__ tab, int n_wp)
+{
+    wd_node_table_body<NFP, true>(pk, hdr, iso_data, iso_stride, mass_cap, n_pops, params, n_nodes, tab, n_wp);
 }
 
 // where the draws go (device pointers, [rows][n_wd] in the caller's star order); the five derived ones and pop may be null

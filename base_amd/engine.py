@@ -199,6 +199,20 @@ class Engine:
         res["star_index"] = self.wd_index.copy()
         return res
 
+    def wd_moments(self, params: np.ndarray, n_nodes: int, acc: Optional[np.ndarray] = None):
+        """b9_wd_moments: the WD-stage stars' posterior moments of the ZAMS mass and the five derived values over `params`'
+        rows on b9_sample_wd_mass's grid of n_nodes steps, exactly (no draws).  Returns (acc [n_wd, abi.WDM_N], star_index):
+        the accumulators in the order of sample_wd_mass's columns and those stars' indices in the catalogue.  acc=None starts
+        from zeros; else the call continues `acc` (B9_WDM_CONTINUE) and returns a new array."""
+        params = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        n_wd = self.n_wd_stars()
+        if acc is None:
+            out, flags = np.zeros((n_wd, abi.WDM_N)), 0
+        else:
+            out, flags = np.array(acc, dtype=np.float64, order="C").reshape(n_wd, abi.WDM_N), abi.WDM_CONTINUE
+        self._check(self.lib.b9_wd_moments(self._ctx, params.ctypes.data_as(_dp), params.shape[0], int(n_nodes), flags, out.ctypes.data_as(_dp)))
+        return out, self.wd_index.copy()
+
     def star_moments(self, rows: np.ndarray, acc: Optional[np.ndarray] = None) -> np.ndarray:
         """b9_star_moments: the per-star posterior moments [n_stars, abi.MOM_N] summed over `rows`, exactly (no draws).
         acc=None starts from zeros; else the call continues `acc` (B9_MOM_CONTINUE) and returns a new array."""
@@ -376,3 +390,11 @@ def star_table(acc: np.ndarray) -> np.ndarray:
     massRatio, massRatioSd, pBinary, pPop2), [n_stars, 8] -- host arithmetic (b9h_star_table)."""
     from . import hostlib
     return hostlib.star_table(acc)
+
+
+def wd_table(acc: np.ndarray) -> np.ndarray:
+    """The derived columns of b9_wd_moments' accumulators (hostlib.WD_TABLE_COLUMNS: rows, member, pCooled, zamsMass,
+    zamsMassSd, then a mean and an sd of wdMass, precLogAge, logCoolAge, logTeff, logg, and pPop2), [n_wd, 16] -- host
+    arithmetic (b9h_wd_table)."""
+    from . import hostlib
+    return hostlib.wd_table(acc)

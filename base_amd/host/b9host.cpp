@@ -523,6 +523,50 @@ void write_star_summary(const std::string &path, const std::vector<std::string> 
 }
 
 // ---------------------------------------------------------------------------------------------
+// wdSummary
+// ---------------------------------------------------------------------------------------------
+void wd_table(const double *acc, long n_wd, double *table)
+{
+    for (long i = 0; i < n_wd; ++i) {
+        const double *a = acc + (size_t)i * B9_WDM_N;
+        double *t = table + (size_t)i * kWdTableCols;
+        for (int c = 0; c < kWdTableCols; ++c) t[c] = 0.0;
+        t[0] = a[B9_WDM_ROWS];
+        if (a[B9_WDM_ROWS] > 0.0) t[1] = a[B9_WDM_MEMBER] / a[B9_WDM_ROWS];
+        if (!(a[B9_WDM_MEMBER] > 0.0)) continue;             // no membership weight: every further value is 0
+        const double w = a[B9_WDM_MEMBER], wc = a[B9_WDM_COOLED];
+        t[2] = wc / w;
+        t[3] = a[B9_WDM_M1] / w;
+        t[4] = std::sqrt(std::max(0.0, a[B9_WDM_M1SQ] / w - t[3] * t[3]));
+        t[15] = a[B9_WDM_POP1] / w;
+        if (!(wc > 0.0)) continue;                           // no cooled weight: the derived values' columns are 0
+        for (int q = 0; q < 5; ++q) {
+            const double mean = a[B9_WDM_WDMASS + 2 * q] / wc;
+            t[5 + 2 * q] = mean;
+            t[6 + 2 * q] = std::sqrt(std::max(0.0, a[B9_WDM_WDMASS_SQ + 2 * q] / wc - mean * mean));
+        }
+    }
+}
+
+void write_wd_summary(const std::string &path, const std::vector<std::string> &ids, const double *acc, int n_pops)
+{
+    const long n = (long)ids.size();
+    std::vector<double> table((size_t)n * kWdTableCols);
+    wd_table(acc, n, table.data());
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) fail("cannot write " + path);
+    std::fprintf(f, "id rows member pCooled zamsMass zamsMassSd wdMass wdMassSd precLogAge precLogAgeSd logCoolAge logCoolAgeSd logTeff logTeffSd "
+                    "logg loggSd%s\n", n_pops == 2 ? " pPop2" : "");
+    for (long i = 0; i < n; ++i) {
+        const double *t = table.data() + (size_t)i * kWdTableCols;
+        std::fprintf(f, "%s %.0f", ids[i].c_str(), t[0]);
+        for (int c = 1; c < (n_pops == 2 ? kWdTableCols : kWdTableCols - 1); ++c) std::fprintf(f, " %.6f", t[c]);
+        std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) fail("cannot write " + path);
+}
+
+// ---------------------------------------------------------------------------------------------
 // massFunction
 // ---------------------------------------------------------------------------------------------
 namespace {

@@ -97,6 +97,18 @@ void star_table(const double *acc, long n_stars, double *table);
 // id rows member mass massSd massRatio massRatioSd pBinary [pPop2 -- two populations only]
 void write_star_summary(const std::string &path, const std::vector<std::string> &ids, const double *acc, int n_pops);
 
+// ---- wdSummary -------------------------------------------------------------------------------------
+// b9_wd_moments' accumulators [n_wd][B9_WDM_N] -> the derived columns [n_wd][kWdTableCols]:
+//   rows = ROWS, member = MEMBER / ROWS, pCooled = COOLED / MEMBER, zamsMass and zamsMassSd from M1, M1SQ over MEMBER, then a
+//   mean and an sd = sqrt(max(0, E[v^2] - E[v]^2)) of wdMass, precLogAge, logCoolAge, logTeff, logg over COOLED, and
+//   pPop2 = POP1 / MEMBER.  A derived column is 0 where its denominator is 0.  Host arithmetic only.
+constexpr int kWdTableCols = 16;
+void wd_table(const double *acc, long n_wd, double *table);
+// <base>.wdSummary (docs/FORMATS.md): a header line, then one line per WD-stage star in the order of `ids`:
+// id rows member pCooled zamsMass zamsMassSd wdMass wdMassSd precLogAge precLogAgeSd logCoolAge logCoolAgeSd logTeff logTeffSd
+// logg loggSd [pPop2 -- two populations only]
+void write_wd_summary(const std::string &path, const std::vector<std::string> &ids, const double *acc, int n_pops);
+
 // ---- massFunction ----------------------------------------------------------------------------------
 // b9_mass_hist's row_hist [n_rows][n_bins + 1] -> the per-bin table [n_bins][kMassFunctionCols]:
 //   lo, hi, then over the rows whose member column (the last) is > 0 the mean, the population standard deviation and the 16th,

@@ -159,6 +159,22 @@ int b9h_write_star_summary(const char *path, const char *const *ids, long n_star
     });
 }
 
+int b9h_wd_table(const double *acc, long n_wd, double *table)
+{
+    return guard([&] {
+        if (n_wd < 0 || (n_wd > 0 && (!acc || !table))) throw std::runtime_error("b9h_wd_table: NULL argument");
+        b9h::wd_table(acc, n_wd, table);
+    });
+}
+
+int b9h_write_wd_summary(const char *path, const char *const *ids, long n_wd, const double *acc, int n_pops)
+{
+    return guard([&] {
+        if (!path || n_wd < 0 || (n_wd > 0 && (!ids || !acc))) throw std::runtime_error("b9h_write_wd_summary: NULL argument");
+        b9h::write_wd_summary(path, std::vector<std::string>(ids, ids + n_wd), acc, n_pops);
+    });
+}
+
 int b9h_mass_function_table(const double *row_hist, long n_rows, const double *edges, int n_bins, double *table)
 {
     return guard([&] {

@@ -36,7 +36,7 @@ HOST_SYMBOLS = [
     "b9h_sampler_n_local", "b9h_sampler_state", "b9h_summary_rows",
     "b9h_load_pack", "b9h_free_pack", "b9h_read_phot", "b9h_free_phot", "b9h_settings_dump", "b9h_merge_parts",
     "b9h_sim_draw_systems", "b9h_sim_field_mags", "b9h_scatter", "b9h_sim_settings", "b9h_read_res_rows",
-    "b9h_star_table", "b9h_write_star_summary",
+    "b9h_star_table", "b9h_write_star_summary", "b9h_wd_table", "b9h_write_wd_summary",
     "b9h_mass_function_table", "b9h_write_mass_function", "b9h_write_star_mass_hist", "b9h_mass_function_settings",
     "b9h_resid_table", "b9h_filter_resid_table", "b9h_write_phot_resid", "b9h_write_filter_resid", "b9h_phot_resid_settings",
     "b9h_pointwise_table", "b9h_score_totals", "b9h_score_compare", "b9h_write_pointwise", "b9h_write_model_score", "b9h_model_score_settings",
@@ -89,6 +89,8 @@ def load() -> C.CDLL:
     lib.b9h_read_res_rows.argtypes = [C.c_char_p, _dp, C.c_int, _dp, C.c_long, C.POINTER(C.c_long)]
     lib.b9h_star_table.argtypes = [_dp, C.c_long, _dp]
     lib.b9h_write_star_summary.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int]
+    lib.b9h_wd_table.argtypes = [_dp, C.c_long, _dp]
+    lib.b9h_write_wd_summary.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int]
     lib.b9h_mass_function_table.argtypes = [_dp, C.c_long, _dp, C.c_int, _dp]
     lib.b9h_write_mass_function.argtypes = [C.c_char_p, _dp, C.c_int]
     lib.b9h_write_star_mass_hist.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int, C.c_long]
@@ -355,6 +357,32 @@ def read_star_summary(path: str):
             ids.append(t[0])
             rows.append([float(x) for x in t[1:]])
     return ids, header[1:], np.array(rows, dtype=np.float64).reshape(len(ids), len(header) - 1)
+
+
+WD_TABLE_COLUMNS = ("rows", "member", "pCooled", "zamsMass", "zamsMassSd", "wdMass", "wdMassSd", "precLogAge", "precLogAgeSd",
+                    "logCoolAge", "logCoolAgeSd", "logTeff", "logTeffSd", "logg", "loggSd", "pPop2")
+
+
+def wd_table(acc) -> np.ndarray:
+    """b9h_wd_table: b9_wd_moments' accumulators [n_wd, 16] -> the derived columns [n_wd, 16] (WD_TABLE_COLUMNS)."""
+    acc = np.ascontiguousarray(acc, dtype=np.float64).reshape(-1, 16)
+    out = np.empty_like(acc)
+    _check(load().b9h_wd_table(acc.ctypes.data_as(_dp), acc.shape[0], out.ctypes.data_as(_dp)))
+    return out
+
+
+def write_wd_summary(path: str, ids, acc, n_pops: int = 1) -> None:
+    """b9h_write_wd_summary: the .wdSummary file of the accumulators `acc` [len(ids), 16]."""
+    acc = np.ascontiguousarray(acc, dtype=np.float64).reshape(-1, 16)
+    if acc.shape[0] != len(ids):
+        raise ValueError("one id per WD-stage star")
+    arr = (C.c_char_p * len(ids))(*[str(i).encode() for i in ids])
+    _check(load().b9h_write_wd_summary(path.encode(), arr, len(ids), acc.ctypes.data_as(_dp), int(n_pops)))
+
+
+def read_wd_summary(path: str):
+    """(ids, columns, table [n_wd, len(columns)]) of a .wdSummary file: the layout of a .starSummary file."""
+    return read_star_summary(path)
 
 
 MASS_FUNCTION_COLUMNS = ("lo", "hi", "mean", "sd", "p16", "p50", "p84", "dNdlogM")

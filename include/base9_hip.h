@@ -294,7 +294,7 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk);
  * b9_set_priors or b9_set_options changes the posterior: the previous block's state carries a log-posterior of the old
  * one, so the next B9_BLOCK_CONTINUE block returns B9_ERR_STATE (the message names the call that intervened) and the chain
  * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags, b9_sample_wd_mass, b9_star_moments,
- * b9_mass_hist, b9_phot_resid and b9_pointwise (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
+ * b9_wd_moments, b9_mass_hist, b9_phot_resid and b9_pointwise (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
  * context's work buffers: b9_logpost / b9_sample_mass / b9_derive_isochrone, the staging calls, b9_set_options and a block
  * with another n_walkers return B9_ERR_STATE until it has been collected.  A driver that adapts the proposal
  * from block b-1 while block b runs keeps the GPU's queue non-empty: enqueue b+1 (CONTINUE | ASYNC), wait(b), ...
@@ -436,6 +436,51 @@ enum b9_moment {
 #define B9_MOM_CONTINUE 1
 int b9_star_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags,
                     double *acc /* host, [n_stars][B9_MOM_N], in/out */);
+
+/*
+ * Exact per-WD posterior moments over a saved chain (the wdSummary counterpart).  Added in ABI 6 without a version change, as
+ * its siblings were: purely additive.  b9_wd_moments is to b9_sample_wd_mass what b9_star_moments is to b9_sample_mass: where
+ * that call DRAWS one node per (row, WD-stage star), this one forms the conditional expectations of the ZAMS mass and of the
+ * five derived values over ALL nodes of the call's grid, weights them by membership and keeps only their sum over the rows:
+ * no random numbers, n_wd * B9_WDM_N doubles back instead of seven [n_rows][n_wd] arrays.
+ *
+ * Definition.  Grid, terms and membership are exactly b9_sample_wd_mass's: per population k the n_nodes equal steps
+ * m_j = tip_k + dM_k j, j = 1 .. n_nodes, dM_k = (m_wd_up - tip_k) / n_nodes (a population with dM_k <= 0 has no nodes);
+ * t_(k,j) = (log prior(m_j) - chi^2 / 2) + log dM_k [+ log lambda_k] through the WD branch with the star's own wd_type at mass
+ * ratio 0; terms that are not finite do not take part; L = logsumexp t, w = exp(t - L), p the membership as b9_sample_wd_mass
+ * forms it.  n_pops is honoured, mode ignored.  No pruning: every finite term takes part.  A node is COOLED if the WD branch
+ * made a white dwarf of it with every derived value set (not: the precursor still alive, a node above m_wd_up or on the tip,
+ * a pack without WD models); the node's status travels with the table -- it is not inferred from a value being zero.  Row r
+ * adds to WD-stage star i
+ *     acc[i][B9_WDM_ROWS]   += 1                     acc[i][B9_WDM_MEMBER] += p
+ *     acc[i][B9_WDM_POP1]   += p sum_{k = 1} w       acc[i][B9_WDM_COOLED] += p sum_cooled w
+ *     acc[i][B9_WDM_M1]     += p sum w m             acc[i][B9_WDM_M1SQ]   += p sum w m^2          (all nodes)
+ *     acc[i][B9_WDM_<V>]    += p sum_cooled w v      acc[i][B9_WDM_<V>_SQ] += p sum_cooled w v^2
+ * for v in {wd_mass, precursor log-age, log cooling age, log Teff, log g}: the values the node's magnitudes were computed FROM.
+ * A (row, star) for which b9_sample_wd_mass reports all zeros -- a row outside the grid, a row whose AGB tips are not below
+ * m_wd_up in any population, a star with no finite term -- adds nothing at all, B9_WDM_ROWS included.
+ *
+ * acc (host, [n_wd][B9_WDM_N], n_wd = b9_n_wd_stars, the order of b9_sample_wd_mass's columns) is in/out: flags = 0 starts
+ * from zeros, B9_WDM_CONTINUE from the caller's values.  Every accumulator is updated as acc + x_r, one plain add per row in
+ * ascending row order, and a star's sums take its terms in ascending node order, population by population: the order is a
+ * function of the data only.  The result is the same bits for any chunking of the rows inside the call (at most 256 rows,
+ * fewer while the chunk's node table -- n_pops * n_nodes * (2 * padded filters + 7) doubles per row -- would exceed 64 MiB,
+ * one row at a time above that), for any split of the rows over successive B9_WDM_CONTINUE calls, for any set of other stars
+ * in the catalogue, for a repeated call and after any other call on the context.  Synchronous; host pointers.  n_wd == 0 is
+ * B9_OK with nothing touched; B9_ERR_INVALID for n_nodes < 1, n_rows < 1 or NULL params / acc; B9_ERR_STATE while a sampler
+ * block is outstanding; B9_ERR_CAPACITY when one row's node table would exceed 8 GiB.  The call uses buffers of its own: a
+ * B9_BLOCK_CONTINUE block enqueued after it gives the same bits as one enqueued without it.
+ */
+enum b9_wd_moment {
+    B9_WDM_ROWS = 0, B9_WDM_MEMBER = 1, B9_WDM_POP1 = 2, B9_WDM_COOLED = 3,
+    B9_WDM_M1 = 4, B9_WDM_M1SQ = 5,
+    B9_WDM_WDMASS = 6,  B9_WDM_WDMASS_SQ = 7,   B9_WDM_PREC = 8,     B9_WDM_PREC_SQ = 9,
+    B9_WDM_LOGCOOL = 10, B9_WDM_LOGCOOL_SQ = 11, B9_WDM_LOGTEFF = 12, B9_WDM_LOGTEFF_SQ = 13,
+    B9_WDM_LOGG = 14,   B9_WDM_LOGG_SQ = 15,    B9_WDM_N = 16
+};
+#define B9_WDM_CONTINUE 1
+int b9_wd_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_nodes, int32_t flags,
+                  double *acc /* host, [b9_n_wd_stars][B9_WDM_N], in/out */);
 
 /*
  * Exact binned mass posteriors over a saved chain (the massFunction counterpart).  Added in ABI 6 without a version change, as

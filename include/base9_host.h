@@ -108,6 +108,15 @@ int b9h_read_res_rows(const char *path, const double *start_row, int stage, doub
  * "id rows member mass massSd massRatio massRatioSd pBinary [pPop2]" (the last column with n_pops == 2 only), in the order of ids. */
 int b9h_star_table(const double *acc, long n_stars, double *table);
 int b9h_write_star_summary(const char *path, const char *const *ids, long n_stars, const double *acc, int n_pops);
+/* wdSummary.  b9h_wd_table: b9_wd_moments' accumulators [n_wd][B9_WDM_N] -> the derived columns [n_wd][16]: rows = ROWS,
+ * member = MEMBER / ROWS, pCooled = COOLED / MEMBER, zamsMass = M1 / MEMBER, zamsMassSd = sqrt(max(0, M1SQ / MEMBER - zamsMass^2)),
+ * then a mean V / COOLED and an sd sqrt(max(0, V_SQ / COOLED - mean^2)) of wdMass, precLogAge, logCoolAge, logTeff and logg, and
+ * pPop2 = POP1 / MEMBER; a derived column is 0 where its denominator is 0.
+ * b9h_write_wd_summary: the file <base>.wdSummary (docs/FORMATS.md) -- one header line, then per WD-stage star "id rows member
+ * pCooled zamsMass zamsMassSd wdMass wdMassSd precLogAge precLogAgeSd logCoolAge logCoolAgeSd logTeff logTeffSd logg loggSd
+ * [pPop2]" (the last column with n_pops == 2 only), in the order of ids. */
+int b9h_wd_table(const double *acc, long n_wd, double *table);
+int b9h_write_wd_summary(const char *path, const char *const *ids, long n_wd, const double *acc, int n_pops);
 /* massFunction.  b9h_mass_function_table: b9_mass_hist's row_hist [n_rows][n_bins + 1] -> the per-bin table [n_bins][8]:
  * lo, hi, then over the rows whose member column (the last) is > 0 the mean, the population standard deviation, the 16th, 50th
  * and 84th percentiles of the bin's expected count (linear interpolation between order statistics, numpy's default) and

@@ -1,0 +1,165 @@
+"""numpy statement of b9_wd_moments (tests only): the sixteen increments of every (row, WD-stage star), built from
+numpy_ref.marg_terms_wd(..., n_nodes=n_nodes) -- the terms and masses of every node of b9_sample_wd_mass's grid -- from
+wd_check.wd_chain -- the derived values -- scipy's logsumexp and moments_ref.membership.  Shares no code with the kernels or
+the C oracle.
+
+For row r and WD-stage star i: the populations' terms are concatenated with log lambda / log(1 - lambda), the finite ones kept,
+L = logsumexp, w = exp(t - L), p the membership; a node is COOLED if m <= M_wd_up, prec < logAge and the pack has WD tables.
+x = (1, p, p sum_{k=1} w, p sum_cooled w, p sum w m, p sum w m^2, then p sum_cooled w v, p sum_cooled w v^2 for
+v = wd_mass, prec, log_cool, log_teff, logg).  A row outside the grid, a row whose AGB tips are not below M_wd_up in any
+population and a star with no finite term contribute nothing.
+
+The keyword MUTATIONS are wrong on purpose: the checks of tests/wdmoments_check.py must reject each of them."""
+import numpy as np
+from scipy.special import logsumexp
+
+import moments_ref
+import numpy_ref
+import wd_check
+from base_amd import abi, synth
+
+N = 16
+(ROWS, MEMBER, POP1, COOLED, M1, M1SQ, WDMASS, WDMASS_SQ, PREC, PREC_SQ, LOGCOOL, LOGCOOL_SQ, LOGTEFF, LOGTEFF_SQ,
+ LOGG, LOGG_SQ) = range(16)
+VALUE_COLS = (M1, M1SQ) + tuple(range(WDMASS, N))            # the columns that carry p sum w |v|: they get an absolute floor
+MUTATIONS = ("second_moment_power", "derived_over_all_nodes", "drop_pop_weight", "drop_log_dm", "da_rows_for_db")
+
+
+def has_wd_tables(pack_d):
+    return len(pack_d.get("wc_mass", ())) > 0 and len(pack_d.get("at_log_teff", ())) > 0
+
+
+def wd_stars(cl):
+    return np.flatnonzero(np.asarray(cl["stage"]) == abi.STAGE_WD)
+
+
+def star_nodes(pack_d, cl, par, n_pops, n_nodes, drop_pop_weight=False, drop_log_dm=False, da_rows_for_db=False):
+    """Per WD-stage star (in catalogue order): (terms, mass, pop, cooled, der [node, 5]) over its finite nodes of every
+    population; None when the row lies outside the grid."""
+    par = np.asarray(par, dtype=np.float64)
+    wd = wd_stars(cl)
+    lam = par[abi.P_LAMBDA]
+    with np.errstate(divide="ignore"):
+        lw = [0.0] if n_pops == 1 else [np.log(lam), np.log1p(-lam)]
+    if drop_pop_weight:
+        lw = [0.0] * n_pops
+    for pop in range(n_pops):
+        if synth.derive_isochrone(pack_d, par[abi.P_LOGAGE], par[abi.P_FEH], par[abi.P_Y2 if pop else abi.P_Y]) is None:
+            return None
+    use = cl
+    if da_rows_for_db:
+        use = dict(cl, wd_type=np.zeros(len(cl["mass1"]), dtype=np.int32))
+    per_pop = []
+    for pop in range(n_pops):
+        t, m = numpy_ref.marg_terms_wd(pack_d, use, par, 1, pop, n_nodes=n_nodes)
+        if t is None:
+            per_pop.append(None)
+            continue
+        if drop_log_dm:
+            tip = synth.derive_isochrone(pack_d, par[abi.P_LOGAGE], par[abi.P_FEH], par[abi.P_Y2 if pop else abi.P_Y])[1][-1]
+            t = t - np.log((pack_d["m_wd_up"] - tip) / n_nodes)
+        der = np.zeros((len(m), 5))
+        cooled = np.zeros(len(m), dtype=bool)
+        if has_wd_tables(pack_d):
+            ok = m <= pack_d["m_wd_up"]                          # (rounding can put the last node a bit above M_wd_up: no WD)
+            if ok.any():
+                wdm, prec, cool, lteff, logg = wd_check.wd_chain(pack_d, par, m[ok], pop=pop)
+                der[ok] = np.stack([wdm, prec, cool, lteff, logg], axis=1)
+                cooled[ok] = prec < par[abi.P_LOGAGE]
+        per_pop.append((t, m, cooled, der))
+    out = []
+    for i in wd:
+        ts, ms, ks, cs, ds = [], [], [], [], []
+        for pop, pp in enumerate(per_pop):
+            if pp is None:
+                continue
+            t, m, cooled, der = pp
+            ti = t[i] + lw[pop]
+            ok = np.isfinite(ti)
+            ts.append(ti[ok]); ms.append(m[ok]); ks.append(np.full(int(ok.sum()), pop)); cs.append(cooled[ok]); ds.append(der[ok])
+        if ts:
+            out.append((np.concatenate(ts), np.concatenate(ms), np.concatenate(ks), np.concatenate(cs), np.concatenate(ds)))
+        else:
+            out.append((np.empty(0), np.empty(0), np.empty(0, int), np.empty(0, bool), np.empty((0, 5))))
+    return out
+
+
+def increments(pack_d, cl, par, n_pops, n_nodes, second_moment_power=2, derived_over_all_nodes=False, drop_pop_weight=False,
+               drop_log_dm=False, da_rows_for_db=False, want_extra=False):
+    """x [n_wd, 16] of one parameter row.  With want_extra also (floor [n_wd, 16], A [n_wd]): floor = p sum w |v| per value
+    column (the scale of the sum a rounding error is relative to), A = sum_cooled w t / (t - 10^prec) with t = 10^logAge, the
+    weighted amplification of an error in prec into log_cool, log_teff and logg; A = -1 marks a star without a finite term."""
+    par = np.asarray(par, dtype=np.float64)
+    wd = wd_stars(cl)
+    x, floor, amp = np.zeros((len(wd), N)), np.zeros((len(wd), N)), np.zeros(len(wd))
+    nodes = star_nodes(pack_d, cl, par, n_pops, n_nodes, drop_pop_weight=drop_pop_weight, drop_log_dm=drop_log_dm,
+                       da_rows_for_db=da_rows_for_db)
+    if nodes is not None:
+        age = 10.0 ** par[abi.P_LOGAGE]
+        for c, i in enumerate(wd):
+            t, m, k, cooled, der = nodes[c]
+            if len(t) == 0:
+                amp[c] = -1.0
+                continue
+            L = logsumexp(t)
+            w = np.exp(t - L)
+            p = moments_ref.membership(cl, i, L)
+            sel = np.ones(len(t), dtype=bool) if derived_over_all_nodes else cooled
+            pw = second_moment_power
+            x[c, :M1SQ + 1] = [1.0, p, p * np.sum(w[k == 1]), p * np.sum(w[cooled]), p * np.sum(w * m), p * np.sum(w * m ** pw)]
+            floor[c, M1], floor[c, M1SQ] = p * np.sum(w * m), p * np.sum(w * m ** 2)
+            for q in range(5):
+                v = der[sel, q]
+                x[c, WDMASS + 2 * q] = p * np.sum(w[sel] * v)
+                x[c, WDMASS + 2 * q + 1] = p * np.sum(w[sel] * v ** pw)
+                floor[c, WDMASS + 2 * q] = p * np.sum(w[sel] * np.abs(v))
+                floor[c, WDMASS + 2 * q + 1] = p * np.sum(w[sel] * v ** 2)
+            amp[c] = np.sum(w[cooled] * age / (age - 10.0 ** der[cooled, 1]))
+    else:
+        amp[:] = 0.0
+    return (x, floor, amp) if want_extra else x
+
+
+def accumulate(pack_d, cl, rows, n_pops, n_nodes, acc=None, **kw):
+    """acc [n_wd, 16]: the rows' increments added in ascending row order (to `acc`, or to zeros)."""
+    acc = np.zeros((len(wd_stars(cl)), N)) if acc is None else np.array(acc, dtype=np.float64)
+    for par in np.asarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM):
+        acc = acc + increments(pack_d, cl, par, n_pops, n_nodes, **kw)
+    return acc
+
+
+def table(acc):
+    """The derived columns (rows, member, pCooled, zamsMass, zamsMassSd, a mean and an sd of wdMass, precLogAge, logCoolAge,
+    logTeff, logg, pPop2), stated independently of b9h_wd_table."""
+    acc = np.asarray(acc, dtype=np.float64).reshape(-1, N)
+    out = np.zeros_like(acc)
+    out[:, 0] = acc[:, ROWS]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out[:, 1] = np.where(acc[:, ROWS] > 0, acc[:, MEMBER] / acc[:, ROWS], 0.0)
+        mem = acc[:, MEMBER] > 0
+        out[:, 2] = np.where(mem, acc[:, COOLED] / acc[:, MEMBER], 0.0)
+        zams = np.where(mem, acc[:, M1] / acc[:, MEMBER], 0.0)
+        out[:, 3] = zams
+        out[:, 4] = np.where(mem, np.sqrt(np.maximum(0.0, acc[:, M1SQ] / acc[:, MEMBER] - zams ** 2)), 0.0)
+        out[:, 15] = np.where(mem, acc[:, POP1] / acc[:, MEMBER], 0.0)
+        cold = mem & (acc[:, COOLED] > 0)
+        for q in range(5):
+            mean = np.where(cold, acc[:, WDMASS + 2 * q] / acc[:, COOLED], 0.0)
+            out[:, 5 + 2 * q] = mean
+            out[:, 6 + 2 * q] = np.where(cold, np.sqrt(np.maximum(0.0, acc[:, WDMASS + 2 * q + 1] / acc[:, COOLED] - mean ** 2)), 0.0)
+    return out
+
+
+def star_moments(nodes_c):
+    """Under one star's node weights: (mean, variance, gamma_1) of the ZAMS mass over all nodes and of wd_mass and log_cool over
+    the cooled ones (conditional on cooled), plus the cooled probability -- what the statistical test takes its variances from."""
+    t, m, k, cooled, der = nodes_c
+    w = np.exp(t - logsumexp(t))
+
+    def mo(w, v):
+        w = w / w.sum()
+        mu = np.sum(w * v)
+        var = np.sum(w * (v - mu) ** 2)
+        return mu, var, (np.sum(w * (v - mu) ** 3) / var ** 1.5 if var > 0 else 0.0)
+    pc = float(np.sum(w[cooled]))
+    return mo(w, m), (mo(w[cooled], der[cooled, 0]) if pc > 0 else None), (mo(w[cooled], der[cooled, 2]) if pc > 0 else None), pc
