@@ -1,7 +1,7 @@
 // b9_capi_eval.cpp -- one log-posterior evaluation through the C ABI: derive -> stars -> finalize (b9_logpost,
 // b9_logpost_device), the per-star mass draws (b9_sample_mass), the isochrone dump (b9_derive_isochrone) and the forward
 // model alone (b9_predict_mags) the WD-stage stars' posterior draws (b9_sample_wd_mass), the
-// per-star posterior moments (b9_star_moments), the binned mass posteriors (b9_mass_hist) and the
+// per-star posterior moments (b9_star_moments), the binned mass posteriors (b9_mass_hist), the per-star bins (b9_star_bins), the
 // posterior-predictive residuals (b9_phot_resid) and the pointwise predictive densities (b9_pointwise).
 #include "b9_ctx.h"
 #include <algorithm>
@@ -392,7 +392,7 @@ int b9_wd_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_n
 
 namespace {
 
-// ---- the reductions over a saved chain: b9_star_moments, b9_mass_hist, b9_phot_resid, b9_pointwise --------------------------
+// ---- the reductions over a saved chain: b9_star_moments, b9_mass_hist, b9_star_bins, b9_phot_resid, b9_pointwise ------------
 // What one of them is to the driver below.  Rows are worked in chunks of at most max_rows, and of as few rows as keep the chunk's
 // increments [rows][n_stars][n_col] within scratch_bytes.
 struct ChainCall {
@@ -479,6 +479,8 @@ int chain_reduce(b9_ctx *ctx, const ChainCall &c, const double *params, int n_ro
 #define B9_MOM_MAX_ROWS 32
 #define B9_HIST_SCRATCH_BYTES ((size_t)64 << 20)
 #define B9_HIST_MAX_ROWS 32
+#define B9_SBIN_SCRATCH_BYTES ((size_t)64 << 20)
+#define B9_SBIN_MAX_ROWS 32
 #define B9_RESID_SCRATCH_BYTES ((size_t)64 << 20)
 #define B9_RESID_MAX_ROWS 32
 // (B9_PW_MAX_ROWS: b9_launch.h -- the reducers hold a chunk's rows in registers; 32 rows up to 65536 stars)
@@ -512,6 +514,30 @@ int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quan
     return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
         return b9k_mass_hist(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, d.K, d.Q, ctx->marg_prune, quantity, edges, n_bins,
                              d.tab, d.wd, d.scratch, d.acc, d.rows, ctx->stream);
+    });
+}
+
+int b9_star_bins(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quantity, const double *edges, int32_t n_bins, int32_t flags, double *acc)
+{
+    if (!ctx || !params || !edges || !acc || n_rows < 1) return B9_ERR_INVALID;
+    if (quantity != B9_HQ_PRIMARY && quantity != B9_HQ_SECONDARY && quantity != B9_HQ_SYSTEM) return fail(ctx, B9_ERR_INVALID, "b9_star_bins: unknown quantity");
+    if (n_bins < 1 || n_bins > B9_SBIN_MAX_BINS) return fail(ctx, B9_ERR_INVALID, "b9_star_bins: n_bins must lie in 1 .. B9_SBIN_MAX_BINS");
+    if (!ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
+    const size_t n = (size_t)ctx->hs.n, ne = (size_t)n_bins + 1, ncol = (size_t)n_bins + 3;
+    for (size_t i = 0; i < n; ++i)
+        for (size_t b = 0; b < ne; ++b)
+            if (!std::isfinite(edges[i * ne + b]) || (b > 0 && !(edges[i * ne + b] > edges[i * ne + b - 1])))
+                return fail(ctx, B9_ERR_INVALID, "b9_star_bins: star " + std::to_string(i) + ": the edges must be finite and strictly ascending");
+    if (const int rc = chain_ready(ctx)) return rc;
+    // the call's part: every star's edges, the caller's star order (the upload's source is the caller's array: it lives until the wait)
+    const ChainCall c{"b9_star_bins", ncol, ncol, 0, B9_SBIN_MAX_ROWS, B9_SBIN_SCRATCH_BYTES, (flags & B9_SBIN_CONTINUE) != 0, acc, nullptr, {8 * n * ne, 0, 0}};
+    auto d_edges = [](const ChainDev &d) { return reinterpret_cast<double *>(d.extra[0]); };
+    return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
+        return b9k_star_bins(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, d.K, d.Q, ctx->marg_prune, quantity, d_edges(d), n_bins,
+                             d.tab, d.wd, d.scratch, d.acc, ctx->stream);
+    }, [&](const ChainDev &d) {
+        HIPCHK(ctx, hipMemcpyAsync(d_edges(d), edges, sizeof(double) * n * ne, hipMemcpyHostToDevice, ctx->stream));
+        return (int)B9_OK;
     });
 }
 

@@ -35,6 +35,8 @@
 //                                     grid (one lane per star, four waves sharing the node table), summed over the rows
 //   k_star_hist / _wd / k_hist_rows   b9_mass_hist: exact binned mass posteriors over the same grid (a
 //                                     per-wave LDS histogram per lane, bins worked in tiles), summed over the rows and the stars
+//   k_star_bins / _wd                b9_star_bins: the same bins on every star's OWN edges with the two open ends kept (the
+//                                     bin is per lane, the edges staged in LDS), summed over the rows
 //   k_star_resid / _wd / k_resid_stage / k_resid_rows   b9_phot_resid: exact posterior-predictive magnitude
 //                                     moments per filter over the same grid, summed over the rows and, standardised, the stars
 //   k_star_lpd / _wd / k_pw_accumulate / k_pw_tail / k_pw_rows   b9_pointwise: every star's marginal log-likelihood per row over
@@ -83,6 +85,7 @@ namespace tree_kd5 {
 #include "b9_star_moments.hip.h"
 #include "b9_wd_moments.hip.h"
 #include "b9_mass_hist.hip.h"
+#include "b9_star_bins.hip.h"
 #include "b9_phot_resid.hip.h"
 #include "b9_pointwise.hip.h"
 
@@ -379,6 +382,31 @@ hipError_t b9k_mass_hist(const DevPack &pk, const DevStars &st, const IsoHdr *hd
             hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
         if (rows)
             hipLaunchKernelGGL(k_hist_rows, dim3((unsigned)((n_rows * ncol + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, st.n, ncol, rows);
+        return hipGetLastError();
+    });
+}
+
+// ---- b9_star_bins: the node tables of a chunk of rows, the stars' increments on their own edges, the accumulation -----------------
+hipError_t b9k_star_bins(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                         const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, int quantity, const double *edges, int n_bins,
+                         double *tab, double *wd_tab, double *scratch, double *acc, hipStream_t stream)
+{
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        if (!tab || !scratch || !acc || !edges || n_bins < 1 || n_bins > B9_SBIN_MAX_BINS || n_rows < 1 || n_rows > 65535 || (st.n_wd > 0 && !wd_tab))
+            return hipErrorInvalidValue;
+        const ChainTables t = chain_tables<NFP>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, prune, tab, wd_tab, stream);
+        if (t.err != hipSuccess) return t.err;
+        // seeds, states, the 64 stars' edges, one histogram [n_bins + 2][64] per wave
+        const auto k = with_lds(k_star_bins<NFP, NPOPS>, sizeof(double) * 64 * (NPOPS * 4 + 4 * 2 + (size_t)(n_bins + 1) + 4 * (size_t)(n_bins + 2)));
+        if (k.err != hipSuccess) return k.err;
+        hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows), dim3(256), k.lds, stream, st, hdr, iso_data, iso_stride, mass_cap,
+                           d_params, K, Q, (const double *)tab, t.L, t.cut2, edges, n_bins, quantity, scratch);
+        if (st.n_wd > 0)
+            hipLaunchKernelGGL((k_star_bins_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, hdr, d_params, K,
+                               (const double *)wd_tab, edges, n_bins, quantity, scratch);
+        const long long n_words = (long long)st.n * (n_bins + 3);
+        hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
         return hipGetLastError();
     });
 }

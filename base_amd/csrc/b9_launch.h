@@ -143,6 +143,13 @@ hipError_t b9k_mass_hist(const DevPack &pk, const DevStars &st, const IsoHdr *hd
                          const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, int quantity, const double *edges, int n_bins,
                          double *tab, double *wd_tab, double *scratch, double *acc, double *rows, hipStream_t stream);
 
+// b9_star_bins: the node tables as b9k_star_moments builds them, every star's increments on its own edges into scratch
+// [n_rows][st.n][n_bins + 3] (below, the bins, at or above, the total), then acc [st.n][n_bins + 3] += the rows in ascending
+// order.  edges: DEVICE, [st.n][n_bins + 1] in the caller's star order, validated by the caller.  Device pointers, all the caller's own.
+hipError_t b9k_star_bins(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                         const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, int quantity, const double *edges, int n_bins,
+                         double *tab, double *wd_tab, double *scratch, double *acc, hipStream_t stream);
+
 // b9_phot_resid.  b9k_resid_stage: the call's pivots piv_in [st.n][pk.nf] (the caller's star order) into the mg_* copy's order,
 // piv_mg [st.mg_pad / 64][pk.nfp][64].  b9k_phot_resid: the node tables as b9k_star_moments builds them, every star's increments
 // into scratch [n_rows][st.n][2 + 2 nf], then acc [st.n][2 + 2 nf] += the rows in ascending order (acc may be null) and

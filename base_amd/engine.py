@@ -67,6 +67,8 @@ class Engine:
     def load_pack(self, pack: abi.Pinned) -> None:
         self._check(self.lib.b9_load_pack(self._ctx, pack.byref()))
         self.n_filt = pack.struct.n_filt
+        # the largest mass a node can take: the isochrones' and the WD-stage steps' (hostlib.star_intervals' first edges)
+        self.max_mass = max(float(np.ctypeslib.as_array(pack.struct.mass, (int(pack.struct.n_points),)).max()), float(pack.struct.m_wd_up))
 
     def load_stars(self, stars: abi.Pinned) -> None:
         self._check(self.lib.b9_load_stars(self._ctx, stars.byref()))
@@ -246,6 +248,21 @@ class Engine:
         self._check(self.lib.b9_mass_hist(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], int(quantity), edges.ctypes.data_as(_dp), n_bins, flags,
                                           ptr(sh), ptr(rh)))
         return sh, rh
+
+    def star_bins(self, rows: np.ndarray, edges: np.ndarray, quantity: int = abi.HQ_PRIMARY, acc: Optional[np.ndarray] = None) -> np.ndarray:
+        """b9_star_bins: every star's node weights over `rows` binned on that star's OWN edges `edges` [n_stars, n_bins + 1] of
+        `quantity` (abi.HQ_*): acc [n_stars, n_bins + 3] -- below, the bins, at or above, the total (membership).  acc=None
+        starts from zeros; else the call continues `acc` (B9_SBIN_CONTINUE) and returns a new array."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(self.n_stars, -1)
+        n_bins = edges.shape[1] - 1
+        if acc is None:
+            out, flags = np.zeros((self.n_stars, n_bins + 3)), 0
+        else:
+            out, flags = np.array(acc, dtype=np.float64, order="C").reshape(self.n_stars, n_bins + 3), abi.SBIN_CONTINUE
+        self._check(self.lib.b9_star_bins(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], int(quantity), edges.ctypes.data_as(_dp), n_bins, flags,
+                                          out.ctypes.data_as(_dp)))
+        return out
 
     def phot_resid(self, rows: np.ndarray, star_resid: Optional[np.ndarray] = None, want_star: bool = True,
                    want_rows: bool = True) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:

@@ -130,6 +130,8 @@ const std::map<std::string, std::string> &Settings::flag_map()
         {"nMassNodes", "sampleWDMass.nMassNodes"},
         {"nBins", "massFunction.nBins"}, {"massFunctionMinMass", "massFunction.minMass"}, {"massFunctionMaxMass", "massFunction.maxMass"},
         {"linearBins", "massFunction.linearBins"}, {"quantity", "massFunction.quantity"}, {"perStar", "massFunction.perStar"},
+        {"starIntervalsQuantity", "starIntervals.quantity"}, {"starIntervalsNPops", "starIntervals.nPops"}, {"levels", "starIntervals.levels"},
+        {"tol", "starIntervals.tol"}, {"maxPasses", "starIntervals.maxPasses"},
         {"photResidualsPerStar", "photResiduals.perStar"}, {"photResidualsNPops", "photResiduals.nPops"},
         {"modelScorePerRow", "modelScore.perRow"}, {"modelScoreNPops", "modelScore.nPops"}, {"compareTo", "modelScore.compareTo"},
         {"nStars", "simCluster.nStars"}, {"percentBinary", "simCluster.percentBinary"}, {"percentDB", "simCluster.percentDB"},
@@ -680,6 +682,230 @@ std::vector<std::string> mass_function_args(int argc, char **argv)
             const std::string flag = std::string("--") + name;
             if (a == flag || a.rfind(flag + "=", 0) == 0)
                 a = std::string("--massFunction") + (char)std::toupper(name[0]) + (name + 1) + a.substr(flag.size());
+        }
+        out.push_back(a);
+    }
+    return out;
+}
+
+// ---------------------------------------------------------------------------------------------
+// starIntervals
+// ---------------------------------------------------------------------------------------------
+namespace {
+void check_levels(const double *levels, int m, int n_bins, const char *who)
+{
+    if (m < 1 || 3 * m > n_bins + 1) fail(std::string(who) + ": the levels need 3 edges each: at most (n_bins + 1) / 3 of them, at least one");
+    for (int l = 0; l < m; ++l)
+        if (!(levels[l] > 0.0 && levels[l] < 1.0) || (l > 0 && !(levels[l] > levels[l - 1])))
+            fail(std::string(who) + ": the levels must lie strictly inside (0, 1) and ascend strictly");
+}
+}  // namespace
+
+void refine_star_edges(const double *edges, const double *acc, long n_stars, int n_bins, const double *levels, int n_levels, double tol,
+                       double *lo, double *hi, double *below, double *inside, double *value, int32_t *is_final, int32_t *flags, double *next_edges)
+{
+    const int B = n_bins, m = n_levels;
+    if (B < 1) fail("refine_star_edges: n_bins must be positive");
+    check_levels(levels, m, B, "refine_star_edges");
+    if (!(tol >= 0.0)) fail("refine_star_edges: tol must not be negative");
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<double> cum((size_t)B + 2), pts, out;
+    std::vector<int> col(m);
+    for (long i = 0; i < n_stars; ++i) {
+        const double *e = edges + (size_t)i * (B + 1), *a = acc + (size_t)i * (B + 3);
+        double *ne = next_edges + (size_t)i * (B + 1);
+        std::copy(e, e + B + 1, ne);                         // a finished star keeps its edges
+        // the counted mass: below, the bins, at or above, summed in that order (the total column may hold more: B9_HQ_SECONDARY)
+        double c = 0.0;
+        for (int k = 0; k < B + 2; ++k) { c = c + a[k]; cum[k] = c; }
+        const double C = cum[B + 1];
+        flags[i] = 0;
+        if (!(C > 0.0)) {
+            flags[i] = kSivNoMass;
+            for (int l = 0; l < m; ++l) {
+                const size_t o = (size_t)i * m + l;
+                lo[o] = hi[o] = value[o] = nan; below[o] = inside[o] = 0.0; is_final[o] = 1;
+            }
+            continue;
+        }
+        auto col_final = [&](int k) {
+            if (k < 1 || k > B) return false;
+            const double L = e[k - 1], H = e[k];
+            return H - L <= tol * std::max(std::fabs(L), std::fabs(H)) || H == std::nextafter(L, inf);
+        };
+        bool open = false;
+        for (int l = 0; l < m; ++l) {
+            const size_t o = (size_t)i * m + l;
+            const double target = levels[l] * C;
+            // the column in which the cumulative sum first reaches the level -- within kSivSlack C, the rounding of the sums: a
+            // level that falls exactly between two nodes (whole rows on either side: 17 of 34 at the median) is a tie that rounding
+            // would decide one way in one pass and the other way in the next; with the slack every pass takes the lower node
+            int k = 0;
+            while (k < B + 1 && !(cum[k] >= target - kSivSlack * C)) ++k;
+            col[l] = k;
+            lo[o] = k == 0 ? -inf : e[k - 1];
+            hi[o] = k == B + 1 ? inf : e[k];
+            below[o] = k == 0 ? 0.0 : cum[k - 1];
+            inside[o] = a[k];
+            is_final[o] = col_final(k);
+            open = open || !is_final[o];
+            if (k == 0) value[o] = e[0];
+            else if (k == B + 1) value[o] = e[B];
+            else {
+                const double t = a[k] > 0.0 ? std::min(1.0, std::max(0.0, (target - below[o]) / a[k])) : 0.0;
+                value[o] = std::min(hi[o], std::max(lo[o], lo[o] + (hi[o] - lo[o]) * t));
+            }
+        }
+        if (!open) continue;
+        flags[i] = kSivOpen;
+        // the next pass's edges: every distinct bracket keeps its two ends (an open one is widened to twice the range), the
+        // unfinished ones share the remaining edges evenly as interior points
+        const double range = e[B] - e[0];
+        struct Iv { double L, H; bool todo; int extra; };
+        std::vector<Iv> iv;
+        for (int l = 0; l < m; ++l) {
+            if (l > 0 && col[l] == col[l - 1]) continue;    // coinciding brackets share their sub-bins
+            const int k = col[l];
+            if (k == 0) iv.push_back({e[0] - 2.0 * range, e[0], true, 0});
+            else if (k == B + 1) iv.push_back({e[B], e[B] + 2.0 * range, true, 0});
+            else iv.push_back({e[k - 1], e[k], !col_final(k), 0});
+        }
+        int mandatory = 0, todo = 0;
+        for (size_t j = 0; j < iv.size(); ++j) {
+            mandatory += (j > 0 && iv[j].L == iv[j - 1].H) ? 1 : 2;
+            todo += iv[j].todo;
+        }
+        int spare = B + 1 - mandatory;
+        if (spare < todo) fail("refine_star_edges: too few bins for the levels");
+        for (int j = 0, t = 0; j < (int)iv.size(); ++j)
+            if (iv[j].todo) { iv[j].extra = spare / todo + (t < spare % todo); ++t; }
+        out.clear();
+        int left_over = 0;
+        for (size_t j = 0; j < iv.size(); ++j) {
+            if (out.empty() || out.back() != iv[j].L) out.push_back(iv[j].L);
+            const int q = iv[j].extra;
+            for (int s = 1; s <= q; ++s) {
+                double x = iv[j].L + (iv[j].H - iv[j].L) * ((double)s / (double)(q + 1));
+                if (!(x > out.back())) x = std::nextafter(out.back(), inf);
+                if (!(x < iv[j].H)) { left_over += q - s + 1; break; }      // no double left inside the bracket
+                out.push_back(x);
+            }
+            out.push_back(iv[j].H);
+        }
+        // (edges a bracket could not take go above the top one, a range apart: they cut nothing that matters)
+        for (int s = 0; s < left_over; ++s) out.push_back(out.back() + std::max(range, std::fabs(out.back())));
+        if ((int)out.size() != B + 1) fail("refine_star_edges: internal error: edge count");
+        for (int b = 0; b <= B; ++b) {
+            if (!std::isfinite(out[b]) || (b > 0 && !(out[b] > out[b - 1]))) fail("refine_star_edges: the next edges of star " + std::to_string(i) + " do not ascend");
+            ne[b] = out[b];
+        }
+    }
+}
+
+StarIntervals star_intervals(const StarBinsFn &bins, long n_stars, long n_rows, int n_bins, double max_mass, const std::vector<double> &levels, double tol,
+                             int max_passes)
+{
+    const int B = n_bins, m = (int)levels.size();
+    check_levels(levels.data(), m, B, "star_intervals");
+    if (max_passes < 1) fail("star_intervals: maxPasses must be positive");
+    if (!(max_mass > 0.0) || !std::isfinite(max_mass)) fail("star_intervals: the largest mass must be positive");
+    StarIntervals r;
+    r.n_levels = m; r.n_stars = n_stars;
+    const size_t nm = (size_t)n_stars * m;
+    r.member.assign(n_stars, 0.0); r.value.assign(nm, 0.0); r.lo.assign(nm, 0.0); r.hi.assign(nm, 0.0);
+    r.is_final.assign(nm, 0); r.passes.assign(n_stars, 0); r.flags.assign(n_stars, 0);
+    std::vector<double> edges((size_t)n_stars * (B + 1)), next(edges.size()), acc((size_t)n_stars * (B + 3)), below(nm), inside(nm);
+    for (long i = 0; i < n_stars; ++i)
+        for (int b = 0; b <= B; ++b) edges[(size_t)i * (B + 1) + b] = (2.0 * max_mass) * ((double)b / (double)B);
+    for (int pass = 1; pass <= max_passes; ++pass) {
+        bins(edges.data(), B, acc.data());
+        refine_star_edges(edges.data(), acc.data(), n_stars, B, levels.data(), m, tol, r.lo.data(), r.hi.data(), below.data(), inside.data(), r.value.data(),
+                          r.is_final.data(), r.flags.data(), next.data());
+        bool all = true;
+        for (long i = 0; i < n_stars; ++i) {
+            const bool done = !(r.flags[i] & kSivOpen);
+            if (r.passes[i] == 0 && (done || pass == max_passes)) r.passes[i] = pass;
+            all = all && done;
+            r.member[i] = n_rows > 0 ? acc[(size_t)i * (B + 3) + B + 2] / (double)n_rows : 0.0;
+        }
+        if (all) break;
+        edges.swap(next);
+    }
+    return r;
+}
+
+void star_intervals_table(const StarIntervals &r, double *table)
+{
+    const int m = r.n_levels;
+    const size_t tcol = 3 * (size_t)m + 3;
+    for (long i = 0; i < r.n_stars; ++i) {
+        double *t = table + (size_t)i * tcol;
+        t[0] = r.member[i];
+        for (int l = 0; l < m; ++l) {
+            const size_t o = (size_t)i * m + l;
+            t[1 + 3 * l] = r.value[o]; t[2 + 3 * l] = r.lo[o]; t[3 + 3 * l] = r.hi[o];
+        }
+        t[tcol - 2] = (double)r.passes[i]; t[tcol - 1] = (double)r.flags[i];
+    }
+}
+
+void write_star_intervals(const std::string &path, const std::vector<std::string> &ids, const std::vector<double> &levels, const double *table)
+{
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) fail("cannot write " + path);
+    std::fprintf(f, "id member");
+    for (double a : levels) std::fprintf(f, " q%.12g q%.12g_lo q%.12g_hi", a, a, a);
+    std::fprintf(f, " passes flags\n");
+    const size_t tcol = 3 * levels.size() + 3;
+    for (size_t i = 0; i < ids.size(); ++i) {
+        const double *t = table + i * tcol;
+        std::fprintf(f, "%s", ids[i].c_str());
+        for (size_t c = 0; c + 2 < tcol; ++c) std::fprintf(f, " %.17g", t[c]);
+        std::fprintf(f, " %.0f %.0f\n", t[tcol - 2], t[tcol - 1]);
+    }
+    if (std::fclose(f) != 0) fail("cannot write " + path);
+}
+
+StarIntervalsConfig star_intervals_config(const Settings &st)
+{
+    StarIntervalsConfig c;
+    const std::string q = st.str("starIntervals.quantity", "primary");
+    if (q == "primary") c.quantity = B9_HQ_PRIMARY;
+    else if (q == "secondary") c.quantity = B9_HQ_SECONDARY;
+    else if (q == "system") c.quantity = B9_HQ_SYSTEM;
+    else fail("starIntervals.quantity must be primary, secondary or system, not '" + q + "'");
+    std::string lv = st.str("starIntervals.levels", "0.025,0.16,0.5,0.84,0.975");
+    for (char &ch : lv) if (ch == ',' || ch == '[' || ch == ']') ch = ' ';
+    std::istringstream ls(lv);
+    std::string tok;
+    while (ls >> tok) {
+        char *end = nullptr;
+        const double v = std::strtod(tok.c_str(), &end);
+        if (end == tok.c_str() || *end) fail("starIntervals.levels: '" + tok + "' is not a number");
+        c.levels.push_back(v);
+    }
+    c.tol = st.num("starIntervals.tol", 1e-4);
+    c.max_passes = (int)st.integer("starIntervals.maxPasses", 12);
+    c.K = (int)st.integer("starIntervals.margIsoIncrem", st.integer("sampleMass.margIsoIncrem", 4));
+    c.Q = (int)st.integer("starIntervals.nMassRatios", st.integer("sampleMass.nMassRatios", 4));
+    c.n_pops = (int)st.integer("starIntervals.nPops", 1);
+    check_levels(c.levels.data(), (int)c.levels.size(), B9_SBIN_MAX_BINS, "starIntervals.levels");
+    if (!(c.tol >= 0.0)) fail("starIntervals.tol must not be negative");
+    if (c.max_passes < 1) fail("starIntervals.maxPasses must be positive");
+    if (c.K < 1 || c.Q < 1) fail("margIsoIncrem and nMassRatios must be positive");
+    if (c.n_pops != 1 && c.n_pops != 2) fail("starIntervals.nPops must be 1 or 2");
+    return c;
+}
+
+std::vector<std::string> star_intervals_args(int argc, char **argv)
+{
+    std::vector<std::string> out;
+    for (int i = 0; i < argc; ++i) {
+        std::string a = argv[i];
+        for (const char *name : {"quantity", "nPops"}) {
+            const std::string flag = std::string("--") + name;
+            if (a == flag || a.rfind(flag + "=", 0) == 0)
+                a = std::string("--starIntervals") + (char)std::toupper(name[0]) + (name + 1) + a.substr(flag.size());
         }
         out.push_back(a);
     }

@@ -10,6 +10,7 @@
 
 #include <cstdint>
 #include <map>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -135,6 +136,50 @@ MassFunctionConfig mass_function_config(const Settings &st, double m_wd_up);
 // --minMass / --maxMass belong to simCluster in the shared flag table: massFunction's command line has them renamed to the
 // flags of its own keys (--massFunctionMinMass / --massFunctionMaxMass) before Settings::parse_args sees it
 std::vector<std::string> mass_function_args(int argc, char **argv);
+
+// ---- starIntervals ---------------------------------------------------------------------------------
+// One pass of the per-star refinement: a pure function of that pass's edges [n_stars][n_bins + 1], b9_star_bins' acc
+// [n_stars][n_bins + 3] (below, the bins, at or above, the total) and the levels 0 < a_1 < .. < a_m < 1 (3 m <= n_bins + 1).  The
+// levels are taken on the counted mass C = below + sum bins + above, summed in that order.  Per star and level ([n_stars][m]):
+//   lo, hi     the bracket [lo, hi) of the column in which the cumulative sum first reaches a C, within kSivSlack C (-inf / +inf:
+//              the level lies in `below` / `above`, and the next pass widens the range)
+//   below, inside   the mass below lo and inside the bracket
+//   value      lo + (hi - lo) (a C - below) / inside, the linear interpolation inside the bracket (an open bracket: its finite end)
+//   is_final   hi - lo <= tol max(|lo|, |hi|), or hi is the next double after lo (an open bracket is never final)
+// flags [n_stars]: kSivNoMass: C = 0 -- every value NaN, nothing left to do; kSivOpen: some bracket is not final.
+// next_edges [n_stars][n_bins + 1], strictly ascending: a star without kSivOpen keeps its edges; else every distinct bracket keeps
+// its two ends, and the edges left over are shared evenly among the unfinished brackets as interior points (coinciding brackets
+// share theirs).  Nothing is carried from pass to pass.  Host arithmetic only.
+constexpr int32_t kSivNoMass = 1, kSivOpen = 2;
+constexpr double kSivSlack = 1e-13;        // "reaches a C" means within this much of C: the rounding of the sums (ties go to the lower node)
+void refine_star_edges(const double *edges, const double *acc, long n_stars, int n_bins, const double *levels, int n_levels, double tol,
+                       double *lo, double *hi, double *below, double *inside, double *value, int32_t *is_final, int32_t *flags, double *next_edges);
+// The loop: the first pass's edges are [0, 2 max_mass] cut evenly for every star; `bins` runs one b9_star_bins over all the rows
+// from zeros; it ends when no star has kSivOpen or after max_passes.  passes: the pass at which the star was finished.
+struct StarIntervals {
+    int n_levels = 0;
+    long n_stars = 0;
+    std::vector<double> member, value, lo, hi;      // [n_stars], then [n_stars][n_levels]
+    std::vector<int32_t> is_final, passes, flags;   // [n_stars][n_levels], [n_stars], [n_stars]
+};
+using StarBinsFn = std::function<void(const double *edges, int n_bins, double *acc)>;
+StarIntervals star_intervals(const StarBinsFn &bins, long n_stars, long n_rows, int n_bins, double max_mass, const std::vector<double> &levels, double tol,
+                             int max_passes);
+// -> [n_stars][3 m + 3]: member, then value, lo, hi per level, passes, flags
+void star_intervals_table(const StarIntervals &r, double *table);
+// <base>.starIntervals (docs/FORMATS.md): "id member {q<a> q<a>_lo q<a>_hi} passes flags", one line per star in the order of ids,
+// 17 significant digits
+void write_star_intervals(const std::string &path, const std::vector<std::string> &ids, const std::vector<double> &levels, const double *table);
+// starIntervals' own settings: starIntervals.{quantity, levels, tol, maxPasses, margIsoIncrem, nMassRatios, nPops} (flags --quantity
+// --levels a,b,.. --tol --maxPasses --nPops; --margIsoIncrem / --nMassRatios as sampleMass).
+struct StarIntervalsConfig {
+    int quantity, K, Q, n_pops, max_passes;
+    double tol;
+    std::vector<double> levels;
+};
+StarIntervalsConfig star_intervals_config(const Settings &st);
+// --quantity and --nPops belong to massFunction and simCluster in the shared flag table: they are renamed to starIntervals' own
+std::vector<std::string> star_intervals_args(int argc, char **argv);
 
 // ---- photResiduals ---------------------------------------------------------------------------------
 // b9_phot_resid's star_resid [n_stars][2 + 2 nf] with the catalogue's obs / sigma [n_stars][nf] -> the per-star table

@@ -219,6 +219,59 @@ int b9h_mass_function_settings(int argc, char **argv, double m_wd_up, char *out,
     });
 }
 
+int b9h_refine_star_edges(const double *edges, const double *acc, long n_stars, int n_bins, const double *levels, int n_levels, double tol,
+                          double *lo, double *hi, double *below, double *inside, double *value, int32_t *is_final, int32_t *flags, double *next_edges)
+{
+    return guard([&] {
+        if (n_stars < 0 || !levels || !lo || !hi || !below || !inside || !value || !is_final || (n_stars > 0 && (!edges || !acc || !flags || !next_edges)))
+            throw std::runtime_error("b9h_refine_star_edges: NULL argument");
+        b9h::refine_star_edges(edges, acc, n_stars, n_bins, levels, n_levels, tol, lo, hi, below, inside, value, is_final, flags, next_edges);
+    });
+}
+
+int b9h_star_intervals_table(long n_stars, int n_levels, const double *member, const double *value, const double *lo, const double *hi,
+                             const int32_t *passes, const int32_t *flags, double *table)
+{
+    return guard([&] {
+        if (n_stars < 0 || n_levels < 1 || (n_stars > 0 && (!member || !value || !lo || !hi || !passes || !flags || !table)))
+            throw std::runtime_error("b9h_star_intervals_table: invalid argument");
+        b9h::StarIntervals r;
+        r.n_levels = n_levels; r.n_stars = n_stars;
+        const size_t nm = (size_t)n_stars * n_levels;
+        r.member.assign(member, member + n_stars); r.value.assign(value, value + nm); r.lo.assign(lo, lo + nm); r.hi.assign(hi, hi + nm);
+        r.passes.assign(passes, passes + n_stars); r.flags.assign(flags, flags + n_stars);
+        b9h::star_intervals_table(r, table);
+    });
+}
+
+int b9h_write_star_intervals(const char *path, const char *const *ids, long n_stars, const double *levels, int n_levels, const double *table)
+{
+    return guard([&] {
+        if (!path || n_stars < 0 || n_levels < 1 || !levels || (n_stars > 0 && (!ids || !table))) throw std::runtime_error("b9h_write_star_intervals: invalid argument");
+        b9h::write_star_intervals(path, std::vector<std::string>(ids, ids + n_stars), std::vector<double>(levels, levels + n_levels), table);
+    });
+}
+
+int b9h_star_intervals_settings(int argc, char **argv, char *out, int cap)
+{
+    return guard([&] {
+        if (!out) throw std::runtime_error("b9h_star_intervals_settings: NULL argument");
+        const std::vector<std::string> args = b9h::star_intervals_args(argc, argv);
+        std::vector<char *> av;
+        for (auto &a : args) av.push_back(const_cast<char *>(a.c_str()));
+        b9h::Settings st;
+        st.parse_args((int)av.size(), av.data());
+        const b9h::StarIntervalsConfig c = b9h::star_intervals_config(st);
+        std::string lv;
+        for (size_t l = 0; l < c.levels.size(); ++l) lv += (l ? "," : "") + g17(c.levels[l]);
+        const std::string d = "quantity = " + std::to_string(c.quantity) + "\nlevels = " + lv + "\ntol = " + g17(c.tol) + "\nmaxPasses = " +
+                              std::to_string(c.max_passes) + "\nmargIsoIncrem = " + std::to_string(c.K) + "\nnMassRatios = " + std::to_string(c.Q) +
+                              "\nnPops = " + std::to_string(c.n_pops) + "\n";
+        if ((int)d.size() >= cap) throw std::runtime_error("b9h_star_intervals_settings: output buffer too small");
+        std::memcpy(out, d.c_str(), d.size() + 1);
+    });
+}
+
 int b9h_resid_table(const double *star_resid, const double *obs, const double *sigma, long n_stars, int n_filt, double *table)
 {
     return guard([&] {

@@ -38,6 +38,7 @@ HOST_SYMBOLS = [
     "b9h_sim_draw_systems", "b9h_sim_field_mags", "b9h_scatter", "b9h_sim_settings", "b9h_read_res_rows",
     "b9h_star_table", "b9h_write_star_summary", "b9h_wd_table", "b9h_write_wd_summary",
     "b9h_mass_function_table", "b9h_write_mass_function", "b9h_write_star_mass_hist", "b9h_mass_function_settings",
+    "b9h_refine_star_edges", "b9h_star_intervals_table", "b9h_write_star_intervals", "b9h_star_intervals_settings",
     "b9h_resid_table", "b9h_filter_resid_table", "b9h_write_phot_resid", "b9h_write_filter_resid", "b9h_phot_resid_settings",
     "b9h_pointwise_table", "b9h_score_totals", "b9h_score_compare", "b9h_write_pointwise", "b9h_write_model_score", "b9h_model_score_settings",
 ]
@@ -95,6 +96,10 @@ def load() -> C.CDLL:
     lib.b9h_write_mass_function.argtypes = [C.c_char_p, _dp, C.c_int]
     lib.b9h_write_star_mass_hist.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int, C.c_long]
     lib.b9h_mass_function_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_double, C.c_char_p, C.c_int, _dp]
+    lib.b9h_refine_star_edges.argtypes = [_dp, _dp, C.c_long, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
+    lib.b9h_star_intervals_table.argtypes = [C.c_long, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
+    lib.b9h_write_star_intervals.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int, _dp]
+    lib.b9h_star_intervals_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     lib.b9h_resid_table.argtypes = [_dp, _dp, _dp, C.c_long, C.c_int, _dp]
     lib.b9h_filter_resid_table.argtypes = [_dp, C.c_long, C.c_int, _dp]
     lib.b9h_write_phot_resid.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, C.POINTER(C.c_char_p), C.c_int, _dp]
@@ -423,6 +428,90 @@ def mass_function_settings(args, m_wd_up: float = 8.0):
         k, v = line.split(" = ")
         d[k] = float(v) if k in ("minMass", "maxMass") else int(v)
     return d, edges[:d["nBins"] + 1].copy()
+
+
+STAR_INTERVALS_LEVELS = (0.025, 0.16, 0.5, 0.84, 0.975)
+SIV_NO_MASS, SIV_OPEN = 1, 2
+
+
+def refine_star_edges(edges, acc, levels=STAR_INTERVALS_LEVELS, tol: float = 1e-4) -> dict:
+    """b9h_refine_star_edges: one pass of the per-star refinement, a pure function of that pass's edges [n, B + 1], b9_star_bins'
+    acc [n, B + 3] and the levels.  Returns lo, hi, below, inside, value, final [n, m], flags [n] (SIV_*) and next_edges [n, B + 1]."""
+    edges = np.ascontiguousarray(edges, dtype=np.float64)
+    n, ne = edges.shape
+    acc = np.ascontiguousarray(acc, dtype=np.float64).reshape(n, ne + 2)
+    lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    m = len(lv)
+    out = {k: np.zeros((n, m)) for k in ("lo", "hi", "below", "inside", "value")}
+    fin, flags, nxt = np.zeros((n, m), dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros((n, ne))
+    _check(load().b9h_refine_star_edges(edges.ctypes.data_as(_dp), acc.ctypes.data_as(_dp), n, ne - 1, lv.ctypes.data_as(_dp), m, float(tol),
+                                        *[out[k].ctypes.data_as(_dp) for k in ("lo", "hi", "below", "inside", "value")],
+                                        fin.ctypes.data_as(_ip), flags.ctypes.data_as(_ip), nxt.ctypes.data_as(_dp)))
+    out.update(final=fin, flags=flags, next_edges=nxt)
+    return out
+
+
+def star_intervals(engine, rows, quantity: int = abi.HQ_PRIMARY, levels=STAR_INTERVALS_LEVELS, tol: float = 1e-4, max_passes: int = 12,
+                   n_bins: int = abi.SBIN_MAX_BINS) -> dict:
+    """Every star's quantiles of `quantity` at `levels` over `rows`, exactly: loops engine.star_bins (b9_star_bins; anything
+    with star_bins(rows, edges, quantity), n_stars and max_mass serves) and refine_star_edges until every bracket is final or
+    max_passes is reached.  The first pass's edges are [0, 2 engine.max_mass] cut evenly for every star.  Returns levels, member [n],
+    value, lo, hi, final [n, m], passes [n] (the pass at which the star was finished), flags [n] (SIV_*), n_passes, edges (the last)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+    n, B = int(engine.n_stars), int(n_bins)
+    if max_passes < 1:
+        raise ValueError("max_passes must be positive")
+    edges = np.tile((2.0 * float(engine.max_mass)) * (np.arange(B + 1, dtype=np.float64) / float(B)), (n, 1))
+    passes = np.zeros(n, dtype=np.int32)
+    for k in range(1, int(max_passes) + 1):
+        acc = engine.star_bins(rows, edges, quantity)
+        r = refine_star_edges(edges, acc, levels, tol)
+        done = (r["flags"] & SIV_OPEN) == 0
+        passes[(passes == 0) & (done | (k == max_passes))] = k
+        if done.all():
+            break
+        if k < max_passes:
+            edges = r["next_edges"]
+    member = acc[:, B + 2] / rows.shape[0] if rows.shape[0] else np.zeros(n)
+    return dict(levels=np.array(levels, dtype=np.float64), member=member, value=r["value"], lo=r["lo"], hi=r["hi"], final=r["final"],
+                passes=passes, flags=r["flags"], n_passes=k, edges=edges, acc=acc)
+
+
+def star_intervals_table(res: dict) -> np.ndarray:
+    """b9h_star_intervals_table: star_intervals' result -> [n, 3 m + 3]: member, then value, lo, hi per level, passes, flags."""
+    n, m = res["value"].shape
+    c = lambda a, t: np.ascontiguousarray(a, dtype=t)      # noqa: E731
+    member, value, lo, hi = (c(res[k], np.float64) for k in ("member", "value", "lo", "hi"))
+    passes, flags = c(res["passes"], np.int32), c(res["flags"], np.int32)
+    out = np.zeros((n, 3 * m + 3))
+    _check(load().b9h_star_intervals_table(n, m, member.ctypes.data_as(_dp), value.ctypes.data_as(_dp), lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp),
+                                           passes.ctypes.data_as(_ip), flags.ctypes.data_as(_ip), out.ctypes.data_as(_dp)))
+    return out
+
+
+def write_star_intervals(path: str, ids, levels, table) -> None:
+    """b9h_write_star_intervals: the .starIntervals file of star_intervals_table's table [len(ids), 3 m + 3]."""
+    lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    table = np.ascontiguousarray(table, dtype=np.float64).reshape(len(ids), 3 * len(lv) + 3)
+    arr = (C.c_char_p * len(ids))(*[str(i).encode() for i in ids])
+    _check(load().b9h_write_star_intervals(path.encode(), arr, len(ids), lv.ctypes.data_as(_dp), len(lv), table.ctypes.data_as(_dp)))
+
+
+def read_star_intervals(path: str):
+    """(ids, columns, table [n, 3 m + 3]) of a .starIntervals file."""
+    return read_table_file(path, "id")
+
+
+def star_intervals_settings(args) -> dict:
+    """starIntervals' settings as the program parses `args` (flags, --config file): a dict of its keys (levels: a tuple)."""
+    argv = (C.c_char_p * (len(args) + 1))(b"starIntervals", *[str(a).encode() for a in args])
+    buf = C.create_string_buffer(4096)
+    _check(load().b9h_star_intervals_settings(len(args) + 1, argv, buf, 4096))
+    d = {}
+    for line in buf.value.decode().splitlines():
+        k, v = line.split(" = ")
+        d[k] = tuple(float(x) for x in v.split(",")) if k == "levels" else float(v) if k == "tol" else int(v)
+    return d
 
 
 def read_table_file(path: str, first: str):

@@ -520,6 +520,37 @@ int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quan
                  double *row_hist  /* host [n_rows][n_bins + 1], out,    may be NULL */);
 
 /*
+ * Per-star bins over a saved chain (the starIntervals counterpart).  Added in ABI 6 without a version change, as its siblings
+ * were: purely additive.  b9_mass_hist bins every star on one shared set of edges; here star i has its OWN strictly ascending
+ * finite edges e_i0 < ... < e_iB (1 <= B = n_bins <= B9_SBIN_MAX_BINS), so that a host can narrow each star's bins around its own
+ * quantile levels pass by pass (base9_host.h: b9h_refine_star_edges) and end with brackets that provably contain them.
+ *
+ * Definition.  Grid, terms, L, w = exp(t - L), the membership p, the pruning and the node value v per `quantity` are exactly
+ * b9_mass_hist's.  Row r adds to star i
+ *     x[0]     = p sum_{v < e_i0} w                 (below)
+ *     x[1 + b] = p sum_{e_ib <= v < e_i,b+1} w      (bin b, closed on the left)
+ *     x[B + 1] = p sum_{v >= e_iB} w                (at or above)
+ *     x[B + 2] = p                                  (the total)
+ * Under B9_HQ_SECONDARY the nodes with j = 0 and the WD-stage stars enter no column but the total.  Where b9_star_moments adds
+ * nothing (a row outside the grid, a star with no live node) every entry is 0.
+ *
+ * acc (host, [n_stars][n_bins + 3], the caller's star order, in/out): acc + x_r, one plain add per row in ascending row order;
+ * flags = 0 starts from zeros, B9_SBIN_CONTINUE from the caller's values.  The same bits for the call's own chunking (at most
+ * 32 rows at a time), for any split of the rows over continued calls, for a repeated call and after any other call on the
+ * context.  A star's line depends on that star's edges and data alone.  With the same edges for every star, acc[:, 1 .. B] and
+ * acc[:, B + 2] are bit for bit b9_mass_hist's star_hist[:, 0 .. B - 1] and star_hist[:, B]; acc[:, B + 2] is b9_star_moments'
+ * B9_MOM_MEMBER.  Synchronous; host pointers.  B9_ERR_INVALID (acc untouched; checked on the host before anything is launched)
+ * for n_bins outside 1 .. B9_SBIN_MAX_BINS, an unknown quantity, n_rows < 1, NULL pointers, or any star's edges not finite or
+ * not strictly ascending; B9_ERR_STATE while a sampler block is outstanding; B9_ERR_CAPACITY as its siblings.  The call uses
+ * buffers of its own: a B9_BLOCK_CONTINUE block enqueued after it gives the same bits as one enqueued without it.
+ */
+#define B9_SBIN_MAX_BINS 30
+#define B9_SBIN_CONTINUE 1
+int b9_star_bins(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quantity,
+                 const double *edges /* host [n_stars][n_bins + 1], caller's star order */, int32_t n_bins, int32_t flags,
+                 double *acc /* host [n_stars][n_bins + 3], in/out */);
+
+/*
  * Exact per-filter posterior-predictive residuals over a saved chain (the photResiduals counterpart).  Added in ABI 6 without a
  * version change, as b9_star_moments and b9_mass_hist were: purely additive.  Where those calls say what the fit implies for a
  * star's masses, this one says what it implies for the star's MAGNITUDES, filter by filter, and how far the observed ones lie

@@ -131,6 +131,25 @@ int b9h_mass_function_table(const double *row_hist, long n_rows, const double *e
 int b9h_write_mass_function(const char *path, const double *table, int n_bins);
 int b9h_write_star_mass_hist(const char *path, const char *const *ids, long n_stars, const double *star_hist, int n_bins, long n_rows);
 int b9h_mass_function_settings(int argc, char **argv, double m_wd_up, char *out, int cap, double *edges);
+/* starIntervals.  b9h_refine_star_edges: one pass of the per-star refinement, a pure function of that pass's edges
+ * [n_stars][n_bins + 1], b9_star_bins' acc [n_stars][n_bins + 3] and the levels 0 < a_1 < .. < a_m < 1 (3 m <= n_bins + 1), taken on
+ * the counted mass C = below + sum bins + above.  Per star and level ([n_stars][n_levels]): the bracket [lo, hi) of the column in
+ * which the cumulative sum first reaches a C, within 1e-13 C: the rounding of the sums, so that a level exactly between two nodes
+ * goes to the lower one in every pass (-inf / +inf where that is `below` / `above`), the mass below lo and inside the
+ * bracket, value = the linear interpolation inside it (an open bracket: its finite end), and is_final: hi - lo <= tol max(|lo|,
+ * |hi|) or hi the next double after lo.  flags [n_stars]: 1 = C is 0 (values NaN), 2 = some bracket is not final.  next_edges
+ * [n_stars][n_bins + 1], strictly ascending: a finished star keeps its edges; else every distinct bracket keeps its ends (an
+ * open one widened) and the unfinished ones share the remaining edges evenly.
+ * b9h_star_intervals_table: -> [n_stars][3 n_levels + 3]: member, then value, lo, hi per level, passes, flags.
+ * b9h_write_star_intervals: the file <base>.starIntervals (docs/FORMATS.md) of that table, 17 significant digits.
+ * b9h_star_intervals_settings: starIntervals' command line (argv[0] is skipped) and YAML parsed as the program parses them --
+ * "key = value" lines of quantity (0 / 1 / 2), levels (comma-separated), tol, maxPasses, margIsoIncrem, nMassRatios, nPops. */
+int b9h_refine_star_edges(const double *edges, const double *acc, long n_stars, int n_bins, const double *levels, int n_levels, double tol,
+                          double *lo, double *hi, double *below, double *inside, double *value, int32_t *is_final, int32_t *flags, double *next_edges);
+int b9h_star_intervals_table(long n_stars, int n_levels, const double *member, const double *value, const double *lo, const double *hi,
+                             const int32_t *passes, const int32_t *flags, double *table);
+int b9h_write_star_intervals(const char *path, const char *const *ids, long n_stars, const double *levels, int n_levels, const double *table);
+int b9h_star_intervals_settings(int argc, char **argv, char *out, int cap);
 /* photResiduals.  b9h_resid_table: b9_phot_resid's star_resid [n_stars][2 + 2 n_filt] with the catalogue's obs and sigma
  * [n_stars][n_filt] (sigma <= 0: filter unused) -> the per-star table [n_stars][2 + 4 n_filt]: rows, member = acc[1] / rows,
  * then per filter predMag = c + acc[2 + 2f] / acc[1] (c = obs for a used filter, else 0), predSd = sqrt(max(0, acc[3 + 2f] / acc[1]

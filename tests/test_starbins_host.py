@@ -1,0 +1,228 @@
+"""The host side of starIntervals without a GPU: b9h_refine_star_edges and hostlib.star_intervals driven by the numpy statement
+tests/starbins_ref.py in the place of the device, the edges the refinement emits, the power of the comparators
+(tests/starbins_check.py) against six mutated references, the table and the file, the program's flags and YAML keys."""
+import functools
+
+import numpy as np
+import pytest
+
+import masshist_ref as hr
+import starbins_check as sc
+import starbins_ref as sr
+from base_amd import abi, hostlib, synth
+from conftest import build_problem
+
+K, Q = 2, 2
+LEVELS = hostlib.STAR_INTERVALS_LEVELS
+
+
+@functools.lru_cache(maxsize=None)
+def case():
+    """dsed, 5 filters, 60 stars (WD-stage among them), one population, 2 x 2 grid, 12 rows; the reference's nodes, built once."""
+    pack_d, cl, _, _, _, _ = build_problem("dsed", 5, n_stars=60, wd_frac=0.1, n_y=3, seed=12)
+    rows = synth.walker_params(cl["truth"], 12, seed=3, scale=0.3)
+    nodes = hr.nodes_of_rows(pack_d, cl, rows, 1, K, Q)
+    return pack_d, cl, rows, nodes, max(float(np.max(pack_d["mass"])), float(pack_d["m_wd_up"]))
+
+
+class PointsEngine:
+    """Stars given as explicit node values and masses: what hostlib.star_intervals needs of an engine."""
+
+    def __init__(self, stars, max_mass):
+        self.stars, self.n_stars, self.max_mass = stars, len(stars), max_mass
+
+    def star_bins(self, rows, edges, quantity=0, acc=None):
+        B = edges.shape[1] - 1
+        out = np.zeros((self.n_stars, B + 3))
+        for i, (v, w) in enumerate(self.stars):
+            v, w = np.asarray(v, dtype=np.float64), np.asarray(w, dtype=np.float64)
+            out[i, :B + 2] = np.bincount(np.searchsorted(edges[i], v, side="right"), weights=w, minlength=B + 2)
+            out[i, B + 2] = w.sum()
+        return out
+
+
+def check_edges(e, B):
+    assert e.shape[1] == B + 1 and np.all(np.isfinite(e)) and np.all(np.diff(e, axis=1) > 0)
+
+
+# ---- 1. the refinement, the numpy reference in the place of the device -----------------------------------------------------------
+@pytest.mark.parametrize("quantity", [hr.PRIMARY, hr.SECONDARY, hr.SYSTEM])
+def test_star_intervals_on_the_reference(quantity):
+    pack_d, cl, rows, nodes, max_mass = case()
+    eng = sr.NumpyEngine(pack_d, cl, 1, K, Q, nodes, max_mass)
+    res = hostlib.star_intervals(eng, rows, quantity)
+    assert res["n_passes"] == eng.calls <= 12
+    has = sc.assert_brackets(cl, nodes, quantity, LEVELS, res["lo"], res["hi"], res["final"], 1e-4, f"quantity {quantity}")
+    good = has & res["final"].all(axis=1) & (res["lo"][:, 1] < res["hi"][:, 3])
+    print(f"{int(good.sum())} of {int(has.sum())} stars final with lo(16 %) < hi(84 %); passes used {np.bincount(res['passes'])}")
+    assert has.sum() >= 45 and good.sum() >= 0.9 * has.sum()
+    assert np.all(res["flags"][~has] == hostlib.SIV_NO_MASS) and np.isnan(res["value"][~has]).all()
+    assert np.all((res["value"][has] >= res["lo"][has]) & (res["value"][has] <= res["hi"][has]))
+    check_edges(res["edges"], abi.SBIN_MAX_BINS)
+    # every pass on its own: the brackets of ONE pass on the first edges are the reference's own statement of them
+    e0 = np.tile(2.0 * max_mass * (np.arange(31) / 30.0), (60, 1))
+    acc = eng.star_bins(rows, e0, quantity)
+    r = hostlib.refine_star_edges(e0, acc, LEVELS, 1e-4)
+    lo, hi, C = sr.brackets(e0, acc, LEVELS)
+    assert np.array_equal(r["lo"], lo, equal_nan=True) and np.array_equal(r["hi"], hi, equal_nan=True)
+    target = np.array(LEVELS) * C[C > 0, None]
+    assert np.all(r["below"][C > 0] < target * (1 - 5e-14)) and np.all(r["below"][C > 0] + r["inside"][C > 0] >= target * (1 - 1e-15))
+    check_edges(r["next_edges"], 30)
+
+
+# ---- 2. the edges the refinement emits ---------------------------------------------------------------------------------------
+def test_emitted_edges():
+    """Coinciding brackets, a level in `below` and in `above`, C = 0, a posterior on one node, a bimodal one, edges that are
+    already adjacent doubles: the next edges are strictly ascending and hold B + 1 values, every bracket keeps its ends, and
+    the loop ends with brackets that hold their levels."""
+    B = 30
+    e = np.tile(np.linspace(1.0, 4.0, B + 1), (7, 1))
+    acc = np.zeros((7, B + 3))
+    acc[0, 5] = 2.0                                       # all five levels in one bin: they share its sub-bins
+    acc[1, 0] = 1.0; acc[1, 7] = 1.0                      # the lower levels in `below`
+    acc[2, B + 1] = 3.0                                   # every level in `above`
+    acc[3, B + 2] = 5.0                                   # C = 0 (the total alone: SECONDARY without a counting node)
+    acc[4, 1:B + 1] = 1.0                                 # five distinct brackets
+    acc[5, 3] = 1.0; acc[5, 4] = 1e-9; acc[5, 28] = 1.0   # bimodal: brackets far apart, two of them neighbours
+    for b in range(B + 1):
+        e[6, b] = 2.0 if b == 0 else np.nextafter(e[6, b - 1], np.inf)
+    acc[6, 10] = 1.0                                      # adjacent doubles: final whatever tol is
+    r = hostlib.refine_star_edges(e, acc, LEVELS, 1e-4)
+    nxt = r["next_edges"]
+    check_edges(nxt, B)
+    assert list(r["flags"]) == [2, 2, 2, 1, 2, 2, 0]
+    assert np.all(r["lo"][0] == e[0, 4]) and np.all(r["hi"][0] == e[0, 5])
+    inner = nxt[0][(nxt[0] > e[0, 4]) & (nxt[0] < e[0, 5])]
+    assert nxt[0, 0] == e[0, 4] and nxt[0, B] == e[0, 5] and len(inner) == B - 1
+    np.testing.assert_allclose(np.diff(nxt[0]), (e[0, 5] - e[0, 4]) / B, rtol=1e-9)            # cut evenly
+    assert np.all(r["lo"][1, :3] == -np.inf) and np.all(r["hi"][1, :3] == e[1, 0]) and not r["final"][1, :3].any()
+    assert nxt[1, 0] < e[1, 0] - (e[1, B] - e[1, 0]) and e[1, 0] in nxt[1] and e[1, 6] in nxt[1] and e[1, 7] in nxt[1]
+    assert np.all(r["hi"][2] == np.inf) and np.all(r["lo"][2] == e[2, B]) and nxt[2, 0] == e[2, B] and nxt[2, B] > e[2, B] + (e[2, B] - e[2, 0])
+    assert np.isnan(r["value"][3]).all() and r["final"][3].all() and np.array_equal(nxt[3], e[3])
+    for l in range(5):                                   # five brackets, each with both ends kept
+        assert r["lo"][4, l] in nxt[4] and r["hi"][4, l] in nxt[4]
+    assert len(set(r["lo"][4])) == 5
+    assert r["final"][6].all() and np.array_equal(nxt[6], e[6]) and np.all(r["lo"][6] == e[6, 9]) and np.all(r["hi"][6] == e[6, 10])
+    assert np.all(r["value"][6] >= e[6, 9]) and np.all(r["value"][6] <= e[6, 10])
+    # too many levels for the edges, levels out of order or outside (0, 1): refused
+    for bad in ([0.5, 0.4], [0.0, 0.5], [0.5, 1.0], list(np.linspace(0.05, 0.95, 11))):
+        with pytest.raises(hostlib.HostError):
+            hostlib.refine_star_edges(e, acc, bad, 1e-4)
+    with pytest.raises(hostlib.HostError):
+        hostlib.refine_star_edges(e[:, :3], acc[:, :5], [0.16, 0.84], 1e-4)
+
+
+def test_loop_on_point_masses():
+    """One node; two nodes far apart; a node beyond the first range (the level lies in `above` and the range widens); nodes
+    one ulp apart; no mass; and a tie: ten rows of weight 0.1 on either of two nodes, so that the median falls exactly between
+    them and the sums' rounding (0.1 ten times over is not 1) would decide it -- the slack gives it to the lower node in every
+    pass.  Every bracket ends final around the node that holds its level, within the default passes."""
+    one = 1.2345678901234
+    stars = [([one], [1.0]), ([0.3, 3.1], [0.5, 0.5]), ([50.0, 51.0], [0.3, 0.7]), ([one, np.nextafter(one, np.inf)], [0.4, 0.6]), ([1.0], [0.0]),
+             ([0.7] * 10 + [2.9] * 10, [0.1] * 20)]
+    eng = PointsEngine(stars, 4.0)
+    res = hostlib.star_intervals(eng, np.zeros((1, abi.B9_NPARAM)))
+    check_edges(res["edges"], 30)
+    print("passes used:", res["passes"], "flags:", res["flags"])
+    assert list(res["flags"]) == [0, 0, 0, 0, 1, 0] and res["final"].all() and res["passes"].max() <= 7
+    assert res["lo"][5, 2] <= 0.7 < res["hi"][5, 2] and res["lo"][5, 3] <= 2.9 < res["hi"][5, 3]
+    for i, (v, w) in enumerate(stars[:4]):
+        v, w = np.array(v), np.array(w)
+        for l, a in enumerate(LEVELS):
+            node = v[np.searchsorted(np.cumsum(w) / w.sum(), a, side="left")]
+            lo, hi = res["lo"][i, l], res["hi"][i, l]
+            assert lo <= node < hi and (hi - lo <= 1e-4 * hi or hi == np.nextafter(lo, np.inf)), (i, a)
+            assert lo <= res["value"][i, l] <= hi
+    assert np.isnan(res["value"][4]).all()
+    # tol = 0: only adjacent doubles are final; the single node is pinned to one double within the passes it takes
+    res0 = hostlib.star_intervals(PointsEngine(stars[:1], 4.0), np.zeros((1, abi.B9_NPARAM)), tol=0.0, max_passes=40)
+    assert res0["final"].all() and np.all(res0["lo"] == one) and np.all(res0["hi"] == np.nextafter(one, np.inf))
+    # max_passes reached: the flag says so, the brackets still hold their levels
+    res1 = hostlib.star_intervals(eng, np.zeros((1, abi.B9_NPARAM)), max_passes=1)
+    assert list(res1["flags"][:4]) == [2, 2, 2, 2] and np.all(res1["passes"] == 1) and res1["lo"][0, 2] <= one < res1["hi"][0, 2]
+
+
+# ---- 3. the comparators' power -----------------------------------------------------------------------------------------------
+def test_comparators_reject_mutations():
+    pack_d, cl, rows, nodes, max_mass = case()
+    q, B = hr.SYSTEM, 30
+    edges = sc.own_edges(cl, nodes, q, B)
+    want = sr.accumulate(pack_d, cl, rows, 1, K, Q, q, edges, nodes_by_row=nodes)
+    k, C = sc.bins_with_mass(want)
+    assert (C > 0).sum() >= 50 and (k[C > 0] >= 3).sum() >= 0.9 * (C > 0).sum()
+    sc.assert_star_bins(want.copy(), want, 356, 12, "the reference itself")
+    # an edge AT a node value of star 7: what closes the bins on the right differs exactly there
+    v7, m7 = sr.star_mixture(cl, nodes, 7, q)
+    on_edge = edges.copy()
+    heavy = v7[np.argmax(m7)]                             # (the node that holds most of the star's mass)
+    on_edge[7, max(int(np.searchsorted(on_edge[7], heavy)) - 1, 1)] = heavy
+    assert np.all(np.diff(on_edge[7]) > 0)
+    want_on = sr.accumulate(pack_d, cl, rows, 1, K, Q, q, on_edge, nodes_by_row=nodes)
+    for name, e, ref, kw in (("bins closed on the right", on_edge, want_on, dict(right_closed=True)),
+                             ("membership dropped", edges, want, dict(drop_membership=True)),
+                             ("below folded into bin 0", edges, want, dict(fold_below=True)),
+                             ("normalised over the edge range", edges, want, dict(normalise_in_range=True)),
+                             ("star 20's edges applied to its lane neighbour", edges, want, dict(neighbour_edges=20))):
+        mutated = sr.accumulate(pack_d, cl, rows, 1, K, Q, q, e, nodes_by_row=nodes, **kw)
+        with pytest.raises(AssertionError):
+            sc.assert_star_bins(mutated, ref, 356, 12, name)
+    # the levels taken on the total instead of the counted mass, under SECONDARY: the brackets no longer hold their levels
+    qs = hr.SECONDARY
+    es = sc.own_edges(cl, nodes, qs, B)
+    acc = sr.accumulate(pack_d, cl, rows, 1, K, Q, qs, es, nodes_by_row=nodes)
+    lo, hi, _ = sr.brackets(es, acc, LEVELS)
+    has = sc.assert_brackets(cl, nodes, qs, LEVELS, lo, hi, label="SECONDARY, on the counted mass")
+    assert has.sum() >= 40
+    lo_t, hi_t, _ = sr.brackets(es, acc, LEVELS, on_total=True)
+    lo_t[~has], hi_t[~has] = np.nan, np.nan
+    with pytest.raises(AssertionError):
+        sc.assert_brackets(cl, nodes, qs, LEVELS, lo_t, hi_t, label="SECONDARY, on the total")
+    # a bracket reported final that is not
+    with pytest.raises(AssertionError):
+        sc.assert_brackets(cl, nodes, qs, LEVELS, lo, hi, np.ones(lo.shape, dtype=np.int32), 1e-9, label="all reported final")
+
+
+# ---- 4. the table and the file -------------------------------------------------------------------------------------------------
+def test_table_and_file_round_trip(tmp_path):
+    pack_d, cl, rows, nodes, max_mass = case()
+    res = hostlib.star_intervals(sr.NumpyEngine(pack_d, cl, 1, K, Q, nodes, max_mass), rows, hr.SECONDARY, (0.16, 0.5, 0.84), 1e-3, 3)
+    tab = hostlib.star_intervals_table(res)
+    assert tab.shape == (60, 12)
+    assert np.array_equal(tab[:, 0], res["member"]) and np.array_equal(tab[:, 10], res["passes"]) and np.array_equal(tab[:, 11], res["flags"])
+    for l in range(3):
+        for c, k in enumerate(("value", "lo", "hi")):
+            assert np.array_equal(tab[:, 1 + 3 * l + c], res[k][:, l], equal_nan=True)
+    assert np.isnan(tab[:, 1]).any() and np.isfinite(tab[:, 1]).sum() >= 40            # stars with and without counted mass
+    ids = [f"s{i}" for i in range(60)]
+    path = str(tmp_path / "x.starIntervals")
+    hostlib.write_star_intervals(path, ids, (0.16, 0.5, 0.84), tab)
+    got_ids, cols, got = hostlib.read_star_intervals(path)
+    assert got_ids == ids and cols == ["member", "q0.16", "q0.16_lo", "q0.16_hi", "q0.5", "q0.5_lo", "q0.5_hi", "q0.84", "q0.84_lo", "q0.84_hi", "passes", "flags"]
+    assert np.array_equal(got, tab, equal_nan=True)                                    # 17 significant digits: the table's bits
+    open_tab = tab.copy(); open_tab[0, 2], open_tab[0, 3] = -np.inf, np.inf           # an open bracket survives the file too
+    hostlib.write_star_intervals(path, ids, (0.16, 0.5, 0.84), open_tab)
+    assert np.array_equal(hostlib.read_star_intervals(path)[2], open_tab, equal_nan=True)
+
+
+# ---- 5. the program's flags and YAML keys -------------------------------------------------------------------------------------
+def test_cli_flags_and_yaml_keys(tmp_path):
+    d = hostlib.star_intervals_settings([])
+    assert d == dict(quantity=0, levels=LEVELS, tol=1e-4, maxPasses=12, margIsoIncrem=4, nMassRatios=4, nPops=1)
+    d = hostlib.star_intervals_settings(["--quantity", "system", "--levels", "0.1,0.5,0.9", "--tol", "1e-6", "--maxPasses", "20", "--nPops", "2",
+                                         "--margIsoIncrem", "3", "--nMassRatios=5"])
+    assert d == dict(quantity=2, levels=(0.1, 0.5, 0.9), tol=1e-6, maxPasses=20, margIsoIncrem=3, nMassRatios=5, nPops=2)
+    y = tmp_path / "s.yaml"
+    y.write_text("starIntervals:\n  quantity: secondary\n  levels: \"0.25, 0.75\"\n  tol: 0.001\n  maxPasses: 5\n  margIsoIncrem: 2\n  nMassRatios: 6\n  nPops: 2\n"
+                 "massFunction:\n  quantity: system\n  nPops: 1\nsampleMass:\n  margIsoIncrem: 7\n")
+    d = hostlib.star_intervals_settings(["--config", str(y)])
+    assert d == dict(quantity=1, levels=(0.25, 0.75), tol=0.001, maxPasses=5, margIsoIncrem=2, nMassRatios=6, nPops=2)
+    assert hostlib.star_intervals_settings(["--config", str(y), "--quantity=primary"])["quantity"] == 0      # a flag overrides the file
+    y.write_text("sampleMass:\n  margIsoIncrem: 7\n  nMassRatios: 3\n")
+    d = hostlib.star_intervals_settings(["--config", str(y)])
+    assert d["margIsoIncrem"] == 7 and d["nMassRatios"] == 3                            # the grid defaults to sampleMass's
+    for bad in (["--quantity", "total"], ["--levels", "0.5,0.4"], ["--levels", "0.5,x"], ["--levels", "0,0.5"], ["--tol", "-1"], ["--maxPasses", "0"],
+                ["--nPops", "3"], ["--levels", ",".join(str(x) for x in np.linspace(0.05, 0.95, 11))]):
+        with pytest.raises(hostlib.HostError):
+            hostlib.star_intervals_settings(bad)
+    # massFunction keeps its own --quantity and --nPops
+    assert hostlib.mass_function_settings(["--quantity", "secondary"])[0]["quantity"] == 1
