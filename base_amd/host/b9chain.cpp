@@ -1,0 +1,738 @@
+// b9chain.cpp -- see b9chain.hpp.  File formats: docs/FORMATS.md.
+#include "b9chain.hpp"
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <limits>
+#include <sstream>
+#include <stdexcept>
+
+namespace b9h {
+
+namespace {
+
+[[noreturn]] void fail(const std::string &msg) { throw std::runtime_error(msg); }
+
+// B9_HQ_* of a <section>.quantity
+int quantity_id(const Settings &st, const std::string &section)
+{
+    const std::string q = st.str(section + ".quantity", "primary");
+    if (q == "primary") return B9_HQ_PRIMARY;
+    if (q == "secondary") return B9_HQ_SECONDARY;
+    if (q == "system") return B9_HQ_SYSTEM;
+    fail(section + ".quantity must be primary, secondary or system, not '" + q + "'");
+}
+
+ChainGrid checked(ChainGrid g)
+{
+    if (g.K < 1 || g.Q < 1) fail("margIsoIncrem and nMassRatios must be positive");
+    return g;
+}
+
+// names, all printed with one format
+std::vector<TableColumn> columns(std::initializer_list<const char *> names, const char *fmt)
+{
+    std::vector<TableColumn> c;
+    for (const char *n : names) c.push_back({n, fmt});
+    return c;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// settings
+// ---------------------------------------------------------------------------------------------
+int chain_n_pops(const Settings &st, const std::string &section)
+{
+    const long n_pops = st.integer(section + ".nPops", 1);
+    if (n_pops != 1 && n_pops != 2) fail(section + ".nPops must be 1 or 2");
+    return (int)n_pops;
+}
+
+ChainGrid chain_grid(const Settings &st, const std::string &section)
+{
+    const int n_pops = chain_n_pops(st, section);
+    return checked({n_pops, (int)st.integer(section + ".margIsoIncrem", st.integer("sampleMass.margIsoIncrem", 4)),
+                    (int)st.integer(section + ".nMassRatios", st.integer("sampleMass.nMassRatios", 4))});
+}
+
+ChainGrid sample_mass_grid(const Settings &st)
+{
+    return checked({1, (int)st.integer("sampleMass.margIsoIncrem", 4), (int)st.integer("sampleMass.nMassRatios", 4)});
+}
+
+long wd_mass_nodes(const Settings &st, const std::string &section)
+{
+    const long nodes = st.integer(section + ".nMassNodes", st.integer("sampleWDMass.nMassNodes", 512));
+    if (nodes < 1 || nodes > 2147483647l) fail("nMassNodes must be a positive 32-bit number");
+    return nodes;
+}
+
+const ProgramFlags kMassFunctionFlags = {{"minMass", "massFunctionMinMass", false}, {"maxMass", "massFunctionMaxMass", false}};
+const ProgramFlags kStarIntervalsFlags = {{"quantity", "starIntervalsQuantity", false}, {"nPops", "starIntervalsNPops", false}};
+const ProgramFlags kPhotResidFlags = {{"perStar", "photResidualsPerStar", true}, {"nPops", "photResidualsNPops", false}};
+const ProgramFlags kModelScoreFlags = {{"perRow", "modelScorePerRow", true}, {"nPops", "modelScoreNPops", false}};
+
+PhotResidConfig phot_resid_config(const Settings &st) { return {st.integer("photResiduals.perStar", 0) != 0}; }
+
+ModelScoreConfig model_score_config(const Settings &st) { return {st.integer("modelScore.perRow", 0) != 0, st.str("modelScore.compareTo", "")}; }
+
+int model_score_tail_len(long n_rows)
+{
+    const double s = (double)n_rows;
+    return (int)std::min(256.0, std::min(std::floor(s / 5.0), std::ceil(3.0 * std::sqrt(s))) + 1.0);
+}
+
+// ---------------------------------------------------------------------------------------------
+// files
+// ---------------------------------------------------------------------------------------------
+void write_table(const std::string &path, const char *label_name, const std::vector<std::string> *labels, const std::vector<TableColumn> &cols,
+                 long n_lines, const double *values, size_t stride)
+{
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) fail("cannot write " + path);
+    const char *first = labels ? " " : "";                   // what stands before a line's first column
+    if (labels) std::fprintf(f, "%s", label_name);
+    for (size_t c = 0; c < cols.size(); ++c) std::fprintf(f, "%s%s", c ? " " : first, cols[c].name.c_str());
+    std::fprintf(f, "\n");
+    for (long i = 0; i < n_lines; ++i) {
+        if (labels) std::fprintf(f, "%s", (*labels)[(size_t)i].c_str());
+        for (size_t c = 0; c < cols.size(); ++c) {
+            const char *fmt = cols[c].fmt;
+            const double v = values[(size_t)i * stride + c];
+            std::fputs(c ? " " : first, f);
+            if (fmt[std::strlen(fmt) - 1] == 'd') std::fprintf(f, fmt, (long)v);
+            else std::fprintf(f, fmt, v);
+        }
+        std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) fail("cannot write " + path);
+}
+
+// ---------------------------------------------------------------------------------------------
+// starSummary
+// ---------------------------------------------------------------------------------------------
+void star_table(const double *acc, long n_stars, double *table)
+{
+    for (long i = 0; i < n_stars; ++i) {
+        const double *a = acc + (size_t)i * B9_MOM_N;
+        double *t = table + (size_t)i * kStarTableCols;
+        for (int c = 0; c < kStarTableCols; ++c) t[c] = 0.0;
+        t[0] = a[B9_MOM_ROWS];
+        if (a[B9_MOM_ROWS] > 0.0) t[1] = a[B9_MOM_MEMBER] / a[B9_MOM_ROWS];
+        if (!(a[B9_MOM_MEMBER] > 0.0)) continue;             // no membership weight: every derived value is 0
+        const double w = a[B9_MOM_MEMBER];
+        t[2] = a[B9_MOM_M1] / w;
+        t[3] = std::sqrt(std::max(0.0, a[B9_MOM_M1SQ] / w - t[2] * t[2]));
+        t[4] = a[B9_MOM_Q] / w;
+        t[5] = std::sqrt(std::max(0.0, a[B9_MOM_QSQ] / w - t[4] * t[4]));
+        t[6] = a[B9_MOM_BINARY] / w;
+        t[7] = a[B9_MOM_POP1] / w;
+    }
+}
+
+void write_star_summary(const std::string &path, const std::vector<std::string> &ids, const double *acc, int n_pops)
+{
+    const long n = (long)ids.size();
+    std::vector<double> table((size_t)n * kStarTableCols);
+    star_table(acc, n, table.data());
+    std::vector<TableColumn> cols = columns({"rows", "member", "mass", "massSd", "massRatio", "massRatioSd", "pBinary", "pPop2"}, "%.6f");
+    cols[0].fmt = "%.0f";
+    if (n_pops != 2) cols.pop_back();
+    write_table(path, "id", &ids, cols, n, table.data(), kStarTableCols);
+}
+
+// ---------------------------------------------------------------------------------------------
+// wdSummary
+// ---------------------------------------------------------------------------------------------
+void wd_table(const double *acc, long n_wd, double *table)
+{
+    for (long i = 0; i < n_wd; ++i) {
+        const double *a = acc + (size_t)i * B9_WDM_N;
+        double *t = table + (size_t)i * kWdTableCols;
+        for (int c = 0; c < kWdTableCols; ++c) t[c] = 0.0;
+        t[0] = a[B9_WDM_ROWS];
+        if (a[B9_WDM_ROWS] > 0.0) t[1] = a[B9_WDM_MEMBER] / a[B9_WDM_ROWS];
+        if (!(a[B9_WDM_MEMBER] > 0.0)) continue;             // no membership weight: every further value is 0
+        const double w = a[B9_WDM_MEMBER], wc = a[B9_WDM_COOLED];
+        t[2] = wc / w;
+        t[3] = a[B9_WDM_M1] / w;
+        t[4] = std::sqrt(std::max(0.0, a[B9_WDM_M1SQ] / w - t[3] * t[3]));
+        t[15] = a[B9_WDM_POP1] / w;
+        if (!(wc > 0.0)) continue;                           // no cooled weight: the derived values' columns are 0
+        for (int q = 0; q < 5; ++q) {
+            const double mean = a[B9_WDM_WDMASS + 2 * q] / wc;
+            t[5 + 2 * q] = mean;
+            t[6 + 2 * q] = std::sqrt(std::max(0.0, a[B9_WDM_WDMASS_SQ + 2 * q] / wc - mean * mean));
+        }
+    }
+}
+
+void write_wd_summary(const std::string &path, const std::vector<std::string> &ids, const double *acc, int n_pops)
+{
+    const long n = (long)ids.size();
+    std::vector<double> table((size_t)n * kWdTableCols);
+    wd_table(acc, n, table.data());
+    std::vector<TableColumn> cols = columns({"rows", "member", "pCooled", "zamsMass", "zamsMassSd", "wdMass", "wdMassSd", "precLogAge", "precLogAgeSd",
+                                             "logCoolAge", "logCoolAgeSd", "logTeff", "logTeffSd", "logg", "loggSd", "pPop2"}, "%.6f");
+    cols[0].fmt = "%.0f";
+    if (n_pops != 2) cols.pop_back();
+    write_table(path, "id", &ids, cols, n, table.data(), kWdTableCols);
+}
+
+// ---------------------------------------------------------------------------------------------
+// massFunction
+// ---------------------------------------------------------------------------------------------
+namespace {
+// numpy's default percentile of an ascending sample: linear interpolation between the order statistics around (n - 1) q
+double percentile_sorted(const std::vector<double> &v, double q)
+{
+    const double pos = (double)(v.size() - 1) * q;
+    const size_t lo = (size_t)std::floor(pos), hi = std::min(lo + 1, v.size() - 1);
+    const double t = pos - (double)lo;
+    return v[lo] + (v[hi] - v[lo]) * t;
+}
+}  // namespace
+
+void mass_function_table(const double *row_hist, long n_rows, const double *edges, int n_bins, double *table)
+{
+    const size_t ncol = (size_t)n_bins + 1;
+    std::vector<long> use;
+    for (long r = 0; r < n_rows; ++r)
+        if (row_hist[(size_t)r * ncol + n_bins] > 0.0) use.push_back(r);
+    std::vector<double> v(use.size());
+    for (int b = 0; b < n_bins; ++b) {
+        double *t = table + (size_t)b * kMassFunctionCols;
+        for (int c = 0; c < kMassFunctionCols; ++c) t[c] = 0.0;
+        t[0] = edges[b]; t[1] = edges[b + 1];
+        if (use.empty()) continue;
+        double sum = 0.0;
+        for (size_t k = 0; k < use.size(); ++k) { v[k] = row_hist[(size_t)use[k] * ncol + b]; sum += v[k]; }
+        const double mean = sum / (double)use.size();
+        double ss = 0.0;
+        for (double x : v) ss += (x - mean) * (x - mean);
+        std::sort(v.begin(), v.end());
+        t[2] = mean;
+        t[3] = std::sqrt(ss / (double)use.size());
+        t[4] = percentile_sorted(v, 0.16); t[5] = percentile_sorted(v, 0.50); t[6] = percentile_sorted(v, 0.84);
+        if (edges[b] > 0.0) t[7] = mean / std::log10(edges[b + 1] / edges[b]);
+    }
+}
+
+void write_mass_function(const std::string &path, const double *table, int n_bins)
+{
+    write_table(path, nullptr, nullptr, columns({"lo", "hi", "mean", "sd", "p16", "p50", "p84", "dNdlogM"}, "%.6f"), n_bins, table, kMassFunctionCols);
+}
+
+void write_star_mass_hist(const std::string &path, const std::vector<std::string> &ids, const double *star_hist, int n_bins, long n_rows)
+{
+    std::vector<TableColumn> cols = {{"rows", "%ld"}, {"member", "%.6f"}};
+    for (int b = 0; b < n_bins; ++b) cols.push_back({"bin" + std::to_string(b), "%.6f"});
+    const size_t ncol = (size_t)n_bins + 1, tcol = cols.size();
+    std::vector<double> table(ids.size() * tcol);
+    for (size_t i = 0; i < ids.size(); ++i) {
+        const double *a = star_hist + i * ncol, tot = a[n_bins];
+        double *t = table.data() + i * tcol;
+        t[0] = (double)n_rows;
+        t[1] = n_rows > 0 ? tot / (double)n_rows : 0.0;
+        for (int b = 0; b < n_bins; ++b) t[2 + b] = tot > 0.0 ? a[b] / tot : 0.0;
+    }
+    write_table(path, "id", &ids, cols, (long)ids.size(), table.data(), tcol);
+}
+
+std::vector<double> MassFunctionConfig::edges() const
+{
+    std::vector<double> e((size_t)n_bins + 1);
+    for (int b = 0; b <= n_bins; ++b) {
+        const double t = (double)b / (double)n_bins;
+        e[b] = linear ? min_mass + (max_mass - min_mass) * t : min_mass * std::pow(max_mass / min_mass, t);
+    }
+    e[0] = min_mass; e[n_bins] = max_mass;
+    for (int b = 0; b < n_bins; ++b)
+        if (!(e[b + 1] > e[b])) fail("massFunction: the bins are too narrow to tell their edges apart");
+    return e;
+}
+
+MassFunctionConfig mass_function_config(const Settings &st, double m_wd_up)
+{
+    MassFunctionConfig c;
+    c.n_bins = (int)st.integer("massFunction.nBins", 24);
+    c.min_mass = st.num("massFunction.minMass", 0.1);
+    c.max_mass = st.num("massFunction.maxMass", m_wd_up);
+    c.linear = st.integer("massFunction.linearBins", 0) != 0;
+    c.per_star = st.integer("massFunction.perStar", 0) != 0;
+    c.quantity = quantity_id(st, "massFunction");
+    if (c.n_bins < 1 || c.n_bins > B9_HIST_MAX_BINS) fail("massFunction.nBins must lie in 1 .. " + std::to_string(B9_HIST_MAX_BINS));
+    if (!std::isfinite(c.min_mass) || !std::isfinite(c.max_mass) || !(c.max_mass > c.min_mass)) fail("massFunction: maxMass must exceed minMass");
+    if (!c.linear && !(c.min_mass > 0.0)) fail("massFunction: log-spaced bins need minMass > 0 (or --linearBins)");
+    return c;
+}
+
+// ---------------------------------------------------------------------------------------------
+// starIntervals
+// ---------------------------------------------------------------------------------------------
+namespace {
+void check_levels(const double *levels, int m, int n_bins, const char *who)
+{
+    if (m < 1 || 3 * m > n_bins + 1) fail(std::string(who) + ": the levels need 3 edges each: at most (n_bins + 1) / 3 of them, at least one");
+    for (int l = 0; l < m; ++l)
+        if (!(levels[l] > 0.0 && levels[l] < 1.0) || (l > 0 && !(levels[l] > levels[l - 1])))
+            fail(std::string(who) + ": the levels must lie strictly inside (0, 1) and ascend strictly");
+}
+}  // namespace
+
+void refine_star_edges(const double *edges, const double *acc, long n_stars, int n_bins, const double *levels, int n_levels, double tol,
+                       double *lo, double *hi, double *below, double *inside, double *value, int32_t *is_final, int32_t *flags, double *next_edges)
+{
+    const int B = n_bins, m = n_levels;
+    if (B < 1) fail("refine_star_edges: n_bins must be positive");
+    check_levels(levels, m, B, "refine_star_edges");
+    if (!(tol >= 0.0)) fail("refine_star_edges: tol must not be negative");
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<double> cum((size_t)B + 2), pts, out;
+    std::vector<int> col(m);
+    for (long i = 0; i < n_stars; ++i) {
+        const double *e = edges + (size_t)i * (B + 1), *a = acc + (size_t)i * (B + 3);
+        double *ne = next_edges + (size_t)i * (B + 1);
+        std::copy(e, e + B + 1, ne);                         // a finished star keeps its edges
+        // the counted mass: below, the bins, at or above, summed in that order (the total column may hold more: B9_HQ_SECONDARY)
+        double c = 0.0;
+        for (int k = 0; k < B + 2; ++k) { c = c + a[k]; cum[k] = c; }
+        const double C = cum[B + 1];
+        flags[i] = 0;
+        if (!(C > 0.0)) {
+            flags[i] = kSivNoMass;
+            for (int l = 0; l < m; ++l) {
+                const size_t o = (size_t)i * m + l;
+                lo[o] = hi[o] = value[o] = nan; below[o] = inside[o] = 0.0; is_final[o] = 1;
+            }
+            continue;
+        }
+        auto col_final = [&](int k) {
+            if (k < 1 || k > B) return false;
+            const double L = e[k - 1], H = e[k];
+            return H - L <= tol * std::max(std::fabs(L), std::fabs(H)) || H == std::nextafter(L, inf);
+        };
+        bool open = false;
+        for (int l = 0; l < m; ++l) {
+            const size_t o = (size_t)i * m + l;
+            const double target = levels[l] * C;
+            // the column in which the cumulative sum first reaches the level -- within kSivSlack C, the rounding of the sums: a
+            // level that falls exactly between two nodes (whole rows on either side: 17 of 34 at the median) is a tie that rounding
+            // would decide one way in one pass and the other way in the next; with the slack every pass takes the lower node
+            int k = 0;
+            while (k < B + 1 && !(cum[k] >= target - kSivSlack * C)) ++k;
+            col[l] = k;
+            lo[o] = k == 0 ? -inf : e[k - 1];
+            hi[o] = k == B + 1 ? inf : e[k];
+            below[o] = k == 0 ? 0.0 : cum[k - 1];
+            inside[o] = a[k];
+            is_final[o] = col_final(k);
+            open = open || !is_final[o];
+            if (k == 0) value[o] = e[0];
+            else if (k == B + 1) value[o] = e[B];
+            else {
+                const double t = a[k] > 0.0 ? std::min(1.0, std::max(0.0, (target - below[o]) / a[k])) : 0.0;
+                value[o] = std::min(hi[o], std::max(lo[o], lo[o] + (hi[o] - lo[o]) * t));
+            }
+        }
+        if (!open) continue;
+        flags[i] = kSivOpen;
+        // the next pass's edges: every distinct bracket keeps its two ends (an open one is widened to twice the range), the
+        // unfinished ones share the remaining edges evenly as interior points
+        const double range = e[B] - e[0];
+        struct Iv { double L, H; bool todo; int extra; };
+        std::vector<Iv> iv;
+        for (int l = 0; l < m; ++l) {
+            if (l > 0 && col[l] == col[l - 1]) continue;    // coinciding brackets share their sub-bins
+            const int k = col[l];
+            if (k == 0) iv.push_back({e[0] - 2.0 * range, e[0], true, 0});
+            else if (k == B + 1) iv.push_back({e[B], e[B] + 2.0 * range, true, 0});
+            else iv.push_back({e[k - 1], e[k], !col_final(k), 0});
+        }
+        int mandatory = 0, todo = 0;
+        for (size_t j = 0; j < iv.size(); ++j) {
+            mandatory += (j > 0 && iv[j].L == iv[j - 1].H) ? 1 : 2;
+            todo += iv[j].todo;
+        }
+        int spare = B + 1 - mandatory;
+        if (spare < todo) fail("refine_star_edges: too few bins for the levels");
+        for (int j = 0, t = 0; j < (int)iv.size(); ++j)
+            if (iv[j].todo) { iv[j].extra = spare / todo + (t < spare % todo); ++t; }
+        out.clear();
+        int left_over = 0;
+        for (size_t j = 0; j < iv.size(); ++j) {
+            if (out.empty() || out.back() != iv[j].L) out.push_back(iv[j].L);
+            const int q = iv[j].extra;
+            for (int s = 1; s <= q; ++s) {
+                double x = iv[j].L + (iv[j].H - iv[j].L) * ((double)s / (double)(q + 1));
+                if (!(x > out.back())) x = std::nextafter(out.back(), inf);
+                if (!(x < iv[j].H)) { left_over += q - s + 1; break; }      // no double left inside the bracket
+                out.push_back(x);
+            }
+            out.push_back(iv[j].H);
+        }
+        // (edges a bracket could not take go above the top one, a range apart: they cut nothing that matters)
+        for (int s = 0; s < left_over; ++s) out.push_back(out.back() + std::max(range, std::fabs(out.back())));
+        if ((int)out.size() != B + 1) fail("refine_star_edges: internal error: edge count");
+        for (int b = 0; b <= B; ++b) {
+            if (!std::isfinite(out[b]) || (b > 0 && !(out[b] > out[b - 1]))) fail("refine_star_edges: the next edges of star " + std::to_string(i) + " do not ascend");
+            ne[b] = out[b];
+        }
+    }
+}
+
+StarIntervals star_intervals(const StarBinsFn &bins, long n_stars, long n_rows, int n_bins, double max_mass, const std::vector<double> &levels, double tol,
+                             int max_passes)
+{
+    const int B = n_bins, m = (int)levels.size();
+    check_levels(levels.data(), m, B, "star_intervals");
+    if (max_passes < 1) fail("star_intervals: maxPasses must be positive");
+    if (!(max_mass > 0.0) || !std::isfinite(max_mass)) fail("star_intervals: the largest mass must be positive");
+    StarIntervals r;
+    r.n_levels = m; r.n_stars = n_stars;
+    const size_t nm = (size_t)n_stars * m;
+    r.member.assign(n_stars, 0.0); r.value.assign(nm, 0.0); r.lo.assign(nm, 0.0); r.hi.assign(nm, 0.0);
+    r.is_final.assign(nm, 0); r.passes.assign(n_stars, 0); r.flags.assign(n_stars, 0);
+    std::vector<double> edges((size_t)n_stars * (B + 1)), next(edges.size()), acc((size_t)n_stars * (B + 3)), below(nm), inside(nm);
+    for (long i = 0; i < n_stars; ++i)
+        for (int b = 0; b <= B; ++b) edges[(size_t)i * (B + 1) + b] = (2.0 * max_mass) * ((double)b / (double)B);
+    for (int pass = 1; pass <= max_passes; ++pass) {
+        bins(edges.data(), B, acc.data());
+        refine_star_edges(edges.data(), acc.data(), n_stars, B, levels.data(), m, tol, r.lo.data(), r.hi.data(), below.data(), inside.data(), r.value.data(),
+                          r.is_final.data(), r.flags.data(), next.data());
+        bool all = true;
+        for (long i = 0; i < n_stars; ++i) {
+            const bool done = !(r.flags[i] & kSivOpen);
+            if (r.passes[i] == 0 && (done || pass == max_passes)) r.passes[i] = pass;
+            all = all && done;
+            r.member[i] = n_rows > 0 ? acc[(size_t)i * (B + 3) + B + 2] / (double)n_rows : 0.0;
+        }
+        if (all) break;
+        edges.swap(next);
+    }
+    return r;
+}
+
+void star_intervals_table(const StarIntervals &r, double *table)
+{
+    const int m = r.n_levels;
+    const size_t tcol = 3 * (size_t)m + 3;
+    for (long i = 0; i < r.n_stars; ++i) {
+        double *t = table + (size_t)i * tcol;
+        t[0] = r.member[i];
+        for (int l = 0; l < m; ++l) {
+            const size_t o = (size_t)i * m + l;
+            t[1 + 3 * l] = r.value[o]; t[2 + 3 * l] = r.lo[o]; t[3 + 3 * l] = r.hi[o];
+        }
+        t[tcol - 2] = (double)r.passes[i]; t[tcol - 1] = (double)r.flags[i];
+    }
+}
+
+void write_star_intervals(const std::string &path, const std::vector<std::string> &ids, const std::vector<double> &levels, const double *table)
+{
+    std::vector<TableColumn> cols = {{"member", "%.17g"}};
+    for (double a : levels) {
+        char q[40];
+        std::snprintf(q, sizeof q, "q%.12g", a);
+        for (const char *end : {"", "_lo", "_hi"}) cols.push_back({std::string(q) + end, "%.17g"});
+    }
+    cols.push_back({"passes", "%.0f"});
+    cols.push_back({"flags", "%.0f"});
+    write_table(path, "id", &ids, cols, (long)ids.size(), table, cols.size());
+}
+
+StarIntervalsConfig star_intervals_config(const Settings &st)
+{
+    StarIntervalsConfig c;
+    c.quantity = quantity_id(st, "starIntervals");
+    std::string lv = st.str("starIntervals.levels", "0.025,0.16,0.5,0.84,0.975");
+    for (char &ch : lv) if (ch == ',' || ch == '[' || ch == ']') ch = ' ';
+    std::istringstream ls(lv);
+    std::string tok;
+    while (ls >> tok) {
+        char *end = nullptr;
+        const double v = std::strtod(tok.c_str(), &end);
+        if (end == tok.c_str() || *end) fail("starIntervals.levels: '" + tok + "' is not a number");
+        c.levels.push_back(v);
+    }
+    c.tol = st.num("starIntervals.tol", 1e-4);
+    c.max_passes = (int)st.integer("starIntervals.maxPasses", 12);
+    check_levels(c.levels.data(), (int)c.levels.size(), B9_SBIN_MAX_BINS, "starIntervals.levels");
+    if (!(c.tol >= 0.0)) fail("starIntervals.tol must not be negative");
+    if (c.max_passes < 1) fail("starIntervals.maxPasses must be positive");
+    return c;
+}
+
+// ---------------------------------------------------------------------------------------------
+// photResiduals
+// ---------------------------------------------------------------------------------------------
+void resid_table(const double *star_resid, const double *obs, const double *sigma, long n_stars, int nf, double *table)
+{
+    const size_t ncol = 2 + 2 * (size_t)nf, tcol = 2 + 4 * (size_t)nf;
+    for (long i = 0; i < n_stars; ++i) {
+        const double *a = star_resid + (size_t)i * ncol;
+        double *t = table + (size_t)i * tcol;
+        for (size_t c = 0; c < tcol; ++c) t[c] = 0.0;
+        t[0] = a[0];
+        if (a[0] > 0.0) t[1] = a[1] / a[0];
+        if (!(a[1] > 0.0)) continue;                         // no membership weight: every derived value is 0
+        for (int f = 0; f < nf; ++f) {
+            const double sg = sigma[(size_t)i * nf + f], o = obs[(size_t)i * nf + f];
+            const bool used = sg > 0.0;
+            const double m1 = a[2 + 2 * f] / a[1], m2 = a[3 + 2 * f] / a[1];
+            double *tf = t + 2 + 4 * (size_t)f;
+            tf[0] = (used ? o : 0.0) + m1;
+            tf[1] = std::sqrt(std::max(0.0, m2 - m1 * m1));
+            if (used) { tf[2] = o - tf[0]; tf[3] = std::sqrt(m2) / sg; }
+        }
+    }
+}
+
+void filter_resid_table(const double *row_resid, long n_rows, int nf, double *table)
+{
+    const size_t ncol = 1 + 5 * (size_t)nf;
+    std::vector<double> v;
+    for (int f = 0; f < nf; ++f) {
+        double *t = table + (size_t)f * kFilterResidCols;
+        for (int c = 0; c < kFilterResidCols; ++c) t[c] = 0.0;
+        std::vector<long> use;
+        for (long r = 0; r < n_rows; ++r)
+            if (row_resid[(size_t)r * ncol + 1 + 5 * f] > 0.0) use.push_back(r);
+        t[0] = (double)use.size();
+        if (use.empty()) continue;
+        for (int q = 0; q < 3; ++q) {
+            v.resize(use.size());
+            double sum = 0.0;
+            for (size_t k = 0; k < use.size(); ++k) {
+                const double *x = row_resid + (size_t)use[k] * ncol + 1 + 5 * f;          // N, R, C, W, D
+                v[k] = q == 0 ? x[1] / x[0] : q == 1 ? x[2] / x[0] : (x[3] > 0.0 ? x[4] / x[3] : 0.0);
+                sum += v[k];
+            }
+            const double mean = sum / (double)use.size();
+            double ss = 0.0;
+            for (double x : v) ss += (x - mean) * (x - mean);
+            std::sort(v.begin(), v.end());
+            double *tq = t + 1 + 5 * q;
+            tq[0] = mean;
+            tq[1] = std::sqrt(ss / (double)use.size());
+            tq[2] = percentile_sorted(v, 0.16); tq[3] = percentile_sorted(v, 0.50); tq[4] = percentile_sorted(v, 0.84);
+        }
+    }
+}
+
+void write_phot_resid(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &filters, const double *table)
+{
+    std::vector<TableColumn> cols = columns({"rows", "member"}, "%.17g");
+    for (const std::string &n : filters)
+        for (const char *what : {"_predMag", "_predSd", "_resid", "_rmsZ"}) cols.push_back({n + what, "%.17g"});
+    write_table(path, "id", &ids, cols, (long)ids.size(), table, cols.size());
+}
+
+void write_filter_resid(const std::string &path, const std::vector<std::string> &filters, const double *table)
+{
+    std::vector<TableColumn> cols = {{"nRows", "%.17g"}};
+    for (const char *q : {"meanZ", "chi2", "offset"})
+        for (const char *s : {"mean", "sd", "p16", "p50", "p84"}) cols.push_back({std::string(q) + "_" + s, "%.17g"});
+    write_table(path, "filter", &filters, cols, (long)filters.size(), table, kFilterResidCols);
+}
+
+// ---------------------------------------------------------------------------------------------
+// modelScore
+// ---------------------------------------------------------------------------------------------
+namespace {
+const double kInf = std::numeric_limits<double>::infinity(), kNaN = std::numeric_limits<double>::quiet_NaN();
+
+// PSIS of one star: r[0 .. n_t) the finite tail values, descending (r[0] = RMAX); -> paretoK, elpdLoo (elpd_is where no fit is made)
+void psis_star(const double *r, long n_t, double n_f, double rmax, double sneg, double elpd_is, double &pareto_k, double &elpd_loo)
+{
+    pareto_k = kNaN;
+    elpd_loo = elpd_is;
+    const long M = std::min({(long)std::floor(n_f / 5.0), (long)std::ceil(3.0 * std::sqrt(n_f)), n_t - 1});
+    if (M < 5) return;
+    const long N = M;
+    std::vector<double> rho((size_t)M + 1), x((size_t)M);
+    for (long j = 0; j <= M; ++j) rho[(size_t)j] = r[j] - r[0];
+    const double ec = std::exp(rho[(size_t)M]);
+    for (long j = 0; j < M; ++j) x[(size_t)(M - 1 - j)] = std::exp(rho[(size_t)j]) - ec;          // ascending: rho descends
+    const double x_n = x[(size_t)N - 1], x_star = x[(size_t)std::floor((double)N / 4.0 + 0.5) - 1];
+    if (x_n == 0.0 || !(x_star > 0.0)) return;
+    // Zhang & Stephens' profile fit of the generalised Pareto distribution, with the weakly informative prior on k
+    const long m = 30 + (long)std::floor(std::sqrt((double)N));
+    std::vector<double> theta((size_t)m), ell((size_t)m);
+    auto mean_log1p = [&](double th) { double sum = 0.0; for (long i = 0; i < N; ++i) sum += std::log1p(-th * x[(size_t)i]); return sum / (double)N; };
+    for (long j = 1; j <= m; ++j) {
+        const double th = 1.0 / x_n + (1.0 - std::sqrt((double)m / ((double)j - 0.5))) / (3.0 * x_star);
+        const double k = mean_log1p(th);
+        theta[(size_t)j - 1] = th;
+        ell[(size_t)j - 1] = (double)N * (std::log(-th / k) - k - 1.0);
+    }
+    double theta_hat = 0.0;
+    for (long j = 0; j < m; ++j) {
+        double den = 0.0;
+        for (long l = 0; l < m; ++l) den += std::exp(ell[(size_t)l] - ell[(size_t)j]);
+        theta_hat += theta[(size_t)j] * (1.0 / den);
+    }
+    double k_hat = mean_log1p(theta_hat);
+    const double sigma = -k_hat / theta_hat;
+    k_hat = ((double)N * k_hat + 5.0) / ((double)N + 10.0);
+    // the smoothed weights, paired by rank: the j-th smallest tail value takes the quantile at p_j = (j - 1/2) / M
+    double num = n_f - (double)M, tail_raw = 0.0, tail_smooth = 0.0;
+    for (long j = 1; j <= M; ++j) {
+        const double p = ((double)j - 0.5) / (double)M, lp = std::log1p(-p);
+        const double q = k_hat == 0.0 ? -sigma * lp : sigma * std::expm1(-k_hat * lp) / k_hat;
+        const double w = std::min(1.0, ec + q), rh = rho[(size_t)(M - j)];
+        num += std::exp(std::log(w) - rh);
+        tail_smooth += w;
+        tail_raw += std::exp(rh);
+    }
+    const double den = std::max(0.0, sneg - tail_raw) + tail_smooth;
+    pareto_k = k_hat;
+    elpd_loo = std::log(num) - std::log(den) - rmax;
+}
+
+// sum and sqrt(N var_ddof1) of v
+void sum_se(const std::vector<double> &v, double &sum, double &se)
+{
+    sum = 0.0; se = 0.0;
+    for (double x : v) sum += x;
+    const size_t n = v.size();
+    if (n < 2) return;
+    const double mean = sum / (double)n;
+    double ss = 0.0;
+    for (double x : v) ss += (x - mean) * (x - mean);
+    se = std::sqrt((double)n * (ss / (double)(n - 1)));
+}
+}  // namespace
+
+void pointwise_table(const double *acc, const double *tail, int tail_len, long n_stars, double *table)
+{
+    for (long i = 0; i < n_stars; ++i) {
+        const double *a = acc + (size_t)i * 8;
+        double *t = table + (size_t)i * kPointwiseCols;
+        for (int c = 0; c < kPointwiseCols; ++c) t[c] = 0.0;
+        const double rows = a[0], n_inf = a[1], n_f = rows - n_inf;
+        t[0] = rows; t[1] = n_inf;
+        if (n_inf > 0.0) {                               // a row gives the star no likelihood at all: no finite score
+            t[2] = n_f > 0.0 ? a[2] + std::log(a[3]) - std::log(rows) : -kInf;
+            t[3] = n_f >= 2.0 ? a[7] / (n_f - 1.0) : 0.0;
+            t[4] = t[5] = t[7] = -kInf; t[6] = kInf; t[8] = kInf;
+            continue;
+        }
+        if (!(n_f > 0.0)) continue;
+        const double lppd = a[2] + std::log(a[3]) - std::log(rows);
+        const double p_waic = n_f >= 2.0 ? a[7] / (n_f - 1.0) : 0.0;
+        const double elpd_is = std::log(n_f) - (a[4] + std::log(a[5]));
+        long n_t = 0;
+        const double *r = tail ? tail + (size_t)i * (size_t)tail_len : nullptr;
+        while (r && n_t < tail_len && std::isfinite(r[n_t])) ++n_t;
+        double k, loo;
+        psis_star(r, n_t, n_f, a[4], a[5], elpd_is, k, loo);
+        t[2] = lppd; t[3] = p_waic; t[4] = lppd - p_waic; t[5] = elpd_is; t[6] = k; t[7] = loo; t[8] = lppd - loo;
+    }
+}
+
+void score_totals(const double *table, long n_stars, double *totals)
+{
+    std::vector<double> lppd, waic, loo;
+    double p_waic = 0.0, p_loo = 0.0, n_infs = 0.0, n_high = 0.0, k_max = kNaN;
+    for (long i = 0; i < n_stars; ++i) {
+        const double *t = table + (size_t)i * kPointwiseCols;
+        if (!(t[0] > 0.0)) continue;
+        lppd.push_back(t[2]); waic.push_back(t[4]); loo.push_back(t[7]);
+        p_waic += t[3]; p_loo += t[8];
+        if (t[1] > 0.0) n_infs += 1.0;
+        if (t[6] > 0.7) n_high += 1.0;
+        if (std::isfinite(t[6]) && !(k_max >= t[6])) k_max = t[6];
+    }
+    totals[0] = (double)lppd.size();
+    sum_se(lppd, totals[1], totals[2]);
+    sum_se(waic, totals[3], totals[4]);
+    sum_se(loo, totals[5], totals[6]);
+    totals[7] = p_waic; totals[8] = p_loo; totals[9] = n_infs; totals[10] = n_high; totals[11] = k_max;
+}
+
+void score_compare(const double *table_a, const std::vector<std::string> &ids_a, const double *table_b, const std::vector<std::string> &ids_b,
+                   double *out)
+{
+    if (ids_a.size() != ids_b.size()) fail("modelScore: the two catalogues differ in their number of stars");
+    for (size_t i = 0; i < ids_a.size(); ++i)
+        if (ids_a[i] != ids_b[i]) fail("modelScore: the two catalogues differ at star " + std::to_string(i) + " ('" + ids_a[i] + "' against '" + ids_b[i] + "')");
+    std::vector<double> d_loo, d_waic;
+    double dropped = 0.0;
+    for (size_t i = 0; i < ids_a.size(); ++i) {
+        const double *a = table_a + i * kPointwiseCols, *b = table_b + i * kPointwiseCols;
+        if ((a[0] > 0.0) != (b[0] > 0.0)) dropped += 1.0;                  // scored by one fit only
+        if (!(a[0] > 0.0) || !(b[0] > 0.0)) continue;
+        d_loo.push_back(a[7] - b[7]);
+        d_waic.push_back(a[4] - b[4]);
+    }
+    out[0] = (double)d_loo.size();
+    sum_se(d_loo, out[1], out[2]);
+    sum_se(d_waic, out[3], out[4]);
+    out[5] = dropped;
+}
+
+static const char *const kPointwiseNames[kPointwiseCols] = {"rows", "nInf", "lppd", "pWaic", "elpdWaic", "elpdIs", "paretoK", "elpdLoo", "pLoo"};
+static const char *const kScoreNames[kScoreTotals] = {"nStars", "lppd", "lppdSe", "elpdWaic", "elpdWaicSe", "elpdLoo", "elpdLooSe", "pWaic", "pLoo",
+                                                      "nInfStars", "nHighK", "maxK"};
+static const char *const kCompareNames[kScoreCompare] = {"nStars", "dElpdLoo", "dElpdLooSe", "dElpdWaic", "dElpdWaicSe", "nDropped"};
+
+namespace {
+std::vector<TableColumn> columns17(const char *const *names, int n)
+{
+    std::vector<TableColumn> c;
+    for (int k = 0; k < n; ++k) c.push_back({names[k], "%.17g"});
+    return c;
+}
+}  // namespace
+
+void write_pointwise(const std::string &path, const std::vector<std::string> &ids, const double *table)
+{
+    write_table(path, "id", &ids, columns17(kPointwiseNames, kPointwiseCols), (long)ids.size(), table, kPointwiseCols);
+}
+void write_model_score(const std::string &path, const double *totals)
+{
+    write_table(path, nullptr, nullptr, columns17(kScoreNames, kScoreTotals), 1, totals, kScoreTotals);
+}
+void write_model_compare(const std::string &path, const double *cmp)
+{
+    write_table(path, nullptr, nullptr, columns17(kCompareNames, kScoreCompare), 1, cmp, kScoreCompare);
+}
+
+void write_row_lpd(const std::string &path, const double *row_lpd, long n_rows)
+{
+    std::vector<double> table(2 * (size_t)n_rows);
+    for (long r = 0; r < n_rows; ++r) { table[2 * (size_t)r] = (double)r; table[2 * (size_t)r + 1] = row_lpd[r]; }
+    write_table(path, nullptr, nullptr, {{"row", "%ld"}, {"lpd", "%.17g"}}, n_rows, table.data(), 2);
+}
+
+void read_pointwise(const std::string &path, std::vector<std::string> &ids, std::vector<double> &table)
+{
+    std::ifstream in(path);
+    if (!in) fail("cannot read " + path);
+    std::string line, word;
+    if (!std::getline(in, line)) fail(path + ": empty file");
+    {
+        std::istringstream hs(line);
+        hs >> word;
+        if (word != "id") fail(path + ": not a .pointwise file (the header starts with '" + word + "')");
+        for (const char *n : kPointwiseNames)
+            if (!(hs >> word) || word != n) fail(path + ": column '" + std::string(n) + "' missing from the header");
+    }
+    ids.clear(); table.clear();
+    while (std::getline(in, line)) {
+        std::istringstream ls(line);
+        if (!(ls >> word)) continue;
+        ids.push_back(word);
+        for (int c = 0; c < kPointwiseCols; ++c) {
+            if (!(ls >> word)) fail(path + ": short line for star '" + ids.back() + "'");
+            table.push_back(std::strtod(word.c_str(), nullptr));         // (strtod reads inf / -inf / nan as printf wrote them)
+        }
+    }
+}
+
+}  // namespace b9h

@@ -18,7 +18,35 @@
 namespace {
 std::string g_err;
 template <class F> int guard(F f) { try { f(); return 0; } catch (const std::exception &e) { g_err = e.what(); return -1; } }
+
+std::string g17(double v)
+{
+    char b[40];
+    std::snprintf(b, sizeof b, "%.17g", v);
+    return b;
 }
+
+std::vector<std::string> strings(const char *const *v, long n) { return std::vector<std::string>(v, v + n); }
+
+// What a program's main makes of a command line, as "key = value" lines: parsed with the program's own flags, then
+// text(settings) copied into out.
+template <class F> int settings_text(const std::string &who, int argc, char **argv, const b9h::ProgramFlags &flags, char *out, int cap, F text)
+{
+    return guard([&] {
+        if (!out) throw std::runtime_error(who + ": NULL argument");
+        b9h::Settings st;
+        st.parse_args(argc, argv, flags);
+        const std::string d = text(st);
+        if ((int)d.size() >= cap) throw std::runtime_error(who + ": output buffer too small");
+        std::memcpy(out, d.c_str(), d.size() + 1);
+    });
+}
+
+std::string grid_text(const b9h::ChainGrid &g)
+{
+    return "margIsoIncrem = " + std::to_string(g.K) + "\nnMassRatios = " + std::to_string(g.Q) + "\nnPops = " + std::to_string(g.n_pops) + "\n";
+}
+}  // namespace
 
 extern "C" {
 
@@ -70,15 +98,6 @@ int b9h_settings_dump(int argc, char **argv, char *out, int cap)
 }
 
 // ---- simCluster / scatterCluster draws (b9sim.hpp) -----------------------------------------------------------------
-namespace {
-std::string g17(double v)
-{
-    char b[40];
-    std::snprintf(b, sizeof b, "%.17g", v);
-    return b;
-}
-}  // namespace
-
 int b9h_sim_draw_systems(uint64_t seed, int64_t i0, int64_t n, double min_mass, double max_mass, double percent_binary,
                          double min_mass_ratio, double percent_db, int n_pops, double lambda, const double *tip,
                          double *mass1, double *mass_ratio, int32_t *wd_type, int32_t *pop)
@@ -155,7 +174,7 @@ int b9h_write_star_summary(const char *path, const char *const *ids, long n_star
 {
     return guard([&] {
         if (!path || n_stars < 0 || (n_stars > 0 && (!ids || !acc))) throw std::runtime_error("b9h_write_star_summary: NULL argument");
-        b9h::write_star_summary(path, std::vector<std::string>(ids, ids + n_stars), acc, n_pops);
+        b9h::write_star_summary(path, strings(ids, n_stars), acc, n_pops);
     });
 }
 
@@ -171,7 +190,7 @@ int b9h_write_wd_summary(const char *path, const char *const *ids, long n_wd, co
 {
     return guard([&] {
         if (!path || n_wd < 0 || (n_wd > 0 && (!ids || !acc))) throw std::runtime_error("b9h_write_wd_summary: NULL argument");
-        b9h::write_wd_summary(path, std::vector<std::string>(ids, ids + n_wd), acc, n_pops);
+        b9h::write_wd_summary(path, strings(ids, n_wd), acc, n_pops);
     });
 }
 
@@ -195,27 +214,19 @@ int b9h_write_star_mass_hist(const char *path, const char *const *ids, long n_st
 {
     return guard([&] {
         if (!path || n_stars < 0 || n_bins < 1 || (n_stars > 0 && (!ids || !star_hist))) throw std::runtime_error("b9h_write_star_mass_hist: invalid argument");
-        b9h::write_star_mass_hist(path, std::vector<std::string>(ids, ids + n_stars), star_hist, n_bins, n_rows);
+        b9h::write_star_mass_hist(path, strings(ids, n_stars), star_hist, n_bins, n_rows);
     });
 }
 
 int b9h_mass_function_settings(int argc, char **argv, double m_wd_up, char *out, int cap, double *edges /* [B9_HIST_MAX_BINS + 1], nullable */)
 {
-    return guard([&] {
-        if (!out) throw std::runtime_error("b9h_mass_function_settings: NULL argument");
-        const std::vector<std::string> args = b9h::mass_function_args(argc, argv);
-        std::vector<char *> av;
-        for (auto &a : args) av.push_back(const_cast<char *>(a.c_str()));
-        b9h::Settings st;
-        st.parse_args((int)av.size(), av.data());
+    return settings_text("b9h_mass_function_settings", argc, argv, b9h::kMassFunctionFlags, out, cap, [&](const b9h::Settings &st) {
         const b9h::MassFunctionConfig c = b9h::mass_function_config(st, m_wd_up);
-        const std::string d = "nBins = " + std::to_string(c.n_bins) + "\nminMass = " + g17(c.min_mass) + "\nmaxMass = " + g17(c.max_mass) +
-                              "\nlinearBins = " + std::to_string((int)c.linear) + "\nquantity = " + std::to_string(c.quantity) +
-                              "\nperStar = " + std::to_string((int)c.per_star) + "\nmargIsoIncrem = " + std::to_string(c.K) +
-                              "\nnMassRatios = " + std::to_string(c.Q) + "\nnPops = " + std::to_string(c.n_pops) + "\n";
-        if ((int)d.size() >= cap) throw std::runtime_error("b9h_mass_function_settings: output buffer too small");
-        std::memcpy(out, d.c_str(), d.size() + 1);
+        const std::string grid = grid_text(b9h::chain_grid(st, "massFunction"));
         if (edges) { const std::vector<double> e = c.edges(); std::copy(e.begin(), e.end(), edges); }
+        return "nBins = " + std::to_string(c.n_bins) + "\nminMass = " + g17(c.min_mass) + "\nmaxMass = " + g17(c.max_mass) +
+               "\nlinearBins = " + std::to_string((int)c.linear) + "\nquantity = " + std::to_string(c.quantity) +
+               "\nperStar = " + std::to_string((int)c.per_star) + "\n" + grid;
     });
 }
 
@@ -248,27 +259,18 @@ int b9h_write_star_intervals(const char *path, const char *const *ids, long n_st
 {
     return guard([&] {
         if (!path || n_stars < 0 || n_levels < 1 || !levels || (n_stars > 0 && (!ids || !table))) throw std::runtime_error("b9h_write_star_intervals: invalid argument");
-        b9h::write_star_intervals(path, std::vector<std::string>(ids, ids + n_stars), std::vector<double>(levels, levels + n_levels), table);
+        b9h::write_star_intervals(path, strings(ids, n_stars), std::vector<double>(levels, levels + n_levels), table);
     });
 }
 
 int b9h_star_intervals_settings(int argc, char **argv, char *out, int cap)
 {
-    return guard([&] {
-        if (!out) throw std::runtime_error("b9h_star_intervals_settings: NULL argument");
-        const std::vector<std::string> args = b9h::star_intervals_args(argc, argv);
-        std::vector<char *> av;
-        for (auto &a : args) av.push_back(const_cast<char *>(a.c_str()));
-        b9h::Settings st;
-        st.parse_args((int)av.size(), av.data());
+    return settings_text("b9h_star_intervals_settings", argc, argv, b9h::kStarIntervalsFlags, out, cap, [&](const b9h::Settings &st) {
         const b9h::StarIntervalsConfig c = b9h::star_intervals_config(st);
         std::string lv;
         for (size_t l = 0; l < c.levels.size(); ++l) lv += (l ? "," : "") + g17(c.levels[l]);
-        const std::string d = "quantity = " + std::to_string(c.quantity) + "\nlevels = " + lv + "\ntol = " + g17(c.tol) + "\nmaxPasses = " +
-                              std::to_string(c.max_passes) + "\nmargIsoIncrem = " + std::to_string(c.K) + "\nnMassRatios = " + std::to_string(c.Q) +
-                              "\nnPops = " + std::to_string(c.n_pops) + "\n";
-        if ((int)d.size() >= cap) throw std::runtime_error("b9h_star_intervals_settings: output buffer too small");
-        std::memcpy(out, d.c_str(), d.size() + 1);
+        return "quantity = " + std::to_string(c.quantity) + "\nlevels = " + lv + "\ntol = " + g17(c.tol) + "\nmaxPasses = " +
+               std::to_string(c.max_passes) + "\n" + grid_text(b9h::chain_grid(st, "starIntervals"));
     });
 }
 
@@ -292,7 +294,7 @@ int b9h_write_phot_resid(const char *path, const char *const *ids, long n_stars,
 {
     return guard([&] {
         if (!path || n_stars < 0 || n_filt < 1 || !filters || (n_stars > 0 && (!ids || !table))) throw std::runtime_error("b9h_write_phot_resid: invalid argument");
-        b9h::write_phot_resid(path, std::vector<std::string>(ids, ids + n_stars), std::vector<std::string>(filters, filters + n_filt), table);
+        b9h::write_phot_resid(path, strings(ids, n_stars), strings(filters, n_filt), table);
     });
 }
 
@@ -300,24 +302,14 @@ int b9h_write_filter_resid(const char *path, const char *const *filters, int n_f
 {
     return guard([&] {
         if (!path || n_filt < 1 || !filters || !table) throw std::runtime_error("b9h_write_filter_resid: invalid argument");
-        b9h::write_filter_resid(path, std::vector<std::string>(filters, filters + n_filt), table);
+        b9h::write_filter_resid(path, strings(filters, n_filt), table);
     });
 }
 
 int b9h_phot_resid_settings(int argc, char **argv, char *out, int cap)
 {
-    return guard([&] {
-        if (!out) throw std::runtime_error("b9h_phot_resid_settings: NULL argument");
-        const std::vector<std::string> args = b9h::phot_resid_args(argc, argv);
-        std::vector<char *> av;
-        for (auto &a : args) av.push_back(const_cast<char *>(a.c_str()));
-        b9h::Settings st;
-        st.parse_args((int)av.size(), av.data());
-        const b9h::PhotResidConfig c = b9h::phot_resid_config(st);
-        const std::string d = "margIsoIncrem = " + std::to_string(c.K) + "\nnMassRatios = " + std::to_string(c.Q) + "\nnPops = " + std::to_string(c.n_pops) +
-                              "\nperStar = " + std::to_string((int)c.per_star) + "\n";
-        if ((int)d.size() >= cap) throw std::runtime_error("b9h_phot_resid_settings: output buffer too small");
-        std::memcpy(out, d.c_str(), d.size() + 1);
+    return settings_text("b9h_phot_resid_settings", argc, argv, b9h::kPhotResidFlags, out, cap, [&](const b9h::Settings &st) {
+        return grid_text(b9h::chain_grid(st, "photResiduals")) + "perStar = " + std::to_string((int)b9h::phot_resid_config(st).per_star) + "\n";
     });
 }
 
@@ -342,7 +334,7 @@ int b9h_score_compare(const double *table_a, const char *const *ids_a, long n_a,
     return guard([&] {
         if (n_a < 0 || n_b < 0 || !out || (n_a > 0 && (!table_a || !ids_a)) || (n_b > 0 && (!table_b || !ids_b)))
             throw std::runtime_error("b9h_score_compare: invalid argument");
-        b9h::score_compare(table_a, std::vector<std::string>(ids_a, ids_a + n_a), table_b, std::vector<std::string>(ids_b, ids_b + n_b), out);
+        b9h::score_compare(table_a, strings(ids_a, n_a), table_b, strings(ids_b, n_b), out);
     });
 }
 
@@ -350,7 +342,7 @@ int b9h_write_pointwise(const char *path, const char *const *ids, long n_stars, 
 {
     return guard([&] {
         if (!path || n_stars < 0 || (n_stars > 0 && (!ids || !table))) throw std::runtime_error("b9h_write_pointwise: invalid argument");
-        b9h::write_pointwise(path, std::vector<std::string>(ids, ids + n_stars), table);
+        b9h::write_pointwise(path, strings(ids, n_stars), table);
     });
 }
 
@@ -364,18 +356,9 @@ int b9h_write_model_score(const char *path, const double *totals)
 
 int b9h_model_score_settings(int argc, char **argv, char *out, int cap)
 {
-    return guard([&] {
-        if (!out) throw std::runtime_error("b9h_model_score_settings: NULL argument");
-        const std::vector<std::string> args = b9h::model_score_args(argc, argv);
-        std::vector<char *> av;
-        for (auto &a : args) av.push_back(const_cast<char *>(a.c_str()));
-        b9h::Settings st;
-        st.parse_args((int)av.size(), av.data());
+    return settings_text("b9h_model_score_settings", argc, argv, b9h::kModelScoreFlags, out, cap, [&](const b9h::Settings &st) {
         const b9h::ModelScoreConfig c = b9h::model_score_config(st);
-        const std::string d = "margIsoIncrem = " + std::to_string(c.K) + "\nnMassRatios = " + std::to_string(c.Q) + "\nnPops = " + std::to_string(c.n_pops) +
-                              "\nperRow = " + std::to_string((int)c.per_row) + "\ncompareTo = " + c.compare_to + "\n";
-        if ((int)d.size() >= cap) throw std::runtime_error("b9h_model_score_settings: output buffer too small");
-        std::memcpy(out, d.c_str(), d.size() + 1);
+        return grid_text(b9h::chain_grid(st, "modelScore")) + "perRow = " + std::to_string((int)c.per_row) + "\ncompareTo = " + c.compare_to + "\n";
     });
 }
 

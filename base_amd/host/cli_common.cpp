@@ -37,10 +37,9 @@ std::string wd_model_name(const std::string &v)
 
 }  // namespace
 
-void open_session(Session &s, int argc, char **argv, int n_pops, bool need_phot)
+void open_session(Session &s, int n_pops, bool need_phot)
 {
-    Settings &st = s.settings;
-    st.parse_args(argc, argv);
+    const Settings &st = s.settings;
     const std::string model_dir = st.str("general.files.modelDirectory");
     if (model_dir.empty()) throw std::runtime_error("no modelDirectory (use --modelDirectory or general.files.modelDirectory)");
     const std::string ms = ms_model_name(st.str("general.main_sequence.msRgbModel", "parsec"));
@@ -433,61 +432,30 @@ std::vector<double> read_res_rows(const std::string &res_path, const std::vector
     return rows;
 }
 
-PhotResidConfig phot_resid_config(const Settings &st)
+SavedChain open_saved_chain(Session &s, const ChainGrid &g)
 {
-    PhotResidConfig c;
-    c.K = (int)st.integer("photResiduals.margIsoIncrem", st.integer("sampleMass.margIsoIncrem", 4));
-    c.Q = (int)st.integer("photResiduals.nMassRatios", st.integer("sampleMass.nMassRatios", 4));
-    c.n_pops = (int)st.integer("photResiduals.nPops", 1);
-    c.per_star = st.integer("photResiduals.perStar", 0) != 0;
-    if (c.K < 1 || c.Q < 1) throw std::runtime_error("margIsoIncrem and nMassRatios must be positive");
-    if (c.n_pops != 1 && c.n_pops != 2) throw std::runtime_error("photResiduals.nPops must be 1 or 2");
+    open_session(s, g.n_pops, true);
+    if (g.K > 0) {
+        const b9_options opt{B9_MODE_GIVEN_MASS, g.n_pops, g.K, g.Q};
+        if (b9_set_options(s.ctx, &opt) != B9_OK) throw std::runtime_error(b9_last_error(s.ctx));
+    }
+    SavedChain c;
+    const std::string res_path = s.output_base + ".res";
+    c.rows = read_res_rows(res_path, s.start, 3);
+    c.n_rows = (long)(c.rows.size() / B9_NPARAM);
+    if (c.n_rows == 0) throw std::runtime_error(res_path + " holds no main-run (stage 3) rows");
     return c;
 }
 
-std::vector<std::string> phot_resid_args(int argc, char **argv)
+std::vector<int> wd_stage_stars(const Session &s, const char *nothing_to)
 {
-    std::vector<std::string> out;
-    for (int i = 0; i < argc; ++i) {
-        std::string a = argv[i];
-        if (a == "--perStar") a = "--photResidualsPerStar=1";
-        else if (a.rfind("--perStar=", 0) == 0) a = "--photResidualsPerStar" + a.substr(9);
-        else if (a == "--nPops" || a.rfind("--nPops=", 0) == 0) a = "--photResidualsNPops" + a.substr(7);
-        out.push_back(a);
-    }
-    return out;
-}
-
-ModelScoreConfig model_score_config(const Settings &st)
-{
-    ModelScoreConfig c;
-    c.K = (int)st.integer("modelScore.margIsoIncrem", st.integer("sampleMass.margIsoIncrem", 4));
-    c.Q = (int)st.integer("modelScore.nMassRatios", st.integer("sampleMass.nMassRatios", 4));
-    c.n_pops = (int)st.integer("modelScore.nPops", 1);
-    c.per_row = st.integer("modelScore.perRow", 0) != 0;
-    c.compare_to = st.str("modelScore.compareTo", "");
-    if (c.K < 1 || c.Q < 1) throw std::runtime_error("margIsoIncrem and nMassRatios must be positive");
-    if (c.n_pops != 1 && c.n_pops != 2) throw std::runtime_error("modelScore.nPops must be 1 or 2");
-    return c;
-}
-
-std::vector<std::string> model_score_args(int argc, char **argv)
-{
-    std::vector<std::string> out;
-    for (int i = 0; i < argc; ++i) {
-        std::string a = argv[i];
-        if (a == "--perRow") a = "--modelScorePerRow=1";
-        else if (a.rfind("--perRow=", 0) == 0) a = "--modelScorePerRow" + a.substr(8);
-        else if (a == "--nPops" || a.rfind("--nPops=", 0) == 0) a = "--modelScoreNPops" + a.substr(7);
-        out.push_back(a);
-    }
-    return out;
-}
-
-int model_score_tail_len(long n_rows)
-{
-    const double s = (double)n_rows;
-    return (int)std::min(256.0, std::min(std::floor(s / 5.0), std::ceil(3.0 * std::sqrt(s))) + 1.0);
+    const int n_wd = b9_n_wd_stars(s.ctx);
+    if (n_wd < 0) throw std::runtime_error(b9_last_error(s.ctx));
+    if (n_wd == 0) throw std::runtime_error(std::string("the photometry holds no WD-stage star (stage 3): nothing to ") + nothing_to);
+    std::vector<int> wd;
+    for (int i = 0; i < s.phot.n_stars(); ++i) if (s.phot.stage[i] == B9_STAGE_WD) wd.push_back(i);
+    if ((int)wd.size() != n_wd) throw std::runtime_error("the staged catalogue and the photometry disagree on the WD-stage stars");
+    return wd;
 }
 
 int report_and_exit_code(const char *prog, const std::exception &e)

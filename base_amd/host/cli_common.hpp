@@ -1,5 +1,6 @@
-// cli_common.hpp -- what singlePopMcmc / multiPopMcmc / makeCMD / sampleMass / sampleWDMass share: settings -> context, and the
-// sampling run (walker-parallel over the GPUs of one node when launched with --gpus N).
+// cli_common.hpp -- what the command-line programs share where a GPU context is involved: settings -> context, the sampling run
+// (walker-parallel over the GPUs of one node when launched with --gpus N), and what every program over a saved chain does before
+// its own work.  (Their settings, tables and files need no context: b9chain.hpp.)
 #pragma once
 #include "b9host.hpp"
 #include "b9sampler.hpp"
@@ -34,9 +35,9 @@ struct Session {
     ~Session() { if (ctx) b9_ctx_destroy(ctx); }
 };
 
-// Parses flags / YAML, loads the photometry (unless `need_phot` is false) and the model pack with
-// the photometry's filters, creates the GPU context and stages everything.  Throws on error.
-void open_session(Session &s, int argc, char **argv, int n_pops, bool need_phot);
+// From s.settings (the caller has parsed its flags / YAML into them): loads the photometry (unless `need_phot` is false) and
+// the model pack with the photometry's filters, creates the GPU context and stages everything.  Throws on error.
+void open_session(Session &s, int n_pops, bool need_phot);
 
 // --gpus N (or gpu.gpus): when this process is not yet a rank of a launch, starts N copies of itself -- one per GPU, with
 // B9_RANK / B9_WORLD_SIZE / B9_LOCAL_RANK / B9_DIST_DIR set -- BEFORE anything touches a GPU, waits for them and
@@ -62,23 +63,19 @@ void merge_result_parts(const std::string &final_path, int world, int per, long 
 // What sampleMass and sampleWDMass read (libbase9host exports it as b9h_read_res_rows).
 std::vector<double> read_res_rows(const std::string &res_path, const std::vector<double> &start, int stage);
 
-// photResiduals' own settings: photResiduals.{margIsoIncrem, nMassRatios, nPops, perStar}, the grid defaulting to sampleMass's
-// (4 each; flags --margIsoIncrem / --nMassRatios as sampleMass), one population, no per-star file.
-struct PhotResidConfig { int K, Q, n_pops; bool per_star; };
-PhotResidConfig phot_resid_config(const Settings &st);
-// --perStar and --nPops belong to massFunction and simCluster in the shared flag table: photResiduals' command line has them
-// renamed to the flags of its own keys (--photResidualsPerStar / --photResidualsNPops) before Settings::parse_args sees it
-std::vector<std::string> phot_resid_args(int argc, char **argv);
-
-// modelScore's own settings: modelScore.{margIsoIncrem, nMassRatios, nPops, perRow, compareTo}, the grid defaulting to
-// sampleMass's (4 each), one population, no per-row file, no comparison.
-struct ModelScoreConfig { int K, Q, n_pops; bool per_row; std::string compare_to; };
-ModelScoreConfig model_score_config(const Settings &st);
-// --perRow and --nPops are renamed to the flags of modelScore's own keys (--modelScorePerRow / --modelScoreNPops) before
-// Settings::parse_args sees them (--nPops belongs to simCluster in the shared flag table); --margIsoIncrem / --nMassRatios as sampleMass
-std::vector<std::string> model_score_args(int argc, char **argv);
-// the tail kept per star for a chain of n_rows rows: min(256, min(floor(S / 5), ceil(3 sqrt S)) + 1)
-int model_score_tail_len(long n_rows);
+// What every program over a saved chain does before its own work, from s.settings: opens the session with the grid's
+// population count, sets the options {given-mass mode, n_pops, K, Q} -- K = 0 (sampleWDMass, wdSummary: their calls read the
+// population count alone) leaves open_session's -- and reads the main-run (stage 3) rows of <output_base>.res.  Throws
+// "<path> holds no main-run (stage 3) rows" when there are none.
+struct SavedChain {
+    std::vector<double> rows;             // [n_rows][B9_NPARAM]
+    long n_rows = 0;
+    const double *row(long r) const { return rows.data() + (size_t)r * B9_NPARAM; }
+};
+SavedChain open_saved_chain(Session &s, const ChainGrid &g);
+// The catalogue indices of the WD-stage stars in .phot order, checked against the staged catalogue's b9_n_wd_stars.  Throws
+// "... no WD-stage star (stage 3): nothing to <nothing_to>" when there is none.
+std::vector<int> wd_stage_stars(const Session &s, const char *nothing_to);
 
 int report_and_exit_code(const char *prog, const std::exception &e);
 

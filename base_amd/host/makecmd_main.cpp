@@ -12,7 +12,8 @@ int main(int argc, char **argv)
 {
     try {
         b9h::Session s;
-        b9h::open_session(s, argc, argv, 1, false);
+        s.settings.parse_args(argc, argv);
+        b9h::open_session(s, 1, false);
         const int nf = (int)s.pack.filters.size();
         int cap = 0;
         for (int n : s.pack.iso_n_eep) cap = std::max(cap, n);

@@ -27,7 +27,8 @@ int main(int argc, char **argv)
             b9h::test_stall("start", r0);                                        // (test hook; nothing has touched a GPU yet)
         }
         b9h::Session s;
-        b9h::open_session(s, argc, argv, B9_N_POPS, true);
+        s.settings.parse_args(argc, argv);
+        b9h::open_session(s, B9_N_POPS, true);
         std::unique_ptr<b9h::Exchange> ex = (s.world > 1 || b9h::forced_ranks()) ? b9h::make_rccl_exchange(s.rank, s.world, b9h::default_bootstrap_dir(), b9_device_id(s.ctx))
                                                          : b9h::make_local_exchange();
         std::vector<std::string> cols;

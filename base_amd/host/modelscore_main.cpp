@@ -16,7 +16,6 @@
 #include "cli_common.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <stdexcept>
 
@@ -40,35 +39,21 @@ static int compare(const std::string &base, const std::string &other)
 int main(int argc, char **argv)
 {
     try {
-        const std::vector<std::string> args = b9h::model_score_args(argc, argv);
-        std::vector<char *> av;
-        for (auto &a : args) av.push_back(const_cast<char *>(a.c_str()));
-        b9h::Settings peek;
-        peek.parse_args((int)av.size(), av.data());
-        const b9h::ModelScoreConfig c = b9h::model_score_config(peek);
-        if (!c.compare_to.empty()) return compare(peek.str("general.files.outputFileBase", "base9"), c.compare_to);
-
         b9h::Session s;
-        b9h::open_session(s, (int)av.size(), av.data(), c.n_pops, true);      // (the population count decides which starting values it reads)
-        b9_options opt{B9_MODE_GIVEN_MASS, c.n_pops, c.K, c.Q};
-        if (b9_set_options(s.ctx, &opt) != B9_OK) throw std::runtime_error(b9_last_error(s.ctx));
-
-        const std::string res_path = s.output_base + ".res";
-        const std::vector<double> rows = b9h::read_res_rows(res_path, s.start, 3);
-        const long n_rows = (long)(rows.size() / B9_NPARAM);
-        if (n_rows == 0) throw std::runtime_error(res_path + " holds no main-run (stage 3) rows");
+        s.settings.parse_args(argc, argv, b9h::kModelScoreFlags);
+        const b9h::ChainGrid g = b9h::chain_grid(s.settings, "modelScore");
+        const b9h::ModelScoreConfig c = b9h::model_score_config(s.settings);
+        if (!c.compare_to.empty()) return compare(s.settings.str("general.files.outputFileBase", "base9"), c.compare_to);     // (no GPU context yet)
+        const b9h::SavedChain chain = b9h::open_saved_chain(s, g);
+        const long n_rows = chain.n_rows;
 
         const int n = s.phot.n_stars(), tail_len = b9h::model_score_tail_len(n_rows);
         std::vector<double> acc((size_t)n * B9_PW_N, 0.0), tail((size_t)n * (size_t)tail_len, 0.0), row_lpd(c.per_row ? (size_t)n_rows : 0, 0.0);
-        const long batch = 256;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (long r0 = 0; r0 < n_rows; r0 += batch) {
-            const long m = std::min(batch, n_rows - r0);
-            if (b9_pointwise(s.ctx, rows.data() + (size_t)r0 * B9_NPARAM, (int32_t)m, r0 ? B9_PW_CONTINUE : 0, tail_len, acc.data(),
+        const double sec = b9h::for_row_batches(n_rows, [&](long r0, long m) {
+            if (b9_pointwise(s.ctx, chain.row(r0), (int32_t)m, r0 ? B9_PW_CONTINUE : 0, tail_len, acc.data(),
                              tail_len > 0 ? tail.data() : nullptr, c.per_row ? row_lpd.data() + r0 : nullptr) != B9_OK)
                 throw std::runtime_error(b9_last_error(s.ctx));
-        }
-        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        });
         std::vector<double> table((size_t)n * b9h::kPointwiseCols);
         b9h::pointwise_table(acc.data(), tail_len > 0 ? tail.data() : nullptr, tail_len, n, table.data());
         double totals[b9h::kScoreTotals];
@@ -80,7 +65,7 @@ int main(int argc, char **argv)
         std::printf("elpd (PSIS-LOO) = %.6f +- %.6f   p_loo = %.3f   stars with pareto k > 0.7: %ld\nelpd (WAIC)     = %.6f +- %.6f   p_waic = %.3f\n",
                     totals[5], totals[6], totals[8], (long)totals[10], totals[3], totals[4], totals[7]);
         std::fprintf(stderr, "modelScore: %ld chain rows x %d stars (%d x %d mass / mass-ratio nodes per EEP interval, tail of %d) in %.3f s (%.3e star rows/s) -> %s\n",
-                     n_rows, n, c.K, c.Q, tail_len, sec, (double)n_rows * n / sec, out.c_str());
+                     n_rows, n, g.K, g.Q, tail_len, sec, (double)n_rows * n / sec, out.c_str());
         return 0;
     } catch (const std::exception &e) {
         return b9h::report_and_exit_code("modelScore", e);

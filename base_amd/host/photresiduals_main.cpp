@@ -12,43 +12,27 @@
 #include "cli_common.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <stdexcept>
 
 int main(int argc, char **argv)
 {
     try {
-        const std::vector<std::string> args = b9h::phot_resid_args(argc, argv);
-        std::vector<char *> av;
-        for (auto &a : args) av.push_back(const_cast<char *>(a.c_str()));
         b9h::Session s;
-        {   // (the population count decides which starting values open_session reads: peek at the settings first)
-            b9h::Settings peek;
-            peek.parse_args((int)av.size(), av.data());
-            b9h::open_session(s, (int)av.size(), av.data(), b9h::phot_resid_config(peek).n_pops, true);
-        }
+        s.settings.parse_args(argc, argv, b9h::kPhotResidFlags);
+        const b9h::ChainGrid g = b9h::chain_grid(s.settings, "photResiduals");
         const b9h::PhotResidConfig c = b9h::phot_resid_config(s.settings);
-        b9_options opt{B9_MODE_GIVEN_MASS, c.n_pops, c.K, c.Q};
-        if (b9_set_options(s.ctx, &opt) != B9_OK) throw std::runtime_error(b9_last_error(s.ctx));
-
-        const std::string res_path = s.output_base + ".res";
-        const std::vector<double> rows = b9h::read_res_rows(res_path, s.start, 3);
-        const long n_rows = (long)(rows.size() / B9_NPARAM);
-        if (n_rows == 0) throw std::runtime_error(res_path + " holds no main-run (stage 3) rows");
+        const b9h::SavedChain chain = b9h::open_saved_chain(s, g);
+        const long n_rows = chain.n_rows;
 
         const int n = s.phot.n_stars(), nf = (int)s.phot.filters.size();
         const size_t ncol = 2 + 2 * (size_t)nf, nrow = 1 + 5 * (size_t)nf;
         std::vector<double> star_resid(c.per_star ? (size_t)n * ncol : 0, 0.0), row_resid((size_t)n_rows * nrow, 0.0);
-        const long batch = 256;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (long r0 = 0; r0 < n_rows; r0 += batch) {
-            const long m = std::min(batch, n_rows - r0);
-            if (b9_phot_resid(s.ctx, rows.data() + (size_t)r0 * B9_NPARAM, (int32_t)m, r0 ? B9_RESID_CONTINUE : 0,
+        const double sec = b9h::for_row_batches(n_rows, [&](long r0, long m) {
+            if (b9_phot_resid(s.ctx, chain.row(r0), (int32_t)m, r0 ? B9_RESID_CONTINUE : 0,
                               c.per_star ? star_resid.data() : nullptr, row_resid.data() + (size_t)r0 * nrow) != B9_OK)
                 throw std::runtime_error(b9_last_error(s.ctx));
-        }
-        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        });
         std::vector<double> ftab((size_t)nf * b9h::kFilterResidCols);
         b9h::filter_resid_table(row_resid.data(), n_rows, nf, ftab.data());
         const std::string out = s.output_base + ".filterResid";
@@ -59,7 +43,7 @@ int main(int argc, char **argv)
             b9h::write_phot_resid(s.output_base + ".photResid", s.phot.ids, s.phot.filters, stab.data());
         }
         std::fprintf(stderr, "photResiduals: %ld chain rows x %d stars x %d filters (%d x %d mass / mass-ratio nodes per EEP interval) in %.3f s (%.3e star rows/s) -> %s\n",
-                     n_rows, n, nf, c.K, c.Q, sec, (double)n_rows * n / sec, out.c_str());
+                     n_rows, n, nf, g.K, g.Q, sec, (double)n_rows * n / sec, out.c_str());
         return 0;
     } catch (const std::exception &e) {
         return b9h::report_and_exit_code("photResiduals", e);

@@ -10,7 +10,6 @@
 #include "cli_common.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <fstream>
 #include <sstream>
@@ -20,17 +19,10 @@ int main(int argc, char **argv)
 {
     try {
         b9h::Session s;
-        b9h::open_session(s, argc, argv, 1, true);
-        const int K = (int)s.settings.integer("sampleMass.margIsoIncrem", 4), Q = (int)s.settings.integer("sampleMass.nMassRatios", 4);
-        if (K < 1 || Q < 1) throw std::runtime_error("margIsoIncrem and nMassRatios must be positive");
-        b9_options opt{B9_MODE_GIVEN_MASS, 1, K, Q};
-        if (b9_set_options(s.ctx, &opt) != B9_OK) throw std::runtime_error(b9_last_error(s.ctx));
-
-        // ---- the chain: header names the sampled parameters, then "logPost stage"; stage 3 = main run
-        const std::string res_path = s.output_base + ".res";
-        const std::vector<double> rows = b9h::read_res_rows(res_path, s.start, 3);
-        const long n_rows = (long)(rows.size() / B9_NPARAM);
-        if (n_rows == 0) throw std::runtime_error(res_path + " holds no main-run (stage 3) rows");
+        s.settings.parse_args(argc, argv);
+        const b9h::ChainGrid g = b9h::sample_mass_grid(s.settings);
+        const b9h::SavedChain chain = b9h::open_saved_chain(s, g);
+        const long n_rows = chain.n_rows;
 
         const int n = s.phot.n_stars();
         const std::string mp = s.output_base + ".massSamples", bp = s.output_base + ".membership";
@@ -40,12 +32,10 @@ int main(int argc, char **argv)
         std::fprintf(fm, "\n");
         for (int i = 0; i < n; ++i) std::fprintf(fb, "%s%s", i ? " " : "", s.phot.ids[i].c_str());
         std::fprintf(fb, "\n");
-        const long batch = 256;
-        std::vector<double> mass((size_t)batch * n), ratio((size_t)batch * n), member((size_t)batch * n);
-        const auto t0 = std::chrono::steady_clock::now();
-        for (long r0 = 0; r0 < n_rows; r0 += batch) {
-            const long m = std::min(batch, n_rows - r0);
-            if (b9_sample_mass(s.ctx, rows.data() + (size_t)r0 * B9_NPARAM, (int32_t)m, s.mcmc.seed, r0, mass.data(), ratio.data(),
+        const size_t cap = (size_t)b9h::kChainBatch * n;
+        std::vector<double> mass(cap), ratio(cap), member(cap);
+        const double sec = b9h::for_row_batches(n_rows, [&](long r0, long m) {
+            if (b9_sample_mass(s.ctx, chain.row(r0), (int32_t)m, s.mcmc.seed, r0, mass.data(), ratio.data(),
                                member.data(), nullptr) != B9_OK)
                 throw std::runtime_error(b9_last_error(s.ctx));
             for (long r = 0; r < m; ++r) {
@@ -55,11 +45,10 @@ int main(int argc, char **argv)
                 for (int i = 0; i < n; ++i) std::fprintf(fb, "%s%.6f", i ? " " : "", member[(size_t)r * n + i]);
                 std::fprintf(fb, "\n");
             }
-        }
+        });
         std::fclose(fm); std::fclose(fb);
-        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::fprintf(stderr, "sampleMass: %ld chain rows x %d stars (%d x %d mass / mass-ratio nodes per EEP interval) in %.3f s (%.3e star draws/s) -> %s, %s\n",
-                     n_rows, n, K, Q, sec, (double)n_rows * n / sec, mp.c_str(), bp.c_str());
+                     n_rows, n, g.K, g.Q, sec, (double)n_rows * n / sec, mp.c_str(), bp.c_str());
         return 0;
     } catch (const std::exception &e) {
         return b9h::report_and_exit_code("sampleMass", e);

@@ -11,7 +11,6 @@
 #include "cli_common.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <stdexcept>
 
@@ -19,20 +18,12 @@ int main(int argc, char **argv)
 {
     try {
         b9h::Session s;
-        b9h::open_session(s, argc, argv, 1, true);
-        const long nodes = s.settings.integer("sampleWDMass.nMassNodes", 512);
-        if (nodes < 1 || nodes > 2147483647l) throw std::runtime_error("nMassNodes must be a positive 32-bit number");
-        const int n_wd = b9_n_wd_stars(s.ctx);
-        if (n_wd < 0) throw std::runtime_error(b9_last_error(s.ctx));
-        if (n_wd == 0) throw std::runtime_error("the photometry holds no WD-stage star (stage 3): nothing to sample");
-        std::vector<int> wd;
-        for (int i = 0; i < s.phot.n_stars(); ++i) if (s.phot.stage[i] == B9_STAGE_WD) wd.push_back(i);
-        if ((int)wd.size() != n_wd) throw std::runtime_error("the staged catalogue and the photometry disagree on the WD-stage stars");
-
-        const std::string res_path = s.output_base + ".res";
-        const std::vector<double> rows = b9h::read_res_rows(res_path, s.start, 3);
-        const long n_rows = (long)(rows.size() / B9_NPARAM);
-        if (n_rows == 0) throw std::runtime_error(res_path + " holds no main-run (stage 3) rows");
+        s.settings.parse_args(argc, argv);
+        const long nodes = b9h::wd_mass_nodes(s.settings, "sampleWDMass");
+        const b9h::SavedChain chain = b9h::open_saved_chain(s, {1, 0, 0});
+        const long n_rows = chain.n_rows;
+        const std::vector<int> wd = b9h::wd_stage_stars(s, "sample");
+        const int n_wd = (int)wd.size();
 
         // the seven files, in the order of b9_sample_wd_mass's outputs
         static const char *const kind[7] = {"zamsMass", "mass", "precLogAge", "coolingAge", "logTeff", "logg", "membership"};
@@ -46,13 +37,10 @@ int main(int argc, char **argv)
             std::fprintf(f[k], "\n");
             names += (k ? ", " : "") + p;
         }
-        const long batch = 256;
         std::vector<double> out[7];
-        for (auto &v : out) v.resize((size_t)batch * n_wd);
-        const auto t0 = std::chrono::steady_clock::now();
-        for (long r0 = 0; r0 < n_rows; r0 += batch) {
-            const long m = std::min(batch, n_rows - r0);
-            if (b9_sample_wd_mass(s.ctx, rows.data() + (size_t)r0 * B9_NPARAM, (int32_t)m, (int32_t)nodes, s.mcmc.seed, r0, out[0].data(),
+        for (auto &v : out) v.resize((size_t)b9h::kChainBatch * n_wd);
+        const double sec = b9h::for_row_batches(n_rows, [&](long r0, long m) {
+            if (b9_sample_wd_mass(s.ctx, chain.row(r0), (int32_t)m, (int32_t)nodes, s.mcmc.seed, r0, out[0].data(),
                                   out[1].data(), out[2].data(), out[3].data(), out[4].data(), out[5].data(), out[6].data(), nullptr) != B9_OK) {
                 for (FILE *p : f) std::fclose(p);
                 throw std::runtime_error(b9_last_error(s.ctx));
@@ -62,9 +50,8 @@ int main(int argc, char **argv)
                     for (int c = 0; c < n_wd; ++c) std::fprintf(f[k], "%s%.6f", c ? " " : "", out[k][(size_t)r * n_wd + c]);
                     std::fprintf(f[k], "\n");
                 }
-        }
+        });
         for (FILE *p : f) std::fclose(p);
-        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::fprintf(stderr, "sampleWDMass: %ld chain rows x %d WD-stage stars (%ld mass nodes) in %.3f s (%.3e star draws/s) -> %s\n",
                      n_rows, n_wd, nodes, sec, (double)n_rows * n_wd / sec, names.c_str());
         return 0;

@@ -13,11 +13,10 @@
 int main(int argc, char **argv)
 {
     try {
-        b9h::Settings pre;
-        pre.parse_args(argc, argv);
-        const b9h::SimConfig cfg = b9h::sim_config(pre);       // (settings errors before anything touches a GPU)
         b9h::Session s;
-        b9h::open_session(s, argc, argv, cfg.n_pops, false);
+        s.settings.parse_args(argc, argv);
+        const b9h::SimConfig cfg = b9h::sim_config(s.settings);       // (settings errors before anything touches a GPU)
+        b9h::open_session(s, cfg.n_pops, false);
         auto check = [&](int rc) { if (rc != B9_OK) throw std::runtime_error(b9_last_error(s.ctx)); };
         const int nf = (int)s.pack.filters.size();
         int cap = 0;

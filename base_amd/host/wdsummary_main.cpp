@@ -12,7 +12,6 @@
 #include "cli_common.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <stdexcept>
 
@@ -20,37 +19,20 @@ int main(int argc, char **argv)
 {
     try {
         b9h::Session s;
-        {   // (the population count decides which starting values open_session reads: peek at the settings first)
-            b9h::Settings peek;
-            peek.parse_args(argc, argv);
-            const long n_pops = peek.integer("wdSummary.nPops", 1);
-            if (n_pops != 1 && n_pops != 2) throw std::runtime_error("wdSummary.nPops must be 1 or 2");
-            b9h::open_session(s, argc, argv, (int)n_pops, true);
-        }
-        const int n_pops = (int)s.settings.integer("wdSummary.nPops", 1);
-        const long nodes = s.settings.integer("wdSummary.nMassNodes", s.settings.integer("sampleWDMass.nMassNodes", 512));
-        if (nodes < 1 || nodes > 2147483647l) throw std::runtime_error("nMassNodes must be a positive 32-bit number");
-        const int n_wd = b9_n_wd_stars(s.ctx);
-        if (n_wd < 0) throw std::runtime_error(b9_last_error(s.ctx));
-        if (n_wd == 0) throw std::runtime_error("the photometry holds no WD-stage star (stage 3): nothing to summarise");
+        s.settings.parse_args(argc, argv);
+        const int n_pops = b9h::chain_n_pops(s.settings, "wdSummary");
+        const long nodes = b9h::wd_mass_nodes(s.settings, "wdSummary");
+        const b9h::SavedChain chain = b9h::open_saved_chain(s, {n_pops, 0, 0});
+        const long n_rows = chain.n_rows;
         std::vector<std::string> ids;
-        for (int i = 0; i < s.phot.n_stars(); ++i) if (s.phot.stage[i] == B9_STAGE_WD) ids.push_back(s.phot.ids[i]);
-        if ((int)ids.size() != n_wd) throw std::runtime_error("the staged catalogue and the photometry disagree on the WD-stage stars");
-
-        const std::string res_path = s.output_base + ".res";
-        const std::vector<double> rows = b9h::read_res_rows(res_path, s.start, 3);
-        const long n_rows = (long)(rows.size() / B9_NPARAM);
-        if (n_rows == 0) throw std::runtime_error(res_path + " holds no main-run (stage 3) rows");
+        for (int i : b9h::wd_stage_stars(s, "summarise")) ids.push_back(s.phot.ids[i]);
+        const int n_wd = (int)ids.size();
 
         std::vector<double> acc((size_t)n_wd * B9_WDM_N, 0.0);
-        const long batch = 256;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (long r0 = 0; r0 < n_rows; r0 += batch) {
-            const long m = std::min(batch, n_rows - r0);
-            if (b9_wd_moments(s.ctx, rows.data() + (size_t)r0 * B9_NPARAM, (int32_t)m, (int32_t)nodes, r0 ? B9_WDM_CONTINUE : 0, acc.data()) != B9_OK)
+        const double sec = b9h::for_row_batches(n_rows, [&](long r0, long m) {
+            if (b9_wd_moments(s.ctx, chain.row(r0), (int32_t)m, (int32_t)nodes, r0 ? B9_WDM_CONTINUE : 0, acc.data()) != B9_OK)
                 throw std::runtime_error(b9_last_error(s.ctx));
-        }
-        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        });
         const std::string out = s.output_base + ".wdSummary";
         b9h::write_wd_summary(out, ids, acc.data(), n_pops);
         std::fprintf(stderr, "wdSummary: %ld chain rows x %d WD-stage stars (%ld mass nodes) in %.3f s (%.3e node evaluations/s) -> %s\n",

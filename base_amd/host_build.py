@@ -30,13 +30,13 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 
 
 def build_host(force: bool = False) -> None:
-    """libbase9host.so = parsers + sampler (g++) + the RCCL exchange and the C surface (hipcc as a host compiler, for the
+    """libbase9host.so = parsers + the saved-chain programs' tables and files + sampler (g++) + the RCCL exchange and the C surface (hipcc as a host compiler, for the
     HIP / RCCL headers: neither file holds device code); it links libbase9hip.so, librccl and libamdhip64."""
     os.makedirs(BIN, exist_ok=True)
-    hdrs = [os.path.join(HOST, f) for f in ("b9host.hpp", "cli_common.hpp", "b9sampler.hpp", "b9dist.hpp", "b9sim.hpp")] + \
+    hdrs = [os.path.join(HOST, f) for f in ("b9host.hpp", "b9chain.hpp", "cli_common.hpp", "b9sampler.hpp", "b9dist.hpp", "b9sim.hpp")] + \
         [os.path.join(HERE, "..", "include", f) for f in ("base9_hip.h", "base9_host.h")]
     lib = os.path.join(HOST, "libbase9host.so")
-    gxx_src = ["b9host.cpp", "b9sampler.cpp", "cli_common.cpp", "b9sim.cpp"]
+    gxx_src = ["b9host.cpp", "b9chain.cpp", "b9sampler.cpp", "cli_common.cpp", "b9sim.cpp"]
     hip_src = ["b9dist.cpp", "capi_host.cpp"]
     link = ["-L" + CSRC, "-lbase9hip", "-Wl,-rpath," + CSRC, "-Wl,-rpath,$ORIGIN/../../csrc"]
     if force or _stale(lib, [os.path.join(HOST, f) for f in gxx_src + hip_src] + hdrs):

@@ -9,8 +9,6 @@ row_hist entry.  Edges are separated from every reference node value by 1e-9 rel
 by two roundings: a node that close to an edge could fall either way)."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,6 +19,7 @@ import moments_ref as mr
 import test_gpu_moments as tm
 from base_amd import abi, synth
 from conftest import build_problem
+from cli_util import cli as _cli
 
 pytestmark = pytest.mark.gpu
 
@@ -411,11 +410,6 @@ def test_errors_leave_the_outputs_untouched():
 
 
 # ---- 7. the CLI ---------------------------------------------------------------------------------------------------------------
-def _cli(name, *args, timeout=600):
-    from base_amd import host_build
-    return subprocess.run([os.path.join(host_build.BIN, name), *args], capture_output=True, text=True, timeout=timeout)
-
-
 def test_cli_mass_function(tmp_path):
     """simCluster (200 stars) -> scatterCluster -> singlePopMcmc (short, 4 walkers x 100 main-run rows: the program passes
     them in two batches, the second continued) -> massFunction --perStar: both files equal, to the printed precision, what

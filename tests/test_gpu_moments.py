@@ -7,8 +7,6 @@ Tolerance of every comparison with the reference: rtol 1e-9 -- the project's per
 and, because the kernel prunes, atol = N_nodes e^-40 on components 1..7 (N_nodes: the nodes of a star's grid, all
 populations; stated per case)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +14,7 @@ import pytest
 import moments_ref as mr
 from base_amd import abi, synth
 from conftest import build_problem
+from cli_util import cli as _cli, read_phot as _read_phot
 
 pytestmark = pytest.mark.gpu
 
@@ -293,26 +292,6 @@ def test_every_instance(n_filt, n_pops):
 
 
 # ---- 8. the CLI ---------------------------------------------------------------------------------------------------------------
-def _cli(name, *args, timeout=600):
-    from base_amd import host_build
-    return subprocess.run([os.path.join(host_build.BIN, name), *args], capture_output=True, text=True, timeout=timeout)
-
-
-def _read_phot(path):
-    from base_amd import hostlib
-    lib = hostlib.load()
-    h, view = C.c_void_p(), abi.b9_stars()
-    buf = C.create_string_buffer(512)
-    assert lib.b9h_read_phot(path.encode(), -1e300, 1e300, 0, C.byref(h), C.byref(view), buf, 512) == 0, lib.b9h_last_error()
-    n, nf = view.n_stars, view.n_filt
-    g = lambda p, k: np.ctypeslib.as_array(p, shape=(k,)).copy()     # noqa: E731
-    d = dict(n_filt=nf, obs=g(view.obs, n * nf), sigma=g(view.sigma, n * nf), mass1=g(view.mass1, n), mass_ratio=g(view.mass_ratio, n),
-             clust_prior=g(view.clust_prior, n), stage=g(view.stage, n), wd_type=g(view.wd_type, n),
-             filter_prior_min=g(view.filter_prior_min, nf), filter_prior_max=g(view.filter_prior_max, nf))
-    lib.b9h_free_phot(h)
-    return d
-
-
 def test_cli_star_summary(tmp_path):
     """simCluster (200 stars) -> scatterCluster -> singlePopMcmc (short) -> starSummary: the file parses, equals
     engine.star_table(Engine.star_moments(stage-3 rows)) to the printed precision, and the member stars' mass lies within

@@ -10,7 +10,6 @@ import functools
 import math
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,6 +19,7 @@ import pointwise_ref as pr
 import test_gpu_moments as tm
 from base_amd import abi, synth
 from conftest import build_problem
+from cli_util import cli as _cli
 
 pytestmark = pytest.mark.gpu
 _dp = C.POINTER(C.c_double)
@@ -448,11 +448,6 @@ def test_two_populations_are_told_from_one():
 
 
 # ---- 10. the CLI --------------------------------------------------------------------------------------------------------------
-def _cli(name, *args, timeout=600):
-    from base_amd import host_build
-    return subprocess.run([os.path.join(host_build.BIN, name), *args], capture_output=True, text=True, timeout=timeout)
-
-
 def test_cli_model_score(tmp_path):
     """simCluster (200 stars) -> scatterCluster -> singlePopMcmc (short, 4 walkers x 100 main-run rows: the program passes them in
     two batches, the second continued) -> modelScore --perRow: the three files parse and equal what Engine.pointwise in ONE call

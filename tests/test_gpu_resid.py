@@ -7,8 +7,6 @@ Tolerances: tests/resid_check.py (rtol 1e-9 + the pruning's bound per column + t
 with b9_tuning.marg_no_pruning the pruning's bound is dropped)."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,6 +17,7 @@ import resid_ref as rr
 import test_gpu_moments as tm
 from base_amd import abi, synth
 from conftest import build_problem
+from cli_util import cli as _cli
 
 pytestmark = pytest.mark.gpu
 _dp = C.POINTER(C.c_double)
@@ -439,11 +438,6 @@ def test_errors_leave_the_outputs_untouched():
 
 
 # ---- 7. the CLI ---------------------------------------------------------------------------------------------------------------
-def _cli(name, *args, timeout=600):
-    from base_amd import host_build
-    return subprocess.run([os.path.join(host_build.BIN, name), *args], capture_output=True, text=True, timeout=timeout)
-
-
 def test_cli_phot_residuals(tmp_path):
     """simCluster (200 stars) -> scatterCluster -> singlePopMcmc (short, 4 walkers x 100 main-run rows: the program passes
     them in two batches, the second continued) -> photResiduals --perStar: both files read back to the bits of what

@@ -12,8 +12,6 @@ for every column.  A star's edges are its own weighted quantiles between the 5 %
 value of that star by 1e-9 relative (the device forms M1 by fma, numpy by two roundings)."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -26,6 +24,7 @@ import starbins_ref as sr
 import test_gpu_moments as tm
 from base_amd import abi, synth
 from conftest import build_problem
+from cli_util import cli as _cli
 
 pytestmark = pytest.mark.gpu
 
@@ -375,11 +374,6 @@ def test_star_intervals_end_to_end(n_pops, quantity):
     if quantity == abi.HQ_SECONDARY:
         assert none[np.asarray(cl["stage"]) == abi.STAGE_WD].all()
     np.testing.assert_allclose(res["member"], mr.accumulate(pack_d, cl, rows, n_pops, K, Q)[:, abi.MOM_MEMBER] / 34, rtol=1e-9, atol=N_NODES[n_pops] * np.exp(-40.0))
-
-
-def _cli(name, *args, timeout=600):
-    from base_amd import host_build
-    return subprocess.run([os.path.join(host_build.BIN, name), *args], capture_output=True, text=True, timeout=timeout)
 
 
 def test_cli_star_intervals(tmp_path):

@@ -2,9 +2,6 @@
 drawn node is the one b9o_sample_mass picks at marg_iso_increm = K), against b9_sample_mass, the derived values against the
 numpy restatement tests/wd_check.py, bit-for-bit invariances, every kernel instance, edges, and the draw's statistics.
 Each test makes its own short-lived engine."""
-import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +11,7 @@ import oracle
 import wd_check
 from base_amd import abi, synth
 from conftest import build_problem
+from cli_util import cli as _cli, read_phot as _read_phot
 
 pytestmark = pytest.mark.gpu
 
@@ -439,26 +437,6 @@ def test_draws_follow_the_categorical_posterior():
 # ---- 8. the CLI loop ------------------------------------------------------------------------------------------------------
 WD_FILES = ("zamsMass", "mass", "precLogAge", "coolingAge", "logTeff", "logg", "membership")
 WD_KEYS = ("zams", "wd_mass", "prec_log_age", "log_cool_age", "log_teff", "logg", "member")
-
-
-def _cli(name, *args, timeout=600):
-    from base_amd import host_build
-    return subprocess.run([os.path.join(host_build.BIN, name), *args], capture_output=True, text=True, timeout=timeout)
-
-
-def _read_phot(path):
-    from base_amd import hostlib
-    lib = hostlib.load()
-    h, view = C.c_void_p(), abi.b9_stars()
-    buf = C.create_string_buffer(512)
-    assert lib.b9h_read_phot(path.encode(), -1e300, 1e300, 0, C.byref(h), C.byref(view), buf, 512) == 0, lib.b9h_last_error()
-    n, nf = view.n_stars, view.n_filt
-    g = lambda p, k: np.ctypeslib.as_array(p, shape=(k,)).copy()     # noqa: E731
-    d = dict(n_filt=nf, obs=g(view.obs, n * nf), sigma=g(view.sigma, n * nf), mass1=g(view.mass1, n), mass_ratio=g(view.mass_ratio, n),
-             clust_prior=g(view.clust_prior, n), stage=g(view.stage, n), wd_type=g(view.wd_type, n),
-             filter_prior_min=g(view.filter_prior_min, nf), filter_prior_max=g(view.filter_prior_max, nf))
-    lib.b9h_free_phot(h)
-    return d
 
 
 def test_cli_loop_files_equal_the_engine_and_recover_the_simulated_masses(tmp_path):

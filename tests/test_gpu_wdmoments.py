@@ -2,8 +2,6 @@
 (tests/wdmoments_ref.py, through the comparator of tests/wdmoments_check.py), ties to b9_star_moments and b9_sample_wd_mass
 on the same rows, bit-for-bit invariances, the edges of the shapes, sampler blocks left alone, the statistics of the device's
 own draws against the table, and the CLI loop.  Each test makes its own short-lived engine."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +11,7 @@ import wdmoments_check as wc
 import wdmoments_ref as wr
 from base_amd import abi, synth
 from conftest import build_problem
+from cli_util import cli as _cli, read_phot as _read_phot
 
 pytestmark = pytest.mark.gpu
 
@@ -328,27 +327,6 @@ def test_statistics_against_device_draws():
 
 
 # ---- 7. the CLI loop --------------------------------------------------------------------------------------------------------------
-def _cli(name, *args, timeout=600):
-    from base_amd import host_build
-    return subprocess.run([os.path.join(host_build.BIN, name), *args], capture_output=True, text=True, timeout=timeout)
-
-
-def _read_phot(path):
-    import ctypes as C
-    from base_amd import hostlib
-    lib = hostlib.load()
-    h, view = C.c_void_p(), abi.b9_stars()
-    buf = C.create_string_buffer(512)
-    assert lib.b9h_read_phot(path.encode(), -1e300, 1e300, 0, C.byref(h), C.byref(view), buf, 512) == 0, lib.b9h_last_error()
-    n, nf = view.n_stars, view.n_filt
-    g = lambda p, k: np.ctypeslib.as_array(p, shape=(k,)).copy()     # noqa: E731
-    d = dict(n_filt=nf, obs=g(view.obs, n * nf), sigma=g(view.sigma, n * nf), mass1=g(view.mass1, n), mass_ratio=g(view.mass_ratio, n),
-             clust_prior=g(view.clust_prior, n), stage=g(view.stage, n), wd_type=g(view.wd_type, n),
-             filter_prior_min=g(view.filter_prior_min, nf), filter_prior_max=g(view.filter_prior_max, nf))
-    lib.b9h_free_phot(h)
-    return d
-
-
 def test_cli_loop_file_equals_the_engine_and_agrees_with_the_draws(tmp_path):
     """simCluster (seeded, WD primaries) -> scatterCluster -> singlePopMcmc (short) -> wdSummary, and sampleWDMass on the same
     chain.  Every step runs under its own time limit and a failed step ends the test."""

@@ -176,3 +176,22 @@ def test_flags_and_yaml_parse(host, tmp_path):
     for bad in (["--nBins", "0"], ["--nBins", "65"], ["--quantity", "total"], ["--minMass", "9"], ["--minMass", "0"]):
         with pytest.raises(hostlib.HostError):
             hostlib.mass_function_settings(bad)
+
+
+def test_short_and_long_flags(host):
+    """--minMass / --maxMass are massFunction's own spellings of --massFunctionMinMass / --massFunctionMaxMass: both give the same
+    settings, on this program's command line only -- the shared table gives the short names to simCluster --, and massFunction
+    takes no other program's short flag for a key of its own."""
+    from cli_util import settings_dump
+    short = hostlib.mass_function_settings(["--minMass", "0.5", "--maxMass=5.5"])
+    long_ = hostlib.mass_function_settings(["--massFunctionMinMass", "0.5", "--massFunctionMaxMass=5.5"])
+    assert short[0] == long_[0] and short[0]["minMass"] == 0.5 and short[0]["maxMass"] == 5.5 and np.array_equal(short[1], long_[1])
+    assert settings_dump(["--minMass", "0.5", "--maxMass=5.5"]) == {"simCluster.minMass": "0.5", "simCluster.maxMass": "5.5"}
+    assert settings_dump(["--massFunctionMinMass", "0.5"]) == {"massFunction.minMass": "0.5"}
+    # --nPops stays simCluster's here: massFunction's population count comes from the YAML only
+    assert hostlib.mass_function_settings(["--nPops", "2"])[0] == hostlib.mass_function_settings([])[0]
+    assert hostlib.mass_function_settings(["--perStar=0"])[0]["perStar"] == 0 and hostlib.mass_function_settings(["--perStar"])[0]["perStar"] == 1
+    with pytest.raises(hostlib.HostError, match="unexpected argument '0'"):
+        hostlib.mass_function_settings(["--perStar", "0"])
+    with pytest.raises(hostlib.HostError):
+        hostlib.mass_function_settings(["--perRow"])                    # modelScore's

@@ -336,3 +336,23 @@ def test_compare_to_on_hand_written_files(host, tmp_path):
         r = _model_score("--outputFileBase", base_a, "--compareTo", str(tmp_path / f"c{k}"))
         assert r.returncode != 0 and "differ" in r.stderr
     assert _model_score("--outputFileBase", base_a, "--compareTo", str(tmp_path / "missing")).returncode != 0
+
+
+def test_short_and_long_flags(host):
+    """--perRow / --nPops are modelScore's own spellings of --modelScorePerRow / --modelScoreNPops: both give the same settings,
+    on this program's command line only; --perRow takes no value."""
+    from cli_util import settings_dump
+    short = hostlib.model_score_settings(["--perRow", "--nPops", "2"])
+    long_ = hostlib.model_score_settings(["--modelScorePerRow=1", "--modelScoreNPops", "2"])
+    assert short == long_ == dict(margIsoIncrem=4, nMassRatios=4, nPops=2, perRow=1, compareTo="")
+    assert hostlib.model_score_settings(["--perRow=1", "--nPops=2"]) == short
+    assert hostlib.model_score_settings(["--perRow=0"])["perRow"] == 0
+    assert settings_dump(["--modelScorePerRow=1", "--modelScoreNPops", "2"]) == {"modelScore.perRow": "1", "modelScore.nPops": "2"}
+    assert settings_dump(["--nPops", "2"]) == {"simCluster.nPops": "2"}
+    for bad in (["--perRow", "0"], ["--nPops", "2", "--perRow", "0"]):
+        with pytest.raises(hostlib.HostError, match="unexpected argument '0'"):
+            hostlib.model_score_settings(bad)
+    with pytest.raises(hostlib.HostError):
+        settings_dump(["--perRow=1"])                                   # no flag of the shared table
+    # photResiduals' and massFunction's --perStar is massFunction's key here: accepted, and nothing of modelScore's changes
+    assert hostlib.model_score_settings(["--perStar", "--quantity", "system"]) == hostlib.model_score_settings([])

@@ -234,3 +234,24 @@ def test_flags_and_yaml_parse(host, tmp_path):
     for bad in (["--nPops", "3"], ["--margIsoIncrem", "0"], ["--nMassRatios", "0"]):
         with pytest.raises(hostlib.HostError):
             hostlib.phot_resid_settings(bad)
+
+
+def test_short_and_long_flags(host):
+    """--perStar / --nPops are photResiduals' own spellings of --photResidualsPerStar / --photResidualsNPops: both give the same
+    settings, on this program's command line only.  The shared table gives --perStar to massFunction: the long spelling sets the
+    program's key and no other, and the program reads the short one as the long one."""
+    from cli_util import settings_dump
+    short = hostlib.phot_resid_settings(["--perStar", "--nPops", "2"])
+    long_ = hostlib.phot_resid_settings(["--photResidualsPerStar=1", "--photResidualsNPops", "2"])
+    assert short == long_ == dict(margIsoIncrem=4, nMassRatios=4, nPops=2, perStar=1)
+    assert hostlib.phot_resid_settings(["--perStar=1", "--nPops=2"]) == short
+    assert hostlib.phot_resid_settings(["--perStar=0"])["perStar"] == 0
+    assert settings_dump(["--photResidualsPerStar=1", "--photResidualsNPops", "2"]) == {"photResiduals.perStar": "1", "photResiduals.nPops": "2"}
+    assert settings_dump(["--perStar", "--nPops", "2"]) == {"massFunction.perStar": "1", "simCluster.nPops": "2"}
+    for bad in (["--perStar", "0"], ["--perStar", "0", "--nPops", "2"]):
+        with pytest.raises(hostlib.HostError, match="unexpected argument '0'"):
+            hostlib.phot_resid_settings(bad)
+    # another program's short flags: known to the shared table -> accepted, and nothing of photResiduals' changes; else refused
+    assert hostlib.phot_resid_settings(["--quantity", "system", "--minMass", "0.5"]) == hostlib.phot_resid_settings([])
+    with pytest.raises(hostlib.HostError):
+        hostlib.phot_resid_settings(["--perRow"])                       # modelScore's

@@ -226,3 +226,19 @@ def test_cli_flags_and_yaml_keys(tmp_path):
             hostlib.star_intervals_settings(bad)
     # massFunction keeps its own --quantity and --nPops
     assert hostlib.mass_function_settings(["--quantity", "secondary"])[0]["quantity"] == 1
+
+
+def test_short_and_long_flags():
+    """--quantity / --nPops are starIntervals' own spellings of --starIntervalsQuantity / --starIntervalsNPops: both give the same
+    settings, on this program's command line only -- the shared table gives the short names to massFunction and simCluster."""
+    from cli_util import settings_dump
+    short = hostlib.star_intervals_settings(["--quantity", "system", "--nPops=2"])
+    long_ = hostlib.star_intervals_settings(["--starIntervalsQuantity", "system", "--starIntervalsNPops=2"])
+    assert short == long_ and short["quantity"] == 2 and short["nPops"] == 2
+    assert hostlib.star_intervals_settings(["--nPops", "2"])["nPops"] == 2
+    assert settings_dump(["--quantity", "system", "--nPops=2"]) == {"massFunction.quantity": "system", "simCluster.nPops": "2"}
+    assert settings_dump(["--starIntervalsQuantity", "system", "--starIntervalsNPops=2"]) == {"starIntervals.quantity": "system", "starIntervals.nPops": "2"}
+    # another program's flags are accepted where the shared table knows them, and set nothing of starIntervals'
+    assert hostlib.star_intervals_settings(["--perStar", "--minMass", "0.5", "--massFunctionMinMass", "0.5"]) == hostlib.star_intervals_settings([])
+    with pytest.raises(hostlib.HostError):
+        hostlib.star_intervals_settings(["--perRow"])                   # modelScore's
