@@ -32,6 +32,11 @@ HIST_CONTINUE = 1
 # b9_star_bins: the most bins of a call and its flag (columns of acc: below, the bins, at or above, the total)
 SBIN_MAX_BINS = 30
 SBIN_CONTINUE = 1
+# b9_wd_bins: what is binned (enum b9_wd_quantity; a call's mask has bit q for quantity q), the most bins of a call and its flag
+WQ_ZAMS, WQ_WDMASS, WQ_PREC, WQ_LOGCOOL, WQ_LOGTEFF, WQ_LOGG, WQ_N = range(7)
+WQ_ALL = (1 << WQ_N) - 1
+WBIN_MAX_BINS = 30
+WBIN_CONTINUE = 1
 # b9_phot_resid: the first two columns of star_resid (then 2 + 2f, 3 + 2f per filter) and its flag
 RESID_ROWS, RESID_MEMBER = 0, 1
 RESID_CONTINUE = 1
@@ -214,7 +219,7 @@ ABI_SYMBOLS = [
     "b9_abi_version", "b9_ctx_create", "b9_ctx_destroy", "b9_last_error",
     "b9_load_pack", "b9_load_stars", "b9_set_priors", "b9_set_options", "b9_set_tuning", "b9_get_tuning",
     "b9_logpost", "b9_logpost_device", "b9_mcmc_run_block", "b9_mcmc_wait", "b9_sample_mass", "b9_derive_isochrone",
-    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_star_moments", "b9_wd_moments", "b9_mass_hist", "b9_star_bins", "b9_phot_resid", "b9_pointwise", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
+    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_star_moments", "b9_wd_moments", "b9_mass_hist", "b9_star_bins", "b9_wd_bins", "b9_phot_resid", "b9_pointwise", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
     "b9_enable_timing", "b9_kernel_time_ms", "b9_calibrate_timing", "b9_clock_stamp", "b9_clock_mhz",
 ]
 
@@ -253,6 +258,7 @@ def load_hip_library(path: Optional[str] = None) -> C.CDLL:
     lib.b9_wd_moments.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp]
     lib.b9_mass_hist.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, _dp]
     lib.b9_star_bins.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _dp]
+    lib.b9_wd_bins.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _dp]
     lib.b9_phot_resid.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, _dp]
     lib.b9_pointwise.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]
     lib.b9_max_eep.argtypes = [vp]

@@ -388,6 +388,67 @@ int b9_wd_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_n
     return B9_OK;
 }
 
+// b9_wd_moments' loop with the lines' edges beside the accumulators: the arguments are checked on the host before anything is
+// launched; a chunk is b9_wd_moments' rows, and fewer while the per-(row, line) scratch would exceed B9_WBIN_SCRATCH_BYTES.
+#define B9_WBIN_SCRATCH_BYTES ((size_t)64 << 20)
+int b9_wd_bins(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_nodes, int32_t quantity_mask, const double *edges, int32_t n_bins,
+               int32_t flags, double *acc)
+{
+    if (!ctx || !params || !edges || !acc || n_rows < 1 || n_nodes < 1) return B9_ERR_INVALID;
+    if (n_bins < 1 || n_bins > B9_WBIN_MAX_BINS) return fail(ctx, B9_ERR_INVALID, "b9_wd_bins: n_bins must lie in 1 .. B9_WBIN_MAX_BINS");
+    if (quantity_mask < 1 || quantity_mask >= (1 << B9_WQ_N)) return fail(ctx, B9_ERR_INVALID, "b9_wd_bins: the quantity mask must select some of the B9_WQ_N quantities and nothing else");
+    if (!ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
+    const int n = ctx->hs.n;
+    std::vector<int> rank(n);            // (an upload's source: it lives until the wait below)
+    int n_wd = 0;
+    for (int i = 0; i < n; ++i) { rank[i] = n_wd; n_wd += ctx->hs.stage[i] == B9_STAGE_WD; }
+    const size_t n_sel = (size_t)__builtin_popcount((unsigned)quantity_mask), ne = (size_t)n_bins + 1, ncol = (size_t)n_bins + 3;
+    const size_t n_lines = (size_t)n_wd * n_sel;
+    for (size_t l = 0; l < n_lines; ++l)
+        for (size_t b = 0; b < ne; ++b)
+            if (!std::isfinite(edges[l * ne + b]) || (b > 0 && !(edges[l * ne + b] > edges[l * ne + b - 1])))
+                return fail(ctx, B9_ERR_INVALID, "b9_wd_bins: WD-stage star " + std::to_string(l / n_sel) + ", selected quantity " + std::to_string(l % n_sel) +
+                                                     ": the edges must be finite and strictly ascending");
+    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
+    if (!ctx->have_pack) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
+    if (n_wd == 0) return B9_OK;
+    const int n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
+    const DevPack &pk = ctx->pk;
+    const int mass_cap = pack_mass_cap(pk.max_eep);
+    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
+    const size_t tab_row = (size_t)n_pops * (size_t)b9k_wd_moments_table_doubles(pk.nfp, n_nodes);       // doubles per row
+    if (tab_row > ((size_t)8 << 30) / sizeof(double)) return fail(ctx, B9_ERR_CAPACITY, "b9_wd_bins: one row's node table would exceed 8 GiB");
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>({(size_t)n_rows, (size_t)B9_WDS_MAX_ROWS, B9_WDS_TABLE_BYTES / (tab_row * sizeof(double)),
+                                                                 B9_WBIN_SCRATCH_BYTES / (n_lines * ncol * sizeof(double))}));
+    const WdbArena a = wdb_arena(chunk, n_pops, iso_stride, tab_row, n_lines, (size_t)n, ncol, ne, sizeof(IsoHdr));
+    RESERVE(ctx, ctx->d_wds, a.bytes);
+    char *base = ctx->d_wds.get();
+    double *d_par = part<double>(base, a.o_par), *d_iso = part<double>(base, a.o_iso), *d_tab = part<double>(base, a.o_tab);
+    double *d_scratch = part<double>(base, a.o_scratch), *d_acc = part<double>(base, a.o_acc), *d_edges = part<double>(base, a.o_edges);
+    IsoHdr *d_hdr = part<IsoHdr>(base, a.o_hdr);
+    int *d_rank = part<int>(base, a.o_rank);
+    hipStream_t s = ctx->stream;
+    const size_t acc_bytes = sizeof(double) * n_lines * ncol;
+    HIPCHK(ctx, hipMemcpyAsync(d_rank, rank.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(d_edges, edges, sizeof(double) * n_lines * ne, hipMemcpyHostToDevice, s));
+    if (flags & B9_WBIN_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_acc, acc, acc_bytes, hipMemcpyHostToDevice, s));
+    else HIPCHK(ctx, hipMemsetAsync(d_acc, 0, acc_bytes, s));
+    const McmcDev off{};
+    for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
+        const int m = std::min((int)chunk, n_rows - r0);
+        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
+        // the star kernel writes every (row, line) of the chunk, so nothing is cleared
+        HIPCHK(ctx, b9k_wd_bins(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, n_nodes, d_tab, d_rank, quantity_mask, d_edges, n_bins,
+                                d_scratch, d_acc, s));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(acc, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return B9_OK;
+}
+
 }  // extern "C"
 
 namespace {

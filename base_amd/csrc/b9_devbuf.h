@@ -121,6 +121,20 @@ inline WdmArena wdm_arena(size_t chunk, int n_pops, long long iso_stride, size_t
     return a;
 }
 
+// b9_wd_bins' chunk of rows, in the same allocation: b9_wd_moments' parts with n_lines = n_wd * n_sel lines of n_col increments
+// in place of the stars' sixteen, and behind them the lines' edges [n_lines][n_edges]
+struct WdbArena { size_t o_par, o_hdr, o_iso, o_tab, o_scratch, o_acc, o_rank, o_edges, bytes; };
+inline WdbArena wdb_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t n_lines, size_t n_stars, size_t n_col, size_t n_edges,
+                          size_t hdr_bytes)
+{
+    const WdmArena m = wdm_arena(chunk, n_pops, iso_stride, tab_row, n_lines, n_stars, n_col, hdr_bytes);
+    Carve c;
+    c.total = m.bytes;
+    WdbArena a{m.o_par, m.o_hdr, m.o_iso, m.o_tab, m.o_scratch, m.o_acc, m.o_rank, c.take(8 * n_lines * n_edges), 0};
+    a.bytes = c.total;
+    return a;
+}
+
 // The reductions over a saved chain (b9_star_moments, b9_mass_hist, b9_phot_resid, b9_pointwise), one chunk of rows:
 // [params][headers][isochrones][node table][WD node table][per-(row, star) increments [chunk][n_stars][n_col]], then the
 // accumulators [n_stars][n_acc], the chunk's per-row sums [chunk][n_rowcol], and the call's own extra parts in the order it

@@ -37,6 +37,8 @@
 //                                     per-wave LDS histogram per lane, bins worked in tiles), summed over the rows and the stars
 //   k_star_bins / _wd                b9_star_bins: the same bins on every star's OWN edges with the two open ends kept (the
 //                                     bin is per lane, the edges staged in LDS), summed over the rows
+//   k_wd_bins                        b9_wd_bins: b9_wd_moments' node weights binned on every (WD-stage star, quantity)'s OWN
+//                                     edges, one selected quantity per blockIdx.z, summed over the rows
 //   k_star_resid / _wd / k_resid_stage / k_resid_rows   b9_phot_resid: exact posterior-predictive magnitude
 //                                     moments per filter over the same grid, summed over the rows and, standardised, the stars
 //   k_star_lpd / _wd / k_pw_accumulate / k_pw_tail / k_pw_rows   b9_pointwise: every star's marginal log-likelihood per row over
@@ -86,6 +88,7 @@ namespace tree_kd5 {
 #include "b9_wd_moments.hip.h"
 #include "b9_mass_hist.hip.h"
 #include "b9_star_bins.hip.h"
+#include "b9_wd_bins.hip.h"
 #include "b9_phot_resid.hip.h"
 #include "b9_pointwise.hip.h"
 
@@ -273,6 +276,30 @@ hipError_t b9k_wd_moments(const DevPack &pk, const DevStars &st, const IsoHdr *h
         hipLaunchKernelGGL((k_wd_moments<NFP, NPOPS>), dim3((st.n_wd + 63) / 64, n_rows), dim3(64), 0, stream, pk, st, hdr, d_params, n_nodes,
                            (const double *)tab, n_wp, wd_rank, scratch);
         const long long n_words = (long long)st.n_wd * B9_WDM_N;
+        hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
+        return hipGetLastError();
+    });
+}
+
+// ---- b9_wd_bins: b9_wd_moments' node table, the WD-stage stars' increments on their own edges per selected quantity, the accumulation ----
+hipError_t b9k_wd_bins(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                       const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const int *wd_rank, int quantity_mask,
+                       const double *edges, int n_bins, double *scratch, double *acc, hipStream_t stream)
+{
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        const int n_sel = __builtin_popcount((unsigned)quantity_mask);
+        if (!tab || !wd_rank || !edges || !scratch || !acc || n_rows < 1 || n_nodes < 1 || st.n_wd < 1 || n_rows * NPOPS > 65535 || n_bins < 1 ||
+            n_bins > B9_WBIN_MAX_BINS || quantity_mask < 1 || quantity_mask >= (1 << B9_WQ_N))
+            return hipErrorInvalidValue;
+        const int n_wp = n_rows * NPOPS;
+        hipLaunchKernelGGL((k_wd_node_table_status<NFP>), dim3((n_nodes + 63) / 64, n_wp), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride, mass_cap,
+                           NPOPS, d_params, n_nodes, tab, n_wp);
+        const auto k = with_lds(k_wd_bins<NFP, NPOPS>, sizeof(double) * 64 * ((size_t)(n_bins + 1) + (size_t)(n_bins + 2)));
+        if (k.err != hipSuccess) return k.err;
+        hipLaunchKernelGGL(k.kern, dim3((st.n_wd + 63) / 64, n_rows, n_sel), dim3(64), k.lds, stream, pk, st, hdr, d_params, n_nodes,
+                           (const double *)tab, n_wp, wd_rank, quantity_mask, n_sel, edges, n_bins, scratch);
+        const long long n_words = (long long)st.n_wd * n_sel * (n_bins + 3);
         hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
         return hipGetLastError();
     });

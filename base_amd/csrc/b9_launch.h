@@ -128,6 +128,14 @@ hipError_t b9k_wd_moments(const DevPack &pk, const DevStars &st, const IsoHdr *h
                           hipStream_t stream);
 long long b9k_wd_moments_table_doubles(int nfp, long long n_nodes);      // per (row, population)
 
+// b9_wd_bins: k_wd_node_table_status (b9_wd_moments' table, built once per chunk) + k_wd_bins on n_rows derived rows (n_rows * n_pops <= 65535):
+// every (WD-stage star, selected quantity)'s increments on its own edges into scratch [n_rows][st.n_wd][n_sel][n_bins + 3] (below, the bins, at
+// or above, the total; star column wd_rank[original index]), then acc [st.n_wd][n_sel][n_bins + 3] += the rows in ascending order.  edges:
+// DEVICE, [st.n_wd][n_sel][n_bins + 1], validated by the caller; n_sel: the bits of quantity_mask.  Device pointers, all the caller's own.
+hipError_t b9k_wd_bins(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                       const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const int *wd_rank, int quantity_mask,
+                       const double *edges, int n_bins, double *scratch, double *acc, hipStream_t stream);
+
 // b9_star_moments: k_marg_table [+ k_marg_wd_table] of n_rows derived rows into tab / wd_tab (b9k_marg_table_doubles /
 // b9k_marg_wd_table_doubles per (row, population)), every star's eight increments into scratch [n_rows][st.n][B9_MOM_N], then
 // acc [st.n][B9_MOM_N] += the rows in ascending order.  Device pointers, all the caller's own.

@@ -215,6 +215,24 @@ class Engine:
         self._check(self.lib.b9_wd_moments(self._ctx, params.ctypes.data_as(_dp), params.shape[0], int(n_nodes), flags, out.ctypes.data_as(_dp)))
         return out, self.wd_index.copy()
 
+    def wd_bins(self, rows: np.ndarray, n_nodes: int, edges: np.ndarray, quantities: int = abi.WQ_ALL, acc: Optional[np.ndarray] = None):
+        """b9_wd_bins: the WD-stage stars' node weights over `rows` on b9_wd_moments' grid of n_nodes steps, binned on every line's
+        OWN edges `edges` [n_wd, n_sel, n_bins + 1] -- a line is (WD-stage star, selected quantity of the mask `quantities`, bit
+        abi.WQ_*, ascending).  Returns (acc [n_wd, n_sel, n_bins + 3] -- below, the bins, at or above, the total (membership) --,
+        star_index).  acc=None starts from zeros; else the call continues `acc` (B9_WBIN_CONTINUE) and returns a new array."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        n_wd, n_sel = self.n_wd_stars(), bin(int(quantities) & 0xffffffff).count("1")
+        edges = np.ascontiguousarray(edges, dtype=np.float64)
+        n_bins = edges.shape[-1] - 1
+        edges = edges.reshape(n_wd, max(n_sel, 1), n_bins + 1)
+        if acc is None:
+            out, flags = np.zeros((n_wd, max(n_sel, 1), n_bins + 3)), 0
+        else:
+            out, flags = np.array(acc, dtype=np.float64, order="C").reshape(n_wd, max(n_sel, 1), n_bins + 3), abi.WBIN_CONTINUE
+        self._check(self.lib.b9_wd_bins(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], int(n_nodes), int(quantities), edges.ctypes.data_as(_dp),
+                                        n_bins, flags, out.ctypes.data_as(_dp)))
+        return out, self.wd_index.copy()
+
     def star_moments(self, rows: np.ndarray, acc: Optional[np.ndarray] = None) -> np.ndarray:
         """b9_star_moments: the per-star posterior moments [n_stars, abi.MOM_N] summed over `rows`, exactly (no draws).
         acc=None starts from zeros; else the call continues `acc` (B9_MOM_CONTINUE) and returns a new array."""

@@ -73,6 +73,8 @@ long wd_mass_nodes(const Settings &st, const std::string &section)
 
 const ProgramFlags kMassFunctionFlags = {{"minMass", "massFunctionMinMass", false}, {"maxMass", "massFunctionMaxMass", false}};
 const ProgramFlags kStarIntervalsFlags = {{"quantity", "starIntervalsQuantity", false}, {"nPops", "starIntervalsNPops", false}};
+const ProgramFlags kWdIntervalsFlags = {{"levels", "wdIntervalsLevels", false}, {"tol", "wdIntervalsTol", false}, {"maxPasses", "wdIntervalsMaxPasses", false},
+                                        {"nMassNodes", "wdIntervalsNMassNodes", false}, {"nPops", "wdIntervalsNPops", false}};
 const ProgramFlags kPhotResidFlags = {{"perStar", "photResidualsPerStar", true}, {"nPops", "photResidualsNPops", false}};
 const ProgramFlags kModelScoreFlags = {{"perRow", "modelScorePerRow", true}, {"nPops", "modelScoreNPops", false}};
 
@@ -385,21 +387,26 @@ void refine_star_edges(const double *edges, const double *acc, long n_stars, int
     }
 }
 
-StarIntervals star_intervals(const StarBinsFn &bins, long n_stars, long n_rows, int n_bins, double max_mass, const std::vector<double> &levels, double tol,
-                             int max_passes)
+StarIntervals interval_loop(const StarBinsFn &bins, long n_lines, long n_rows, int n_bins, const double *first_lo, const double *first_hi,
+                            const std::vector<double> &levels, double tol, int max_passes, std::vector<double> *counted)
 {
     const int B = n_bins, m = (int)levels.size();
-    check_levels(levels.data(), m, B, "star_intervals");
-    if (max_passes < 1) fail("star_intervals: maxPasses must be positive");
-    if (!(max_mass > 0.0) || !std::isfinite(max_mass)) fail("star_intervals: the largest mass must be positive");
+    const long n_stars = n_lines;
+    check_levels(levels.data(), m, B, "interval_loop");
+    if (max_passes < 1) fail("interval_loop: maxPasses must be positive");
     StarIntervals r;
     r.n_levels = m; r.n_stars = n_stars;
     const size_t nm = (size_t)n_stars * m;
     r.member.assign(n_stars, 0.0); r.value.assign(nm, 0.0); r.lo.assign(nm, 0.0); r.hi.assign(nm, 0.0);
     r.is_final.assign(nm, 0); r.passes.assign(n_stars, 0); r.flags.assign(n_stars, 0);
     std::vector<double> edges((size_t)n_stars * (B + 1)), next(edges.size()), acc((size_t)n_stars * (B + 3)), below(nm), inside(nm);
-    for (long i = 0; i < n_stars; ++i)
-        for (int b = 0; b <= B; ++b) edges[(size_t)i * (B + 1) + b] = (2.0 * max_mass) * ((double)b / (double)B);
+    for (long i = 0; i < n_stars; ++i) {
+        const double lo = first_lo[i], hi = first_hi[i];
+        if (!std::isfinite(lo) || !std::isfinite(hi) || !(hi > lo)) fail("interval_loop: line " + std::to_string(i) + ": the first range must be finite and not empty");
+        for (int b = 0; b <= B; ++b) edges[(size_t)i * (B + 1) + b] = lo + (hi - lo) * ((double)b / (double)B);
+        for (int b = 1; b <= B; ++b)
+            if (!(edges[(size_t)i * (B + 1) + b] > edges[(size_t)i * (B + 1) + b - 1])) fail("interval_loop: line " + std::to_string(i) + ": the first range is too narrow to cut");
+    }
     for (int pass = 1; pass <= max_passes; ++pass) {
         bins(edges.data(), B, acc.data());
         refine_star_edges(edges.data(), acc.data(), n_stars, B, levels.data(), m, tol, r.lo.data(), r.hi.data(), below.data(), inside.data(), r.value.data(),
@@ -414,7 +421,27 @@ StarIntervals star_intervals(const StarBinsFn &bins, long n_stars, long n_rows, 
         if (all) break;
         edges.swap(next);
     }
+    if (counted) {
+        counted->assign(n_stars, 0.0);
+        for (long i = 0; i < n_stars; ++i) {
+            const double *a = acc.data() + (size_t)i * (B + 3);
+            double c = 0.0;
+            for (int k = 0; k < B + 2; ++k) c = c + a[k];       // (refine_star_edges' order)
+            if (a[B + 2] > 0.0) (*counted)[i] = c / a[B + 2];
+        }
+    }
     return r;
+}
+
+StarIntervals star_intervals(const StarBinsFn &bins, long n_stars, long n_rows, int n_bins, double max_mass, const std::vector<double> &levels, double tol,
+                             int max_passes)
+{
+    check_levels(levels.data(), (int)levels.size(), n_bins, "star_intervals");
+    if (max_passes < 1) fail("star_intervals: maxPasses must be positive");
+    if (!(max_mass > 0.0) || !std::isfinite(max_mass)) fail("star_intervals: the largest mass must be positive");
+    // (0 + (2 max_mass - 0) (b / B) is (2 max_mass) (b / B) bit for bit)
+    const std::vector<double> lo(n_stars, 0.0), hi(n_stars, 2.0 * max_mass);
+    return interval_loop(bins, n_stars, n_rows, n_bins, lo.data(), hi.data(), levels, tol, max_passes);
 }
 
 void star_intervals_table(const StarIntervals &r, double *table)
@@ -445,26 +472,151 @@ void write_star_intervals(const std::string &path, const std::vector<std::string
     write_table(path, "id", &ids, cols, (long)ids.size(), table, cols.size());
 }
 
-StarIntervalsConfig star_intervals_config(const Settings &st)
+namespace {
+// "a,b,.." or "[a, b, ..]" -> the numbers
+std::vector<double> parse_levels(const Settings &st, const std::string &key)
 {
-    StarIntervalsConfig c;
-    c.quantity = quantity_id(st, "starIntervals");
-    std::string lv = st.str("starIntervals.levels", "0.025,0.16,0.5,0.84,0.975");
+    std::vector<double> levels;
+    std::string lv = st.str(key, "0.025,0.16,0.5,0.84,0.975");
     for (char &ch : lv) if (ch == ',' || ch == '[' || ch == ']') ch = ' ';
     std::istringstream ls(lv);
     std::string tok;
     while (ls >> tok) {
         char *end = nullptr;
         const double v = std::strtod(tok.c_str(), &end);
-        if (end == tok.c_str() || *end) fail("starIntervals.levels: '" + tok + "' is not a number");
-        c.levels.push_back(v);
+        if (end == tok.c_str() || *end) fail(key + ": '" + tok + "' is not a number");
+        levels.push_back(v);
     }
+    return levels;
+}
+}  // namespace
+
+StarIntervalsConfig star_intervals_config(const Settings &st)
+{
+    StarIntervalsConfig c;
+    c.quantity = quantity_id(st, "starIntervals");
+    c.levels = parse_levels(st, "starIntervals.levels");
     c.tol = st.num("starIntervals.tol", 1e-4);
     c.max_passes = (int)st.integer("starIntervals.maxPasses", 12);
     check_levels(c.levels.data(), (int)c.levels.size(), B9_SBIN_MAX_BINS, "starIntervals.levels");
     if (!(c.tol >= 0.0)) fail("starIntervals.tol must not be negative");
     if (c.max_passes < 1) fail("starIntervals.maxPasses must be positive");
     return c;
+}
+
+// ---------------------------------------------------------------------------------------------
+// wdIntervals
+// ---------------------------------------------------------------------------------------------
+const char *const kWdQuantityNames[B9_WQ_N] = {"zamsMass", "wdMass", "precLogAge", "logCoolAge", "logTeff", "logg"};
+
+WdIntervalsConfig wd_intervals_config(const Settings &st)
+{
+    WdIntervalsConfig c;
+    c.quantity_mask = 0;
+    std::string qs = st.str("wdIntervals.quantities", "zamsMass,wdMass,precLogAge,logCoolAge,logTeff,logg");
+    for (char &ch : qs) if (ch == ',' || ch == '[' || ch == ']') ch = ' ';
+    std::istringstream is(qs);
+    std::string tok;
+    while (is >> tok) {
+        int q = 0;
+        while (q < B9_WQ_N && tok != kWdQuantityNames[q]) ++q;
+        if (q == B9_WQ_N) fail("wdIntervals.quantities: '" + tok + "' is none of zamsMass, wdMass, precLogAge, logCoolAge, logTeff, logg");
+        c.quantity_mask |= 1 << q;
+    }
+    if (c.quantity_mask == 0) fail("wdIntervals.quantities: at least one quantity");
+    c.levels = parse_levels(st, "wdIntervals.levels");
+    c.tol = st.num("wdIntervals.tol", 1e-4);
+    c.max_passes = (int)st.integer("wdIntervals.maxPasses", 12);
+    c.n_nodes = st.integer("wdIntervals.nMassNodes", st.integer("wdSummary.nMassNodes", st.integer("sampleWDMass.nMassNodes", 512)));
+    check_levels(c.levels.data(), (int)c.levels.size(), B9_WBIN_MAX_BINS, "wdIntervals.levels");
+    if (!(c.tol >= 0.0)) fail("wdIntervals.tol must not be negative");
+    if (c.max_passes < 1) fail("wdIntervals.maxPasses must be positive");
+    if (c.n_nodes < 1 || c.n_nodes > 2147483647l) fail("nMassNodes must be a positive 32-bit number");
+    return c;
+}
+
+void wd_first_ranges(const double *wd_acc, long n_wd, int quantity_mask, double *first_lo, double *first_hi)
+{
+    if (quantity_mask < 1 || quantity_mask >= (1 << B9_WQ_N)) fail("wd_first_ranges: the quantity mask selects nothing, or something unknown");
+    size_t o = 0;
+    for (long i = 0; i < n_wd; ++i) {
+        const double *a = wd_acc + (size_t)i * B9_WDM_N;
+        for (int q = 0; q < B9_WQ_N; ++q) {
+            if (!(quantity_mask >> q & 1)) continue;
+            const double w = q == B9_WQ_ZAMS ? a[B9_WDM_MEMBER] : a[B9_WDM_COOLED];
+            const double s1 = q == B9_WQ_ZAMS ? a[B9_WDM_M1] : a[B9_WDM_WDMASS + 2 * (q - 1)];
+            const double s2 = q == B9_WQ_ZAMS ? a[B9_WDM_M1SQ] : a[B9_WDM_WDMASS_SQ + 2 * (q - 1)];
+            double lo = 0.0, hi = 1.0;
+            if (w > 0.0) {
+                const double mean = s1 / w, sd = std::sqrt(std::max(0.0, s2 / w - mean * mean));
+                double half = std::max(6.0 * sd, 1e-3 * std::fabs(mean));
+                if (!(half > 0.0) || !std::isfinite(half)) half = 1.0;
+                if (std::isfinite(mean)) { lo = mean - half; hi = mean + half; }
+            }
+            first_lo[o] = lo; first_hi[o] = hi;
+            ++o;
+        }
+    }
+}
+
+WdIntervals wd_intervals(const WdMomentsFn &moments, const StarBinsFn &bins, long n_wd, long n_rows, int quantity_mask, const std::vector<double> &levels,
+                         double tol, int max_passes)
+{
+    WdIntervals r;
+    r.n_wd = n_wd; r.n_sel = __builtin_popcount((unsigned)quantity_mask);
+    const long n_lines = n_wd * r.n_sel;
+    std::vector<double> wd_acc((size_t)n_wd * B9_WDM_N, 0.0), lo(n_lines), hi(n_lines);
+    moments(wd_acc.data());
+    wd_first_ranges(wd_acc.data(), n_wd, quantity_mask, lo.data(), hi.data());
+    r.lines = interval_loop(bins, n_lines, n_rows, B9_WBIN_MAX_BINS, lo.data(), hi.data(), levels, tol, max_passes, &r.counted);
+    return r;
+}
+
+void wd_intervals_table(long n_wd, int n_sel, int n_levels, const double *member, const double *counted, const double *value, const double *lo,
+                        const double *hi, const int32_t *passes, const int32_t *flags, double *table)
+{
+    const int m = n_levels;
+    const size_t per = 3 * (size_t)m + 3, tcol = 1 + (size_t)n_sel * per;
+    for (long i = 0; i < n_wd; ++i) {
+        double *t = table + (size_t)i * tcol;
+        t[0] = member[(size_t)i * n_sel];
+        for (int s = 0; s < n_sel; ++s) {
+            const size_t line = (size_t)i * n_sel + s;
+            double *ts = t + 1 + (size_t)s * per;
+            ts[0] = counted[line];
+            for (int l = 0; l < m; ++l) {
+                const size_t o = line * m + l;
+                ts[1 + 3 * l] = value[o]; ts[2 + 3 * l] = lo[o]; ts[3 + 3 * l] = hi[o];
+            }
+            ts[per - 2] = (double)passes[line]; ts[per - 1] = (double)flags[line];
+        }
+    }
+}
+
+void wd_intervals_table(const WdIntervals &r, double *table)
+{
+    const StarIntervals &l = r.lines;
+    wd_intervals_table(r.n_wd, r.n_sel, l.n_levels, l.member.data(), r.counted.data(), l.value.data(), l.lo.data(), l.hi.data(), l.passes.data(),
+                       l.flags.data(), table);
+}
+
+void write_wd_intervals(const std::string &path, const std::vector<std::string> &ids, int quantity_mask, const std::vector<double> &levels,
+                        const double *table)
+{
+    std::vector<TableColumn> cols = {{"member", "%.17g"}};
+    for (int q = 0; q < B9_WQ_N; ++q) {
+        if (!(quantity_mask >> q & 1)) continue;
+        const std::string n = kWdQuantityNames[q];
+        cols.push_back({n + "_counted", "%.17g"});
+        for (double a : levels) {
+            char lv[40];
+            std::snprintf(lv, sizeof lv, "q%.12g", a);
+            for (const char *end : {"", "_lo", "_hi"}) cols.push_back({n + "_" + lv + end, "%.17g"});
+        }
+        cols.push_back({n + "_passes", "%.0f"});
+        cols.push_back({n + "_flags", "%.0f"});
+    }
+    write_table(path, "id", &ids, cols, (long)ids.size(), table, cols.size());
 }
 
 // ---------------------------------------------------------------------------------------------

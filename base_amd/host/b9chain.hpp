@@ -1,4 +1,4 @@
-// b9chain.hpp -- what the programs over a saved chain (sampleMass, sampleWDMass, starSummary, wdSummary, massFunction,
+// b9chain.hpp -- what the programs over a saved chain (sampleMass, sampleWDMass, starSummary, wdSummary, wdIntervals, massFunction,
 // starIntervals, photResiduals, modelScore) share above the C ABI and below their mains: their settings, the loop over the
 // chain's rows, the tables derived from the device's sums and the files they are written to (docs/FORMATS.md).  Host arithmetic
 // only: nothing here needs a context or a GPU.  b9host.hpp includes this header.
@@ -136,10 +136,53 @@ struct StarIntervals {
 using StarBinsFn = std::function<void(const double *edges, int n_bins, double *acc)>;
 StarIntervals star_intervals(const StarBinsFn &bins, long n_stars, long n_rows, int n_bins, double max_mass, const std::vector<double> &levels, double tol,
                              int max_passes);
+// ... and the loop itself, over n_lines independent lines whose first pass cuts [first_lo[i], first_hi[i]] (finite, lo < hi)
+// evenly: star_intervals is this loop with [0, 2 max_mass] for every star.  counted [n_lines] (may be null): the last pass's
+// counted mass C over its total column (0 where the total is 0).
+StarIntervals interval_loop(const StarBinsFn &bins, long n_lines, long n_rows, int n_bins, const double *first_lo, const double *first_hi,
+                            const std::vector<double> &levels, double tol, int max_passes, std::vector<double> *counted = nullptr);
 // -> [n_stars][3 m + 3]: member, then value, lo, hi per level, passes, flags
 void star_intervals_table(const StarIntervals &r, double *table);
 // <base>.starIntervals: "id member {q<a> q<a>_lo q<a>_hi} passes flags", one line per star in the order of ids, 17 significant digits
 void write_star_intervals(const std::string &path, const std::vector<std::string> &ids, const std::vector<double> &levels, const double *table);
+
+// ---- wdIntervals -----------------------------------------------------------------------------------
+// wdIntervals.{quantities, levels, tol, maxPasses, nMassNodes} (flags --quantities zamsMass,wdMass,.. --levels a,b,.. --tol
+// --maxPasses --nMassNodes).  Default: all six quantities at starIntervals' levels, 1e-4 relative, 12 passes; nMassNodes
+// defaults to wdSummary's, then sampleWDMass's, then 512.
+extern const ProgramFlags kWdIntervalsFlags;
+extern const char *const kWdQuantityNames[B9_WQ_N];         // zamsMass wdMass precLogAge logCoolAge logTeff logg
+struct WdIntervalsConfig {
+    int quantity_mask, max_passes;
+    long n_nodes;
+    double tol;
+    std::vector<double> levels;
+    int n_sel() const { return __builtin_popcount((unsigned)quantity_mask); }
+};
+WdIntervalsConfig wd_intervals_config(const Settings &st);
+// The first ranges of the lines [n_wd][n_sel] from one b9_wd_moments pass over the same rows and nodes (acc [n_wd][B9_WDM_N]):
+// the quantity's mean over its counted mass (MEMBER for the ZAMS mass, COOLED for the derived ones) -/+ max(6 sd, 1e-3 |mean|)
+// (1 where that is not positive); a line with no counted mass gets [0, 1].  The open columns widen a range that is too narrow.
+void wd_first_ranges(const double *wd_acc, long n_wd, int quantity_mask, double *first_lo, double *first_hi);
+// The loop: interval_loop over the n_wd * n_sel lines with those first ranges; `moments` runs one b9_wd_moments over all the
+// rows from zeros, `bins` one b9_wd_bins.
+struct WdIntervals {
+    long n_wd = 0;
+    int n_sel = 0;
+    StarIntervals lines;                  // n_stars = n_wd * n_sel
+    std::vector<double> counted;          // [n_wd][n_sel]
+};
+using WdMomentsFn = std::function<void(double *acc /* [n_wd][B9_WDM_N] */)>;
+WdIntervals wd_intervals(const WdMomentsFn &moments, const StarBinsFn &bins, long n_wd, long n_rows, int quantity_mask, const std::vector<double> &levels,
+                         double tol, int max_passes);
+// -> [n_wd][1 + n_sel (3 m + 3)]: member, then per selected quantity counted, {value, lo, hi} per level, passes, flags
+void wd_intervals_table(long n_wd, int n_sel, int n_levels, const double *member, const double *counted, const double *value, const double *lo,
+                        const double *hi, const int32_t *passes, const int32_t *flags, double *table);
+void wd_intervals_table(const WdIntervals &r, double *table);
+// <base>.wdIntervals: "id member {N_counted {N_q<a> N_q<a>_lo N_q<a>_hi} N_passes N_flags}" for the selected quantities' names
+// N, one line per WD-stage star in the order of ids, 17 significant digits
+void write_wd_intervals(const std::string &path, const std::vector<std::string> &ids, int quantity_mask, const std::vector<double> &levels,
+                        const double *table);
 
 // ---- photResiduals ---------------------------------------------------------------------------------
 // b9_phot_resid's star_resid [n_stars][2 + 2 nf] with the catalogue's obs / sigma [n_stars][nf] -> the per-star table

@@ -132,6 +132,8 @@ const std::map<std::string, std::string> &Settings::flag_map()
         {"linearBins", "massFunction.linearBins"}, {"quantity", "massFunction.quantity"}, {"perStar", "massFunction.perStar"},
         {"starIntervalsQuantity", "starIntervals.quantity"}, {"starIntervalsNPops", "starIntervals.nPops"}, {"levels", "starIntervals.levels"},
         {"tol", "starIntervals.tol"}, {"maxPasses", "starIntervals.maxPasses"},
+        {"quantities", "wdIntervals.quantities"}, {"wdIntervalsLevels", "wdIntervals.levels"}, {"wdIntervalsTol", "wdIntervals.tol"},
+        {"wdIntervalsMaxPasses", "wdIntervals.maxPasses"}, {"wdIntervalsNMassNodes", "wdIntervals.nMassNodes"}, {"wdIntervalsNPops", "wdIntervals.nPops"},
         {"photResidualsPerStar", "photResiduals.perStar"}, {"photResidualsNPops", "photResiduals.nPops"},
         {"modelScorePerRow", "modelScore.perRow"}, {"modelScoreNPops", "modelScore.nPops"}, {"compareTo", "modelScore.compareTo"},
         {"nStars", "simCluster.nStars"}, {"percentBinary", "simCluster.percentBinary"}, {"percentDB", "simCluster.percentDB"},

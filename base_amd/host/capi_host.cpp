@@ -274,6 +274,45 @@ int b9h_star_intervals_settings(int argc, char **argv, char *out, int cap)
     });
 }
 
+int b9h_wd_first_ranges(const double *wd_acc, long n_wd, int quantity_mask, double *first_lo, double *first_hi)
+{
+    return guard([&] {
+        if (n_wd < 0 || (n_wd > 0 && (!wd_acc || !first_lo || !first_hi))) throw std::runtime_error("b9h_wd_first_ranges: NULL argument");
+        b9h::wd_first_ranges(wd_acc, n_wd, quantity_mask, first_lo, first_hi);
+    });
+}
+
+int b9h_wd_intervals_table(long n_wd, int n_sel, int n_levels, const double *member, const double *counted, const double *value, const double *lo,
+                           const double *hi, const int32_t *passes, const int32_t *flags, double *table)
+{
+    return guard([&] {
+        if (n_wd < 0 || n_sel < 1 || n_sel > B9_WQ_N || n_levels < 1 || (n_wd > 0 && (!member || !counted || !value || !lo || !hi || !passes || !flags || !table)))
+            throw std::runtime_error("b9h_wd_intervals_table: invalid argument");
+        b9h::wd_intervals_table(n_wd, n_sel, n_levels, member, counted, value, lo, hi, passes, flags, table);
+    });
+}
+
+int b9h_write_wd_intervals(const char *path, const char *const *ids, long n_wd, int quantity_mask, const double *levels, int n_levels, const double *table)
+{
+    return guard([&] {
+        if (!path || n_wd < 0 || n_levels < 1 || !levels || quantity_mask < 1 || quantity_mask >= (1 << B9_WQ_N) || (n_wd > 0 && (!ids || !table)))
+            throw std::runtime_error("b9h_write_wd_intervals: invalid argument");
+        b9h::write_wd_intervals(path, strings(ids, n_wd), quantity_mask, std::vector<double>(levels, levels + n_levels), table);
+    });
+}
+
+int b9h_wd_intervals_settings(int argc, char **argv, char *out, int cap)
+{
+    return settings_text("b9h_wd_intervals_settings", argc, argv, b9h::kWdIntervalsFlags, out, cap, [&](const b9h::Settings &st) {
+        const b9h::WdIntervalsConfig c = b9h::wd_intervals_config(st);
+        std::string lv;
+        for (size_t l = 0; l < c.levels.size(); ++l) lv += (l ? "," : "") + g17(c.levels[l]);
+        return "quantities = " + std::to_string(c.quantity_mask) + "\nlevels = " + lv + "\ntol = " + g17(c.tol) + "\nmaxPasses = " +
+               std::to_string(c.max_passes) + "\nnMassNodes = " + std::to_string(c.n_nodes) + "\nnPops = " +
+               std::to_string(b9h::chain_n_pops(st, "wdIntervals")) + "\n";
+    });
+}
+
 int b9h_resid_table(const double *star_resid, const double *obs, const double *sigma, long n_stars, int n_filt, double *table)
 {
     return guard([&] {

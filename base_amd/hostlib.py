@@ -39,6 +39,7 @@ HOST_SYMBOLS = [
     "b9h_star_table", "b9h_write_star_summary", "b9h_wd_table", "b9h_write_wd_summary",
     "b9h_mass_function_table", "b9h_write_mass_function", "b9h_write_star_mass_hist", "b9h_mass_function_settings",
     "b9h_refine_star_edges", "b9h_star_intervals_table", "b9h_write_star_intervals", "b9h_star_intervals_settings",
+    "b9h_wd_first_ranges", "b9h_wd_intervals_table", "b9h_write_wd_intervals", "b9h_wd_intervals_settings",
     "b9h_resid_table", "b9h_filter_resid_table", "b9h_write_phot_resid", "b9h_write_filter_resid", "b9h_phot_resid_settings",
     "b9h_pointwise_table", "b9h_score_totals", "b9h_score_compare", "b9h_write_pointwise", "b9h_write_model_score", "b9h_model_score_settings",
 ]
@@ -100,6 +101,10 @@ def load() -> C.CDLL:
     lib.b9h_star_intervals_table.argtypes = [C.c_long, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
     lib.b9h_write_star_intervals.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int, _dp]
     lib.b9h_star_intervals_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
+    lib.b9h_wd_first_ranges.argtypes = [_dp, C.c_long, C.c_int, _dp, _dp]
+    lib.b9h_wd_intervals_table.argtypes = [C.c_long, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
+    lib.b9h_write_wd_intervals.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, C.c_int, _dp, C.c_int, _dp]
+    lib.b9h_wd_intervals_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     lib.b9h_resid_table.argtypes = [_dp, _dp, _dp, C.c_long, C.c_int, _dp]
     lib.b9h_filter_resid_table.argtypes = [_dp, C.c_long, C.c_int, _dp]
     lib.b9h_write_phot_resid.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, C.POINTER(C.c_char_p), C.c_int, _dp]
@@ -451,20 +456,23 @@ def refine_star_edges(edges, acc, levels=STAR_INTERVALS_LEVELS, tol: float = 1e-
     return out
 
 
-def star_intervals(engine, rows, quantity: int = abi.HQ_PRIMARY, levels=STAR_INTERVALS_LEVELS, tol: float = 1e-4, max_passes: int = 12,
-                   n_bins: int = abi.SBIN_MAX_BINS) -> dict:
-    """Every star's quantiles of `quantity` at `levels` over `rows`, exactly: loops engine.star_bins (b9_star_bins; anything
-    with star_bins(rows, edges, quantity), n_stars and max_mass serves) and refine_star_edges until every bracket is final or
-    max_passes is reached.  The first pass's edges are [0, 2 engine.max_mass] cut evenly for every star.  Returns levels, member [n],
-    value, lo, hi, final [n, m], passes [n] (the pass at which the star was finished), flags [n] (SIV_*), n_passes, edges (the last)."""
-    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
-    n, B = int(engine.n_stars), int(n_bins)
+def interval_loop(bins, first_lo, first_hi, n_rows: int, levels=STAR_INTERVALS_LEVELS, tol: float = 1e-4, max_passes: int = 12,
+                  n_bins: int = abi.SBIN_MAX_BINS) -> dict:
+    """The refinement loop over n independent lines: the first pass cuts [first_lo[i], first_hi[i]] evenly into n_bins bins,
+    `bins(edges [n, B + 1]) -> acc [n, B + 3]` bins all the rows from zeros, refine_star_edges narrows every line's edges, until
+    every bracket is final or max_passes is reached.  Returns levels, member [n] (the total over n_rows), counted [n] (the
+    counted mass over the total, 0 without a total), value, lo, hi, final [n, m], passes [n] (the pass at which the line was
+    finished), flags [n] (SIV_*), n_passes, edges (the last), acc (the last)."""
+    lo, hi = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (first_lo, first_hi))
+    n, B = len(lo), int(n_bins)
     if max_passes < 1:
         raise ValueError("max_passes must be positive")
-    edges = np.tile((2.0 * float(engine.max_mass)) * (np.arange(B + 1, dtype=np.float64) / float(B)), (n, 1))
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
+        raise ValueError("the first ranges must be finite and not empty")
+    edges = lo[:, None] + (hi - lo)[:, None] * (np.arange(B + 1, dtype=np.float64) / float(B))[None, :]
     passes = np.zeros(n, dtype=np.int32)
     for k in range(1, int(max_passes) + 1):
-        acc = engine.star_bins(rows, edges, quantity)
+        acc = np.ascontiguousarray(bins(edges), dtype=np.float64).reshape(n, B + 3)
         r = refine_star_edges(edges, acc, levels, tol)
         done = (r["flags"] & SIV_OPEN) == 0
         passes[(passes == 0) & (done | (k == max_passes))] = k
@@ -472,9 +480,26 @@ def star_intervals(engine, rows, quantity: int = abi.HQ_PRIMARY, levels=STAR_INT
             break
         if k < max_passes:
             edges = r["next_edges"]
-    member = acc[:, B + 2] / rows.shape[0] if rows.shape[0] else np.zeros(n)
-    return dict(levels=np.array(levels, dtype=np.float64), member=member, value=r["value"], lo=r["lo"], hi=r["hi"], final=r["final"],
+    member = acc[:, B + 2] / n_rows if n_rows else np.zeros(n)
+    c = np.zeros(n)
+    for b in range(B + 2):                      # (refine_star_edges' order: below, the bins, at or above)
+        c = c + acc[:, b]
+    counted = np.divide(c, acc[:, B + 2], out=np.zeros(n), where=acc[:, B + 2] > 0.0)
+    return dict(levels=np.array(levels, dtype=np.float64), member=member, counted=counted, value=r["value"], lo=r["lo"], hi=r["hi"], final=r["final"],
                 passes=passes, flags=r["flags"], n_passes=k, edges=edges, acc=acc)
+
+
+def star_intervals(engine, rows, quantity: int = abi.HQ_PRIMARY, levels=STAR_INTERVALS_LEVELS, tol: float = 1e-4, max_passes: int = 12,
+                   n_bins: int = abi.SBIN_MAX_BINS) -> dict:
+    """Every star's quantiles of `quantity` at `levels` over `rows`, exactly: loops engine.star_bins (b9_star_bins; anything
+    with star_bins(rows, edges, quantity), n_stars and max_mass serves) and refine_star_edges until every bracket is final or
+    max_passes is reached (interval_loop).  The first pass's edges are [0, 2 engine.max_mass] cut evenly for every star.  Returns
+    levels, member [n], value, lo, hi, final [n, m], passes [n] (the pass at which the star was finished), flags [n] (SIV_*),
+    n_passes, edges (the last)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+    n = int(engine.n_stars)
+    return interval_loop(lambda edges: engine.star_bins(rows, edges, quantity), np.zeros(n), np.full(n, 2.0 * float(engine.max_mass)),
+                         rows.shape[0], levels, tol, max_passes, n_bins)
 
 
 def star_intervals_table(res: dict) -> np.ndarray:
@@ -507,6 +532,91 @@ def star_intervals_settings(args) -> dict:
     argv = (C.c_char_p * (len(args) + 1))(b"starIntervals", *[str(a).encode() for a in args])
     buf = C.create_string_buffer(4096)
     _check(load().b9h_star_intervals_settings(len(args) + 1, argv, buf, 4096))
+    d = {}
+    for line in buf.value.decode().splitlines():
+        k, v = line.split(" = ")
+        d[k] = tuple(float(x) for x in v.split(",")) if k == "levels" else float(v) if k == "tol" else int(v)
+    return d
+
+
+WD_QUANTITY_NAMES = ("zamsMass", "wdMass", "precLogAge", "logCoolAge", "logTeff", "logg")
+
+
+def wd_quantity_mask(quantities) -> int:
+    """The mask of b9_wd_bins for an int (taken as it is) or for names of WD_QUANTITY_NAMES."""
+    if isinstance(quantities, (int, np.integer)):
+        return int(quantities)
+    mask = 0
+    for q in quantities:
+        mask |= 1 << WD_QUANTITY_NAMES.index(q)
+    return mask
+
+
+def wd_first_ranges(wd_acc, quantities=abi.WQ_ALL):
+    """b9h_wd_first_ranges: the lines' first ranges (lo, hi) [n_wd, n_sel] from b9_wd_moments' accumulators [n_wd, 16]: the
+    quantity's mean over its counted mass -/+ max(6 sd, 1e-3 |mean|); [0, 1] without counted mass."""
+    mask = wd_quantity_mask(quantities)
+    acc = np.ascontiguousarray(wd_acc, dtype=np.float64).reshape(-1, abi.WDM_N)
+    n_sel = bin(mask).count("1")
+    lo, hi = np.zeros((acc.shape[0], n_sel)), np.zeros((acc.shape[0], n_sel))
+    _check(load().b9h_wd_first_ranges(acc.ctypes.data_as(_dp), acc.shape[0], mask, lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp)))
+    return lo, hi
+
+
+def wd_intervals(engine, rows, n_nodes: int = 512, quantities=abi.WQ_ALL, levels=STAR_INTERVALS_LEVELS, tol: float = 1e-4,
+                 max_passes: int = 12) -> dict:
+    """Every WD-stage star's quantiles of the selected quantities at `levels` over `rows` on the grid of n_nodes steps, exactly:
+    one engine.wd_moments pass gives every line (star, quantity) its first range (wd_first_ranges), then engine.wd_bins
+    (b9_wd_bins) and refine_star_edges are looped (interval_loop) until every bracket is final or max_passes is reached --
+    the program wdIntervals' loop.  Returns interval_loop's dict over the n_wd * n_sel lines (member, counted, passes, flags
+    [n_wd * n_sel]; value, lo, hi, final [n_wd * n_sel, m]) with n_wd, n_sel, quantities (the mask), star_index, first_lo, first_hi."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+    mask = wd_quantity_mask(quantities)
+    n_sel = bin(mask).count("1")
+    wd_acc, star_index = engine.wd_moments(rows, n_nodes)
+    n_wd = wd_acc.shape[0]
+    lo, hi = wd_first_ranges(wd_acc, mask)
+    res = interval_loop(lambda edges: engine.wd_bins(rows, n_nodes, edges.reshape(n_wd, n_sel, -1), mask)[0], lo.reshape(-1), hi.reshape(-1),
+                        rows.shape[0], levels, tol, max_passes, abi.WBIN_MAX_BINS)
+    res.update(n_wd=n_wd, n_sel=n_sel, quantities=mask, star_index=star_index, first_lo=lo, first_hi=hi)
+    return res
+
+
+def wd_intervals_table(res: dict) -> np.ndarray:
+    """b9h_wd_intervals_table: wd_intervals' result -> [n_wd, 1 + n_sel (3 m + 3)]: member, then per selected quantity counted,
+    {value, lo, hi} per level, passes, flags."""
+    n_wd, n_sel = int(res["n_wd"]), int(res["n_sel"])
+    m = res["value"].shape[1]
+    c = lambda a, t: np.ascontiguousarray(a, dtype=t)      # noqa: E731
+    member, counted, value, lo, hi = (c(res[k], np.float64) for k in ("member", "counted", "value", "lo", "hi"))
+    passes, flags = c(res["passes"], np.int32), c(res["flags"], np.int32)
+    out = np.zeros((n_wd, 1 + n_sel * (3 * m + 3)))
+    _check(load().b9h_wd_intervals_table(n_wd, n_sel, m, member.ctypes.data_as(_dp), counted.ctypes.data_as(_dp), value.ctypes.data_as(_dp),
+                                         lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp), passes.ctypes.data_as(_ip), flags.ctypes.data_as(_ip),
+                                         out.ctypes.data_as(_dp)))
+    return out
+
+
+def write_wd_intervals(path: str, ids, quantities, levels, table) -> None:
+    """b9h_write_wd_intervals: the .wdIntervals file of wd_intervals_table's table [len(ids), 1 + n_sel (3 m + 3)]."""
+    mask = wd_quantity_mask(quantities)
+    lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    table = np.ascontiguousarray(table, dtype=np.float64).reshape(len(ids), 1 + bin(mask).count("1") * (3 * len(lv) + 3))
+    arr = (C.c_char_p * len(ids))(*[str(i).encode() for i in ids])
+    _check(load().b9h_write_wd_intervals(path.encode(), arr, len(ids), mask, lv.ctypes.data_as(_dp), len(lv), table.ctypes.data_as(_dp)))
+
+
+def read_wd_intervals(path: str):
+    """(ids, columns, table [n_wd, 1 + n_sel (3 m + 3)]) of a .wdIntervals file."""
+    return read_table_file(path, "id")
+
+
+def wd_intervals_settings(args) -> dict:
+    """wdIntervals' settings as the program parses `args` (flags, --config file): a dict of its keys (quantities: the mask;
+    levels: a tuple)."""
+    argv = (C.c_char_p * (len(args) + 1))(b"wdIntervals", *[str(a).encode() for a in args])
+    buf = C.create_string_buffer(4096)
+    _check(load().b9h_wd_intervals_settings(len(args) + 1, argv, buf, 4096))
     d = {}
     for line in buf.value.decode().splitlines():
         k, v = line.split(" = ")

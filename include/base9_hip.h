@@ -294,7 +294,7 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk);
  * b9_set_priors or b9_set_options changes the posterior: the previous block's state carries a log-posterior of the old
  * one, so the next B9_BLOCK_CONTINUE block returns B9_ERR_STATE (the message names the call that intervened) and the chain
  * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags, b9_sample_wd_mass, b9_star_moments,
- * b9_wd_moments, b9_mass_hist, b9_phot_resid and b9_pointwise (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
+ * b9_wd_moments, b9_wd_bins, b9_mass_hist, b9_phot_resid and b9_pointwise (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
  * context's work buffers: b9_logpost / b9_sample_mass / b9_derive_isochrone, the staging calls, b9_set_options and a block
  * with another n_walkers return B9_ERR_STATE until it has been collected.  A driver that adapts the proposal
  * from block b-1 while block b runs keeps the GPU's queue non-empty: enqueue b+1 (CONTINUE | ASYNC), wait(b), ...
@@ -549,6 +549,51 @@ int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quan
 int b9_star_bins(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quantity,
                  const double *edges /* host [n_stars][n_bins + 1], caller's star order */, int32_t n_bins, int32_t flags,
                  double *acc /* host [n_stars][n_bins + 3], in/out */);
+
+/*
+ * Per-WD bins over a saved chain (the wdIntervals counterpart).  Added in ABI 6 without a version change, as its siblings
+ * were: purely additive.  b9_wd_bins is to b9_wd_moments what b9_star_bins is to b9_star_moments: where that call keeps a mean
+ * and a second moment of a WD-stage star's six quantities, this one bins the node weights of the same grid on every WD's OWN
+ * edges, for any subset of the six quantities in one call, so that a host can narrow each line's bins around its own quantile
+ * levels (base9_host.h: b9h_refine_star_edges, with n = n_wd * n_sel lines) -- the summary a truncated, stretched or bimodal
+ * posterior needs.
+ *
+ * Definition.  Grid, terms t_(k,j), L = logsumexp t, w = exp(t - L), the membership p, "no pruning" and the COOLED status of a
+ * node are exactly b9_wd_moments'.  quantity_mask selects quantities (bit q = enum b9_wd_quantity q); n_sel is the number of its
+ * bits and the selected quantities appear in ascending q.  Line (i, s) -- WD-stage star i in the column order of
+ * b9_sample_wd_mass, s-th selected quantity -- has its own finite edges e_0 < ... < e_B (1 <= B = n_bins <= B9_WBIN_MAX_BINS).
+ * A node's value v is, under B9_WQ_ZAMS, m_j = tip_k + dM_k * (double)j; under the other five the node's derived value (WD mass,
+ * precursor log-age, log cooling age, log Teff, log g: the values the node's magnitudes were computed FROM), and there only
+ * COOLED nodes count: a node that is not COOLED enters no column but the total.  Row r adds to line (i, s)
+ *     x[0]     = p sum_{v < e_0} w                  (below)
+ *     x[1 + b] = p sum_{e_b <= v < e_(b+1)} w       (bin b, closed on the left, decided on the value's own bits)
+ *     x[B + 1] = p sum_{v >= e_B} w                 (at or above)
+ *     x[B + 2] = p                                  (the total)
+ * and nothing at all (every entry 0) where b9_wd_moments adds nothing.
+ *
+ * Order of the sums (a function of the data only): a star's terms enter its population's online log-sum-exp one by one in
+ * ascending j, every column rescaled together on a jump of the reference; each column is divided by that population's sum of
+ * weights, the populations are mixed with the membership's population weights in population order, then multiplied by p --
+ * the sequence b9_wd_moments applies to B9_WDM_COOLED.  Hence a line's total is B9_WDM_MEMBER bit for bit, and with n_bins = 1
+ * and edges that enclose every value column 1 of a derived quantity is B9_WDM_COOLED bit for bit.
+ *
+ * acc (host, [n_wd][n_sel][n_bins + 3], in/out): acc + x_r, one plain add per row in ascending row order; flags = 0 starts from
+ * zeros, B9_WBIN_CONTINUE from the caller's values.  The same bits for the call's own chunking (at most 256 rows, fewer while
+ * the chunk's node table -- b9_wd_moments' size -- or the per-(row, line) scratch would exceed 64 MiB, down to one row at a
+ * time), for any split of the rows over continued calls, for any other stars in the catalogue, any other line's edges, any
+ * other quantities in the mask, for a repeated call and after any other call on the context.  Synchronous; host pointers.
+ * n_wd == 0 is B9_OK with nothing touched.  B9_ERR_INVALID (acc untouched; checked on the host before anything is launched) for
+ * n_bins outside 1 .. B9_WBIN_MAX_BINS, a mask of 0 or with bits at or above B9_WQ_N, n_nodes < 1, n_rows < 1, NULL pointers, or
+ * any line's edges not finite or not strictly ascending; B9_ERR_STATE and B9_ERR_CAPACITY as b9_wd_moments.  The call uses
+ * buffers of its own: a B9_BLOCK_CONTINUE block enqueued after it gives the same bits as one enqueued without it.
+ */
+enum b9_wd_quantity { B9_WQ_ZAMS = 0, B9_WQ_WDMASS = 1, B9_WQ_PREC = 2, B9_WQ_LOGCOOL = 3,
+                      B9_WQ_LOGTEFF = 4, B9_WQ_LOGG = 5, B9_WQ_N = 6 };
+#define B9_WBIN_MAX_BINS 30
+#define B9_WBIN_CONTINUE 1
+int b9_wd_bins(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_nodes, int32_t quantity_mask,
+               const double *edges /* host [n_wd][n_sel][n_bins + 1] */, int32_t n_bins, int32_t flags,
+               double *acc         /* host [n_wd][n_sel][n_bins + 3], in/out */);
 
 /*
  * Exact per-filter posterior-predictive residuals over a saved chain (the photResiduals counterpart).  Added in ABI 6 without a

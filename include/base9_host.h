@@ -150,6 +150,22 @@ int b9h_star_intervals_table(long n_stars, int n_levels, const double *member, c
                              const int32_t *passes, const int32_t *flags, double *table);
 int b9h_write_star_intervals(const char *path, const char *const *ids, long n_stars, const double *levels, int n_levels, const double *table);
 int b9h_star_intervals_settings(int argc, char **argv, char *out, int cap);
+/* wdIntervals.  The lines are [n_wd][n_sel]: WD-stage star i, s-th selected quantity of quantity_mask (bit q = enum
+ * b9_wd_quantity q, ascending); b9h_refine_star_edges serves them unchanged with n_stars = n_wd n_sel.
+ * b9h_wd_first_ranges: the lines' first ranges from b9_wd_moments' accumulators [n_wd][B9_WDM_N] over the same rows and nodes:
+ * the quantity's mean over its counted mass (MEMBER for the ZAMS mass, COOLED for the derived ones) -/+ max(6 sd, 1e-3 |mean|)
+ * (1 where that is not positive); a line with no counted mass gets [0, 1].
+ * b9h_wd_intervals_table: -> [n_wd][1 + n_sel (3 n_levels + 3)]: member (of the star's first line), then per selected quantity
+ * counted, {value, lo, hi} per level, passes, flags; member, counted, passes, flags are [n_wd][n_sel], the others
+ * [n_wd][n_sel][n_levels].
+ * b9h_write_wd_intervals: the file <base>.wdIntervals (docs/FORMATS.md) of that table, 17 significant digits.
+ * b9h_wd_intervals_settings: wdIntervals' command line (argv[0] is skipped) and YAML parsed as the program parses them --
+ * "key = value" lines of quantities (the mask), levels (comma-separated), tol, maxPasses, nMassNodes, nPops. */
+int b9h_wd_first_ranges(const double *wd_acc, long n_wd, int quantity_mask, double *first_lo, double *first_hi);
+int b9h_wd_intervals_table(long n_wd, int n_sel, int n_levels, const double *member, const double *counted, const double *value, const double *lo,
+                           const double *hi, const int32_t *passes, const int32_t *flags, double *table);
+int b9h_write_wd_intervals(const char *path, const char *const *ids, long n_wd, int quantity_mask, const double *levels, int n_levels, const double *table);
+int b9h_wd_intervals_settings(int argc, char **argv, char *out, int cap);
 /* photResiduals.  b9h_resid_table: b9_phot_resid's star_resid [n_stars][2 + 2 n_filt] with the catalogue's obs and sigma
  * [n_stars][n_filt] (sigma <= 0: filter unused) -> the per-star table [n_stars][2 + 4 n_filt]: rows, member = acc[1] / rows,
  * then per filter predMag = c + acc[2 + 2f] / acc[1] (c = obs for a used filter, else 0), predSd = sqrt(max(0, acc[3 + 2f] / acc[1]
