@@ -74,15 +74,18 @@ def weights(nodes_i):
     return np.exp(t - L), L
 
 
-def increments(pack_d, cl, par, n_pops, K, n_q, second_moment_power=2, drop_pop_weight=False):
+def increments(pack_d, cl, par, n_pops, K, n_q, second_moment_power=2, drop_pop_weight=False, nodes=None):
     """x[star, 8] of one parameter row.  second_moment_power / drop_pop_weight: the two MUTATIONS the statistical checks
-    must reject (second moments built from M1 instead of M1^2; the population weight log lambda_k left out)."""
+    must reject (second moments built from M1 instead of M1^2; the population weight log lambda_k left out).  nodes: the
+    row's star_nodes, where the caller has them already."""
     n = len(cl["mass1"])
     x = np.zeros((n, N))
     if drop_pop_weight and n_pops == 2:
         par = np.array(par, dtype=np.float64)
         par[abi.P_LAMBDA] = 0.5                              # equal weights: log lambda_k only shifts every term alike
-    nodes = star_nodes(pack_d, cl, par, n_pops, K, n_q)
+        nodes = None
+    if nodes is None:
+        nodes = star_nodes(pack_d, cl, par, n_pops, K, n_q)
     if nodes is None:
         return x
     for i in range(n):

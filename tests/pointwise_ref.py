@@ -26,10 +26,11 @@ def field_term(cl, i):
     return -np.inf if pm >= 1.0 else math.log1p(-pm) + log_fs
 
 
-def values(pack_d, cl, par, n_pops, K, n_q, drop_field=False, drop_pop_weight=False):
+def values(pack_d, cl, par, n_pops, K, n_q, drop_field=False, drop_pop_weight=False, nodes=None):
     """(v [star], live [star]: the star has a node) of one parameter row, or None for a row outside the grid.  drop_field /
     drop_pop_weight: two MUTATIONS the comparators must reject (the field term left out; log lambda_k left out of every term)."""
-    nodes = mr.star_nodes(pack_d, cl, par, n_pops, K, n_q)
+    if nodes is None:                                    # (nodes: the row's moments_ref.star_nodes, where the caller has them)
+        nodes = mr.star_nodes(pack_d, cl, par, n_pops, K, n_q)
     if nodes is None:
         return None
     n = len(cl["mass1"])

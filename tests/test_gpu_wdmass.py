@@ -66,7 +66,7 @@ def against_oracle(pack_d, cl, pack, stars, priors, n_pops, n_nodes, n_rows, max
           f"distinct masses {len(np.unique(om[:-1]))}")
     assert left_out <= max_left_out
     assert np.array_equal(g["pop"][safe], opop[safe])
-    np.testing.assert_allclose(g["zams"][safe], om[safe], rtol=1e-12, atol=0)
+    np.testing.assert_allclose(g["zams"][safe], om[safe], rtol=wd_check.ZAMS_RTOL, atol=0)
     np.testing.assert_allclose(g["member"], omem, rtol=1e-9, atol=1e-300)
     return g, om
 

@@ -79,7 +79,7 @@ def test_ties_to_star_moments(K):
     mine = acc[:, [wr.ROWS, wr.MEMBER, wr.M1, wr.M1SQ, wr.POP1]]
     theirs = mom[idx][:, [abi.MOM_ROWS, abi.MOM_MEMBER, abi.MOM_M1, abi.MOM_M1SQ, abi.MOM_POP1]]
     print("largest relative difference per column:", np.max(np.abs(mine - theirs) / np.maximum(np.abs(theirs), 1e-300), axis=0))
-    np.testing.assert_allclose(mine, theirs, rtol=1e-12, atol=0)
+    np.testing.assert_allclose(mine, theirs, rtol=wc.TIE_RTOL, atol=0)
     assert np.any(acc[:, wr.POP1] > 0)
 
 

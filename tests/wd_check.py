@@ -7,6 +7,7 @@ import numpy as np
 from base_amd import abi, synth
 
 LOG_G_PLUS_LOG_MSUN = 26.12302173752
+ZAMS_RTOL = 1e-12         # a drawn ZAMS mass against the node it names (tests/test_gpu_wdmass.py, tests/ragged_chain.py)
 
 
 def ifmr(pack, par, m):

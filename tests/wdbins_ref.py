@@ -25,10 +25,11 @@ def selected(mask):
     return [q for q in range(N_Q) if mask >> q & 1]
 
 
-def row_lines(pack_d, cl, par, n_pops, n_nodes, drop_pop_weight=False):
+def row_lines(pack_d, cl, par, n_pops, n_nodes, drop_pop_weight=False, nodes=None):
     """Per WD-stage star of one row: (p, w, m, cooled, der [node, 5]) over its finite nodes, or None for a star without a
     finite term; None altogether for a row outside the grid."""
-    nodes = wr.star_nodes(pack_d, cl, par, n_pops, n_nodes, drop_pop_weight=drop_pop_weight)
+    if nodes is None:                                    # (nodes: the row's wdmoments_ref.star_nodes, where the caller has them)
+        nodes = wr.star_nodes(pack_d, cl, par, n_pops, n_nodes, drop_pop_weight=drop_pop_weight)
     if nodes is None:
         return None
     out = []

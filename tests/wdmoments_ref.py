@@ -85,15 +85,16 @@ def star_nodes(pack_d, cl, par, n_pops, n_nodes, drop_pop_weight=False, drop_log
 
 
 def increments(pack_d, cl, par, n_pops, n_nodes, second_moment_power=2, derived_over_all_nodes=False, drop_pop_weight=False,
-               drop_log_dm=False, da_rows_for_db=False, want_extra=False):
+               drop_log_dm=False, da_rows_for_db=False, want_extra=False, nodes=None):
     """x [n_wd, 16] of one parameter row.  With want_extra also (floor [n_wd, 16], A [n_wd]): floor = p sum w |v| per value
     column (the scale of the sum a rounding error is relative to), A = sum_cooled w t / (t - 10^prec) with t = 10^logAge, the
     weighted amplification of an error in prec into log_cool, log_teff and logg; A = -1 marks a star without a finite term."""
     par = np.asarray(par, dtype=np.float64)
     wd = wd_stars(cl)
     x, floor, amp = np.zeros((len(wd), N)), np.zeros((len(wd), N)), np.zeros(len(wd))
-    nodes = star_nodes(pack_d, cl, par, n_pops, n_nodes, drop_pop_weight=drop_pop_weight, drop_log_dm=drop_log_dm,
-                       da_rows_for_db=da_rows_for_db)
+    if nodes is None:                                    # (nodes: the row's star_nodes, where the caller has them already)
+        nodes = star_nodes(pack_d, cl, par, n_pops, n_nodes, drop_pop_weight=drop_pop_weight, drop_log_dm=drop_log_dm,
+                           da_rows_for_db=da_rows_for_db)
     if nodes is not None:
         age = 10.0 ** par[abi.P_LOGAGE]
         for c, i in enumerate(wd):
