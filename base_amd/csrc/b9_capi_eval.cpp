@@ -1,8 +1,10 @@
 // b9_capi_eval.cpp -- one log-posterior evaluation through the C ABI: derive -> stars -> finalize (b9_logpost,
 // b9_logpost_device), the per-star mass draws (b9_sample_mass), the isochrone dump (b9_derive_isochrone) and the forward
-// model alone (b9_predict_mags) the WD-stage stars' posterior draws (b9_sample_wd_mass), the
-// per-star posterior moments (b9_star_moments), the binned mass posteriors (b9_mass_hist), the per-star bins (b9_star_bins), the
-// posterior-predictive residuals (b9_phot_resid) and the pointwise predictive densities (b9_pointwise).
+// model alone (b9_predict_mags); the five reductions over a saved chain through chain_reduce -- the per-star posterior moments
+// (b9_star_moments), the binned mass posteriors (b9_mass_hist), the per-star bins (b9_star_bins), the posterior-predictive
+// residuals (b9_phot_resid) and the pointwise predictive densities (b9_pointwise) --; and the three calls on a WD mass grid of the
+// caller's own size through wd_grid_reduce -- the WD-stage stars' posterior draws (b9_sample_wd_mass), their exact posterior
+// moments (b9_wd_moments) and their per-line bins (b9_wd_bins).
 #include "b9_ctx.h"
 #include <algorithm>
 #include <cmath>
@@ -283,172 +285,6 @@ int b9_n_wd_stars(const b9_ctx *ctx)
     return ctx->n_wd_stage;
 }
 
-// Rows are worked in chunks: at most 256 rows, and as few as keep the chunk's node table within B9_WDS_TABLE_BYTES (one
-// row's table, whatever its size, when that alone is larger).
-#define B9_WDS_TABLE_BYTES ((size_t)64 << 20)
-#define B9_WDS_MAX_ROWS 256
-
-int b9_sample_wd_mass(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_nodes, uint64_t seed, int64_t row0,
-                      double *out_zams, double *out_wd_mass, double *out_prec_log_age, double *out_log_cool_age,
-                      double *out_log_teff, double *out_logg, double *out_member, int32_t *out_pop)
-{
-    if (!ctx || !params || n_rows < 1 || n_nodes < 1 || !out_zams || !out_member) return B9_ERR_INVALID;
-    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
-    if (!ctx->have_pack || !ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
-    const int n_wd = ctx->st.n_wd, n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
-    if (n_wd == 0) return B9_OK;
-    const DevPack &pk = ctx->pk;
-    const int mass_cap = pack_mass_cap(pk.max_eep);
-    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
-    const size_t tab_row = (size_t)n_pops * (size_t)b9k_wd_table_doubles(pk.nfp, n_nodes);       // doubles per row
-    if (tab_row > ((size_t)8 << 30) / sizeof(double)) return fail(ctx, B9_ERR_CAPACITY, "b9_sample_wd_mass: one row's node table would exceed 8 GiB");
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_rows, (size_t)B9_WDS_MAX_ROWS, B9_WDS_TABLE_BYTES / (tab_row * sizeof(double))}));
-    // one allocation: [params][headers][isochrones][table][7 outputs][pop][columns]
-    const size_t per = (size_t)chunk * n_wd;
-    const WdsArena a = wds_arena((size_t)chunk, n_pops, iso_stride, tab_row, (size_t)n_wd, (size_t)n, sizeof(IsoHdr));
-    RESERVE(ctx, ctx->d_wds, a.bytes);
-    char *base = ctx->d_wds.get();
-    double *d_par = part<double>(base, a.o_par), *d_iso = part<double>(base, a.o_iso);
-    double *d_tab = part<double>(base, a.o_tab), *d_out = part<double>(base, a.o_out);
-    IsoHdr *d_hdr = part<IsoHdr>(base, a.o_hdr);
-    int *d_pop = part<int>(base, a.o_pop), *d_rank = part<int>(base, a.o_rank);
-    std::vector<int> rank(n);
-    for (int i = 0, k = 0; i < n; ++i) { rank[i] = k; k += ctx->hs.stage[i] == B9_STAGE_WD; }
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(d_rank, rank.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
-    double *const host[7] = {out_zams, out_member, out_wd_mass, out_prec_log_age, out_log_cool_age, out_log_teff, out_logg};
-    const McmcDev off{};
-    for (int r0 = 0; r0 < n_rows; r0 += chunk) {
-        const int m = std::min(chunk, n_rows - r0);
-        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * per * 7, s));        // rows outside the grid write nothing
-        HIPCHK(ctx, hipMemsetAsync(d_pop, 0, sizeof(int) * per, s));
-        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
-        B9WdSample smp{};
-        smp.zams = d_out; smp.member = d_out + per;
-        smp.wd_mass = out_wd_mass ? d_out + 2 * per : nullptr; smp.prec_log_age = out_prec_log_age ? d_out + 3 * per : nullptr;
-        smp.log_cool_age = out_log_cool_age ? d_out + 4 * per : nullptr; smp.log_teff = out_log_teff ? d_out + 5 * per : nullptr;
-        smp.logg = out_logg ? d_out + 6 * per : nullptr;
-        smp.pop = d_pop; smp.wd_rank = d_rank;
-        split_seed(seed, &smp.k0, &smp.k1); smp.row0 = (long long)(row0 + r0);
-        // the kernel indexes its outputs [row][n_wd] with the launch's own rows: they are contiguous for any m
-        HIPCHK(ctx, b9k_wd_sample(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, n_nodes, d_tab, smp, s));
-        const size_t cnt = (size_t)m * n_wd, o = (size_t)r0 * n_wd;
-        for (int q = 0; q < 7; ++q)
-            if (host[q]) HIPCHK(ctx, hipMemcpyAsync(host[q] + o, d_out + q * per, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
-        if (out_pop) HIPCHK(ctx, hipMemcpyAsync(out_pop + o, d_pop, sizeof(int) * cnt, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));      // (the next chunk reuses the same device buffers)
-    }
-    return B9_OK;
-}
-
-// The rows in b9_sample_wd_mass's chunks (the table has one more double per node); the accumulators go in (or are cleared) before
-// the first chunk and come out after the last, with the one wait: a chunk's buffers are reused in stream order.
-int b9_wd_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_nodes, int32_t flags, double *acc)
-{
-    if (!ctx || !params || !acc || n_rows < 1 || n_nodes < 1) return B9_ERR_INVALID;
-    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
-    if (!ctx->have_pack || !ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
-    const int n_wd = ctx->st.n_wd, n = ctx->st.n, n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
-    if (n_wd == 0) return B9_OK;
-    const DevPack &pk = ctx->pk;
-    const int mass_cap = pack_mass_cap(pk.max_eep);
-    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
-    const size_t tab_row = (size_t)n_pops * (size_t)b9k_wd_moments_table_doubles(pk.nfp, n_nodes);       // doubles per row
-    if (tab_row > ((size_t)8 << 30) / sizeof(double)) return fail(ctx, B9_ERR_CAPACITY, "b9_wd_moments: one row's node table would exceed 8 GiB");
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_rows, (size_t)B9_WDS_MAX_ROWS, B9_WDS_TABLE_BYTES / (tab_row * sizeof(double))}));
-    const WdmArena a = wdm_arena((size_t)chunk, n_pops, iso_stride, tab_row, (size_t)n_wd, (size_t)n, B9_WDM_N, sizeof(IsoHdr));
-    RESERVE(ctx, ctx->d_wds, a.bytes);
-    char *base = ctx->d_wds.get();
-    double *d_par = part<double>(base, a.o_par), *d_iso = part<double>(base, a.o_iso), *d_tab = part<double>(base, a.o_tab);
-    double *d_scratch = part<double>(base, a.o_scratch), *d_acc = part<double>(base, a.o_acc);
-    IsoHdr *d_hdr = part<IsoHdr>(base, a.o_hdr);
-    int *d_rank = part<int>(base, a.o_rank);
-    std::vector<int> rank(n);            // (an upload's source: it lives until the wait below)
-    for (int i = 0, k = 0; i < n; ++i) { rank[i] = k; k += ctx->hs.stage[i] == B9_STAGE_WD; }
-    hipStream_t s = ctx->stream;
-    const size_t acc_bytes = sizeof(double) * (size_t)n_wd * B9_WDM_N;
-    HIPCHK(ctx, hipMemcpyAsync(d_rank, rank.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
-    if (flags & B9_WDM_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_acc, acc, acc_bytes, hipMemcpyHostToDevice, s));
-    else HIPCHK(ctx, hipMemsetAsync(d_acc, 0, acc_bytes, s));
-    const McmcDev off{};
-    for (int r0 = 0; r0 < n_rows; r0 += chunk) {
-        const int m = std::min(chunk, n_rows - r0);
-        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
-        // the star kernel writes every (row, WD-stage star) of the chunk, so nothing is cleared
-        HIPCHK(ctx, b9k_wd_moments(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, n_nodes, d_tab, d_rank, d_scratch, d_acc, s));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(acc, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return B9_OK;
-}
-
-// b9_wd_moments' loop with the lines' edges beside the accumulators: the arguments are checked on the host before anything is
-// launched; a chunk is b9_wd_moments' rows, and fewer while the per-(row, line) scratch would exceed B9_WBIN_SCRATCH_BYTES.
-#define B9_WBIN_SCRATCH_BYTES ((size_t)64 << 20)
-int b9_wd_bins(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_nodes, int32_t quantity_mask, const double *edges, int32_t n_bins,
-               int32_t flags, double *acc)
-{
-    if (!ctx || !params || !edges || !acc || n_rows < 1 || n_nodes < 1) return B9_ERR_INVALID;
-    if (n_bins < 1 || n_bins > B9_WBIN_MAX_BINS) return fail(ctx, B9_ERR_INVALID, "b9_wd_bins: n_bins must lie in 1 .. B9_WBIN_MAX_BINS");
-    if (quantity_mask < 1 || quantity_mask >= (1 << B9_WQ_N)) return fail(ctx, B9_ERR_INVALID, "b9_wd_bins: the quantity mask must select some of the B9_WQ_N quantities and nothing else");
-    if (!ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
-    const int n = ctx->hs.n;
-    std::vector<int> rank(n);            // (an upload's source: it lives until the wait below)
-    int n_wd = 0;
-    for (int i = 0; i < n; ++i) { rank[i] = n_wd; n_wd += ctx->hs.stage[i] == B9_STAGE_WD; }
-    const size_t n_sel = (size_t)__builtin_popcount((unsigned)quantity_mask), ne = (size_t)n_bins + 1, ncol = (size_t)n_bins + 3;
-    const size_t n_lines = (size_t)n_wd * n_sel;
-    for (size_t l = 0; l < n_lines; ++l)
-        for (size_t b = 0; b < ne; ++b)
-            if (!std::isfinite(edges[l * ne + b]) || (b > 0 && !(edges[l * ne + b] > edges[l * ne + b - 1])))
-                return fail(ctx, B9_ERR_INVALID, "b9_wd_bins: WD-stage star " + std::to_string(l / n_sel) + ", selected quantity " + std::to_string(l % n_sel) +
-                                                     ": the edges must be finite and strictly ascending");
-    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
-    if (!ctx->have_pack) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->stars_dirty) { const int rc = build_stars(ctx); if (rc) return rc; }
-    if (n_wd == 0) return B9_OK;
-    const int n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
-    const DevPack &pk = ctx->pk;
-    const int mass_cap = pack_mass_cap(pk.max_eep);
-    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
-    const size_t tab_row = (size_t)n_pops * (size_t)b9k_wd_moments_table_doubles(pk.nfp, n_nodes);       // doubles per row
-    if (tab_row > ((size_t)8 << 30) / sizeof(double)) return fail(ctx, B9_ERR_CAPACITY, "b9_wd_bins: one row's node table would exceed 8 GiB");
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>({(size_t)n_rows, (size_t)B9_WDS_MAX_ROWS, B9_WDS_TABLE_BYTES / (tab_row * sizeof(double)),
-                                                                 B9_WBIN_SCRATCH_BYTES / (n_lines * ncol * sizeof(double))}));
-    const WdbArena a = wdb_arena(chunk, n_pops, iso_stride, tab_row, n_lines, (size_t)n, ncol, ne, sizeof(IsoHdr));
-    RESERVE(ctx, ctx->d_wds, a.bytes);
-    char *base = ctx->d_wds.get();
-    double *d_par = part<double>(base, a.o_par), *d_iso = part<double>(base, a.o_iso), *d_tab = part<double>(base, a.o_tab);
-    double *d_scratch = part<double>(base, a.o_scratch), *d_acc = part<double>(base, a.o_acc), *d_edges = part<double>(base, a.o_edges);
-    IsoHdr *d_hdr = part<IsoHdr>(base, a.o_hdr);
-    int *d_rank = part<int>(base, a.o_rank);
-    hipStream_t s = ctx->stream;
-    const size_t acc_bytes = sizeof(double) * n_lines * ncol;
-    HIPCHK(ctx, hipMemcpyAsync(d_rank, rank.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(d_edges, edges, sizeof(double) * n_lines * ne, hipMemcpyHostToDevice, s));
-    if (flags & B9_WBIN_CONTINUE) HIPCHK(ctx, hipMemcpyAsync(d_acc, acc, acc_bytes, hipMemcpyHostToDevice, s));
-    else HIPCHK(ctx, hipMemsetAsync(d_acc, 0, acc_bytes, s));
-    const McmcDev off{};
-    for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
-        const int m = std::min((int)chunk, n_rows - r0);
-        HIPCHK(ctx, hipMemcpyAsync(d_par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, b9k_derive_iso(pk, d_par, m, n_pops, d_hdr, d_iso, iso_stride, mass_cap, off, ctx->pr, no_prev(), s));
-        // the star kernel writes every (row, line) of the chunk, so nothing is cleared
-        HIPCHK(ctx, b9k_wd_bins(pk, ctx->st, d_hdr, d_iso, iso_stride, mass_cap, d_par, m, n_pops, n_nodes, d_tab, d_rank, quantity_mask, d_edges, n_bins,
-                                d_scratch, d_acc, s));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(acc, d_acc, acc_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return B9_OK;
-}
-
 }  // extern "C"
 
 namespace {
@@ -530,6 +366,87 @@ int chain_reduce(b9_ctx *ctx, const ChainCall &c, const double *params, int n_ro
     }
     if (d.acc) HIPCHK(ctx, hipMemcpyAsync(c.acc, d.acc, acc_bytes, hipMemcpyDeviceToHost, s));
     if (end) { const int rc = end(d); if (rc) return rc; }
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return B9_OK;
+}
+
+// ---- the calls on a WD mass grid of the caller's own size: b9_sample_wd_mass, b9_wd_moments, b9_wd_bins ----------------------
+// Rows are worked in chunks: at most B9_WDS_MAX_ROWS rows, and as few as keep the chunk's node table within B9_WDS_TABLE_BYTES
+// and its words [rows][n_lines][n_col] within the call's scratch_bytes (one row, whatever its size, when that alone is larger).
+#define B9_WDS_TABLE_BYTES ((size_t)64 << 20)
+#define B9_WDS_MAX_ROWS 256
+#define B9_WBIN_SCRATCH_BYTES ((size_t)64 << 20)
+
+// What one of them is to the driver below; a line is a WD-stage star, or for the bins a (WD-stage star, selected quantity).
+struct WdGridCall {
+    const char *name;
+    bool status;                         // the node table keeps every node's status
+    size_t lines_per_wd, n_col, n_acc;   // lines per WD-stage star; words per (row, line); accumulator words per line (0: acc null)
+    size_t scratch_bytes;                // 0: the table alone limits the chunk
+    bool pop;                            // the draws' populations, an int per (row, WD-stage star)
+    size_t n_edges;                      // edges per line
+    bool cont;                           // the call's CONTINUE flag: acc comes in
+    double *acc;                         // host: the accumulators [n_lines][n_acc]
+};
+// ... and what the call's hooks see: the arena's parts (acc / pop / edges null when the call has none)
+struct WdGridDev {
+    double *par, *iso, *tab, *scratch, *acc, *edges;
+    IsoHdr *hdr;
+    int *pop, *rank;
+    int n_wd, n_pops, mass_cap;
+    long long iso_stride;
+    size_t per;                          // (row, WD-stage star) pairs of a whole chunk
+};
+using WdGridHook = std::function<int(const WdGridDev &)>;
+using WdGridChunk = std::function<int(const WdGridDev &, int /* first row */, int /* rows */)>;
+using WdGridBody = std::function<hipError_t(const WdGridDev &, int /* first row */, int /* rows */)>;
+
+// The chunked driver (after chain_ready): sizes, one arena in ctx->d_wds, every star's column up, the accumulators in (or cleared),
+// `begin`, then per chunk the parameter rows, their isochrones, `body` and `after`; at last the accumulators out and the wait: a
+// chunk's buffers are reused in stream order.  A catalogue without WD-stage stars: nothing is allocated or launched.
+int wd_grid_reduce(b9_ctx *ctx, const WdGridCall &c, const double *params, int n_rows, int n_nodes, const WdGridBody &body, const WdGridHook &begin = nullptr,
+                   const WdGridChunk &after = nullptr)
+{
+    const int n = ctx->st.n;
+    if (ctx->st.n_wd == 0) return B9_OK;
+    const DevPack &pk = ctx->pk;
+    WdGridDev d{};
+    d.n_wd = ctx->st.n_wd; d.n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
+    d.mass_cap = pack_mass_cap(pk.max_eep); d.iso_stride = pack_iso_stride(d.mass_cap, pk.nfp);
+    const size_t n_lines = (size_t)d.n_wd * c.lines_per_wd;
+    const size_t tab_row = (size_t)d.n_pops * (size_t)b9k_wd_grid_table_doubles(pk.nfp, n_nodes, c.status);       // doubles per row
+    if (tab_row > ((size_t)8 << 30) / sizeof(double)) return fail(ctx, B9_ERR_CAPACITY, std::string(c.name) + ": one row's node table would exceed 8 GiB");
+    size_t chunk = std::min<size_t>({(size_t)n_rows, (size_t)B9_WDS_MAX_ROWS, B9_WDS_TABLE_BYTES / (tab_row * sizeof(double))});
+    if (c.scratch_bytes) chunk = std::min(chunk, c.scratch_bytes / (n_lines * c.n_col * sizeof(double)));
+    chunk = std::max<size_t>(1, chunk);
+    d.per = chunk * d.n_wd;
+    const WdGridArena a = wd_grid_arena(chunk, d.n_pops, d.iso_stride, tab_row, n_lines, (size_t)n, c.n_col, c.n_acc, c.pop ? (size_t)d.n_wd : 0, c.n_edges,
+                                        sizeof(IsoHdr));
+    RESERVE(ctx, ctx->d_wds, a.bytes);
+    char *base = ctx->d_wds.get();
+    d.par = part<double>(base, a.o_par); d.hdr = part<IsoHdr>(base, a.o_hdr); d.iso = part<double>(base, a.o_iso); d.tab = part<double>(base, a.o_tab);
+    d.scratch = part<double>(base, a.o_scratch); d.acc = c.acc ? part<double>(base, a.o_acc) : nullptr;
+    d.pop = c.pop ? part<int>(base, a.o_pop) : nullptr; d.rank = part<int>(base, a.o_rank);
+    d.edges = c.n_edges ? part<double>(base, a.o_edges) : nullptr;
+    std::vector<int> rank(n);            // wd_rank[star]: the WD-stage stars before it (an upload's source: it lives until the wait below)
+    for (int i = 0, k = 0; i < n; ++i) { rank[i] = k; k += ctx->hs.stage[i] == B9_STAGE_WD; }
+    hipStream_t s = ctx->stream;
+    const size_t acc_bytes = sizeof(double) * n_lines * c.n_acc;
+    HIPCHK(ctx, hipMemcpyAsync(d.rank, rank.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
+    if (begin) { const int rc = begin(d); if (rc) return rc; }
+    if (d.acc) {
+        if (c.cont) HIPCHK(ctx, hipMemcpyAsync(d.acc, c.acc, acc_bytes, hipMemcpyHostToDevice, s));
+        else HIPCHK(ctx, hipMemsetAsync(d.acc, 0, acc_bytes, s));
+    }
+    const McmcDev off{};
+    for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
+        const int m = std::min((int)chunk, n_rows - r0);
+        HIPCHK(ctx, hipMemcpyAsync(d.par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, b9k_derive_iso(pk, d.par, m, d.n_pops, d.hdr, d.iso, d.iso_stride, d.mass_cap, off, ctx->pr, no_prev(), s));
+        HIPCHK(ctx, body(d, r0, m));
+        if (after) { const int rc = after(d, r0, m); if (rc) return rc; }
+    }
+    if (d.acc) HIPCHK(ctx, hipMemcpyAsync(c.acc, d.acc, acc_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return B9_OK;
 }
@@ -658,6 +575,76 @@ int b9_pointwise(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flag
         if (!T) return (int)B9_OK;
         HIPCHK(ctx, b9k_pw_tail_store(d_tail(d), n, T, d_tail_io(d), ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(tail, d_tail_io(d), tail_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return (int)B9_OK;
+    });
+}
+
+int b9_sample_wd_mass(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_nodes, uint64_t seed, int64_t row0,
+                      double *out_zams, double *out_wd_mass, double *out_prec_log_age, double *out_log_cool_age,
+                      double *out_log_teff, double *out_logg, double *out_member, int32_t *out_pop)
+{
+    if (!ctx || !params || n_rows < 1 || n_nodes < 1 || !out_zams || !out_member) return B9_ERR_INVALID;
+    if (const int rc = chain_ready(ctx)) return rc;
+    // the seven outputs are the chunk's scratch columns [7][rows][n_wd]; nothing is accumulated
+    const WdGridCall c{"b9_sample_wd_mass", false, 1, 7, 0, 0, true, 0, false, nullptr};
+    double *const host[7] = {out_zams, out_member, out_wd_mass, out_prec_log_age, out_log_cool_age, out_log_teff, out_logg};
+    hipStream_t s = ctx->stream;
+    return wd_grid_reduce(ctx, c, params, n_rows, n_nodes, [&](const WdGridDev &d, int r0, int m) {
+        hipError_t e = hipMemsetAsync(d.scratch, 0, sizeof(double) * d.per * 7, s);        // rows outside the grid write nothing
+        if (e == hipSuccess) e = hipMemsetAsync(d.pop, 0, sizeof(int) * d.per, s);
+        if (e != hipSuccess) return e;
+        const auto col = [&](int q) { return host[q] ? d.scratch + q * d.per : nullptr; };
+        B9WdSample smp{};
+        smp.zams = col(0); smp.member = col(1);
+        smp.wd_mass = col(2); smp.prec_log_age = col(3); smp.log_cool_age = col(4); smp.log_teff = col(5); smp.logg = col(6);
+        smp.pop = d.pop; smp.wd_rank = d.rank;
+        split_seed(seed, &smp.k0, &smp.k1); smp.row0 = (long long)(row0 + r0);
+        // the kernel indexes its outputs [row][n_wd] with the launch's own rows: they are contiguous for any m
+        return b9k_wd_sample(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, n_nodes, d.tab, smp, s);
+    }, nullptr, [&](const WdGridDev &d, int r0, int m) {
+        const size_t cnt = (size_t)m * d.n_wd, o = (size_t)r0 * d.n_wd;
+        for (int q = 0; q < 7; ++q)
+            if (host[q]) HIPCHK(ctx, hipMemcpyAsync(host[q] + o, d.scratch + q * d.per, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
+        if (out_pop) HIPCHK(ctx, hipMemcpyAsync(out_pop + o, d.pop, sizeof(int) * cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));      // (the next chunk reuses the same device buffers)
+        return (int)B9_OK;
+    });
+}
+
+int b9_wd_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_nodes, int32_t flags, double *acc)
+{
+    if (!ctx || !params || !acc || n_rows < 1 || n_nodes < 1) return B9_ERR_INVALID;
+    if (const int rc = chain_ready(ctx)) return rc;
+    const WdGridCall c{"b9_wd_moments", true, 1, B9_WDM_N, B9_WDM_N, 0, false, 0, (flags & B9_WDM_CONTINUE) != 0, acc};
+    // the star kernel writes every (row, WD-stage star) of the chunk, so nothing is cleared
+    return wd_grid_reduce(ctx, c, params, n_rows, n_nodes, [&](const WdGridDev &d, int, int m) {
+        return b9k_wd_moments(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, n_nodes, d.tab, d.rank, d.scratch, d.acc, ctx->stream);
+    });
+}
+
+int b9_wd_bins(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_nodes, int32_t quantity_mask, const double *edges, int32_t n_bins,
+               int32_t flags, double *acc)
+{
+    if (!ctx || !params || !edges || !acc || n_rows < 1 || n_nodes < 1) return B9_ERR_INVALID;
+    if (n_bins < 1 || n_bins > B9_WBIN_MAX_BINS) return fail(ctx, B9_ERR_INVALID, "b9_wd_bins: n_bins must lie in 1 .. B9_WBIN_MAX_BINS");
+    if (quantity_mask < 1 || quantity_mask >= (1 << B9_WQ_N)) return fail(ctx, B9_ERR_INVALID, "b9_wd_bins: the quantity mask must select some of the B9_WQ_N quantities and nothing else");
+    if (!ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
+    const size_t n_sel = (size_t)__builtin_popcount((unsigned)quantity_mask), ne = (size_t)n_bins + 1, ncol = (size_t)n_bins + 3;
+    const size_t n_lines = (size_t)ctx->n_wd_stage * n_sel;
+    for (size_t l = 0; l < n_lines; ++l)
+        for (size_t b = 0; b < ne; ++b)
+            if (!std::isfinite(edges[l * ne + b]) || (b > 0 && !(edges[l * ne + b] > edges[l * ne + b - 1])))
+                return fail(ctx, B9_ERR_INVALID, "b9_wd_bins: WD-stage star " + std::to_string(l / n_sel) + ", selected quantity " + std::to_string(l % n_sel) +
+                                                     ": the edges must be finite and strictly ascending");
+    if (const int rc = chain_ready(ctx)) return rc;
+    // the call's part: every line's edges, the caller's order (the upload's source is the caller's array: it lives until the wait)
+    const WdGridCall c{"b9_wd_bins", true, n_sel, ncol, ncol, B9_WBIN_SCRATCH_BYTES, false, ne, (flags & B9_WBIN_CONTINUE) != 0, acc};
+    // the star kernel writes every (row, line) of the chunk, so nothing is cleared
+    return wd_grid_reduce(ctx, c, params, n_rows, n_nodes, [&](const WdGridDev &d, int, int m) {
+        return b9k_wd_bins(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, n_nodes, d.tab, d.rank, quantity_mask, d.edges, n_bins,
+                           d.scratch, d.acc, ctx->stream);
+    }, [&](const WdGridDev &d) {
+        HIPCHK(ctx, hipMemcpyAsync(d.edges, edges, sizeof(double) * n_lines * ne, hipMemcpyHostToDevice, ctx->stream));
         return (int)B9_OK;
     });
 }

@@ -153,8 +153,9 @@ struct b9_ctx {
     b9i::DeviceBuf<double> d_pred_par;    // [B9_NPARAM]
     b9i::DeviceBuf<char> d_pred_io;       // one chunk of systems (pred_arena): mass1, mass ratio, magnitudes, then wd_type, pop, stage
 
-    // b9_sample_wd_mass: one allocation of its own (grown on demand, never shrunk), for the same reason: a chunk of rows'
-    // parameters, headers, derived isochrones and node table, the chunk's outputs, the stars' columns (wds_arena)
+    // b9_sample_wd_mass, b9_wd_moments, b9_wd_bins: one allocation for the three (grown on demand, never shrunk), for the same
+    // reason: a chunk of rows' parameters, headers, derived isochrones and node table, the chunk's outputs or increments, the
+    // accumulators, the stars' columns and the lines' edges (wd_grid_arena)
     b9i::DeviceBuf<char> d_wds;
 
     // b9_star_moments, b9_mass_hist, b9_phot_resid, b9_pointwise: one allocation for the four (grown on demand, never shrunk),

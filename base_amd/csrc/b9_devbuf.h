@@ -97,40 +97,20 @@ inline PredArena pred_arena(size_t chunk, int nf)
     return a;
 }
 
-// b9_sample_wd_mass' chunk of rows: [params][headers][isochrones][node table][7 outputs][pop], then the stars' columns
-// (tab_row: doubles of one row's node table, all populations; chunk * n_wd draws per output)
-struct WdsArena { size_t o_par, o_hdr, o_iso, o_tab, o_out, o_pop, o_rank, bytes; };
-inline WdsArena wds_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t n_wd, size_t n_stars, size_t hdr_bytes)
+// The three calls on a WD mass grid (b9_sample_wd_mass, b9_wd_moments, b9_wd_bins), one chunk of rows:
+// [params][headers][isochrones][node table][per-(row, line) words [chunk][n_lines][n_col]], then the accumulators [n_lines][n_acc],
+// the drawn populations [chunk][n_pop] ints, the stars' columns [n_stars] ints and the lines' edges [n_lines][n_edges].  tab_row:
+// doubles of one row's node table, all populations.  A part of 0 bytes is empty: it shares its offset with the next one.
+//   the draws    n_lines = n_wd, their seven outputs are the scratch (n_col = 7), n_acc = 0, n_pop = n_wd, n_edges = 0
+//   the moments  n_lines = n_wd, n_col = n_acc = B9_WDM_N, n_pop = 0, n_edges = 0
+//   the bins     n_lines = n_wd * n_sel, n_col = n_acc = n_bins + 3, n_pop = 0, n_edges = n_bins + 1
+struct WdGridArena { size_t o_par, o_hdr, o_iso, o_tab, o_scratch, o_acc, o_pop, o_rank, o_edges, bytes; };
+inline WdGridArena wd_grid_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t n_lines, size_t n_stars, size_t n_col, size_t n_acc,
+                                 size_t n_pop, size_t n_edges, size_t hdr_bytes)
 {
     Carve c;
-    WdsArena a{c.take(8 * B9_NPARAM * chunk), c.take(hdr_bytes * chunk * n_pops), c.take(8 * chunk * n_pops * (size_t)iso_stride), c.take(8 * chunk * tab_row),
-               c.take(8 * chunk * n_wd * 7), c.take(4 * chunk * n_wd), c.take(4 * n_stars), 0};
-    a.bytes = c.total;
-    return a;
-}
-
-// b9_wd_moments' chunk of rows, in the same allocation: [params][headers][isochrones][node table with the nodes' status]
-// [per-(row, star) increments [chunk][n_wd][n_col]], then the accumulators [n_wd][n_col] and the stars' columns
-struct WdmArena { size_t o_par, o_hdr, o_iso, o_tab, o_scratch, o_acc, o_rank, bytes; };
-inline WdmArena wdm_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t n_wd, size_t n_stars, size_t n_col, size_t hdr_bytes)
-{
-    Carve c;
-    WdmArena a{c.take(8 * B9_NPARAM * chunk), c.take(hdr_bytes * chunk * n_pops), c.take(8 * chunk * n_pops * (size_t)iso_stride), c.take(8 * chunk * tab_row),
-               c.take(8 * chunk * n_wd * n_col), c.take(8 * n_wd * n_col), c.take(4 * n_stars), 0};
-    a.bytes = c.total;
-    return a;
-}
-
-// b9_wd_bins' chunk of rows, in the same allocation: b9_wd_moments' parts with n_lines = n_wd * n_sel lines of n_col increments
-// in place of the stars' sixteen, and behind them the lines' edges [n_lines][n_edges]
-struct WdbArena { size_t o_par, o_hdr, o_iso, o_tab, o_scratch, o_acc, o_rank, o_edges, bytes; };
-inline WdbArena wdb_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t n_lines, size_t n_stars, size_t n_col, size_t n_edges,
-                          size_t hdr_bytes)
-{
-    const WdmArena m = wdm_arena(chunk, n_pops, iso_stride, tab_row, n_lines, n_stars, n_col, hdr_bytes);
-    Carve c;
-    c.total = m.bytes;
-    WdbArena a{m.o_par, m.o_hdr, m.o_iso, m.o_tab, m.o_scratch, m.o_acc, m.o_rank, c.take(8 * n_lines * n_edges), 0};
+    WdGridArena a{c.take(8 * B9_NPARAM * chunk), c.take(hdr_bytes * chunk * n_pops), c.take(8 * chunk * n_pops * (size_t)iso_stride), c.take(8 * chunk * tab_row),
+                  c.take(8 * chunk * n_lines * n_col), c.take(8 * n_lines * n_acc), c.take(4 * chunk * n_pop), c.take(4 * n_stars), c.take(8 * n_lines * n_edges), 0};
     a.bytes = c.total;
     return a;
 }

@@ -82,8 +82,8 @@ namespace tree_kd5 {
 #include "b9_star_marg.hip.h"
 #include "b9_marg_step.hip.h"
 #include "b9_predict.hip.h"
-#include "b9_wd_sample.hip.h"
 #include "b9_chain_walk.hip.h"
+#include "b9_wd_sample.hip.h"
 #include "b9_star_moments.hip.h"
 #include "b9_wd_moments.hip.h"
 #include "b9_mass_hist.hip.h"
@@ -238,18 +238,32 @@ hipError_t b9k_predict_mags(const DevPack &pk, const IsoHdr *hdr, const double *
     });
 }
 
-// ---- b9_sample_wd_mass: the node table of a chunk of rows, then the WD-stage stars against it -----------------------------
-long long b9k_wd_table_doubles(int nfp, long long n_nodes) { return n_nodes * B9_WDS_NODE_DOUBLES(nfp); }       // per (row, population)
+// ---- the WD-grid calls (b9_sample_wd_mass, b9_wd_moments, b9_wd_bins): the node table of a chunk of rows, then the call's star kernel ----
+long long b9k_wd_grid_table_doubles(int nfp, long long n_nodes, bool status)       // per (row, population)
+{
+    return n_nodes * (status ? B9_WDM_NODE_DOUBLES(nfp) : B9_WDS_NODE_DOUBLES(nfp));
+}
+
+// The chunk's node table (STATUS: with every node's status behind it) behind the guard the three calls share.  Returns
+// n_wp = n_rows * NPOPS, or 0: invalid arguments, nothing launched.
+template <int NFP, int NPOPS, bool STATUS>
+static int launch_wd_grid_table(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
+                                const double *d_params, int n_rows, int n_nodes, double *tab, hipStream_t stream)
+{
+    if (!tab || n_rows < 1 || n_nodes < 1 || st.n_wd < 1 || n_rows * NPOPS > 65535) return 0;
+    const int n_wp = n_rows * NPOPS;
+    hipLaunchKernelGGL(STATUS ? k_wd_node_table_status<NFP> : k_wd_node_table<NFP>, dim3((n_nodes + 63) / 64, n_wp), dim3(128), 0, stream, pk, hdr, iso_data,
+                       iso_stride, mass_cap, NPOPS, d_params, n_nodes, tab, n_wp);
+    return n_wp;
+}
 
 hipError_t b9k_wd_sample(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
                          const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const B9WdSample &smp, hipStream_t stream)
 {
     return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        if (!tab || n_rows < 1 || n_nodes < 1 || st.n_wd < 1 || n_rows * NPOPS > 65535) return hipErrorInvalidValue;
-        const int n_wp = n_rows * NPOPS;
-        hipLaunchKernelGGL((k_wd_node_table<NFP>), dim3((n_nodes + 63) / 64, n_wp), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride, mass_cap,
-                           NPOPS, d_params, n_nodes, tab, n_wp);
+        const int n_wp = launch_wd_grid_table<NFP, NPOPS, false>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, n_nodes, tab, stream);
+        if (!n_wp) return hipErrorInvalidValue;
         WdSampleOut out{};
         out.zams = smp.zams; out.member = smp.member; out.pop = smp.pop; out.wd_rank = smp.wd_rank;
         out.der[0] = smp.wd_mass; out.der[1] = smp.prec_log_age; out.der[2] = smp.log_cool_age; out.der[3] = smp.log_teff; out.der[4] = smp.logg;
@@ -260,19 +274,15 @@ hipError_t b9k_wd_sample(const DevPack &pk, const DevStars &st, const IsoHdr *hd
     });
 }
 
-// ---- b9_wd_moments: the node table with every node's status, the WD-stage stars' increments, the accumulation -----------------
-long long b9k_wd_moments_table_doubles(int nfp, long long n_nodes) { return n_nodes * B9_WDM_NODE_DOUBLES(nfp); }       // per (row, population)
-
 hipError_t b9k_wd_moments(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
                           const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const int *wd_rank, double *scratch, double *acc,
                           hipStream_t stream)
 {
     return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        if (!tab || !wd_rank || !scratch || !acc || n_rows < 1 || n_nodes < 1 || st.n_wd < 1 || n_rows * NPOPS > 65535) return hipErrorInvalidValue;
-        const int n_wp = n_rows * NPOPS;
-        hipLaunchKernelGGL((k_wd_node_table_status<NFP>), dim3((n_nodes + 63) / 64, n_wp), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride, mass_cap,
-                           NPOPS, d_params, n_nodes, tab, n_wp);
+        if (!wd_rank || !scratch || !acc) return hipErrorInvalidValue;
+        const int n_wp = launch_wd_grid_table<NFP, NPOPS, true>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, n_nodes, tab, stream);
+        if (!n_wp) return hipErrorInvalidValue;
         hipLaunchKernelGGL((k_wd_moments<NFP, NPOPS>), dim3((st.n_wd + 63) / 64, n_rows), dim3(64), 0, stream, pk, st, hdr, d_params, n_nodes,
                            (const double *)tab, n_wp, wd_rank, scratch);
         const long long n_words = (long long)st.n_wd * B9_WDM_N;
@@ -281,7 +291,6 @@ hipError_t b9k_wd_moments(const DevPack &pk, const DevStars &st, const IsoHdr *h
     });
 }
 
-// ---- b9_wd_bins: b9_wd_moments' node table, the WD-stage stars' increments on their own edges per selected quantity, the accumulation ----
 hipError_t b9k_wd_bins(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
                        const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const int *wd_rank, int quantity_mask,
                        const double *edges, int n_bins, double *scratch, double *acc, hipStream_t stream)
@@ -289,12 +298,10 @@ hipError_t b9k_wd_bins(const DevPack &pk, const DevStars &st, const IsoHdr *hdr,
     return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
         const int n_sel = __builtin_popcount((unsigned)quantity_mask);
-        if (!tab || !wd_rank || !edges || !scratch || !acc || n_rows < 1 || n_nodes < 1 || st.n_wd < 1 || n_rows * NPOPS > 65535 || n_bins < 1 ||
-            n_bins > B9_WBIN_MAX_BINS || quantity_mask < 1 || quantity_mask >= (1 << B9_WQ_N))
+        if (!wd_rank || !edges || !scratch || !acc || n_bins < 1 || n_bins > B9_WBIN_MAX_BINS || quantity_mask < 1 || quantity_mask >= (1 << B9_WQ_N))
             return hipErrorInvalidValue;
-        const int n_wp = n_rows * NPOPS;
-        hipLaunchKernelGGL((k_wd_node_table_status<NFP>), dim3((n_nodes + 63) / 64, n_wp), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride, mass_cap,
-                           NPOPS, d_params, n_nodes, tab, n_wp);
+        const int n_wp = launch_wd_grid_table<NFP, NPOPS, true>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, n_nodes, tab, stream);
+        if (!n_wp) return hipErrorInvalidValue;
         const auto k = with_lds(k_wd_bins<NFP, NPOPS>, sizeof(double) * 64 * ((size_t)(n_bins + 1) + (size_t)(n_bins + 2)));
         if (k.err != hipSuccess) return k.err;
         hipLaunchKernelGGL(k.kern, dim3((st.n_wd + 63) / 64, n_rows, n_sel), dim3(64), k.lds, stream, pk, st, hdr, d_params, n_nodes,

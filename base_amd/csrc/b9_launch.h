@@ -114,19 +114,20 @@ struct B9WdSample {
     unsigned k0, k1;
     long long row0;
 };
-// k_wd_node_table + k_wd_sample on n_rows derived rows (n_rows * n_pops <= 65535); tab: n_rows * n_pops * b9k_wd_table_doubles doubles
+// The node table of the three WD-grid calls, doubles per (row, population): k_wd_node_table's, or with status k_wd_node_table_status'
+// (every node's wd_chain status behind it)
+long long b9k_wd_grid_table_doubles(int nfp, long long n_nodes, bool status);
+// k_wd_node_table + k_wd_sample on n_rows derived rows (n_rows * n_pops <= 65535); tab: n_rows * n_pops table doubles, no status
 hipError_t b9k_wd_sample(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
                          const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const B9WdSample &smp, hipStream_t stream);
-long long b9k_wd_table_doubles(int nfp, long long n_nodes);      // per (row, population)
 
-// b9_wd_moments: k_wd_node_table_status (k_wd_node_table's table with every node's status; b9k_wd_moments_table_doubles per (row, population)) +
+// b9_wd_moments: k_wd_node_table_status (the table with status) +
 // k_wd_moments on n_rows derived rows (n_rows * n_pops <= 65535): every WD-stage star's sixteen increments into scratch
 // [n_rows][st.n_wd][B9_WDM_N] (column wd_rank[original index], as B9WdSample's), then acc [st.n_wd][B9_WDM_N] += the rows in
 // ascending order.  Device pointers, all the caller's own.
 hipError_t b9k_wd_moments(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
                           const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const int *wd_rank, double *scratch, double *acc,
                           hipStream_t stream);
-long long b9k_wd_moments_table_doubles(int nfp, long long n_nodes);      // per (row, population)
 
 // b9_wd_bins: k_wd_node_table_status (b9_wd_moments' table, built once per chunk) + k_wd_bins on n_rows derived rows (n_rows * n_pops <= 65535):
 // every (WD-stage star, selected quantity)'s increments on its own edges into scratch [n_rows][st.n_wd][n_sel][n_bins + 3] (below, the bins, at

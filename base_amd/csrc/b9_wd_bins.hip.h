@@ -12,9 +12,8 @@
 // Increments go per (row, star, selected quantity) to a scratch [row][n_wd][n_sel][B + 3] in the order of b9_sample_wd_mass's
 // columns and k_chain_accumulate adds the rows.
 //
-// k_wd_bins is k_wd_moments' frame -- one wave per (64 stars, row), 64-node tiles of the row's table in LDS, every lane reads the
-// SAME node -- with blockIdx.z the selected quantity: beside the rows, the log prior and the status a block stages that
-// quantity's derived column alone.  The binning is k_star_bins': the 64 lanes' edges staged once per block as [edge][64]
+// k_wd_bins goes through wd_grid_walk (b9_wd_sample.hip.h: the lane's star, the tiles, the terms) with blockIdx.z the selected
+// quantity: beside the walk's rows and log prior a block stages the status and that quantity's derived column alone.  The binning is k_star_bins': the 64 lanes' edges staged once per block as [edge][64]
 // (gathered from the caller's order through wd_rank; the lane is the bank), the wave's histogram [B + 2][64] in LDS, a bank per
 // lane; a lane keeps its current bin and that bin's two edges in registers and searches its own column (sbin_search) only when
 // a value leaves them -- neighbouring nodes have neighbouring values.
@@ -45,17 +44,11 @@ __global__ __launch_bounds__(64) void k_wd_bins(DevPack pk, DevStars st, const I
     const bool zams = quantity == B9_WQ_ZAMS;
     const int k_wd = blockIdx.x * 64 + lane;
     const bool live = k_wd < st.n_wd;
-    const int slot = st.wd_slot[live ? k_wd : 0], orig = st.perm[slot];
-    double obs[NFP], wgt[NFP];
-#pragma unroll
-    for (int f = 0; f < NFP; ++f) { obs[f] = st.obs[B9_SIDX(NFP, f, slot)]; wgt[f] = st.w[B9_SIDX(NFP, f, slot)]; }
-    const int wd_type = st.flags[slot] & 1;
-    const size_t line = (size_t)wd_rank[orig] * n_sel + sel;                 // the caller's line (a padding lane: star 0's, never written)
+    const WdStar<NFP> star = wd_star<NFP, NPOPS>(st, hdr, params, live ? k_wd : 0, r);
+    const int slot = star.slot;
+    const size_t line = (size_t)wd_rank[star.orig] * n_sel + sel;            // the caller's line (a padding lane: star 0's, never written)
     double *__restrict__ const out = scratch + ((size_t)r * st.n_wd * n_sel + line) * ncol;
-    bool valid = true;
-#pragma unroll
-    for (int kp = 0; kp < NPOPS; ++kp) valid = valid && hdr[r * NPOPS + kp].valid;
-    if (!valid) {                                            // a row outside the grid contributes nothing
+    if (!star.valid) {                                       // a row outside the grid contributes nothing
         if (live)
             for (int c = 0; c < ncol; ++c) out[c] = 0.0;
         return;
@@ -64,7 +57,7 @@ __global__ __launch_bounds__(64) void k_wd_bins(DevPack pk, DevStars st, const I
     for (int b = 0; b <= n_bins; ++b) s_edge[b * 64 + lane] = live ? edges[line * (n_bins + 1) + b] : 0.0;
     double *const h_mine = s_hist + lane;
     const double *const e_mine = s_edge + lane;
-    const double *par = params + (size_t)r * B9_NPARAM;
+    const double *par = star.par;
     const WdTable<const double> t = wd_table_view(tab, NFP, n_wp, n_nodes);
     const double *__restrict__ const stat_all = t.der + (size_t)n_wp * n_nodes * B9_WDS_DER;
     double lg[NPOPS];
@@ -78,46 +71,22 @@ __global__ __launch_bounds__(64) void k_wd_bins(DevPack pk, DevStars st, const I
         double c_lo = __builtin_inf(), c_hi = NEG_INF;
         int c_b = -1;
         const int wp = r * NPOPS + kp;
-        const double tip = hdr[wp].agb_tip;
-        const double dM = (pk.m_wd_up - tip) / n_nodes;
-        if (dM > 0.0) {                                      // (wave-uniform: one row)
-            const double log_w = log(dM);
-            const double *__restrict__ const lpm = t.lpm + (size_t)wp * n_nodes;
-            const double *__restrict__ const der = t.der + (size_t)wp * n_nodes * B9_WDS_DER;
-            const double *__restrict__ const stat = stat_all + (size_t)wp * n_nodes;
-            for (int t0 = 0; t0 < n_nodes; t0 += B9_WDS_TILE) {
-                const int cnt = n_nodes - t0 < B9_WDS_TILE ? n_nodes - t0 : B9_WDS_TILE;
-                __syncthreads();                             // (the previous tile's reads are done)
-#pragma unroll
-                for (int ty = 0; ty < 2; ++ty) {
-                    const double *__restrict__ const src = t.rows + (((size_t)wp * 2 + ty) * n_nodes + t0) * NFP;
-                    for (int x = lane; x < cnt * NFP; x += 64) s_rows[ty * B9_WDS_TYPE_STRIDE(NFP) + x] = src[x];
-                }
-                if (lane < cnt) {
-                    s_lpm[lane] = lpm[t0 + lane]; s_stat[lane] = stat[t0 + lane];
-                    s_val[lane] = zams ? 0.0 : der[(size_t)(t0 + lane) * B9_WDS_DER + (quantity - 1)];
-                }
-                __syncthreads();
-                const double *const mine = s_rows + wd_type * B9_WDS_TYPE_STRIDE(NFP);
-                for (int i = 0; i < cnt; ++i) {
-                    const double *const row = mine + i * NFP;
-                    double chi2 = 0.0;
-#pragma unroll
-                    for (int f = 0; f < NFP; ++f) { const double d = row[f] - obs[f]; chi2 = fma(wgt[f] * d, d, chi2); }
-                    if (live && isfinite(chi2)) {
-                        const double term = (s_lpm[i] - 0.5 * chi2) + log_w;
-                        const bool counts = zams || s_stat[i] == 2.0;
-                        const double v = zams ? tip + dM * (double)(t0 + i + 1) : s_val[i];
-                        if (counts && !(v >= c_lo && v < c_hi)) {
-                            c_b = sbin_search(e_mine, n_bins, v);
-                            c_lo = c_b >= 0 ? e_mine[c_b * 64] : NEG_INF;
-                            c_hi = c_b < n_bins ? e_mine[(c_b + 1) * 64] : __builtin_inf();
-                        }
-                        hist_term(term, counts ? c_b + 1 : -1, tb, ref, s0, h_mine);
-                    }
-                }
+        const double *__restrict__ const der = t.der + (size_t)wp * n_nodes * B9_WDS_DER;
+        const double *__restrict__ const stat = stat_all + (size_t)wp * n_nodes;
+        double tip, dM;
+        wd_grid_walk<NFP>(t, star, live, hdr, wp, n_nodes, pk.m_wd_up, s_rows, s_lpm, tip, dM, [&](int i, int j) {
+            s_stat[i] = stat[j - 1];
+            s_val[i] = zams ? 0.0 : der[(size_t)(j - 1) * B9_WDS_DER + (quantity - 1)];
+        }, [&](int i, int j, double term) {
+            const bool counts = zams || s_stat[i] == 2.0;
+            const double v = zams ? tip + dM * (double)j : s_val[i];
+            if (counts && !(v >= c_lo && v < c_hi)) {
+                c_b = sbin_search(e_mine, n_bins, v);
+                c_lo = c_b >= 0 ? e_mine[c_b * 64] : NEG_INF;
+                c_hi = c_b < n_bins ? e_mine[(c_b + 1) * 64] : __builtin_inf();
             }
-        }
+            hist_term(term, counts ? c_b + 1 : -1, tb, ref, s0, h_mine);
+        });
         const bool has = ref != NEG_INF;
         lg[kp] = has ? ref + log(s0) : NEG_INF;
         has_k[kp] = has; s0_k[kp] = s0;

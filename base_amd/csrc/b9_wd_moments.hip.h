@@ -1,6 +1,6 @@
 // b9_wd_moments.hip.h -- b9_wd_moments (the wdSummary counterpart): k_wd_moments, one LANE per WD-stage star against
 // k_wd_node_table_status' table: k_wd_node_table's (the same body, b9_wd_sample.hip.h) with every node's wd_chain status kept.
-// Part of the single translation unit b9_kernels.hip (included there, after b9_chain_walk.hip.h); gfx950 only.
+// Part of the single translation unit b9_kernels.hip (included there, after b9_wd_sample.hip.h); gfx950 only.
 #pragma once
 
 // ------------------------------------------------------------------------------------------
@@ -14,8 +14,10 @@
 //   stat [wp][n_nodes]               wd_chain's status of the node as a double (2.0: a white dwarf with every derived value set)
 // b9_sample_wd_mass builds and k_wd_sample reads the table without it, as before.
 //
-// k_wd_moments is k_wd_sample's frame: one wave per (64 stars, row), 64-node tiles of the row's table in LDS (both atmosphere
-// types, the log prior, the derived values, the status), every lane reads the SAME node -- a broadcast.
+// k_wd_moments is wd_grid_walk's frame (b9_wd_sample.hip.h) on wd_star's lane, with the walk WRITTEN OUT and the derived values and
+// the status of a tile's nodes staged beside the rows: through wd_grid_walk the call took 0.94 - 0.97 ms against 0.88 - 0.91 ms
+// (1000 WD-stage stars, 256 rows, 512 nodes; docs/LABNOTES.md section 31), in both forms of its stage callback.  The loop below
+// and wd_grid_walk's must stay the same statement: test_ties_to_wd_moments and test_ties_to_sample_wd_mass hold them together.
 // ORDER OF THE SUMS (a function of the data only): a star's terms enter its population's online log-sum-exp (lse_step: the
 // reference stays while terms lie within 600 e-folds above it; every sum is rescaled together on the rare jump) one by one in
 // ascending node order j = 1 .. n_nodes, by this one lane; a lane that does not jump while a launch-mate does multiplies by 1.0.
@@ -35,23 +37,17 @@ __global__ __launch_bounds__(64) void k_wd_moments(DevPack pk, DevStars st, cons
     const int lane = threadIdx.x, r = blockIdx.y;
     const int k_wd = blockIdx.x * 64 + lane;
     const bool live = k_wd < st.n_wd;
-    const int slot = st.wd_slot[live ? k_wd : 0], orig = st.perm[slot];
-    double obs[NFP], wgt[NFP];
-#pragma unroll
-    for (int f = 0; f < NFP; ++f) { obs[f] = st.obs[B9_SIDX(NFP, f, slot)]; wgt[f] = st.w[B9_SIDX(NFP, f, slot)]; }
-    const int wd_type = st.flags[slot] & 1;
-    double *__restrict__ const out = scratch + ((size_t)r * st.n_wd + wd_rank[orig]) * B9_WDM_N;
-    bool valid = true;
-#pragma unroll
-    for (int kp = 0; kp < NPOPS; ++kp) valid = valid && hdr[r * NPOPS + kp].valid;
-    if (!valid) {                                            // a row outside the grid contributes nothing
+    const WdStar<NFP> star = wd_star<NFP, NPOPS>(st, hdr, params, live ? k_wd : 0, r);
+    const int slot = star.slot;
+    double *__restrict__ const out = scratch + ((size_t)r * st.n_wd + wd_rank[star.orig]) * B9_WDM_N;
+    if (!star.valid) {                                       // a row outside the grid contributes nothing
         if (live) {
 #pragma unroll
             for (int c = 0; c < B9_WDM_N; ++c) out[c] = 0.0;
         }
         return;
     }
-    const double *par = params + (size_t)r * B9_NPARAM;
+    const double *par = star.par;
     const WdTable<const double> t = wd_table_view(tab, NFP, n_wp, n_nodes);
     const double *__restrict__ const stat_all = t.der + (size_t)n_wp * n_nodes * B9_WDS_DER;
     double lg[NPOPS], mean[NPOPS][B9_WDM_SUMS - 1];
@@ -79,12 +75,12 @@ __global__ __launch_bounds__(64) void k_wd_moments(DevPack pk, DevStars st, cons
                 for (int x = lane; x < cnt * B9_WDS_DER; x += 64) s_der[x] = der[(size_t)t0 * B9_WDS_DER + x];
                 if (lane < cnt) { s_lpm[lane] = lpm[t0 + lane]; s_stat[lane] = stat[t0 + lane]; }
                 __syncthreads();
-                const double *const mine = s_rows + wd_type * B9_WDS_TYPE_STRIDE(NFP);
+                const double *const mine = s_rows + star.wd_type * B9_WDS_TYPE_STRIDE(NFP);
                 for (int i = 0; i < cnt; ++i) {
                     const double *const row = mine + i * NFP;
                     double chi2 = 0.0;
 #pragma unroll
-                    for (int f = 0; f < NFP; ++f) { const double d = row[f] - obs[f]; chi2 = fma(wgt[f] * d, d, chi2); }
+                    for (int f = 0; f < NFP; ++f) { const double d = row[f] - star.obs[f]; chi2 = fma(star.wgt[f] * d, d, chi2); }
                     if (live && isfinite(chi2)) {
                         const double term = (s_lpm[i] - 0.5 * chi2) + log_w;
                         const double e = lse_step(term, ref, [&](double scale) {

@@ -1,6 +1,7 @@
 // b9_wd_sample.hip.h -- b9_sample_wd_mass (the sampleWDMass counterpart): k_wd_node_table (the WD chain once per node, derived
-// values kept) and k_wd_sample (one LANE per WD-stage star against the table: Gumbel-max draw, membership, derived values).
-// Part of the single translation unit b9_kernels.hip (included there, in this order); gfx950 only.
+// values kept), wd_grid_walk (the frame of the three star kernels against that table: k_wd_sample, k_wd_moments, k_wd_bins) and
+// k_wd_sample (one LANE per WD-stage star: Gumbel-max draw, membership, derived values).
+// Part of the single translation unit b9_kernels.hip (included there, after b9_chain_walk.hip.h); gfx950 only.
 #pragma once
 
 // ------------------------------------------------------------------------------------------
@@ -94,35 +95,71 @@ struct WdSampleOut {
     long long row0;
 };
 
-// k_wd_sample: one LANE per WD-stage star, one wave per (64 stars, row); the wave stages 64-node tiles of the row's table
-// (both atmosphere types) in LDS and every lane reads the SAME node -- a broadcast read -- so a node row is fetched once per
-// 64 stars.  Per lane: the star's observations and weights in registers, a running log-sum-exp and the best (key, k, j).
+// ------------------------------------------------------------------------------------------
+// The star kernels' frame, stated once for k_wd_sample and k_wd_bins; k_wd_moments keeps the walk written out, for its speed
+// (b9_wd_moments.hip.h).  The three must agree in it to the bit (test_ties_to_wd_moments, test_ties_to_sample_wd_mass): one LANE per WD-stage star (wd_star, b9_chain_walk.hip.h; a padding lane
+// reads star 0 and is never `live`), one wave per (64 stars, row); the wave stages 64-node tiles of the row's table (both
+// atmosphere types) in LDS and every lane reads the SAME node -- a broadcast read -- so a node row is fetched once per 64 stars.
+//
+// wd_grid_walk: one population's walk over (row, population) wp.  Per tile, between the two barriers, the rows of both types and
+// the log prior go to the kernel's s_rows / s_lpm, and lane i of the tile's nodes calls stage(i, j) to put the call's own columns
+// of ITS node j at slot i (beside the log prior's load, under the one guard: the loads share one wait, as in the kernels before);
+// then on_node(i, j, term) is called in ascending node order j = t0 + i + 1 = 1 .. n_nodes for exactly the lanes where the star is
+// live and the node's chi-square finite, with term = (log prior - chi^2 / 2) + log dM.  tip, dM: out, the grid m_j = tip + dM j
+// (set before the first on_node; without steps, dM <= 0, nothing is called).
+// ------------------------------------------------------------------------------------------
+#define B9_WDS_TILE 64
+#define B9_WDS_TYPE_STRIDE(NFP) (B9_WDS_TILE * (NFP) + 2)            // (+ 2: the DB tile starts on other banks than the DA tile)
+template <int NFP, class S, class F>
+__device__ __forceinline__ void wd_grid_walk(const WdTable<const double> &t, const WdStar<NFP> &s, bool live, const IsoHdr *__restrict__ hdr, int wp,
+                                             int n_nodes, double m_wd_up, double *s_rows, double *s_lpm, double &tip, double &dM, S stage, F on_node)
+{
+    const int lane = threadIdx.x;
+    tip = hdr[wp].agb_tip;
+    dM = (m_wd_up - tip) / n_nodes;
+    if (!(dM > 0.0)) return;                                 // (wave-uniform: one row)
+    const double log_w = log(dM);
+    const double *__restrict__ const lpm = t.lpm + (size_t)wp * n_nodes;
+    for (int t0 = 0; t0 < n_nodes; t0 += B9_WDS_TILE) {
+        const int cnt = n_nodes - t0 < B9_WDS_TILE ? n_nodes - t0 : B9_WDS_TILE;
+        __syncthreads();                                     // (the previous tile's reads are done)
+#pragma unroll
+        for (int ty = 0; ty < 2; ++ty) {
+            const double *__restrict__ const src = t.rows + (((size_t)wp * 2 + ty) * n_nodes + t0) * NFP;
+            for (int x = lane; x < cnt * NFP; x += 64) s_rows[ty * B9_WDS_TYPE_STRIDE(NFP) + x] = src[x];
+        }
+        if (lane < cnt) { s_lpm[lane] = lpm[t0 + lane]; stage(lane, t0 + lane + 1); }
+        __syncthreads();
+        const double *const mine = s_rows + s.wd_type * B9_WDS_TYPE_STRIDE(NFP);
+        for (int i = 0; i < cnt; ++i) {
+            const double *const row = mine + i * NFP;
+            double chi2 = 0.0;
+#pragma unroll
+            for (int f = 0; f < NFP; ++f) { const double d = row[f] - s.obs[f]; chi2 = fma(s.wgt[f] * d, d, chi2); }
+            if (live && isfinite(chi2)) on_node(i, t0 + i + 1, (s_lpm[i] - 0.5 * chi2) + log_w);
+        }
+    }
+}
+
+// k_wd_sample: per lane a running log-sum-exp and the best (key, k, j) over the walk.
 // ORDER OF THE SUM (out_member is a function of the data only): a star's terms enter its population's log-sum-exp one
 // by one in ascending node order j = 1 .. n_nodes, by this one lane; the populations are then mixed as b9_sample_mass
 // mixes them.  Nothing of it depends on the chunk of rows, the grid or the call.  Equal keys keep the first one met:
 // lowest population, then lowest node.
-#define B9_WDS_TILE 64
-#define B9_WDS_TYPE_STRIDE(NFP) (B9_WDS_TILE * (NFP) + 2)            // (+ 2: the DB tile starts on other banks than the DA tile)
 template <int NFP, int NPOPS>
 __global__ __launch_bounds__(64) void k_wd_sample(DevPack pk, DevStars st, const IsoHdr *__restrict__ hdr, const double *__restrict__ params,
                                                   int n_nodes, const double *__restrict__ tab, int n_wp, WdSampleOut out)
 {
     __shared__ __attribute__((aligned(16))) double s_rows[2 * B9_WDS_TYPE_STRIDE(NFP)];
     __shared__ double s_lpm[B9_WDS_TILE];
-    const int lane = threadIdx.x, r = blockIdx.y;
-    const int k_wd = blockIdx.x * 64 + lane;
+    const int r = blockIdx.y;
+    const int k_wd = blockIdx.x * 64 + threadIdx.x;
     const bool live = k_wd < st.n_wd;
-    const int slot = st.wd_slot[live ? k_wd : 0], orig = st.perm[slot];
-    double obs[NFP], wgt[NFP];
-#pragma unroll
-    for (int f = 0; f < NFP; ++f) { obs[f] = st.obs[B9_SIDX(NFP, f, slot)]; wgt[f] = st.w[B9_SIDX(NFP, f, slot)]; }
-    const double c0m = st.c0m[slot], la = st.la[slot];
-    const int wd_type = st.flags[slot] & 1;
-    bool valid = true;
-#pragma unroll
-    for (int kp = 0; kp < NPOPS; ++kp) valid = valid && hdr[r * NPOPS + kp].valid;
-    if (!valid) return;                                      // a row outside the grid: the outputs stay 0
-    const double *par = params + (size_t)r * B9_NPARAM;
+    const WdStar<NFP> s = wd_star<NFP, NPOPS>(st, hdr, params, live ? k_wd : 0, r);
+    const int orig = s.orig;
+    const double c0m = st.c0m[s.slot], la = st.la[s.slot];
+    if (!s.valid) return;                                    // a row outside the grid: the outputs stay 0
+    const double *par = s.par;
     const WdTable<const double> t = wd_table_view(tab, NFP, n_wp, n_nodes);
     const unsigned long long g_row = (unsigned long long)(out.row0 + r);
     double lw_pop[2] = {0.0, 0.0};
@@ -133,38 +170,12 @@ __global__ __launch_bounds__(64) void k_wd_sample(DevPack pk, DevStars st, const
 #pragma unroll
     for (int kp = 0; kp < NPOPS; ++kp) {
         Lse acc; acc.mx = NEG_INF; acc.sm = 0.0;
-        const int wp = r * NPOPS + kp;
-        const double tip = hdr[wp].agb_tip;
-        const double dM = (pk.m_wd_up - tip) / n_nodes;
-        if (dM > 0.0) {                                      // (wave-uniform: one row)
-            const double log_w = log(dM);
-            const double *__restrict__ const lpm = t.lpm + (size_t)wp * n_nodes;
-            for (int t0 = 0; t0 < n_nodes; t0 += B9_WDS_TILE) {
-                const int cnt = n_nodes - t0 < B9_WDS_TILE ? n_nodes - t0 : B9_WDS_TILE;
-                __syncthreads();                             // (the previous tile's reads are done)
-#pragma unroll
-                for (int ty = 0; ty < 2; ++ty) {
-                    const double *__restrict__ const src = t.rows + (((size_t)wp * 2 + ty) * n_nodes + t0) * NFP;
-                    for (int x = lane; x < cnt * NFP; x += 64) s_rows[ty * B9_WDS_TYPE_STRIDE(NFP) + x] = src[x];
-                }
-                if (lane < cnt) s_lpm[lane] = lpm[t0 + lane];
-                __syncthreads();
-                const double *const mine = s_rows + wd_type * B9_WDS_TYPE_STRIDE(NFP);
-                for (int i = 0; i < cnt; ++i) {
-                    const double *const row = mine + i * NFP;
-                    double chi2 = 0.0;
-#pragma unroll
-                    for (int f = 0; f < NFP; ++f) { const double d = row[f] - obs[f]; chi2 = fma(wgt[f] * d, d, chi2); }
-                    if (live && isfinite(chi2)) {
-                        const int j = t0 + i + 1;
-                        const double term = (s_lpm[i] - 0.5 * chi2) + log_w;
-                        lse_add(acc, term);
-                        const double key = term + lw_pop[kp] + gumbel(out.k0, out.k1, g_row, (unsigned)orig, (unsigned long long)j, (unsigned)kp);
-                        if (key > best_key) { best_key = key; best_mass = tip + dM * (double)j; best_j = j; best_k = kp; }
-                    }
-                }
-            }
-        }
+        double tip, dM;
+        wd_grid_walk<NFP>(t, s, live, hdr, r * NPOPS + kp, n_nodes, pk.m_wd_up, s_rows, s_lpm, tip, dM, [](int, int) {}, [&](int, int j, double term) {
+            lse_add(acc, term);
+            const double key = term + lw_pop[kp] + gumbel(out.k0, out.k1, g_row, (unsigned)orig, (unsigned long long)j, (unsigned)kp);
+            if (key > best_key) { best_key = key; best_mass = tip + dM * (double)j; best_j = j; best_k = kp; }
+        });
         ll[kp] = (acc.mx == NEG_INF) ? NEG_INF : c0m + (acc.mx + log(acc.sm));
     }
     if (!live) return;

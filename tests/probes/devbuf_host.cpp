@@ -285,17 +285,43 @@ void carve_checks()
         }
         CHECK(c.total == sum && kArenaAlign == 256);
     }
-    // b9_sample_wd_mass: the parts and the total its body computed before it called wds_arena
+    // b9_sample_wd_mass through wd_grid_arena (its seven outputs are the scratch; no accumulators, no edges): the parts and the
+    // total its body computed before any arena existed
     struct { size_t chunk; int n_pops; long long stride; size_t tab_row, n_wd, n; } wds[] = {{256, 2, 122 * 9, 40000, 37, 1000}, {3, 1, 62 * 5, 1234, 1, 13}};
     for (const auto &s : wds) {
         const size_t per = s.chunk * s.n_wd;
         const size_t o_hdr = up256(8 * B9_NPARAM * s.chunk), o_iso = o_hdr + up256(sizeof(Hdr) * s.chunk * s.n_pops);
         const size_t o_tab = o_iso + up256(8 * s.chunk * s.n_pops * (size_t)s.stride), o_out = o_tab + up256(8 * s.chunk * s.tab_row);
         const size_t o_pop = o_out + up256(8 * per * 7), o_rank = o_pop + up256(4 * per), bytes = o_rank + up256(4 * s.n);
-        const WdsArena a = wds_arena(s.chunk, s.n_pops, s.stride, s.tab_row, s.n_wd, s.n, sizeof(Hdr));
-        CHECK(a.o_par == 0 && a.o_hdr == o_hdr && a.o_iso == o_iso && a.o_tab == o_tab && a.o_out == o_out && a.o_pop == o_pop && a.o_rank == o_rank && a.bytes == bytes);
-        const size_t offs[] = {a.o_par, a.o_hdr, a.o_iso, a.o_tab, a.o_out, a.o_pop, a.o_rank, a.bytes};
+        const WdGridArena a = wd_grid_arena(s.chunk, s.n_pops, s.stride, s.tab_row, s.n_wd, s.n, 7, 0, s.n_wd, 0, sizeof(Hdr));
+        CHECK(a.o_par == 0 && a.o_hdr == o_hdr && a.o_iso == o_iso && a.o_tab == o_tab && a.o_scratch == o_out && a.o_pop == o_pop && a.o_rank == o_rank && a.bytes == bytes);
+        CHECK(a.o_acc == a.o_pop && a.o_edges == a.bytes);                                              // the two empty parts
+        const size_t offs[] = {a.o_par, a.o_hdr, a.o_iso, a.o_tab, a.o_scratch, a.o_pop, a.o_rank, a.bytes};
         for (int k = 0; k < 7; ++k) CHECK(offs[k] % 256 == 0 && offs[k] < offs[k + 1]);
+    }
+    // b9_wd_moments (16 words a star, no populations, no edges) and b9_wd_bins (6 and 1 selected quantities at 7 and 64 bins: n_lines
+    // lines of n_bins + 3 words, n_bins + 1 edges a line) through the same function: in order, disjoint, aligned, an empty part
+    // starts where the next one does, and the total is the sum of the rounded sizes -- for the moments [par][hdr][iso][tab][scratch]
+    // [acc][rank], for the bins the same with [edges] behind, as the two calls' own arenas gave before this one
+    struct { size_t chunk; int n_pops; long long stride; size_t tab_row, n_lines, n, n_col, n_edges; } wdg[] = {
+        {256, 2, 122 * 9, 2 * 1000 * 23, 37, 1000, 16, 0}, {3, 1, 62 * 5, 1234, 1, 13, 16, 0},
+        {64, 2, 122 * 9, 2 * 200 * 23, 37 * 6, 1000, 10, 8}, {5, 1, 122 * 17, 65 * 39, 3, 13, 67, 65},
+    };
+    for (const auto &s : wdg) {
+        const WdGridArena a = wd_grid_arena(s.chunk, s.n_pops, s.stride, s.tab_row, s.n_lines, s.n, s.n_col, s.n_col, 0, s.n_edges, sizeof(Hdr));
+        const size_t offs[] = {a.o_par, a.o_hdr, a.o_iso, a.o_tab, a.o_scratch, a.o_acc, a.o_pop, a.o_rank, a.o_edges, a.bytes};
+        const size_t sizes[] = {8 * B9_NPARAM * s.chunk, sizeof(Hdr) * s.chunk * s.n_pops, 8 * s.chunk * s.n_pops * (size_t)s.stride, 8 * s.chunk * s.tab_row,
+                                8 * s.chunk * s.n_lines * s.n_col, 8 * s.n_lines * s.n_col, 0, 4 * s.n, 8 * s.n_lines * s.n_edges};
+        CHECK(a.o_par == 0);
+        for (int k = 0; k < 9; ++k) {
+            CHECK(offs[k] % 8 == 0 && offs[k] % kArenaAlign == 0);
+            CHECK(offs[k] + sizes[k] <= offs[k + 1] && offs[k + 1] == offs[k] + up256(sizes[k]));      // disjoint, in order, no slack beyond the rounding
+            if (sizes[k] == 0) CHECK(offs[k] == offs[k + 1]);                                           // an empty part
+        }
+        CHECK(a.o_pop == a.o_rank);
+        const size_t moments = up256(sizes[0]) + up256(sizes[1]) + up256(sizes[2]) + up256(sizes[3]) + up256(sizes[4]) + up256(sizes[5]) + up256(sizes[7]);
+        CHECK(a.bytes == moments + up256(sizes[8]) && a.o_edges == moments);
+        if (s.n_edges == 0) CHECK(a.bytes == moments);
     }
     // the reductions over a saved chain: the four calls' shapes (moments; hist with row sums; resid with its three extra parts;
     // pointwise with flags and two tails), a call without WD-stage stars, and one without a tail or row sums.  Every part lies

@@ -6,7 +6,8 @@ a moved-from buffer frees nothing, nothing is live at the end, the upload list f
 buffers' and the tree buffers' groups hold what the sizing functions ask for after every step, the carve is ordered, disjoint
 and aligned -- the one arena of the four reductions over a saved chain (chain_arena) included: its parts do not overlap, lie
 on 8-byte boundaries, `bytes` is the end of the last part, and a call without WD-stage stars, row sums or a tail carves empty
-parts.
+parts; and the one arena of the three calls on a WD mass grid (wd_grid_arena) the same way, at the offsets and totals the draws,
+the moments and the bins had from an arena each.
 
 There is no GPU test of these paths on purpose: allocation failures are not provoked on a device, and the tree-buffer defect
 this header removed wrote out of bounds.  That defect as arithmetic -- the rule the tree buffers were sized by before:
