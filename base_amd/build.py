@@ -23,6 +23,10 @@ HIP_LIB = os.path.join(CSRC, "libbase9hip.so")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
              "-fno-fast-math", "-Wall", "-Wno-unused-function"]
+# b9_kernels.hip only: a wave starts with its kernel's first argument dwords already in SGPRs (gfx950 preloads up to 16);
+# k_mcmc_step's whole argument list is 8 (the block descriptor's pointer + the launch's own words).  Kernels whose first
+# argument is a by-value struct are untouched by it.
+KERNEL_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 
 
 def _newer(target: str, sources: List[str]) -> bool:
@@ -59,7 +63,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
         src, obj = so
         if not force and _newer(obj, [src] + hdrs):
             return
-        cmd = [HIPCC] + HIP_FLAGS + ["-c", "-o", obj, "-x", "hip", src]
+        cmd = [HIPCC] + HIP_FLAGS + (KERNEL_FLAGS if src.endswith("b9_kernels.hip") else []) + ["-c", "-o", obj, "-x", "hip", src]
         if verbose:
             cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
         _run(cmd)

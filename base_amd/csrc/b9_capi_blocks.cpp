@@ -14,14 +14,16 @@ using McmcSlot = b9_ctx::McmcSlot;
 
 // Fused block: one device allocation, laid out so that the block needs ONE upload and ONE download (each small pageable copy
 // costs 10-20 us of host time, a block used to make six + four of them):
-//   [cur0][lp0][chol][origin][decided][free, ids][n_acc][state 0] | [state 1][rows][lps][samples]
-//   upload   = cur0 .. state 0        (starting state, proposal factor, moment origin, RNG streams, cleared counters)
+//   [step descriptor][cur0][lp0][chol][origin][decided][free, ids][n_acc][state 0] | [state 1][rows][lps][samples]
+//   upload   = descriptor .. state 0  (k_mcmc_step's per-block descriptor -- whole 64-byte lines at the block's head --,
+//              starting state, proposal factor, moment origin, RNG streams, cleared counters)
 //   download = n_acc .. lps (.. samples when the caller wants the chain)   (acceptance count, both state parities,
 //              summary rows, log-posterior record, chain record)
 void layout_fused(BlockLayout &L, size_t W, size_t d, size_t)
 {
     const size_t n_state = W * B9_STATE_STRIDE;
-    L.o_cur0 = 0; L.o_lp0 = L.o_cur0 + W * B9_NPARAM; L.o_chol = L.o_lp0 + W; L.o_org = L.o_chol + d * d; L.o_dec = L.o_org + d;
+    L.o_desc = 0; L.o_cur0 = L.o_desc + B9_STEP_DESC_DOUBLES;
+    L.o_lp0 = L.o_cur0 + W * B9_NPARAM; L.o_chol = L.o_lp0 + W; L.o_org = L.o_chol + d * d; L.o_dec = L.o_org + d;
     L.o_int = L.o_dec + W; L.o_nacc = L.o_int + L.n_int; L.o_st[0] = L.o_nacc + 1; L.o_st[1] = L.o_st[0] + n_state;
     L.o_rows = L.o_st[1] + n_state; L.o_lps = L.o_rows + L.n_rows; L.o_samp = L.o_lps + L.n_lps; L.n_total = L.o_samp + L.n_samp;
 }
@@ -213,6 +215,25 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
     int *d_free = reinterpret_cast<int *>(dev + L.o_int), *d_ids = d_free + d;
     unsigned long long *d_nacc = reinterpret_cast<unsigned long long *>(dev + L.o_nacc);
     hipStream_t s = ctx->stream;
+    StepDev sd{};
+    sd.d = d; sd.n_walkers = W; sd.n_pops = n_pops;
+    sd.n_partial = marg ? mb.n_partial : partial_count(ctx, plan); sd.mass_cap = ctx->work.mass_cap; sd.heavy_parts = marg ? 0 : ctx->heavy_parts;
+    split_seed(blk->seed, &sd.k0, &sd.k1);
+    sd.partial_stride = marg ? mb.stride : partial_stride(ctx); sd.iso_stride = ctx->work.iso_stride;
+    sd.state = d_state; sd.partial = marg ? mb.partial : ctx->d_partial.get();
+    sd.cand_par = ctx->work.params.get(); sd.cand_hdr = ctx->work.hdr.get(); sd.cand_iso = ctx->work.iso.get();
+    sd.chol = d_chol; sd.free_idx = d_free; sd.walker_ids = d_ids;
+    sd.samples = L.n_samp ? dev + L.o_samp : nullptr; sd.lps = L.n_lps ? dev + L.o_lps : nullptr; sd.n_acc = d_nacc; sd.decided = d_decided;
+    sd.rows = nullptr; sd.row_origin = dev + L.o_org; sd.n_steps = S;
+    // (a parity's row: the hot waves' partials + one set of heavy-star partials per candidate)
+    if (2 * ((long long)sd.n_partial + sd.heavy_parts) > sd.partial_stride) return fail(ctx, B9_ERR_CAPACITY, "partial buffer too small for two parities");
+    // k_mcmc_step's descriptor of THIS block (views, block-constant step fields, the grid's cut), rebuilt for every block --
+    // priors, tuning or the catalogue may have changed since the slot's last one -- at the head of the upload: it reaches the
+    // device with the starting state, in k_mcmc_begin.  `desc` stays with the host to size the launches.
+    StepBlockDev desc{};                  // (k_marg_step keeps its by-value arguments: its block uploads zeros here)
+    const StepBlockDev *const d_desc = reinterpret_cast<const StepBlockDev *>(dev + L.o_desc);
+    if (!marg) b9k_mcmc_step_desc(&desc, ctx->pk, ctx->st, sd, ctx->pr, plan, ctx->heavy_parts, derive_parts, ctx->derive_order);
+    std::memcpy(stage + L.o_desc, &desc, sizeof desc);
     {
         std::memset(stage + L.o_cur0, 0, (n_cur + W) * 8);
         if (!f.cont) {
@@ -233,18 +254,6 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
         // block's final state in place of the starting state
         HIPCHK(ctx, b9k_mcmc_begin(f.mirror, dev, (int)L.o_st[1], f.prev_final, d_cur0, d_lp0, d_state, W, s));
     }
-    StepDev sd{};
-    sd.d = d; sd.n_walkers = W; sd.n_pops = n_pops;
-    sd.n_partial = marg ? mb.n_partial : partial_count(ctx, plan); sd.mass_cap = ctx->work.mass_cap; sd.heavy_parts = marg ? 0 : ctx->heavy_parts;
-    split_seed(blk->seed, &sd.k0, &sd.k1);
-    sd.partial_stride = marg ? mb.stride : partial_stride(ctx); sd.iso_stride = ctx->work.iso_stride;
-    sd.state = d_state; sd.partial = marg ? mb.partial : ctx->d_partial.get();
-    sd.cand_par = ctx->work.params.get(); sd.cand_hdr = ctx->work.hdr.get(); sd.cand_iso = ctx->work.iso.get();
-    sd.chol = d_chol; sd.free_idx = d_free; sd.walker_ids = d_ids;
-    sd.samples = L.n_samp ? dev + L.o_samp : nullptr; sd.lps = L.n_lps ? dev + L.o_lps : nullptr; sd.n_acc = d_nacc; sd.decided = d_decided;
-    sd.rows = nullptr; sd.row_origin = dev + L.o_org; sd.n_steps = S;
-    // (a parity's row: the hot waves' partials + one set of heavy-star partials per candidate)
-    if (2 * ((long long)sd.n_partial + sd.heavy_parts) > sd.partial_stride) return fail(ctx, B9_ERR_CAPACITY, "partial buffer too small for two parities");
     {   // D0: proposal of step 0 and its isochrones -> candidate 0 of parity 1 (K(t) has parity (t + 1) & 1)
         McmcDev mc{};
         mc.enabled = 1; mc.d = d; mc.n_walkers = W; mc.has_prev = 0; mc.pin = 0; mc.row = 0;
@@ -269,7 +278,7 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
             HIPCHK(ctx, b9k_marg_step(ctx->pk, ctx->st, sd, ctx->pr, mb.K, mb.Q, ctx->marg_prune, ctx->d_marg_tab.get(), ctx->d_marg_wd_tab.get(), mb.wd_stride,
                                       ctx->d_marg_shares.get(), ctx->n_cu, s));
         else
-            HIPCHK(ctx, b9k_mcmc_step(ctx->pk, ctx->st, sd, ctx->pr, plan, ctx->heavy_parts, derive_parts, ctx->derive_order, s));
+            HIPCHK(ctx, b9k_mcmc_step(desc, d_desc, sd, s));
         rc = bracket_after(ctx, s, tb, t == S - 1);
         if (rc) return rc;
     }

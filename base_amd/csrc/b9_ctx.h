@@ -44,6 +44,7 @@ struct BlockLayout {
     size_t o_nacc = 0;                                        // fused, two-launch: the accepted count (64 bits)
     size_t o_st[2] = {0, 0};                                  // fused, tree: the two parities' state rows
     size_t o_cur0 = 0, o_lp0 = 0, o_dec = 0;                  // fused: starting state as D0 reads it, decision words
+    size_t o_desc = 0;                                        // fused: the step kernel's per-block descriptor (StepBlockDev), 64-byte aligned
     size_t o_tab = 0;                                         // tree: step table
     size_t o_cur = 0, o_lp = 0;                               // two-launch: [cur] and [lp], two halves each
 };

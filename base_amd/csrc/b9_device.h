@@ -238,6 +238,29 @@ struct StepDev {
     double *host_rows;               // [W][B9_ROW_LEN(d)]
 };
 
+// How k_mcmc_step's grid is cut into roles (b9k_mcmc_step forms it from the block's plan; fixed for a block).
+struct StepGridDev {
+    int group_tiles, n_groups, groups_per_block, n_blocks;     // the hot role's canonical tile groups (B9Groups, b9_launch.h)
+    int front_blocks, hot_blocks;                              // [writers, derivation, heavy, pad to 8] | [hot] | trailing derivation
+    int heavy_parts, derive_parts, derive_first;
+};
+
+// Per-BLOCK descriptor of the fused step, in device memory: everything k_mcmc_step needs that is the same for every launch
+// of a block -- pack, catalogue and priors views, the block-constant fields of StepDev, the grid's cut.  A launch passes a
+// pointer to it and the five words that do change (set, has_prev, derive_next, row, step): 32 bytes of arguments instead
+// of 1.1 KB that the host wrote anew, into lines cold by construction, for every launch.  The descriptor's lines are
+// written once per block (with the block's upload, k_mcmc_begin) and stay in the L2s from launch to launch.  Each of a
+// context's two block slots owns one (BlockLayout::o_desc), so a block enqueued behind a running one touches none of
+// the running block's words.  sd's per-launch fields are zero here; k_mcmc_step fills them from its arguments.
+struct alignas(64) StepBlockDev {
+    DevPack pk;
+    DevStars st;
+    DevPriors pr;
+    StepDev sd;
+    StepGridDev grid;
+};
+#define B9_STEP_DESC_DOUBLES (sizeof(StepBlockDev) / 8)      // its slot at the head of a fused block (whole 64-byte lines)
+
 // Summary row of one walker over one block (b9_mcmc_block::rows; include/base9_hip.h documents the layout).
 #define B9_ROW_LP 0
 #define B9_ROW_POS 1                 // [1..12] position after the block

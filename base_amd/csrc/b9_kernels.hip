@@ -690,22 +690,37 @@ hipError_t b9k_mcmc_step_occupancy(const DevPack &pk, int n_pops, int mass_cap, 
     });
 }
 
-hipError_t b9k_mcmc_step(const DevPack &pk, const DevStars &st, const StepDev &sd, const DevPriors &pr,
-                         const B9Groups &gr, int heavy_parts, int derive_parts, int derive_order, hipStream_t stream)
+void b9k_mcmc_step_desc(StepBlockDev *desc, const DevPack &pk, const DevStars &st, const StepDev &sd, const DevPriors &pr,
+                        const B9Groups &gr, int heavy_parts, int derive_parts, int derive_order)
 {
-    return dispatch(pk.nfp, sd.n_pops, [&](auto nfp_c, auto npops_c) {
+    std::memset(desc, 0, sizeof *desc);         // (padding too: the image is copied whole)
+    desc->pk = pk; desc->st = st; desc->pr = pr; desc->sd = sd;
+    desc->sd.set = desc->sd.has_prev = desc->sd.derive_next = desc->sd.row = 0; desc->sd.step = 0;      // the launch's own words
+    desc->sd.rows = nullptr; desc->sd.host_state = nullptr; desc->sd.host_rows = nullptr;               // k_mcmc_finish's own
+    const int W = sd.n_walkers, NPOPS = sd.n_pops;
+    const int derive_first = derive_order >= 0 ? (derive_order == 1 ? 2 : 1) : 0;
+    const int n_derive = W * 2 * NPOPS * derive_parts;
+    StepGridDev &g = desc->grid;
+    g.group_tiles = gr.group_tiles; g.n_groups = gr.n_groups; g.groups_per_block = gr.groups_per_block; g.n_blocks = gr.n_blocks;
+    g.front_blocks = (W * heavy_parts + W + (derive_first ? n_derive : 0) + 7) / 8 * 8;     // heavy, writers, (derivation), pad
+    g.hot_blocks = 8 * ((gr.n_blocks * NPOPS + 7) / 8) * W;
+    g.heavy_parts = heavy_parts; g.derive_parts = derive_parts; g.derive_first = derive_first;
+}
+
+hipError_t b9k_mcmc_step(const StepBlockDev &desc, const StepBlockDev *d_desc, const StepDev &sd, hipStream_t stream)
+{
+    return dispatch(desc.pk.nfp, desc.sd.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        const auto k = mcmc_step_kernel<NFP, NPOPS>(pk, sd.mass_cap);
+        const auto k = mcmc_step_kernel<NFP, NPOPS>(desc.pk, desc.sd.mass_cap);
         if (k.err != hipSuccess) return k.err;
-        const int W = sd.n_walkers;
-        const int hot = 8 * ((gr.n_blocks * NPOPS + 7) / 8) * W;
-        const int derive_first = derive_order >= 0 ? (derive_order == 1 ? 2 : 1) : 0;
-        const int n_derive = W * 2 * NPOPS * derive_parts;
-        const int front = (W * heavy_parts + W + (derive_first ? n_derive : 0) + 7) / 8 * 8;     // heavy, writers, (derivation), pad
-        const int back = (!derive_first && sd.derive_next) ? n_derive : 0;
-        hipLaunchKernelGGL(k.kern, dim3(front + hot + back), dim3(256), k.lds, stream, pk, st, sd, pr, gr.group_tiles, gr.n_groups,
-                           gr.groups_per_block, gr.n_blocks, front, hot, heavy_parts, derive_parts, derive_first);
-        return hipGetLastError();
+        const StepGridDev &g = desc.grid;
+        const int back = (!g.derive_first && sd.derive_next) ? desc.sd.n_walkers * 2 * NPOPS * g.derive_parts : 0;
+        // (the kernel's first parameter is a reference into the constant address space: the argument list holds the descriptor's
+        //  device address, handed over here as the pointer it is)
+        int set = sd.set, has_prev = sd.has_prev, derive_next = sd.derive_next, row = sd.row;
+        unsigned long long step = sd.step;
+        void *args[] = {&d_desc, &set, &has_prev, &derive_next, &row, &step};
+        return hipLaunchKernel(reinterpret_cast<const void *>(k.kern), dim3(g.front_blocks + g.hot_blocks + back), dim3(256), args, k.lds, stream);
     });
 }
 

@@ -75,11 +75,15 @@ size_t b9k_marg_step_lds(int nfp, int mass_cap);
 // the most dynamic LDS k_marg_step may take and keep the star role's occupancy (7 workgroups per CU up to 8 filters, 4 with 16)
 #define B9_MSTEP_LDS_MAX(nfp) ((nfp) > 8 ? (size_t)30 * 1024 : (size_t)15 * 1024)
 
-// fused sampler step (given-mass mode): decision of step t-1 + stars of step t + candidates of step t+1
-// (tiles_per_block < 0: a workgroup's |tiles_per_block| tiles are strided n_groups apart instead of consecutive)
-hipError_t b9k_mcmc_step(const DevPack &pk, const DevStars &st, const StepDev &sd, const DevPriors &pr,
-                         const B9Groups &gr, int heavy_parts, int derive_parts,
-                         int derive_order /* >= 0: derivation workgroups lead the grid, < 0: they trail it */, hipStream_t stream);
+// fused sampler step (given-mass mode): decision of step t-1 + stars of step t + candidates of step t+1.
+// b9k_mcmc_step_desc: the HOST image of a block's descriptor (StepBlockDev, b9_device.h) from the views, sd's block-constant
+// fields and the plan; the caller puts it into device memory once per block (the block's upload).
+// b9k_mcmc_step: one launch -- desc: that image (sizes the grid), d_desc: its device copy, sd: the launch's own words
+// (set, has_prev, derive_next, row, step; nothing else of it is read).
+void b9k_mcmc_step_desc(StepBlockDev *desc, const DevPack &pk, const DevStars &st, const StepDev &sd, const DevPriors &pr,
+                        const B9Groups &gr, int heavy_parts, int derive_parts,
+                        int derive_order /* >= 0: derivation workgroups lead the grid, < 0: they trail it */);
+hipError_t b9k_mcmc_step(const StepBlockDev &desc, const StepBlockDev *d_desc, const StepDev &sd, hipStream_t stream);
 // resident workgroups per CU of k_mcmc_step's instantiation for this pack (occupancy query; no launch)
 hipError_t b9k_mcmc_step_occupancy(const DevPack &pk, int n_pops, int mass_cap, int *blocks_per_cu);
 // the block's opening: upload from the mapped host mirror (+ the previous block's final state when continuing), one launch

@@ -469,15 +469,37 @@ __device__ __forceinline__ int step_body(const DevPack &pk, const DevStars &st, 
     return role;
 }
 
+// The block descriptor (StepBlockDev, b9_device.h) as the kernel sees it: a REFERENCE parameter into the constant address space
+// -- for the compiler a pointer argument that is dereferenceable over the whole struct, which is exactly what a by-value struct
+// argument is.  The kernel's copy of it below is then never made: the compiler reads every field where a role uses it, straight
+// from the descriptor, by scalar loads into SGPRs it may hoist and repeat at will, indexes the arrays in place, and knows the
+// pointers it finds there for global ones -- the roles compile as they did with by-value arguments (same vector loads, same
+// registers, no scratch).  Measured on the way: a plain pointer parameter copied member by member leaves DevPack on the stack
+// (its arrays are indexed at run time: 416-472 B of scratch per lane); read in place through a plain pointer, every use
+// re-loads its field inside its branch and the table pointers turn generic (392 global loads -> 172 global + 260 flat).
+typedef const __attribute__((address_space(4))) StepBlockDev b9_cdesc;
+__device__ __forceinline__ void desc_copy(StepBlockDev &dst, b9_cdesc *src) { __builtin_memcpy(&dst, src, sizeof(StepBlockDev)); }
+
+// Arguments: the block's descriptor and the five words that change from launch to launch -- 8 dwords, which the hardware
+// hands a wave in SGPRs as it starts (kernel-argument preload, base_amd/build.py).  A role's first chain is: pointer in
+// SGPRs -> descriptor words from lines that earlier launches of the block left in the L2 -> its vector loads.
 template <int NFP, int NPOPS>
 __global__ __launch_bounds__(256, B9_K1_WAVES(NFP, NPOPS))
-void k_mcmc_step(DevPack pk, DevStars st, StepDev sd, DevPriors pr, int group_tiles, int n_groups, int groups_per_block, int n_blocks,
-                 int front_blocks, int hot_blocks, int heavy_parts, int derive_parts, int derive_first)
+void k_mcmc_step(b9_cdesc &blk, int set, int has_prev, int derive_next, int row, unsigned long long step)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     B9_GANTT_ENTER();
-    const int role = step_body<NFP, NPOPS>(pk, st, sd, pr, group_tiles, n_groups, groups_per_block, n_blocks, front_blocks, hot_blocks, heavy_parts, derive_parts, derive_first, smem);
-    B9_GANTT_EXIT(sd.step, role);
+    StepBlockDev B;
+    desc_copy(B, &blk);
+    const DevPack &pk = B.pk;
+    const DevStars &st = B.st;
+    const DevPriors &pr = B.pr;
+    const StepGridDev &g = B.grid;
+    StepDev sd = B.sd;
+    sd.set = set; sd.has_prev = has_prev; sd.derive_next = derive_next; sd.row = row; sd.step = step;
+    const int role = step_body<NFP, NPOPS>(pk, st, sd, pr, g.group_tiles, g.n_groups, g.groups_per_block, g.n_blocks, g.front_blocks, g.hot_blocks,
+                                           g.heavy_parts, g.derive_parts, g.derive_first, smem);
+    B9_GANTT_EXIT(step, role);
 }
 
 // Summary row of walker w over the block (the multi-GPU driver all-gathers these rows straight from HBM and pools

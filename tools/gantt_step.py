@@ -30,7 +30,7 @@ chol = np.diag([mcmc.DEFAULT_STEP[int(k)] for k in free]) * 0.3
 ids = np.arange(W, dtype=np.int32)
 for _ in range(3):
     eng.mcmc_run_block(start, lp, ids, free, chol, 7, 0, 200, record=False)      # warm clocks; the last 8 launches stay in the buffer
-NWG = 4096
+NWG = 8192                                           # B9_GANTT_WG (b9_diag.hip.h): the library copies the whole buffer out
 buf = np.zeros((8, NWG, 4), dtype=np.uint64)
 eng.lib.b9_debug_read_gantt.argtypes = [C.c_void_p]
 assert eng.lib.b9_debug_read_gantt(buf.ctypes.data) == 0

@@ -25,7 +25,7 @@ def main():
     flt = args[0] if args else ""
     src = os.path.join(b.CSRC, "b9_kernels.hip")
     asm = "/tmp/b9_kernel_resources.s"
-    cmd = [b.HIPCC] + b.HIP_FLAGS + extra + ["-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-S", "-o", asm, "-x", "hip", src]
+    cmd = [b.HIPCC] + b.HIP_FLAGS + b.KERNEL_FLAGS + extra + ["-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-S", "-o", asm, "-x", "hip", src]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode:
         sys.stderr.write(r.stderr)
