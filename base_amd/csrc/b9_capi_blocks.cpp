@@ -171,9 +171,9 @@ int close_block(b9_ctx *ctx, b9_mcmc_block *blk, const BlockFrame &f, int final_
  * The marginalised mode runs the same block with k_marg_step in K(t)'s place (b9_marg_step.hip.h: the candidates are node
  * tables, built inside the launch; no isochrone is materialised) and, for the block's first proposal, k_marg_table behind D0. */
 struct MargBlock {             // what the marginalised flavour adds to a fused block
-    int K = 1, Q = 1;
+    B9Marg mg{};                               // the grid; four candidate sets (two parities x two candidates) of node tables, WD tables and split shares
     double *partial = nullptr;                 // [W][stride]: two parities of (star chunks + WD-stage stars) partials
-    long long stride = 0, tab_doubles = 0, wd_stride = 0;
+    long long stride = 0, tab_doubles = 0, wd_doubles = 0;       // (the two tables' doubles per (walker, population))
     int n_partial = 0;
 };
 
@@ -187,17 +187,16 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
     StepPlan sp{};
     MargBlock mb;
     if (marg) {
-        mb.K = marg_grid(ctx).K; mb.Q = marg_grid(ctx).Q;
-        // four candidate sets (two parities x two candidates) of node tables, WD tables and split shares
-        int rc = ensure_marg_table(ctx, 4 * W, n_pops, mb.K, mb.Q);
+        int rc = ensure_marg_table(ctx, 4 * W, n_pops, marg_grid(ctx).K, marg_grid(ctx).Q);
         if (rc) return rc;
+        mb.mg = marg_tables(ctx);
         mb.n_partial = ctx->st.mg_pad / 64 + (ctx->st.n_wd + 3) / 4;
         mb.stride = 2 * (((long long)mb.n_partial + 7) & ~7ll);
         rc = ensure_capacity(ctx, W, n_pops, (size_t)std::max<long long>(mb.stride, partial_stride(ctx)) * W, false);
         if (rc) return rc;
         mb.partial = ctx->d_partial.get();
-        mb.tab_doubles = b9k_marg_table_doubles(ctx->pk.nfp, ctx->work.mass_cap, mb.K, mb.Q);
-        mb.wd_stride = (long long)W * n_pops * b9k_marg_wd_table_doubles(ctx->pk.nfp, mb.K);
+        mb.tab_doubles = b9k_marg_table_doubles(ctx->pk.nfp, ctx->work.mass_cap, mb.mg.K, mb.mg.Q);
+        mb.wd_doubles = b9k_marg_wd_table_doubles(ctx->pk.nfp, mb.mg.K);
     } else {
         sp = make_step_plan(ctx, W, n_pops);
     }
@@ -215,13 +214,14 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
     int *d_free = reinterpret_cast<int *>(dev + L.o_int), *d_ids = d_free + d;
     unsigned long long *d_nacc = reinterpret_cast<unsigned long long *>(dev + L.o_nacc);
     hipStream_t s = ctx->stream;
+    const B9IsoSet cand = buffer_set(ctx, 0);      // the work buffers from their start: the block's four candidate sets, W walkers each (cand_at)
     StepDev sd{};
     sd.d = d; sd.n_walkers = W; sd.n_pops = n_pops;
-    sd.n_partial = marg ? mb.n_partial : partial_count(ctx, plan); sd.mass_cap = ctx->work.mass_cap; sd.heavy_parts = marg ? 0 : ctx->heavy_parts;
+    sd.n_partial = marg ? mb.n_partial : partial_count(ctx, plan); sd.mass_cap = cand.mass_cap; sd.heavy_parts = marg ? 0 : ctx->heavy_parts;
     split_seed(blk->seed, &sd.k0, &sd.k1);
-    sd.partial_stride = marg ? mb.stride : partial_stride(ctx); sd.iso_stride = ctx->work.iso_stride;
+    sd.partial_stride = marg ? mb.stride : partial_stride(ctx); sd.iso_stride = cand.iso_stride;
     sd.state = d_state; sd.partial = marg ? mb.partial : ctx->d_partial.get();
-    sd.cand_par = ctx->work.params.get(); sd.cand_hdr = ctx->work.hdr.get(); sd.cand_iso = ctx->work.iso.get();
+    sd.cand_par = cand.params; sd.cand_hdr = cand.hdr; sd.cand_iso = cand.iso;
     sd.chol = d_chol; sd.free_idx = d_free; sd.walker_ids = d_ids;
     sd.samples = L.n_samp ? dev + L.o_samp : nullptr; sd.lps = L.n_lps ? dev + L.o_lps : nullptr; sd.n_acc = d_nacc; sd.decided = d_decided;
     sd.rows = nullptr; sd.row_origin = dev + L.o_org; sd.n_steps = S;
@@ -259,14 +259,15 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
         mc.enabled = 1; mc.d = d; mc.n_walkers = W; mc.has_prev = 0; mc.pin = 0; mc.row = 0;
         mc.cur = d_cur0; mc.lp_cur = d_lp0; mc.chol = d_chol; mc.free_idx = d_free; mc.walker_ids = d_ids;
         mc.k0 = sd.k0; mc.k1 = sd.k1; mc.step = (unsigned long long)blk->step0; mc.n_acc = d_nacc;
-        const size_t rows = (size_t)W * n_pops, c10 = 2;     // (parity 1, candidate 0)
-        HIPCHK(ctx, b9k_derive_iso(ctx->pk, sd.cand_par + c10 * W * B9_NPARAM, W, n_pops, sd.cand_hdr + c10 * rows,
-                                   sd.cand_iso + c10 * rows * ctx->work.iso_stride, ctx->work.iso_stride, ctx->work.mass_cap,
-                                   mc, ctx->pr, no_prev(), s));
-        if (marg)       // ... and its node tables (every later candidate's are built inside k_marg_step)
-            HIPCHK(ctx, b9k_marg_tables(ctx->pk, sd.cand_hdr + c10 * rows, sd.cand_iso + c10 * rows * ctx->work.iso_stride, ctx->work.iso_stride, ctx->work.mass_cap,
-                                        sd.cand_par + c10 * W * B9_NPARAM, W, n_pops, mb.K, mb.Q, ctx->d_marg_tab.get() + c10 * rows * mb.tab_doubles,
-                                        ctx->st.n_wd > 0 ? ctx->d_marg_wd_tab.get() + c10 * mb.wd_stride : nullptr, s));
+        const CandAt c10 = cand_at(1, 0, W, n_pops);
+        const B9IsoSet first = cand.at(c10.row);
+        HIPCHK(ctx, b9k_derive_iso(ctx->pk, first, W, mc, ctx->pr, no_prev(), s));
+        if (marg) {     // ... and its node tables (every later candidate's are built inside k_marg_step)
+            B9Marg mg = mb.mg;
+            mg.tab += c10.wp * mb.tab_doubles;
+            mg.wd_tab = ctx->st.n_wd > 0 ? mg.wd_tab + c10.wp * mb.wd_doubles : nullptr;
+            HIPCHK(ctx, b9k_marg_tables(ctx->pk, first, W, mg, s));
+        }
     }
     TimingBracket tb;
     for (int t = 0; t < S; ++t) {
@@ -275,8 +276,7 @@ int run_block_fused(b9_ctx *ctx, b9_mcmc_block *blk, bool marg)
         rc = bracket_before(ctx, s, tb);
         if (rc) return rc;
         if (marg)
-            HIPCHK(ctx, b9k_marg_step(ctx->pk, ctx->st, sd, ctx->pr, mb.K, mb.Q, ctx->marg_prune, ctx->d_marg_tab.get(), ctx->d_marg_wd_tab.get(), mb.wd_stride,
-                                      ctx->d_marg_shares.get(), ctx->n_cu, s));
+            HIPCHK(ctx, b9k_marg_step(ctx->pk, ctx->st, sd, ctx->pr, mb.mg, ctx->n_cu, s));
         else
             HIPCHK(ctx, b9k_mcmc_step(desc, d_desc, sd, s));
         rc = bracket_after(ctx, s, tb, t == S - 1);
@@ -325,14 +325,15 @@ int run_block_tree(b9_ctx *ctx, b9_mcmc_block *blk, const TreePlan &tp)
                 }
         HIPCHK(ctx, b9k_tree_begin(f.mirror, dev, (int)L.o_rows, f.prev_final, dev + L.o_st[0], W, s));
     }
+    const B9IsoSet cand{ctx->tree.par.get(), ctx->tree.hdr.get(), ctx->tree.iso.get(), ctx->work.iso_stride, ctx->work.mass_cap, n_pops};     // every candidate of the tree
     TreeDev td{};
-    td.d = d; td.n_walkers = W; td.n_pops = n_pops; td.depth = depth;
-    td.n_groups = tp.n_groups; td.heavy_parts = ctx->heavy_parts; td.mass_cap = ctx->work.mass_cap;
+    td.d = d; td.n_walkers = W; td.n_pops = cand.n_pops; td.depth = depth;
+    td.n_groups = tp.n_groups; td.heavy_parts = ctx->heavy_parts; td.mass_cap = cand.mass_cap;
     td.part_stride = (int)tree_part_stride(tp.n_groups, ctx->heavy_parts);
     split_seed(blk->seed, &td.k0, &td.k1);
-    td.iso_stride = ctx->work.iso_stride;
+    td.iso_stride = cand.iso_stride;
     td.state = dev + L.o_st[0]; td.partial = ctx->tree.partial.get();
-    td.cand_par = ctx->tree.par.get(); td.cand_hdr = ctx->tree.hdr.get(); td.cand_iso = ctx->tree.iso.get();
+    td.cand_par = cand.params; td.cand_hdr = cand.hdr; td.cand_iso = cand.iso;
     td.chol = dev + L.o_chol; td.free_idx = reinterpret_cast<int *>(dev + L.o_int); td.walker_ids = td.free_idx + d;
     td.samples = L.n_samp ? dev + L.o_samp : nullptr; td.lps = L.n_lps ? dev + L.o_lps : nullptr;
     td.row_origin = dev + L.o_org; td.n_steps = S;
@@ -383,7 +384,7 @@ int run_block_tree(b9_ctx *ctx, b9_mcmc_block *blk, const TreePlan &tp)
  * speed; it gives a multi-GPU driver ONE way to run blocks and to read rows, whatever the evaluation mode. */
 int run_block_two_launch(b9_ctx *ctx, b9_mcmc_block *blk, const B9Groups &plan)
 {
-    const int W = blk->n_walkers, d = blk->n_free, S = blk->n_steps, n_pops = ctx->opt.n_pops;
+    const int W = blk->n_walkers, d = blk->n_free, S = blk->n_steps;
     BlockFrame f;
     int rc = open_block(ctx, blk, BlockKind::TwoLaunch, layout_two_launch, &f);
     if (rc) return rc;
@@ -411,28 +412,25 @@ int run_block_two_launch(b9_ctx *ctx, b9_mcmc_block *blk, const B9Groups &plan)
     mc.samples = L.n_samp ? dev + L.o_samp : nullptr; mc.lps = L.n_lps ? dev + L.o_lps : nullptr;
     mc.n_acc = reinterpret_cast<unsigned long long *>(dev + L.o_nacc);
     split_seed(blk->seed, &mc.k0, &mc.k1);
-    const int n_part = partial_count(ctx, plan);
+    const B9Partial part = partials(ctx, plan);
     for (int t = 0; t < S; ++t) {
-        const Bufs bf = buffer_set(ctx, t & 1), bp = buffer_set(ctx, (t & 1) ^ 1);
+        const B9IsoSet bf = buffer_set(ctx, t & 1);
         mc.step = (unsigned long long)(blk->step0 + t);     // the step being proposed
         mc.has_prev = t > 0;
         mc.pin = t > 0 ? (t - 1) & 1 : 0;                   // state half on entry
         mc.row = t - 1;                                     // chain row of the step being finished
-        const B9Prev prev{ctx->d_partial.get(), n_part, partial_stride(ctx), bp.hdr, bp.params};
-        HIPCHK(ctx, b9k_derive_iso(ctx->pk, bf.params, W, n_pops, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap,
-                                   mc, ctx->pr, prev, s));
+        HIPCHK(ctx, b9k_derive_iso(ctx->pk, bf, W, mc, ctx->pr, B9Prev{part, buffer_set(ctx, (t & 1) ^ 1)}, s));
         rc = launch_stars(ctx, bf, W, nullptr, plan, s);
         if (rc) return rc;
     }
     {   // finish the last step
-        const Bufs bf = buffer_set(ctx, (S - 1) & 1);
+        const B9IsoSet bf = buffer_set(ctx, (S - 1) & 1);
         mc.step = (unsigned long long)(blk->step0 + S - 1);
         mc.has_prev = 0;
         mc.pin = S > 1 ? (S - 2) & 1 : 0;                   // the half D(S-1) wrote (or the initial half)
         if (S > 1) mc.pin ^= 1;
         mc.row = S - 1;
-        HIPCHK(ctx, b9k_finalize(bf.hdr, ctx->d_partial.get(), n_part, partial_stride(ctx), n_pops, bf.params, ctx->pr, W,
-                                 ctx->work.logpost.get(), nullptr, ctx->st.n, mc, s));
+        HIPCHK(ctx, b9k_finalize(bf, part, ctx->pr, W, ctx->work.logpost.get(), nullptr, ctx->st.n, mc, s));
     }
     const int fin = mc.pin ^ 1;                             // half that holds the final state
     if (f.want_rows) {

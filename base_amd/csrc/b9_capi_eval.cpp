@@ -4,7 +4,10 @@
 // (b9_star_moments), the binned mass posteriors (b9_mass_hist), the per-star bins (b9_star_bins), the posterior-predictive
 // residuals (b9_phot_resid) and the pointwise predictive densities (b9_pointwise) --; and the three calls on a WD mass grid of the
 // caller's own size through wd_grid_reduce -- the WD-stage stars' posterior draws (b9_sample_wd_mass), their exact posterior
-// moments (b9_wd_moments) and their per-line bins (b9_wd_bins).
+// moments (b9_wd_moments) and their per-line bins (b9_wd_bins).  Every launch wrapper takes its derived isochrone set as one
+// view (B9IsoSet, b9_launch.h): buffer_set hands out the context's, b9_predict_mags and the two drivers build theirs where they
+// carve their buffers.  A driver fills what its call works on once (ChainDev : B9Chain, WdGridDev : B9WdGrid) and a body hands
+// it to its wrapper whole, with the chunk's row count and the call's own few arguments.
 #include "b9_ctx.h"
 #include <algorithm>
 #include <cmath>
@@ -17,12 +20,19 @@ using namespace b9i;
 
 namespace b9i {
 
-// ping-pong work-buffer set (0 / 1)
-Bufs buffer_set(const b9_ctx *ctx, int set)
+// ping-pong work-buffer set (0 / 1) of the context's populations: the sets lie cap_walkers rows of cap_pops populations apart
+B9IsoSet buffer_set(const b9_ctx *ctx, int set)
 {
-    const size_t rows = (size_t)ctx->work.cap_walkers * ctx->work.cap_pops;
-    return Bufs{ctx->work.params.get() + (size_t)set * ctx->work.cap_walkers * B9_NPARAM, ctx->work.hdr.get() + (size_t)set * rows,
-                ctx->work.iso.get() + (size_t)set * rows * ctx->work.iso_stride};
+    const B9IsoSet all{ctx->work.params.get(), ctx->work.hdr.get(), ctx->work.iso.get(), ctx->work.iso_stride, ctx->work.mass_cap, ctx->work.cap_pops};
+    B9IsoSet s = all.at((size_t)set * ctx->work.cap_walkers);
+    s.n_pops = ctx->opt.n_pops;
+    return s;
+}
+
+// the context's marginalisation grid and node tables (ensure_marg_table)
+B9Marg marg_tables(const b9_ctx *ctx)
+{
+    return B9Marg{marg_grid(ctx).K, marg_grid(ctx).Q, ctx->marg_prune, ctx->d_marg_tab.get(), ctx->d_marg_wd_tab.get(), ctx->d_marg_shares.get()};
 }
 
 // number of partial sums one walker gets from the star kernel under the current plan / mode
@@ -35,24 +45,23 @@ int partial_count(const b9_ctx *ctx, const B9Groups &plan)
 // doubles between two walkers' partial rows (room for either mode's row)
 long long partial_stride(const b9_ctx *ctx) { return (long long)ctx->st.n_pad + ctx->st.n_pad / 64; }
 
+// the context's partial sums under the current plan / mode (after ensure_capacity)
+B9Partial partials(const b9_ctx *ctx, const B9Groups &plan) { return B9Partial{ctx->d_partial.get(), partial_count(ctx, plan), partial_stride(ctx)}; }
+
 // The star-likelihood launch (given-mass: hot + heavy workgroups; marginalised: one wave per star)
 // on buffer set `set`, bracketed by timing events when sampled.
-int launch_stars(b9_ctx *ctx, const Bufs &bf, int32_t n_walkers, double *d_perstar, const B9Groups &plan,
+int launch_stars(b9_ctx *ctx, const B9IsoSet &bf, int32_t n_walkers, double *d_perstar, const B9Groups &plan,
                         hipStream_t stream)
 {
-    const int n_pops = ctx->opt.n_pops;
     TimingBracket tb;
     int rc = bracket_before(ctx, stream, tb);
     if (rc) return rc;
     if (ctx->opt.mode == B9_MODE_MARGINALISED) {
-        const int K = marg_grid(ctx).K, Q = marg_grid(ctx).Q;
-        rc = ensure_marg_table(ctx, n_walkers, n_pops, K, Q);
+        rc = ensure_marg_table(ctx, n_walkers, bf.n_pops, marg_grid(ctx).K, marg_grid(ctx).Q);
         if (rc) return rc;
-        HIPCHK(ctx, b9k_star_marg(ctx->pk, ctx->st, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap, bf.params,
-                                  n_walkers, n_pops, ctx->d_partial.get(), partial_stride(ctx), d_perstar, K, Q, nullptr, ctx->marg_prune, ctx->d_marg_tab.get(), ctx->d_marg_wd_tab.get(), ctx->d_marg_shares.get(), ctx->n_cu, stream));
+        HIPCHK(ctx, b9k_star_marg(ctx->pk, ctx->st, bf, n_walkers, partials(ctx, plan), d_perstar, marg_tables(ctx), nullptr, ctx->n_cu, stream));
     } else {
-        HIPCHK(ctx, b9k_star_like(ctx->pk, ctx->st, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap, bf.params,
-                                  n_walkers, n_pops, ctx->d_partial.get(), partial_stride(ctx), d_perstar, plan, ctx->heavy_parts, stream));
+        HIPCHK(ctx, b9k_star_like(ctx->pk, ctx->st, bf, n_walkers, partials(ctx, plan), d_perstar, plan, ctx->heavy_parts, stream));
     }
     return bracket_after(ctx, stream, tb, true);
 }
@@ -73,19 +82,16 @@ int launch_logpost(b9_ctx *ctx, double *d_params, int32_t n_walkers, double *d_l
     int rc = ensure_capacity(ctx, n_walkers, n_pops, (size_t)partial_stride(ctx) * n_walkers, false);
     if (rc) return rc;
     const B9Groups plan = make_plan(ctx, n_walkers, n_pops);
-    Bufs bf = buffer_set(ctx, 0);
+    B9IsoSet bf = buffer_set(ctx, 0);
     bf.params = d_params;
     const McmcDev off{};
     if (host_rows)      // <= 8 rows travel in the kernel arguments: no upload
-        HIPCHK(ctx, b9k_derive_iso_rows(ctx->pk, host_rows, bf.params, n_walkers, n_pops, bf.hdr, bf.iso, ctx->work.iso_stride,
-                                        ctx->work.mass_cap, stream));
+        HIPCHK(ctx, b9k_derive_iso_rows(ctx->pk, host_rows, bf, n_walkers, stream));
     else
-        HIPCHK(ctx, b9k_derive_iso(ctx->pk, bf.params, n_walkers, n_pops, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap,
-                                   off, ctx->pr, no_prev(), stream));
+        HIPCHK(ctx, b9k_derive_iso(ctx->pk, bf, n_walkers, off, ctx->pr, no_prev(), stream));
     rc = launch_stars(ctx, bf, n_walkers, d_perstar, plan, stream);
     if (rc) return rc;
-    HIPCHK(ctx, b9k_finalize(bf.hdr, ctx->d_partial.get(), partial_count(ctx, plan), partial_stride(ctx), n_pops, bf.params, ctx->pr,
-                             n_walkers, d_logpost, d_perstar, ctx->st.n, off, stream, done_flag, done_seq));
+    HIPCHK(ctx, b9k_finalize(bf, partials(ctx, plan), ctx->pr, n_walkers, d_logpost, d_perstar, ctx->st.n, off, stream, done_flag, done_seq));
     return B9_OK;
 }
 
@@ -179,19 +185,19 @@ int b9_sample_mass(b9_ctx *ctx, const double *params, int32_t n_rows, uint64_t s
     double *const d_out = out.get();
     int *const d_pop = pop.get();
     hipStream_t s = ctx->stream;
-    const Bufs bf = buffer_set(ctx, 0);
+    const B9IsoSet bf = buffer_set(ctx, 0);
+    const B9Partial part{ctx->d_partial.get(), 0, partial_stride(ctx)};
     const McmcDev off{};
     for (int r0 = 0; r0 < n_rows; r0 += chunk) {
         const int m = std::min(chunk, n_rows - r0);
         HIPCHK(ctx, hipMemcpyAsync(bf.params, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
         HIPCHK(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * per * 3, s));     // rows outside the grid write nothing
         if (d_pop) HIPCHK(ctx, hipMemsetAsync(d_pop, 0, sizeof(int) * per, s));
-        HIPCHK(ctx, b9k_derive_iso(ctx->pk, bf.params, m, n_pops, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap, off, ctx->pr, no_prev(), s));
+        HIPCHK(ctx, b9k_derive_iso(ctx->pk, bf, m, off, ctx->pr, no_prev(), s));
         B9MargSample smp{d_out, d_out + per, d_out + 2 * per, d_pop, 0, 0, (long long)(row0 + r0)};
         split_seed(seed, &smp.k0, &smp.k1);
         // the kernel indexes its outputs [row][n_stars] with the launch's own row count: rows are contiguous for any m
-        HIPCHK(ctx, b9k_star_marg(ctx->pk, ctx->st, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap, bf.params, m, n_pops,
-                                  ctx->d_partial.get(), partial_stride(ctx), nullptr, K, Q, &smp, ctx->marg_prune, ctx->d_marg_tab.get(), ctx->d_marg_wd_tab.get(), ctx->d_marg_shares.get(), ctx->n_cu, s));
+        HIPCHK(ctx, b9k_star_marg(ctx->pk, ctx->st, bf, m, part, nullptr, marg_tables(ctx), &smp, ctx->n_cu, s));
         const size_t cnt = (size_t)m * n, o = (size_t)r0 * n;
         HIPCHK(ctx, hipMemcpyAsync(out_mass + o, d_out, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipMemcpyAsync(out_ratio + o, d_out + per, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
@@ -215,7 +221,9 @@ int b9_derive_isochrone(b9_ctx *ctx, const double *param_row, int32_t pop, int32
     std::memcpy(row, param_row, sizeof row);
     if (pop) row[B9_P_Y] = row[B9_P_Y2];
     HIPCHK(ctx, hipMemcpyAsync(ctx->work.params.get(), row, sizeof row, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, b9k_derive_iso(ctx->pk, ctx->work.params.get(), 1, 1, ctx->work.hdr.get(), ctx->work.iso.get(), ctx->work.iso_stride, ctx->work.mass_cap, McmcDev{}, ctx->pr, no_prev(), ctx->stream));
+    B9IsoSet one = buffer_set(ctx, 0);
+    one.n_pops = 1;
+    HIPCHK(ctx, b9k_derive_iso(ctx->pk, one, 1, McmcDev{}, ctx->pr, no_prev(), ctx->stream));
     IsoHdr h;
     HIPCHK(ctx, hipMemcpyAsync(&h, ctx->work.hdr.get(), sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -247,13 +255,15 @@ int b9_predict_mags(b9_ctx *ctx, const double *param_row, int64_t n, const doubl
     if (n == 0) return B9_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const DevPack &pk = ctx->pk;
-    const int nf = pk.nf, mass_cap = pack_mass_cap(pk.max_eep);
-    const long long iso_stride = pack_iso_stride(mass_cap, pk.nfp);
-    if (b9k_predict_lds(pk.nfp, mass_cap, n_pops) > 160 * 1024)
+    const int nf = pk.nf;
+    B9IsoSet set{nullptr, nullptr, nullptr, 0, pack_mass_cap(pk.max_eep), n_pops};
+    set.iso_stride = pack_iso_stride(set.mass_cap, pk.nfp);
+    if (b9k_predict_lds(pk.nfp, set.mass_cap, n_pops) > 160 * 1024)
         return fail(ctx, B9_ERR_CAPACITY, "b9_predict_mags: the derived isochrones do not fit the kernel's LDS");
     RESERVE(ctx, ctx->d_pred_hdr, 2);
     RESERVE(ctx, ctx->d_pred_par, B9_NPARAM);
-    RESERVE(ctx, ctx->d_pred_iso, (size_t)(2 * iso_stride));
+    RESERVE(ctx, ctx->d_pred_iso, (size_t)(2 * set.iso_stride));
+    set.params = ctx->d_pred_par.get(); set.hdr = ctx->d_pred_hdr.get(); set.iso = ctx->d_pred_iso.get();
     // systems in chunks of at most 2^20 (every system's result depends on that system alone, so the chunking is invisible)
     const int64_t chunk = std::min<int64_t>(n, (int64_t)1 << 20);
     const PredArena a = pred_arena((size_t)chunk, nf);
@@ -262,15 +272,14 @@ int b9_predict_mags(b9_ctx *ctx, const double *param_row, int64_t n, const doubl
     double *d_m1 = part<double>(io, a.o_m1), *d_q = part<double>(io, a.o_q), *d_mags = part<double>(io, a.o_mags);
     int *d_wd = part<int>(io, a.o_wd), *d_pop = part<int>(io, a.o_pop), *d_stage = part<int>(io, a.o_stage);
     hipStream_t s = ctx->stream;
-    HIPCHK(ctx, b9k_derive_iso_rows(pk, param_row, ctx->d_pred_par.get(), 1, n_pops, ctx->d_pred_hdr.get(), ctx->d_pred_iso.get(), iso_stride, mass_cap, s));
+    HIPCHK(ctx, b9k_derive_iso_rows(pk, param_row, set, 1, s));
     for (int64_t i0 = 0; i0 < n; i0 += chunk) {
         const int64_t m = std::min(chunk, n - i0);
         HIPCHK(ctx, hipMemcpyAsync(d_m1, mass1 + i0, sizeof(double) * m, hipMemcpyHostToDevice, s));
         HIPCHK(ctx, hipMemcpyAsync(d_q, mass_ratio + i0, sizeof(double) * m, hipMemcpyHostToDevice, s));
         if (wd_type) HIPCHK(ctx, hipMemcpyAsync(d_wd, wd_type + i0, sizeof(int) * m, hipMemcpyHostToDevice, s));
         if (pop) HIPCHK(ctx, hipMemcpyAsync(d_pop, pop + i0, sizeof(int) * m, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, b9k_predict_mags(pk, ctx->d_pred_hdr.get(), ctx->d_pred_iso.get(), iso_stride, mass_cap, n_pops, ctx->d_pred_par.get(), m, d_m1, d_q,
-                                     wd_type ? d_wd : nullptr, pop ? d_pop : nullptr, d_mags, d_stage, 4 * ctx->n_cu, s));
+        HIPCHK(ctx, b9k_predict_mags(pk, set, m, d_m1, d_q, wd_type ? d_wd : nullptr, pop ? d_pop : nullptr, d_mags, d_stage, 4 * ctx->n_cu, s));
         HIPCHK(ctx, hipMemcpyAsync(out_mags + (size_t)i0 * nf, d_mags, sizeof(double) * m * nf, hipMemcpyDeviceToHost, s));
         if (out_stage) HIPCHK(ctx, hipMemcpyAsync(out_stage + i0, d_stage, sizeof(int) * m, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipStreamSynchronize(s));      // (the host arrays of the next chunk reuse the same device buffers)
@@ -300,13 +309,10 @@ struct ChainCall {
     double *acc, *rows;                  // host: the per-star accumulators [n_stars][n_acc], the per-row sums [n_rows][n_rowcol] (null: not asked for)
     size_t extra_bytes[kChainExtras];    // the call's own parts of the arena
 };
-// ... and what the call's hooks see: the arena's parts (acc / rows null when the caller did not ask for them; wd without WD-stage stars)
-struct ChainDev {
-    double *par, *iso, *tab, *wd, *scratch, *acc, *rows;
-    IsoHdr *hdr;
+// ... and what the call's hooks see: the arena's parts as the launch wrappers take them (B9Chain: acc / rows null when the caller
+// did not ask for them; mg.wd_tab without WD-stage stars) and the call's own
+struct ChainDev : B9Chain {
     char *extra[kChainExtras];
-    int n_pops, K, Q, mass_cap;
-    long long iso_stride;
 };
 using ChainHook = std::function<int(const ChainDev &)>;
 using ChainBody = std::function<hipError_t(const ChainDev &, int /* rows of the chunk */)>;
@@ -334,19 +340,21 @@ int chain_reduce(b9_ctx *ctx, const ChainCall &c, const double *params, int n_ro
     }
     const DevPack &pk = ctx->pk;
     ChainDev d{};
-    d.n_pops = ctx->opt.n_pops == 2 ? 2 : 1; d.K = marg_grid(ctx).K; d.Q = marg_grid(ctx).Q;
-    d.mass_cap = pack_mass_cap(pk.max_eep); d.iso_stride = pack_iso_stride(d.mass_cap, pk.nfp);
-    const size_t tab_row = (size_t)d.n_pops * (size_t)b9k_marg_table_doubles(pk.nfp, d.mass_cap, d.K, d.Q);
-    const size_t wd_row = ctx->st.n_wd > 0 ? (size_t)d.n_pops * (size_t)b9k_marg_wd_table_doubles(pk.nfp, d.K) : 0;
+    B9IsoSet &set = d.set;
+    B9Marg &mg = d.mg;
+    set.n_pops = ctx->opt.n_pops == 2 ? 2 : 1; mg.K = marg_grid(ctx).K; mg.Q = marg_grid(ctx).Q; mg.prune = ctx->marg_prune;
+    set.mass_cap = pack_mass_cap(pk.max_eep); set.iso_stride = pack_iso_stride(set.mass_cap, pk.nfp);
+    const size_t tab_row = (size_t)set.n_pops * (size_t)b9k_marg_table_doubles(pk.nfp, set.mass_cap, mg.K, mg.Q);
+    const size_t wd_row = ctx->st.n_wd > 0 ? (size_t)set.n_pops * (size_t)b9k_marg_wd_table_doubles(pk.nfp, mg.K) : 0;
     const size_t chunk = mom_chunk_rows((size_t)n_rows, (size_t)n, c.n_col, c.max_rows, c.scratch_bytes);
     if (chunk * (tab_row + wd_row) > ((size_t)8 << 30) / sizeof(double))
         return fail(ctx, B9_ERR_CAPACITY, std::string(c.name) + ": marginalisation grid too fine: the node tables would exceed 8 GiB");
-    const ChainArena a = chain_arena(chunk, d.n_pops, d.iso_stride, tab_row, wd_row, (size_t)n, c.n_col, c.n_acc, c.rows ? c.n_rowcol : 0, sizeof(IsoHdr),
+    const ChainArena a = chain_arena(chunk, set.n_pops, set.iso_stride, tab_row, wd_row, (size_t)n, c.n_col, c.n_acc, c.rows ? c.n_rowcol : 0, sizeof(IsoHdr),
                                      c.extra_bytes);
     RESERVE(ctx, ctx->d_chain, a.bytes);
     char *base = ctx->d_chain.get();
-    d.par = part<double>(base, a.o_par); d.hdr = part<IsoHdr>(base, a.o_hdr); d.iso = part<double>(base, a.o_iso); d.tab = part<double>(base, a.o_tab);
-    d.wd = wd_row ? part<double>(base, a.o_wd) : nullptr; d.scratch = part<double>(base, a.o_scratch);
+    set.params = part<double>(base, a.o_par); set.hdr = part<IsoHdr>(base, a.o_hdr); set.iso = part<double>(base, a.o_iso); mg.tab = part<double>(base, a.o_tab);
+    mg.wd_tab = wd_row ? part<double>(base, a.o_wd) : nullptr; d.scratch = part<double>(base, a.o_scratch);
     d.acc = c.acc ? part<double>(base, a.o_acc) : nullptr; d.rows = c.rows ? part<double>(base, a.o_rows) : nullptr;
     for (int k = 0; k < kChainExtras; ++k) d.extra[k] = base + a.o_extra[k];
     const size_t acc_bytes = sizeof(double) * (size_t)n * c.n_acc;
@@ -359,8 +367,8 @@ int chain_reduce(b9_ctx *ctx, const ChainCall &c, const double *params, int n_ro
     const McmcDev off{};
     for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
         const int m = std::min((int)chunk, n_rows - r0);
-        HIPCHK(ctx, hipMemcpyAsync(d.par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, b9k_derive_iso(pk, d.par, m, d.n_pops, d.hdr, d.iso, d.iso_stride, d.mass_cap, off, ctx->pr, no_prev(), s));
+        HIPCHK(ctx, hipMemcpyAsync(set.params, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, b9k_derive_iso(pk, set, m, off, ctx->pr, no_prev(), s));
         HIPCHK(ctx, body(d, m));
         if (d.rows) HIPCHK(ctx, hipMemcpyAsync(c.rows + (size_t)r0 * c.n_rowcol, d.rows, sizeof(double) * m * c.n_rowcol, hipMemcpyDeviceToHost, s));
     }
@@ -388,13 +396,11 @@ struct WdGridCall {
     bool cont;                           // the call's CONTINUE flag: acc comes in
     double *acc;                         // host: the accumulators [n_lines][n_acc]
 };
-// ... and what the call's hooks see: the arena's parts (acc / pop / edges null when the call has none)
-struct WdGridDev {
-    double *par, *iso, *tab, *scratch, *acc, *edges;
-    IsoHdr *hdr;
-    int *pop, *rank;
-    int n_wd, n_pops, mass_cap;
-    long long iso_stride;
+// ... and what the call's hooks see: the arena's parts as the launch wrappers take them (B9WdGrid: acc / edges null when the call
+// has none) and the driver's own
+struct WdGridDev : B9WdGrid {
+    int *pop;                            // the draws' populations (null when the call has none)
+    int n_wd;
     size_t per;                          // (row, WD-stage star) pairs of a whole chunk
 };
 using WdGridHook = std::function<int(const WdGridDev &)>;
@@ -411,20 +417,21 @@ int wd_grid_reduce(b9_ctx *ctx, const WdGridCall &c, const double *params, int n
     if (ctx->st.n_wd == 0) return B9_OK;
     const DevPack &pk = ctx->pk;
     WdGridDev d{};
-    d.n_wd = ctx->st.n_wd; d.n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
-    d.mass_cap = pack_mass_cap(pk.max_eep); d.iso_stride = pack_iso_stride(d.mass_cap, pk.nfp);
+    B9IsoSet &set = d.set;
+    d.n_wd = ctx->st.n_wd; d.n_nodes = n_nodes; set.n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
+    set.mass_cap = pack_mass_cap(pk.max_eep); set.iso_stride = pack_iso_stride(set.mass_cap, pk.nfp);
     const size_t n_lines = (size_t)d.n_wd * c.lines_per_wd;
-    const size_t tab_row = (size_t)d.n_pops * (size_t)b9k_wd_grid_table_doubles(pk.nfp, n_nodes, c.status);       // doubles per row
+    const size_t tab_row = (size_t)set.n_pops * (size_t)b9k_wd_grid_table_doubles(pk.nfp, n_nodes, c.status);       // doubles per row
     if (tab_row > ((size_t)8 << 30) / sizeof(double)) return fail(ctx, B9_ERR_CAPACITY, std::string(c.name) + ": one row's node table would exceed 8 GiB");
     size_t chunk = std::min<size_t>({(size_t)n_rows, (size_t)B9_WDS_MAX_ROWS, B9_WDS_TABLE_BYTES / (tab_row * sizeof(double))});
     if (c.scratch_bytes) chunk = std::min(chunk, c.scratch_bytes / (n_lines * c.n_col * sizeof(double)));
     chunk = std::max<size_t>(1, chunk);
     d.per = chunk * d.n_wd;
-    const WdGridArena a = wd_grid_arena(chunk, d.n_pops, d.iso_stride, tab_row, n_lines, (size_t)n, c.n_col, c.n_acc, c.pop ? (size_t)d.n_wd : 0, c.n_edges,
+    const WdGridArena a = wd_grid_arena(chunk, set.n_pops, set.iso_stride, tab_row, n_lines, (size_t)n, c.n_col, c.n_acc, c.pop ? (size_t)d.n_wd : 0, c.n_edges,
                                         sizeof(IsoHdr));
     RESERVE(ctx, ctx->d_wds, a.bytes);
     char *base = ctx->d_wds.get();
-    d.par = part<double>(base, a.o_par); d.hdr = part<IsoHdr>(base, a.o_hdr); d.iso = part<double>(base, a.o_iso); d.tab = part<double>(base, a.o_tab);
+    set.params = part<double>(base, a.o_par); set.hdr = part<IsoHdr>(base, a.o_hdr); set.iso = part<double>(base, a.o_iso); d.tab = part<double>(base, a.o_tab);
     d.scratch = part<double>(base, a.o_scratch); d.acc = c.acc ? part<double>(base, a.o_acc) : nullptr;
     d.pop = c.pop ? part<int>(base, a.o_pop) : nullptr; d.rank = part<int>(base, a.o_rank);
     d.edges = c.n_edges ? part<double>(base, a.o_edges) : nullptr;
@@ -441,8 +448,8 @@ int wd_grid_reduce(b9_ctx *ctx, const WdGridCall &c, const double *params, int n
     const McmcDev off{};
     for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
         const int m = std::min((int)chunk, n_rows - r0);
-        HIPCHK(ctx, hipMemcpyAsync(d.par, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, b9k_derive_iso(pk, d.par, m, d.n_pops, d.hdr, d.iso, d.iso_stride, d.mass_cap, off, ctx->pr, no_prev(), s));
+        HIPCHK(ctx, hipMemcpyAsync(set.params, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, b9k_derive_iso(pk, set, m, off, ctx->pr, no_prev(), s));
         HIPCHK(ctx, body(d, r0, m));
         if (after) { const int rc = after(d, r0, m); if (rc) return rc; }
     }
@@ -472,8 +479,7 @@ int b9_star_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t f
     if (const int rc = chain_ready(ctx)) return rc;
     const ChainCall c{"b9_star_moments", B9_MOM_N, B9_MOM_N, 0, B9_MOM_MAX_ROWS, B9_MOM_SCRATCH_BYTES, (flags & B9_MOM_CONTINUE) != 0, acc, nullptr, {}};
     return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
-        return b9k_star_moments(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, d.K, d.Q, ctx->marg_prune, d.tab, d.wd,
-                                d.scratch, d.acc, ctx->stream);
+        return b9k_star_moments(ctx->pk, ctx->st, d, m, ctx->stream);
     });
 }
 
@@ -490,8 +496,7 @@ int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quan
     const size_t ncol = (size_t)n_bins + 1;
     const ChainCall c{"b9_mass_hist", ncol, ncol, ncol, B9_HIST_MAX_ROWS, B9_HIST_SCRATCH_BYTES, (flags & B9_HIST_CONTINUE) != 0, star_hist, row_hist, {}};
     return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
-        return b9k_mass_hist(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, d.K, d.Q, ctx->marg_prune, quantity, edges, n_bins,
-                             d.tab, d.wd, d.scratch, d.acc, d.rows, ctx->stream);
+        return b9k_mass_hist(ctx->pk, ctx->st, d, m, quantity, edges, n_bins, ctx->stream);
     });
 }
 
@@ -511,8 +516,7 @@ int b9_star_bins(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quan
     const ChainCall c{"b9_star_bins", ncol, ncol, 0, B9_SBIN_MAX_ROWS, B9_SBIN_SCRATCH_BYTES, (flags & B9_SBIN_CONTINUE) != 0, acc, nullptr, {8 * n * ne, 0, 0}};
     auto d_edges = [](const ChainDev &d) { return reinterpret_cast<double *>(d.extra[0]); };
     return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
-        return b9k_star_bins(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, d.K, d.Q, ctx->marg_prune, quantity, d_edges(d), n_bins,
-                             d.tab, d.wd, d.scratch, d.acc, ctx->stream);
+        return b9k_star_bins(ctx->pk, ctx->st, d, m, quantity, d_edges(d), n_bins, ctx->stream);
     }, [&](const ChainDev &d) {
         HIPCHK(ctx, hipMemcpyAsync(d_edges(d), edges, sizeof(double) * n * ne, hipMemcpyHostToDevice, ctx->stream));
         return (int)B9_OK;
@@ -532,8 +536,7 @@ int b9_phot_resid(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t fla
     auto isig = [](const ChainDev &d) { return reinterpret_cast<double *>(d.extra[2]); };
     std::vector<double> piv, is;         // (the uploads' sources: they live until the driver has waited for the stream)
     return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
-        return b9k_phot_resid(pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, d.K, d.Q, ctx->marg_prune, piv_mg(d), isig(d),
-                              d.tab, d.wd, d.scratch, d.acc, d.rows, ctx->stream);
+        return b9k_phot_resid(pk, ctx->st, d, m, piv_mg(d), isig(d), ctx->stream);
     }, [&](const ChainDev &d) {
         // the pivots (the caller's obs bits where sigma > 0, else 0) and 1 / sigma (0: filter unused), the caller's star order
         const HostStars &h = ctx->hs;
@@ -564,8 +567,7 @@ int b9_pointwise(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flag
     auto d_tail = [&](const ChainDev &d) { return T ? reinterpret_cast<double *>(d.extra[1]) : nullptr; };
     auto d_tail_io = [](const ChainDev &d) { return reinterpret_cast<double *>(d.extra[2]); };
     return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
-        return b9k_pointwise(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, d.K, d.Q, ctx->marg_prune, d.tab, d.wd,
-                             d.scratch, reinterpret_cast<int *>(d.extra[0]), d.acc, d_tail(d), T, d.rows, ctx->stream);
+        return b9k_pointwise(ctx->pk, ctx->st, d, m, reinterpret_cast<int *>(d.extra[0]), d_tail(d), T, ctx->stream);
     }, [&](const ChainDev &d) {
         if (!T) return (int)B9_OK;
         if (cont) HIPCHK(ctx, hipMemcpyAsync(d_tail_io(d), tail, tail_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -597,10 +599,10 @@ int b9_sample_wd_mass(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t
         B9WdSample smp{};
         smp.zams = col(0); smp.member = col(1);
         smp.wd_mass = col(2); smp.prec_log_age = col(3); smp.log_cool_age = col(4); smp.log_teff = col(5); smp.logg = col(6);
-        smp.pop = d.pop; smp.wd_rank = d.rank;
+        smp.pop = d.pop;
         split_seed(seed, &smp.k0, &smp.k1); smp.row0 = (long long)(row0 + r0);
         // the kernel indexes its outputs [row][n_wd] with the launch's own rows: they are contiguous for any m
-        return b9k_wd_sample(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, n_nodes, d.tab, smp, s);
+        return b9k_wd_sample(ctx->pk, ctx->st, d, m, smp, s);
     }, nullptr, [&](const WdGridDev &d, int r0, int m) {
         const size_t cnt = (size_t)m * d.n_wd, o = (size_t)r0 * d.n_wd;
         for (int q = 0; q < 7; ++q)
@@ -618,7 +620,7 @@ int b9_wd_moments(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_n
     const WdGridCall c{"b9_wd_moments", true, 1, B9_WDM_N, B9_WDM_N, 0, false, 0, (flags & B9_WDM_CONTINUE) != 0, acc};
     // the star kernel writes every (row, WD-stage star) of the chunk, so nothing is cleared
     return wd_grid_reduce(ctx, c, params, n_rows, n_nodes, [&](const WdGridDev &d, int, int m) {
-        return b9k_wd_moments(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, n_nodes, d.tab, d.rank, d.scratch, d.acc, ctx->stream);
+        return b9k_wd_moments(ctx->pk, ctx->st, d, m, ctx->stream);
     });
 }
 
@@ -641,8 +643,7 @@ int b9_wd_bins(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_node
     const WdGridCall c{"b9_wd_bins", true, n_sel, ncol, ncol, B9_WBIN_SCRATCH_BYTES, false, ne, (flags & B9_WBIN_CONTINUE) != 0, acc};
     // the star kernel writes every (row, line) of the chunk, so nothing is cleared
     return wd_grid_reduce(ctx, c, params, n_rows, n_nodes, [&](const WdGridDev &d, int, int m) {
-        return b9k_wd_bins(ctx->pk, ctx->st, d.hdr, d.iso, d.iso_stride, d.mass_cap, d.par, m, d.n_pops, n_nodes, d.tab, d.rank, quantity_mask, d.edges, n_bins,
-                           d.scratch, d.acc, ctx->stream);
+        return b9k_wd_bins(ctx->pk, ctx->st, d, m, quantity_mask, n_bins, ctx->stream);
     }, [&](const WdGridDev &d) {
         HIPCHK(ctx, hipMemcpyAsync(d.edges, edges, sizeof(double) * n_lines * ne, hipMemcpyHostToDevice, ctx->stream));
         return (int)B9_OK;

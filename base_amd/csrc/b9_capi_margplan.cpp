@@ -51,17 +51,17 @@ void reference_row(const b9_ctx *ctx, double *row)
 int counting_pass(b9_ctx *ctx, const double *row, int K, int Q, std::vector<unsigned> &h_cost, bool &valid)
 {
     const int n_pops = ctx->opt.n_pops, n_mc = ctx->st.mg_pad / 64;
-    const Bufs bf = buffer_set(ctx, 0);
+    const B9IsoSet bf = buffer_set(ctx, 0);
+    const B9Marg mg{K, Q, ctx->marg_prune, ctx->d_marg_tab.get(), nullptr, nullptr};      // one row's node table alone
     std::vector<IsoHdr> h_hdr(n_pops);
     DeviceBuf<unsigned> cost;            // (of this call alone: released at return, before the host arrays it is copied into)
     RESERVE(ctx, cost, (size_t)4 * n_mc);
     unsigned *const d_cost = cost.get();
     hipStream_t s = ctx->stream;
     HIPCHK(ctx, hipMemsetAsync(d_cost, 0, sizeof(unsigned) * 4 * n_mc, s));
-    HIPCHK(ctx, b9k_derive_iso_rows(ctx->pk, row, bf.params, 1, n_pops, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap, s));
-    HIPCHK(ctx, b9k_marg_tables(ctx->pk, bf.hdr, bf.iso, ctx->work.iso_stride, ctx->work.mass_cap, bf.params, 1, n_pops, K, Q, ctx->d_marg_tab.get(), nullptr, s));
-    HIPCHK(ctx, b9k_star_marg_cost(ctx->pk, ctx->st, bf.hdr, ctx->work.mass_cap, bf.params, n_pops, ctx->d_partial.get(), partial_stride(ctx), K, Q,
-                                   ctx->marg_prune, ctx->d_marg_tab.get(), d_cost, s));
+    HIPCHK(ctx, b9k_derive_iso_rows(ctx->pk, row, bf, 1, s));
+    HIPCHK(ctx, b9k_marg_tables(ctx->pk, bf, 1, mg, s));
+    HIPCHK(ctx, b9k_star_marg_cost(ctx->pk, ctx->st, bf, B9Partial{ctx->d_partial.get(), 0, partial_stride(ctx)}, mg, d_cost, s));
     h_cost.assign(4 * (size_t)n_mc, 0u);
     HIPCHK(ctx, hipMemcpyAsync(h_cost.data(), d_cost, sizeof(unsigned) * h_cost.size(), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipMemcpyAsync(h_hdr.data(), bf.hdr, sizeof(IsoHdr) * n_pops, hipMemcpyDeviceToHost, s));

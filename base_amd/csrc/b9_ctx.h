@@ -232,7 +232,7 @@ inline MargGrid marg_grid(const b9_ctx *ctx)
     return MargGrid{ctx->opt.marg_iso_increm > 0 ? ctx->opt.marg_iso_increm : 1, ctx->opt.marg_n_q > 0 ? ctx->opt.marg_n_q : 1};
 }
 // k_derive_iso with no previous step to finish
-inline B9Prev no_prev() { return B9Prev{nullptr, 0, 0, nullptr, nullptr}; }
+inline B9Prev no_prev() { return B9Prev{}; }
 // a 64-bit seed as the RNG's two key words
 inline void split_seed(uint64_t seed, unsigned *k0, unsigned *k1) { *k0 = (unsigned)(seed & 0xFFFFFFFFull); *k1 = (unsigned)(seed >> 32); }
 
@@ -281,10 +281,11 @@ void apply_tuning(b9_ctx *ctx, const b9_tuning &t);
 bool tuning_from_env(b9_tuning *t);
 
 // ---- b9_capi_eval.cpp
-struct Bufs { double *params; IsoHdr *hdr; double *iso; };
-Bufs buffer_set(const b9_ctx *ctx, int set);
+B9IsoSet buffer_set(const b9_ctx *ctx, int set);
+B9Marg marg_tables(const b9_ctx *ctx);
 int partial_count(const b9_ctx *ctx, const B9Groups &plan);
 long long partial_stride(const b9_ctx *ctx);
-int launch_stars(b9_ctx *ctx, const Bufs &bf, int32_t n_walkers, double *d_perstar, const B9Groups &plan, hipStream_t stream);
+B9Partial partials(const b9_ctx *ctx, const B9Groups &plan);
+int launch_stars(b9_ctx *ctx, const B9IsoSet &bf, int32_t n_walkers, double *d_perstar, const B9Groups &plan, hipStream_t stream);
 
 }  // namespace b9i

@@ -145,6 +145,17 @@ inline size_t mom_chunk_rows(size_t n_rows, size_t n_stars, size_t n_mom, size_t
 inline int pack_mass_cap(int max_eep) { return (max_eep + 1) & ~1; }
 inline long long pack_iso_stride(int mass_cap, int nfp) { return (long long)mass_cap * (nfp + 1); }
 
+// A fused block keeps four candidate sets of W walkers in the work buffers, [2 parities][2 candidates] (StepDev), and the
+// marginalised one its node tables alike.  Where candidate `cand` of parity `parity` starts: `row`, its first walker (parameter
+// rows; the set's sub-set, B9IsoSet::at), and `wp`, its first (walker, population): headers, isochrones and node tables, each
+// times its own length per (walker, population).
+struct CandAt { size_t row, wp; };
+inline CandAt cand_at(int parity, int cand, int W, int n_pops)
+{
+    const size_t c = (size_t)parity * 2 + cand;
+    return CandAt{c * W, c * W * n_pops};
+}
+
 // The work buffers, in elements.  FOUR sets of each: the two-launch sampler (marginalised mode) ping-pongs between sets 0 and
 // 1; the fused sampler step (given-mass mode) keeps two candidates for each of two step parities (StepDev).
 struct WorkNeed { size_t hdr, iso, params, logpost; };

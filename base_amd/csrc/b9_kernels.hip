@@ -58,6 +58,7 @@
 // stamps), B9_ABL_* (ablation builds used for the attribution in docs/LABNOTES.md section 8).
 #include "b9_device.h"
 #include "b9_launch.h"
+#include "b9_devbuf.h"
 #include <algorithm>
 #include <cstring>
 #include "../../include/base9_hip.h"
@@ -157,26 +158,24 @@ static hipError_t dispatch(int nfp, int n_pops, F &&f)
     return dispatch_nfp(nfp, [&](auto nfp_c) { return n_pops == 2 ? f(nfp_c, Int<2>{}) : f(nfp_c, Int<1>{}); });
 }
 
-hipError_t b9k_derive_iso(const DevPack &pk, double *d_params, int n_walkers, int n_pops,
-                          IsoHdr *hdr, double *iso_data, long long iso_stride, int mass_cap,
-                          const McmcDev &mc, const DevPriors &pr, const B9Prev &prev, hipStream_t stream)
+hipError_t b9k_derive_iso(const DevPack &pk, const B9IsoSet &set, int n_walkers, const McmcDev &mc, const DevPriors &pr, const B9Prev &prev,
+                          hipStream_t stream)
 {
-    const int gy = (mass_cap * (pk.nfp + 1) + 255) / 256;
-    hipLaunchKernelGGL(k_derive_iso, dim3(n_walkers * n_pops, gy), dim3(256), 0, stream,
-                       pk, d_params, n_pops, hdr, iso_data, iso_stride, mass_cap, mc, pr,
-                       prev.partial, prev.n_partial, prev.partial_stride, prev.hdr, prev.params);
+    const int gy = (set.mass_cap * (pk.nfp + 1) + 255) / 256;
+    hipLaunchKernelGGL(k_derive_iso, dim3(n_walkers * set.n_pops, gy), dim3(256), 0, stream,
+                       pk, set.params, set.n_pops, set.hdr, set.iso, set.iso_stride, set.mass_cap, mc, pr,
+                       prev.partial.ptr, prev.partial.n, prev.partial.stride, prev.set.hdr, prev.set.params);
     return hipGetLastError();
 }
 
-hipError_t b9k_derive_iso_rows(const DevPack &pk, const double *host_rows, double *d_params, int n_walkers, int n_pops,
-                               IsoHdr *hdr, double *iso_data, long long iso_stride, int mass_cap, hipStream_t stream)
+hipError_t b9k_derive_iso_rows(const DevPack &pk, const double *host_rows, const B9IsoSet &set, int n_walkers, hipStream_t stream)
 {
     if (n_walkers < 1 || n_walkers > 8) return hipErrorInvalidValue;
     HostRows rows{};
     std::memcpy(rows.v, host_rows, sizeof(double) * B9_NPARAM * n_walkers);
-    const int gy = (mass_cap * (pk.nfp + 1) + 255) / 256;
-    hipLaunchKernelGGL(k_derive_iso_rows, dim3(n_walkers * n_pops, gy), dim3(256), 0, stream,
-                       pk, rows, d_params, n_pops, hdr, iso_data, iso_stride, mass_cap);
+    const int gy = (set.mass_cap * (pk.nfp + 1) + 255) / 256;
+    hipLaunchKernelGGL(k_derive_iso_rows, dim3(n_walkers * set.n_pops, gy), dim3(256), 0, stream,
+                       pk, rows, set.params, set.n_pops, set.hdr, set.iso, set.iso_stride, set.mass_cap);
     return hipGetLastError();
 }
 
@@ -192,50 +191,51 @@ static size_t heavy_lds_doubles(const DevPack &pk, int n_pops, int n_cand, int m
     return 8 + (size_t)pk.hc_len + tips + (size_t)n_pops * n_cand * mass_cap + (size_t)n_cand * B9_NPARAM + 8;
 }
 
-hipError_t b9k_star_like(const DevPack &pk, const DevStars &st, const IsoHdr *hdr,
-                         const double *iso_data, long long iso_stride, int mass_cap,
-                         const double *d_params, int n_walkers, int n_pops,
-                         double *partial, long long partial_stride, double *perstar, const B9Groups &gr,
-                         int heavy_parts, hipStream_t stream)
+hipError_t b9k_star_like(const DevPack &pk, const DevStars &st, const B9IsoSet &set, int n_walkers, const B9Partial &partial, double *perstar,
+                         const B9Groups &gr, int heavy_parts, hipStream_t stream)
 {
-    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+    return dispatch(pk.nfp, set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
         // + 8: find_bracket's last stage may read up to 6 entries past a column's end (masked out)
-        const auto k = with_lds(k_star_like<NFP, NPOPS>, sizeof(double) * std::max((size_t)NPOPS * mass_cap + 8, heavy_lds_doubles(pk, NPOPS, 1, mass_cap)));
+        const auto k = with_lds(k_star_like<NFP, NPOPS>, sizeof(double) * std::max((size_t)NPOPS * set.mass_cap + 8, heavy_lds_doubles(pk, NPOPS, 1, set.mass_cap)));
         if (k.err != hipSuccess) return k.err;
         const int hot = 8 * ((gr.n_blocks * NPOPS + 7) / 8) * n_walkers;     // padded so every XCD sees whole walker sets (two populations: a workgroup per half tile)
         const int heavy = (n_walkers * heavy_parts + 7) / 8 * 8;     // heavy-star workgroups lead the grid
-        hipLaunchKernelGGL(k.kern, dim3(heavy + hot), dim3(256), k.lds, stream, pk, st, hdr, iso_data,
-                           iso_stride, mass_cap, d_params, n_walkers, partial, partial_stride, gr.n_groups, gr.group_tiles,
+        hipLaunchKernelGGL(k.kern, dim3(heavy + hot), dim3(256), k.lds, stream, pk, st, set.hdr, set.iso,
+                           set.iso_stride, set.mass_cap, set.params, n_walkers, partial.ptr, partial.stride, gr.n_groups, gr.group_tiles,
                            gr.groups_per_block, gr.n_blocks, perstar, heavy, heavy_parts);
         return hipGetLastError();
     });
 }
 
-hipError_t b9k_finalize(const IsoHdr *hdr, const double *partial, int n_partial, long long partial_stride,
-                        int n_pops, const double *d_params, const DevPriors &pr, int n_walkers, double *d_logpost,
-                        double *perstar, int n_stars, const McmcDev &mc, hipStream_t stream, unsigned long long *done_flag, unsigned long long done_seq)
+hipError_t b9k_finalize(const B9IsoSet &set, const B9Partial &partial, const DevPriors &pr, int n_walkers, double *d_logpost, double *perstar,
+                        int n_stars, const McmcDev &mc, hipStream_t stream, unsigned long long *done_flag, unsigned long long done_seq)
 {
-    hipLaunchKernelGGL(k_finalize, dim3(n_walkers), dim3(256), 0, stream, hdr, partial, n_partial, partial_stride,
-                       n_pops, d_params, pr, d_logpost, perstar, n_stars, mc, done_flag, done_seq);
+    hipLaunchKernelGGL(k_finalize, dim3(n_walkers), dim3(256), 0, stream, set.hdr, partial.ptr, partial.n, partial.stride,
+                       set.n_pops, set.params, pr, d_logpost, perstar, n_stars, mc, done_flag, done_seq);
     return hipGetLastError();
 }
 
 size_t b9k_predict_lds(int nfp, int mass_cap, int n_pops) { return sizeof(double) * (size_t)n_pops * mass_cap * (nfp + 1); }
 
-hipError_t b9k_predict_mags(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap, int n_pops,
-                            const double *d_params, long long n, const double *mass1, const double *mass_ratio, const int *wd_type,
+hipError_t b9k_predict_mags(const DevPack &pk, const B9IsoSet &set, long long n, const double *mass1, const double *mass_ratio, const int *wd_type,
                             const int *pop, double *out_mags, int *out_stage, int n_wgs, hipStream_t stream)
 {
     return dispatch_nfp(pk.nfp, [&](auto nfp_c) {
         constexpr int NFP = decltype(nfp_c)::value;
-        const auto k = with_lds(k_predict_mags<NFP>, b9k_predict_lds(NFP, mass_cap, n_pops));
+        const auto k = with_lds(k_predict_mags<NFP>, b9k_predict_lds(NFP, set.mass_cap, set.n_pops));
         if (k.err != hipSuccess) return k.err;
         const long long need = (n + 255) / 256;
-        hipLaunchKernelGGL(k.kern, dim3((unsigned)std::max(1ll, std::min<long long>(need, n_wgs))), dim3(256), k.lds, stream, pk, hdr, iso_data,
-                           iso_stride, mass_cap, n_pops, d_params, n, mass1, mass_ratio, wd_type, pop, out_mags, out_stage);
+        hipLaunchKernelGGL(k.kern, dim3((unsigned)std::max(1ll, std::min<long long>(need, n_wgs))), dim3(256), k.lds, stream, pk, set.hdr, set.iso,
+                           set.iso_stride, set.mass_cap, set.n_pops, set.params, n, mass1, mass_ratio, wd_type, pop, out_mags, out_stage);
         return hipGetLastError();
     });
+}
+
+// acc [n_words] += the n_rows rows of scratch [n_rows][n_words], ascending: the last launch of every reduction over a chunk of rows
+static void launch_chain_accumulate(const double *scratch, int n_rows, long long n_words, double *acc, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, scratch, n_rows, n_words, acc);
 }
 
 // ---- the WD-grid calls (b9_sample_wd_mass, b9_wd_moments, b9_wd_bins): the node table of a chunk of rows, then the call's star kernel ----
@@ -247,67 +247,59 @@ long long b9k_wd_grid_table_doubles(int nfp, long long n_nodes, bool status)    
 // The chunk's node table (STATUS: with every node's status behind it) behind the guard the three calls share.  Returns
 // n_wp = n_rows * NPOPS, or 0: invalid arguments, nothing launched.
 template <int NFP, int NPOPS, bool STATUS>
-static int launch_wd_grid_table(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                                const double *d_params, int n_rows, int n_nodes, double *tab, hipStream_t stream)
+static int launch_wd_grid_table(const DevPack &pk, const DevStars &st, const B9WdGrid &g, int n_rows, hipStream_t stream)
 {
-    if (!tab || n_rows < 1 || n_nodes < 1 || st.n_wd < 1 || n_rows * NPOPS > 65535) return 0;
+    if (!g.tab || n_rows < 1 || g.n_nodes < 1 || st.n_wd < 1 || n_rows * NPOPS > 65535) return 0;
     const int n_wp = n_rows * NPOPS;
-    hipLaunchKernelGGL(STATUS ? k_wd_node_table_status<NFP> : k_wd_node_table<NFP>, dim3((n_nodes + 63) / 64, n_wp), dim3(128), 0, stream, pk, hdr, iso_data,
-                       iso_stride, mass_cap, NPOPS, d_params, n_nodes, tab, n_wp);
+    hipLaunchKernelGGL(STATUS ? k_wd_node_table_status<NFP> : k_wd_node_table<NFP>, dim3((g.n_nodes + 63) / 64, n_wp), dim3(128), 0, stream, pk, g.set.hdr, g.set.iso,
+                       g.set.iso_stride, g.set.mass_cap, NPOPS, g.set.params, g.n_nodes, g.tab, n_wp);
     return n_wp;
 }
 
-hipError_t b9k_wd_sample(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                         const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const B9WdSample &smp, hipStream_t stream)
+hipError_t b9k_wd_sample(const DevPack &pk, const DevStars &st, const B9WdGrid &g, int n_rows, const B9WdSample &smp, hipStream_t stream)
 {
-    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+    return dispatch(pk.nfp, g.set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        const int n_wp = launch_wd_grid_table<NFP, NPOPS, false>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, n_nodes, tab, stream);
+        const int n_wp = launch_wd_grid_table<NFP, NPOPS, false>(pk, st, g, n_rows, stream);
         if (!n_wp) return hipErrorInvalidValue;
         WdSampleOut out{};
-        out.zams = smp.zams; out.member = smp.member; out.pop = smp.pop; out.wd_rank = smp.wd_rank;
+        out.zams = smp.zams; out.member = smp.member; out.pop = smp.pop; out.wd_rank = g.rank;
         out.der[0] = smp.wd_mass; out.der[1] = smp.prec_log_age; out.der[2] = smp.log_cool_age; out.der[3] = smp.log_teff; out.der[4] = smp.logg;
         out.k0 = smp.k0; out.k1 = smp.k1; out.row0 = smp.row0;
-        hipLaunchKernelGGL((k_wd_sample<NFP, NPOPS>), dim3((st.n_wd + 63) / 64, n_rows), dim3(64), 0, stream, pk, st, hdr, d_params, n_nodes,
-                           (const double *)tab, n_wp, out);
+        hipLaunchKernelGGL((k_wd_sample<NFP, NPOPS>), dim3((st.n_wd + 63) / 64, n_rows), dim3(64), 0, stream, pk, st, g.set.hdr, g.set.params, g.n_nodes,
+                           g.tab, n_wp, out);
         return hipGetLastError();
     });
 }
 
-hipError_t b9k_wd_moments(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                          const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const int *wd_rank, double *scratch, double *acc,
-                          hipStream_t stream)
+hipError_t b9k_wd_moments(const DevPack &pk, const DevStars &st, const B9WdGrid &g, int n_rows, hipStream_t stream)
 {
-    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+    return dispatch(pk.nfp, g.set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        if (!wd_rank || !scratch || !acc) return hipErrorInvalidValue;
-        const int n_wp = launch_wd_grid_table<NFP, NPOPS, true>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, n_nodes, tab, stream);
+        if (!g.rank || !g.scratch || !g.acc) return hipErrorInvalidValue;
+        const int n_wp = launch_wd_grid_table<NFP, NPOPS, true>(pk, st, g, n_rows, stream);
         if (!n_wp) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_wd_moments<NFP, NPOPS>), dim3((st.n_wd + 63) / 64, n_rows), dim3(64), 0, stream, pk, st, hdr, d_params, n_nodes,
-                           (const double *)tab, n_wp, wd_rank, scratch);
-        const long long n_words = (long long)st.n_wd * B9_WDM_N;
-        hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
+        hipLaunchKernelGGL((k_wd_moments<NFP, NPOPS>), dim3((st.n_wd + 63) / 64, n_rows), dim3(64), 0, stream, pk, st, g.set.hdr, g.set.params, g.n_nodes,
+                           g.tab, n_wp, g.rank, g.scratch);
+        launch_chain_accumulate(g.scratch, n_rows, (long long)st.n_wd * B9_WDM_N, g.acc, stream);
         return hipGetLastError();
     });
 }
 
-hipError_t b9k_wd_bins(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                       const double *d_params, int n_rows, int n_pops, int n_nodes, double *tab, const int *wd_rank, int quantity_mask,
-                       const double *edges, int n_bins, double *scratch, double *acc, hipStream_t stream)
+hipError_t b9k_wd_bins(const DevPack &pk, const DevStars &st, const B9WdGrid &g, int n_rows, int quantity_mask, int n_bins, hipStream_t stream)
 {
-    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+    return dispatch(pk.nfp, g.set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
         const int n_sel = __builtin_popcount((unsigned)quantity_mask);
-        if (!wd_rank || !edges || !scratch || !acc || n_bins < 1 || n_bins > B9_WBIN_MAX_BINS || quantity_mask < 1 || quantity_mask >= (1 << B9_WQ_N))
+        if (!g.rank || !g.edges || !g.scratch || !g.acc || n_bins < 1 || n_bins > B9_WBIN_MAX_BINS || quantity_mask < 1 || quantity_mask >= (1 << B9_WQ_N))
             return hipErrorInvalidValue;
-        const int n_wp = launch_wd_grid_table<NFP, NPOPS, true>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, n_nodes, tab, stream);
+        const int n_wp = launch_wd_grid_table<NFP, NPOPS, true>(pk, st, g, n_rows, stream);
         if (!n_wp) return hipErrorInvalidValue;
         const auto k = with_lds(k_wd_bins<NFP, NPOPS>, sizeof(double) * 64 * ((size_t)(n_bins + 1) + (size_t)(n_bins + 2)));
         if (k.err != hipSuccess) return k.err;
-        hipLaunchKernelGGL(k.kern, dim3((st.n_wd + 63) / 64, n_rows, n_sel), dim3(64), k.lds, stream, pk, st, hdr, d_params, n_nodes,
-                           (const double *)tab, n_wp, wd_rank, quantity_mask, n_sel, edges, n_bins, scratch);
-        const long long n_words = (long long)st.n_wd * n_sel * (n_bins + 3);
-        hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
+        hipLaunchKernelGGL(k.kern, dim3((st.n_wd + 63) / 64, n_rows, n_sel), dim3(64), k.lds, stream, pk, st, g.set.hdr, g.set.params, g.n_nodes,
+                           g.tab, n_wp, g.rank, quantity_mask, n_sel, g.edges, n_bins, g.scratch);
+        launch_chain_accumulate(g.scratch, n_rows, (long long)st.n_wd * n_sel * (n_bins + 3), g.acc, stream);
         return hipGetLastError();
     });
 }
@@ -334,113 +326,107 @@ static bool marg_sparse(long long wgs, int n_cu)
 // The node tables of n_walkers x n_pops derived isochrones: one workgroup per (walker-population, 64-node chunk).  Returns what
 // the LDS opt-in said; the caller collects the launch's own error.
 template <int NFP>
-static hipError_t launch_marg_table(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                                    const double *d_params, int n_walkers, int n_pops, int K, int Q, double *tab, hipStream_t stream)
+static hipError_t launch_marg_table(const DevPack &pk, const B9IsoSet &s, int n_walkers, const B9Marg &mg, hipStream_t stream)
 {
-    const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
-    const auto k = with_lds(k_marg_table<NFP>, sizeof(double) * ((size_t)mass_cap + 8 + 8 * NFP));
+    const MargLayout L = marg_layout(NFP, s.mass_cap, mg.K, mg.Q);
+    const auto k = with_lds(k_marg_table<NFP>, sizeof(double) * ((size_t)s.mass_cap + 8 + 8 * NFP));
     if (k.err != hipSuccess) return k.err;
-    hipLaunchKernelGGL(k.kern, dim3(n_walkers * n_pops, L.n_chunks), dim3(256), k.lds, stream, pk, hdr, iso_data,
-                       iso_stride, mass_cap, n_pops, d_params, K, Q, tab, L);
+    hipLaunchKernelGGL(k.kern, dim3(n_walkers * s.n_pops, L.n_chunks), dim3(256), k.lds, stream, pk, s.hdr, s.iso,
+                       s.iso_stride, s.mass_cap, s.n_pops, s.params, mg.K, mg.Q, mg.tab, L);
     return hipSuccess;
 }
 // ... and the WD-stage stars' node table (2 x 8 K WD chains per walker and population)
 template <int NFP>
-static void launch_marg_wd_table(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                                 const double *d_params, int n_walkers, int n_pops, int K, double *wd_tab, hipStream_t stream)
+static void launch_marg_wd_table(const DevPack &pk, const B9IsoSet &s, int n_walkers, const B9Marg &mg, hipStream_t stream)
 {
-    hipLaunchKernelGGL((k_marg_wd_table<NFP>), dim3(n_walkers * n_pops, (8 * K + 63) / 64), dim3(128), 0, stream, pk, hdr, iso_data, iso_stride,
-                       mass_cap, n_pops, d_params, K, wd_tab, n_walkers * n_pops);
+    hipLaunchKernelGGL((k_marg_wd_table<NFP>), dim3(n_walkers * s.n_pops, (8 * mg.K + 63) / 64), dim3(128), 0, stream, pk, s.hdr, s.iso, s.iso_stride,
+                       s.mass_cap, s.n_pops, s.params, mg.K, mg.wd_tab, n_walkers * s.n_pops);
 }
+// the pruning width the star kernels take
+static double marg_cut2(const B9Marg &mg) { return mg.prune ? 2.0 * B9_MARG_CUT : __builtin_inf(); }
 
-// What the four reductions over a saved chain launch first: the node table of a chunk of rows (k_marg_table, its layout L) into
-// the call's own buffer, with WD-stage stars k_marg_wd_table too, and the pruning width cut2 the star kernels take.
+// What the five reductions over a saved chain launch first, behind the guard they share (the tables, the scratch, 1 .. 65535
+// rows): the node table of a chunk of rows (k_marg_table, its layout L) into the call's own buffer, with WD-stage stars
+// k_marg_wd_table too, and the pruning width cut2 the star kernels take.  err: nothing of the call's own may be launched.
 struct ChainTables { hipError_t err; MargLayout L; double cut2; };
 template <int NFP>
-static ChainTables chain_tables(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                                const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, double *tab, double *wd_tab, hipStream_t stream)
+static ChainTables chain_tables(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, hipStream_t stream)
 {
-    const ChainTables t{launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, n_pops, K, Q, tab, stream),
-                        marg_layout(NFP, mass_cap, K, Q), prune ? 2.0 * B9_MARG_CUT : __builtin_inf()};
-    if (t.err == hipSuccess && st.n_wd > 0) launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, n_pops, K, wd_tab, stream);
+    ChainTables t{hipErrorInvalidValue, marg_layout(NFP, c.set.mass_cap, c.mg.K, c.mg.Q), marg_cut2(c.mg)};
+    if (!c.mg.tab || !c.scratch || n_rows < 1 || n_rows > 65535 || (st.n_wd > 0 && !c.mg.wd_tab)) return t;
+    t.err = launch_marg_table<NFP>(pk, c.set, n_rows, c.mg, stream);
+    if (t.err == hipSuccess && st.n_wd > 0) launch_marg_wd_table<NFP>(pk, c.set, n_rows, c.mg, stream);
     return t;
 }
 
 // ---- b9_star_moments: the node tables of a chunk of rows into the call's own buffers, the stars' increments, the accumulation -----
-hipError_t b9k_star_moments(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                            const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, double *tab, double *wd_tab,
-                            double *scratch, double *acc, hipStream_t stream)
+hipError_t b9k_star_moments(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, hipStream_t stream)
 {
-    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+    return dispatch(pk.nfp, c.set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        if (!tab || !scratch || !acc || n_rows < 1 || n_rows > 65535 || (st.n_wd > 0 && !wd_tab)) return hipErrorInvalidValue;
-        const ChainTables t = chain_tables<NFP>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, prune, tab, wd_tab, stream);
+        const B9IsoSet &s = c.set;
+        if (!c.acc) return hipErrorInvalidValue;
+        const ChainTables t = chain_tables<NFP>(pk, st, c, n_rows, stream);
         if (t.err != hipSuccess) return t.err;
-        hipLaunchKernelGGL((k_star_moments<NFP, NPOPS>), dim3(st.mg_pad / 64, n_rows), dim3(256), 0, stream, st, hdr, iso_data, iso_stride, mass_cap,
-                           d_params, K, Q, (const double *)tab, t.L, t.cut2, scratch);
+        hipLaunchKernelGGL((k_star_moments<NFP, NPOPS>), dim3(st.mg_pad / 64, n_rows), dim3(256), 0, stream, st, s.hdr, s.iso, s.iso_stride, s.mass_cap,
+                           s.params, c.mg.K, c.mg.Q, c.mg.tab, t.L, t.cut2, c.scratch);
         if (st.n_wd > 0)
-            hipLaunchKernelGGL((k_star_moments_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, hdr, d_params, K,
-                               (const double *)wd_tab, scratch);
-        const long long n_words = (long long)st.n * B9_MOM_N;
-        hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
+            hipLaunchKernelGGL((k_star_moments_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, s.hdr, s.params, c.mg.K,
+                               c.mg.wd_tab, c.scratch);
+        launch_chain_accumulate(c.scratch, n_rows, (long long)st.n * B9_MOM_N, c.acc, stream);
         return hipGetLastError();
     });
 }
 
 // ---- b9_mass_hist: the node tables of a chunk of rows, the stars' binned increments, the accumulation, the rows' sums -----------
-hipError_t b9k_mass_hist(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                         const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, int quantity, const double *edges, int n_bins,
-                         double *tab, double *wd_tab, double *scratch, double *acc, double *rows, hipStream_t stream)
+hipError_t b9k_mass_hist(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, int quantity, const double *edges, int n_bins,
+                         hipStream_t stream)
 {
-    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+    return dispatch(pk.nfp, c.set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        if (!tab || !scratch || !edges || n_bins < 1 || n_bins > B9_HIST_MAX_BINS || n_rows < 1 || n_rows > 65535 || (st.n_wd > 0 && !wd_tab))
-            return hipErrorInvalidValue;
+        const B9IsoSet &s = c.set;
+        if (!edges || n_bins < 1 || n_bins > B9_HIST_MAX_BINS) return hipErrorInvalidValue;
         HistEdges ed{};
         for (int b = 0; b <= n_bins; ++b) ed.e[b] = edges[b];
         ed.n_bins = n_bins; ed.quantity = quantity;
-        const ChainTables t = chain_tables<NFP>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, prune, tab, wd_tab, stream);
+        const ChainTables t = chain_tables<NFP>(pk, st, c, n_rows, stream);
         if (t.err != hipSuccess) return t.err;
         // a tile of bins: one histogram [bins][64] per wave
         const int tb = std::min(n_bins, B9_HIST_TILE), n_tiles = (n_bins + B9_HIST_TILE - 1) / B9_HIST_TILE;
         const auto k = with_lds(k_star_hist<NFP, NPOPS>, sizeof(double) * 64 * (NPOPS * 4 + 4 * 2 + 4 * (size_t)tb));   // seeds, states, histograms
         if (k.err != hipSuccess) return k.err;
-        hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows, n_tiles), dim3(256), k.lds, stream, st, hdr, iso_data, iso_stride, mass_cap,
-                           d_params, K, Q, (const double *)tab, t.L, t.cut2, ed, tb, scratch);
+        hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows, n_tiles), dim3(256), k.lds, stream, st, s.hdr, s.iso, s.iso_stride, s.mass_cap,
+                           s.params, c.mg.K, c.mg.Q, c.mg.tab, t.L, t.cut2, ed, tb, c.scratch);
         if (st.n_wd > 0)
-            hipLaunchKernelGGL((k_star_hist_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, hdr, d_params, K,
-                               (const double *)wd_tab, ed, scratch);
+            hipLaunchKernelGGL((k_star_hist_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, s.hdr, s.params, c.mg.K,
+                               c.mg.wd_tab, ed, c.scratch);
         const int ncol = n_bins + 1;
-        const long long n_words = (long long)st.n * ncol;
-        if (acc)
-            hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
-        if (rows)
-            hipLaunchKernelGGL(k_hist_rows, dim3((unsigned)((n_rows * ncol + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, st.n, ncol, rows);
+        if (c.acc) launch_chain_accumulate(c.scratch, n_rows, (long long)st.n * ncol, c.acc, stream);
+        if (c.rows)
+            hipLaunchKernelGGL(k_hist_rows, dim3((unsigned)((n_rows * ncol + 255) / 256)), dim3(256), 0, stream, c.scratch, n_rows, st.n, ncol, c.rows);
         return hipGetLastError();
     });
 }
 
 // ---- b9_star_bins: the node tables of a chunk of rows, the stars' increments on their own edges, the accumulation -----------------
-hipError_t b9k_star_bins(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                         const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, int quantity, const double *edges, int n_bins,
-                         double *tab, double *wd_tab, double *scratch, double *acc, hipStream_t stream)
+hipError_t b9k_star_bins(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, int quantity, const double *edges, int n_bins,
+                         hipStream_t stream)
 {
-    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+    return dispatch(pk.nfp, c.set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        if (!tab || !scratch || !acc || !edges || n_bins < 1 || n_bins > B9_SBIN_MAX_BINS || n_rows < 1 || n_rows > 65535 || (st.n_wd > 0 && !wd_tab))
-            return hipErrorInvalidValue;
-        const ChainTables t = chain_tables<NFP>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, prune, tab, wd_tab, stream);
+        const B9IsoSet &s = c.set;
+        if (!c.acc || !edges || n_bins < 1 || n_bins > B9_SBIN_MAX_BINS) return hipErrorInvalidValue;
+        const ChainTables t = chain_tables<NFP>(pk, st, c, n_rows, stream);
         if (t.err != hipSuccess) return t.err;
         // seeds, states, the 64 stars' edges, one histogram [n_bins + 2][64] per wave
         const auto k = with_lds(k_star_bins<NFP, NPOPS>, sizeof(double) * 64 * (NPOPS * 4 + 4 * 2 + (size_t)(n_bins + 1) + 4 * (size_t)(n_bins + 2)));
         if (k.err != hipSuccess) return k.err;
-        hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows), dim3(256), k.lds, stream, st, hdr, iso_data, iso_stride, mass_cap,
-                           d_params, K, Q, (const double *)tab, t.L, t.cut2, edges, n_bins, quantity, scratch);
+        hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows), dim3(256), k.lds, stream, st, s.hdr, s.iso, s.iso_stride, s.mass_cap,
+                           s.params, c.mg.K, c.mg.Q, c.mg.tab, t.L, t.cut2, edges, n_bins, quantity, c.scratch);
         if (st.n_wd > 0)
-            hipLaunchKernelGGL((k_star_bins_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, hdr, d_params, K,
-                               (const double *)wd_tab, edges, n_bins, quantity, scratch);
-        const long long n_words = (long long)st.n * (n_bins + 3);
-        hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
+            hipLaunchKernelGGL((k_star_bins_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, s.hdr, s.params, c.mg.K,
+                               c.mg.wd_tab, edges, n_bins, quantity, c.scratch);
+        launch_chain_accumulate(c.scratch, n_rows, (long long)st.n * (n_bins + 3), c.acc, stream);
         return hipGetLastError();
     });
 }
@@ -456,30 +442,27 @@ hipError_t b9k_resid_stage(const DevPack &pk, const DevStars &st, const double *
     });
 }
 
-hipError_t b9k_phot_resid(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                          const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, const double *piv_mg, const double *isig,
-                          double *tab, double *wd_tab, double *scratch, double *acc, double *rows, hipStream_t stream)
+hipError_t b9k_phot_resid(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, const double *piv_mg, const double *isig, hipStream_t stream)
 {
-    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+    return dispatch(pk.nfp, c.set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        if (!tab || !scratch || !piv_mg || (rows && !isig) || n_rows < 1 || n_rows > 65535 || (st.n_wd > 0 && !wd_tab)) return hipErrorInvalidValue;
+        const B9IsoSet &s = c.set;
+        if (!piv_mg || (c.rows && !isig)) return hipErrorInvalidValue;
         const int nf = pk.nf;
-        const ChainTables t = chain_tables<NFP>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, prune, tab, wd_tab, stream);
+        const ChainTables t = chain_tables<NFP>(pk, st, c, n_rows, stream);
         if (t.err != hipSuccess) return t.err;
         const auto k = with_lds(k_star_resid<NFP, NPOPS>, sizeof(double) * 64 * (NPOPS * 4 + 4 * (2 + 2 * (size_t)NFP)));      // seeds, one population's states
         if (k.err != hipSuccess) return k.err;
-        hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows), dim3(256), k.lds, stream, st, nf, piv_mg, hdr, iso_data, iso_stride, mass_cap,
-                           d_params, K, Q, (const double *)tab, t.L, t.cut2, scratch);
+        hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows), dim3(256), k.lds, stream, st, nf, piv_mg, s.hdr, s.iso, s.iso_stride, s.mass_cap,
+                           s.params, c.mg.K, c.mg.Q, c.mg.tab, t.L, t.cut2, c.scratch);
         if (st.n_wd > 0)
-            hipLaunchKernelGGL((k_star_resid_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, nf, pk.m_wd_up, hdr, d_params, K,
-                               (const double *)wd_tab, scratch);
-        const long long n_words = (long long)st.n * (2 + 2 * nf);
-        if (acc)
-            hipLaunchKernelGGL(k_chain_accumulate, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, stream, (const double *)scratch, n_rows, n_words, acc);
-        if (rows) {
+            hipLaunchKernelGGL((k_star_resid_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, nf, pk.m_wd_up, s.hdr, s.params, c.mg.K,
+                               c.mg.wd_tab, c.scratch);
+        if (c.acc) launch_chain_accumulate(c.scratch, n_rows, (long long)st.n * (2 + 2 * nf), c.acc, stream);
+        if (c.rows) {
             const auto kr = with_lds(k_resid_rows, sizeof(double) * 2 * B9_RESID_TILE * (2 + 3 * (size_t)nf));      // two tiles of {x, 1 / sigma}
             if (kr.err != hipSuccess) return kr.err;
-            hipLaunchKernelGGL(kr.kern, dim3(n_rows), dim3(256), kr.lds, stream, (const double *)scratch, isig, st.n, nf, rows);
+            hipLaunchKernelGGL(kr.kern, dim3(n_rows), dim3(256), kr.lds, stream, c.scratch, isig, st.n, nf, c.rows);
         }
         return hipGetLastError();
     });
@@ -503,32 +486,29 @@ hipError_t b9k_pw_tail_store(const double *tail, int n_stars, int tail_len, doub
     return hipGetLastError();
 }
 
-hipError_t b9k_pointwise(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                         const double *d_params, int n_rows, int n_pops, int K, int Q, bool prune, double *tab, double *wd_tab,
-                         double *scratch, int *row_in, double *acc, double *tail, int tail_len, double *rows, hipStream_t stream)
+hipError_t b9k_pointwise(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, int *row_in, double *tail, int tail_len, hipStream_t stream)
 {
-    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+    return dispatch(pk.nfp, c.set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        if (!tab || !scratch || !row_in || n_rows < 1 || n_rows > B9_PW_MAX_ROWS || (st.n_wd > 0 && !wd_tab) || (tail && (!acc || tail_len < 1 || tail_len > B9_PW_MAX_TAIL)))
-            return hipErrorInvalidValue;
-        const ChainTables t = chain_tables<NFP>(pk, st, hdr, iso_data, iso_stride, mass_cap, d_params, n_rows, NPOPS, K, Q, prune, tab, wd_tab, stream);
+        const B9IsoSet &s = c.set;
+        if (!row_in || n_rows > B9_PW_MAX_ROWS || (tail && (!c.acc || tail_len < 1 || tail_len > B9_PW_MAX_TAIL))) return hipErrorInvalidValue;
+        const ChainTables t = chain_tables<NFP>(pk, st, c, n_rows, stream);
         if (t.err != hipSuccess) return t.err;
-        hipLaunchKernelGGL((k_star_lpd<NFP, NPOPS>), dim3(st.mg_pad / 64, n_rows), dim3(256), 0, stream, st, hdr, iso_data, iso_stride, mass_cap,
-                           d_params, K, Q, (const double *)tab, t.L, t.cut2, scratch, row_in);
+        hipLaunchKernelGGL((k_star_lpd<NFP, NPOPS>), dim3(st.mg_pad / 64, n_rows), dim3(256), 0, stream, st, s.hdr, s.iso, s.iso_stride, s.mass_cap,
+                           s.params, c.mg.K, c.mg.Q, c.mg.tab, t.L, t.cut2, c.scratch, row_in);
         if (st.n_wd > 0)
-            hipLaunchKernelGGL((k_star_lpd_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, hdr, d_params, K,
-                               (const double *)wd_tab, scratch);
+            hipLaunchKernelGGL((k_star_lpd_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, s.hdr, s.params, c.mg.K,
+                               c.mg.wd_tab, c.scratch);
         const unsigned star_wgs = (unsigned)((st.n + 255) / 256);
-        if (acc)
-            hipLaunchKernelGGL(k_pw_accumulate, dim3(star_wgs), dim3(256), 0, stream, (const double *)scratch, (const int *)row_in, n_rows, st.n, acc);
+        if (c.acc)
+            hipLaunchKernelGGL(k_pw_accumulate, dim3(star_wgs), dim3(256), 0, stream, c.scratch, row_in, n_rows, st.n, c.acc);
         if (tail) {
             const auto kt = with_lds(k_pw_tail, sizeof(double) * 64 * (size_t)tail_len);          // the wave's 64 lists
             if (kt.err != hipSuccess) return kt.err;
-            hipLaunchKernelGGL(kt.kern, dim3((unsigned)((st.n + 63) / 64)), dim3(64), kt.lds, stream, (const double *)scratch, (const int *)row_in,
-                               n_rows, st.n, tail_len, tail);
+            hipLaunchKernelGGL(kt.kern, dim3((unsigned)((st.n + 63) / 64)), dim3(64), kt.lds, stream, c.scratch, row_in, n_rows, st.n, tail_len, tail);
         }
-        if (rows)
-            hipLaunchKernelGGL(k_pw_rows, dim3((unsigned)n_rows), dim3(64), 0, stream, (const double *)scratch, (const int *)row_in, st.n, rows);
+        if (c.rows)
+            hipLaunchKernelGGL(k_pw_rows, dim3((unsigned)n_rows), dim3(64), 0, stream, c.scratch, row_in, st.n, c.rows);
         return hipGetLastError();
     });
 }
@@ -550,28 +530,27 @@ static MargGrid marg_star_grid(const DevStars &st, int n_walkers, bool split)
 }
 
 // smp == nullptr: the plain marginal likelihood; else every star also draws one (mass, ratio[, population]) node
-hipError_t b9k_star_marg(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, const double *iso_data,
-                         long long iso_stride, int mass_cap, const double *d_params, int n_walkers, int n_pops,
-                         double *partial, long long partial_stride, double *perstar, int K, int Q, const B9MargSample *smp, bool prune, double *tab, double *wd_tab, double *shares, int n_cu, hipStream_t stream)
+hipError_t b9k_star_marg(const DevPack &pk, const DevStars &st, const B9IsoSet &set, int n_walkers, const B9Partial &partial, double *perstar,
+                         const B9Marg &mg, const B9MargSample *smp, int n_cu, hipStream_t stream)
 {
-    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+    return dispatch(pk.nfp, set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
         const auto launch = [&](auto sample_c) {
             constexpr bool SAMPLE = decltype(sample_c)::value;
             MargSample ms{};
             if (SAMPLE) { ms.mass = smp->mass; ms.ratio = smp->ratio; ms.member = smp->member; ms.pop = smp->pop; ms.k0 = smp->k0; ms.k1 = smp->k1; ms.row0 = smp->row0; }
-            if (!tab) return hipErrorInvalidValue;
-            const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
-            const hipError_t e = launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, NPOPS, K, Q, tab, stream);      // the call's node table
+            if (!mg.tab) return hipErrorInvalidValue;
+            const MargLayout L = marg_layout(NFP, set.mass_cap, mg.K, mg.Q);
+            const hipError_t e = launch_marg_table<NFP>(pk, set, n_walkers, mg, stream);      // the call's node table
             if (e != hipSuccess) return e;
             // SPLIT: a small catalogue's launch lasts as long as its heaviest star chunk (giants: 100 us where the median chunk takes
             // 40) while most of the chip idles, so several workgroups share a chunk's window (DevStars::mg_piece; k_marg_merge).  A
             // function of the CATALOGUE only -- it decides how a star's sum rounds, and a walker's chain must not depend on how many
             // walkers share the GPU.  The sampleMass draws keep one workgroup per chunk.
             const bool split = !SAMPLE && st.mg_n_pieces > 0;
-            if (split && !shares) return hipErrorInvalidValue;
+            if (split && !mg.shares) return hipErrorInvalidValue;
             const MargGrid g = marg_star_grid(st, n_walkers, split);
-            const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
+            const double cut2 = marg_cut2(mg);
             // rows through LDS tiles or through scalar registers (star_marg_body, TILE): measured per instance -- 8 (4) filters x one
             // population, unsplit, is the one shape the scalar path still wins in this kernel (2.20 against 2.17e9 star-evals/s)
             const bool sparse = !SAMPLE && split && marg_sparse((long long)st.mg_n_pieces * n_walkers, n_cu);
@@ -581,16 +560,16 @@ hipError_t b9k_star_marg(const DevPack &pk, const DevStars &st, const IsoHdr *hd
                             : tiled  ? k_star_marg<NFP, NPOPS, SAMPLE, false, false, SAMPLE ? 0 : 1>
                                      : k_star_marg<NFP, NPOPS, SAMPLE, false>;
             const size_t tile_lds = tiled ? sizeof(double) * 4 * B9_TILE_DOUBLES(NFP) : 0;
-            hipLaunchKernelGGL(kern, dim3(8 * g.per_xcd), dim3(256), tile_lds, stream, pk, st, hdr, iso_data, iso_stride,
-                               mass_cap, d_params, partial, partial_stride, perstar, K, Q, ms, tab, L, n_walkers, cut2, g.wsplit, shares);
+            hipLaunchKernelGGL(kern, dim3(8 * g.per_xcd), dim3(256), tile_lds, stream, pk, st, set.hdr, set.iso, set.iso_stride,
+                               set.mass_cap, set.params, partial.ptr, partial.stride, perstar, mg.K, mg.Q, ms, mg.tab, L, n_walkers, cut2, g.wsplit, mg.shares);
             if (split)
-                hipLaunchKernelGGL((k_marg_merge<NPOPS>), dim3(st.mg_pad / 64, n_walkers), dim3(64), 0, stream, st, hdr, d_params, partial, partial_stride,
-                                   perstar, shares);
+                hipLaunchKernelGGL((k_marg_merge<NPOPS>), dim3(st.mg_pad / 64, n_walkers), dim3(64), 0, stream, st, set.hdr, set.params, partial.ptr, partial.stride,
+                                   perstar, mg.shares);
             if (st.n_wd > 0) {        // the catalogue's WD-stage stars: their node table, then a wave per star
-                if (!wd_tab) return hipErrorInvalidValue;
-                launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, NPOPS, K, wd_tab, stream);
-                hipLaunchKernelGGL((k_star_marg_wd<NFP, NPOPS, SAMPLE>), dim3((st.n_wd + 3) / 4, n_walkers), dim3(256), 0, stream, pk, st, hdr,
-                                   iso_data, iso_stride, mass_cap, d_params, partial, partial_stride, perstar, K, ms, wd_tab);
+                if (!mg.wd_tab) return hipErrorInvalidValue;
+                launch_marg_wd_table<NFP>(pk, set, n_walkers, mg, stream);
+                hipLaunchKernelGGL((k_star_marg_wd<NFP, NPOPS, SAMPLE>), dim3((st.n_wd + 3) / 4, n_walkers), dim3(256), 0, stream, pk, st, set.hdr,
+                                   set.iso, set.iso_stride, set.mass_cap, set.params, partial.ptr, partial.stride, perstar, mg.K, ms, mg.wd_tab);
             }
             return hipGetLastError();
         };
@@ -600,18 +579,17 @@ hipError_t b9k_star_marg(const DevPack &pk, const DevStars &st, const IsoHdr *hd
 
 // The catalogue plan's counting pass: the unsplit star kernel on ONE row (the reference row), every wave leaving the number of
 // (16 nodes x one mass ratio) units it evaluated in cost[star chunk][4].
-hipError_t b9k_star_marg_cost(const DevPack &pk, const DevStars &st, const IsoHdr *hdr, int mass_cap, const double *d_params, int n_pops,
-                              double *partial, long long partial_stride, int K, int Q, bool prune, const double *tab, unsigned *cost, hipStream_t stream)
+hipError_t b9k_star_marg_cost(const DevPack &pk, const DevStars &st, const B9IsoSet &set, const B9Partial &partial, const B9Marg &mg, unsigned *cost,
+                              hipStream_t stream)
 {
-    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+    return dispatch(pk.nfp, set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
         MargSample ms{};
         ms.cost = cost;
-        const MargLayout L = marg_layout(NFP, mass_cap, K, Q);
+        const MargLayout L = marg_layout(NFP, set.mass_cap, mg.K, mg.Q);
         const int n_chunks = st.mg_pad / 64;
-        const double cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
-        hipLaunchKernelGGL((k_star_marg<NFP, NPOPS, false, false, true>), dim3(8 * ((n_chunks + 7) / 8)), dim3(256), 0, stream, pk, st, hdr, (const double *)nullptr, 0ll,
-                           mass_cap, d_params, partial, partial_stride, (double *)nullptr, K, Q, ms, tab, L, 1, cut2, 1, (double *)nullptr);
+        hipLaunchKernelGGL((k_star_marg<NFP, NPOPS, false, false, true>), dim3(8 * ((n_chunks + 7) / 8)), dim3(256), 0, stream, pk, st, set.hdr, (const double *)nullptr, 0ll,
+                           set.mass_cap, set.params, partial.ptr, partial.stride, (double *)nullptr, mg.K, mg.Q, ms, mg.tab, L, 1, marg_cut2(mg), 1, (double *)nullptr);
         return hipGetLastError();
     });
 }
@@ -619,14 +597,13 @@ hipError_t b9k_star_marg_cost(const DevPack &pk, const DevStars &st, const IsoHd
 // ---- the marginalised mode's fused sampler step (k_marg_step) -----------------------------------------------------------
 // The node tables of a set of derived isochrones WITHOUT the star launch: the prologue of a fused block (its first
 // proposal comes from k_derive_iso; every later one is built inside k_marg_step).
-hipError_t b9k_marg_tables(const DevPack &pk, const IsoHdr *hdr, const double *iso_data, long long iso_stride, int mass_cap,
-                           const double *d_params, int n_walkers, int n_pops, int K, int Q, double *tab, double *wd_tab, hipStream_t stream)
+hipError_t b9k_marg_tables(const DevPack &pk, const B9IsoSet &set, int n_walkers, const B9Marg &mg, hipStream_t stream)
 {
     return dispatch_nfp(pk.nfp, [&](auto nfp_c) {
         constexpr int NFP = decltype(nfp_c)::value;
-        const hipError_t e = launch_marg_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, n_pops, K, Q, tab, stream);
+        const hipError_t e = launch_marg_table<NFP>(pk, set, n_walkers, mg, stream);
         if (e != hipSuccess) return e;
-        if (wd_tab) launch_marg_wd_table<NFP>(pk, hdr, iso_data, iso_stride, mass_cap, d_params, n_walkers, n_pops, K, wd_tab, stream);
+        if (mg.wd_tab) launch_marg_wd_table<NFP>(pk, set, n_walkers, mg, stream);
         return hipGetLastError();
     });
 }
@@ -635,32 +612,32 @@ hipError_t b9k_marg_tables(const DevPack &pk, const IsoHdr *hdr, const double *i
 // leaves the star role its workgroups per CU (B9_MSTEP_LDS_MAX: 160 KB / 7 less the kernel's static arrays, with 8 filters)
 size_t b9k_marg_step_lds(int nfp, int mass_cap) { return sizeof(double) * B9_MSTEP_LDS_DOUBLES(nfp, mass_cap); }
 
-hipError_t b9k_marg_step(const DevPack &pk, const DevStars &st, const StepDev &sd, const DevPriors &pr, int K, int Q, bool prune,
-                         double *tab, double *wd_tab, long long wd_stride, double *shares, int n_cu, hipStream_t stream)
+hipError_t b9k_marg_step(const DevPack &pk, const DevStars &st, const StepDev &sd, const DevPriors &pr, const B9Marg &mg, int n_cu, hipStream_t stream)
 {
     return dispatch(pk.nfp, sd.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        const int W = sd.n_walkers;
+        const int W = sd.n_walkers, K = mg.K;
         const bool split = st.mg_n_pieces > 0;
         const MargGrid g = marg_star_grid(st, W, split);
+        const long long wd_doubles = b9k_marg_wd_table_doubles(NFP, K);
         MargStep mx{};
-        mx.K = K; mx.Q = Q; mx.L = marg_layout(NFP, sd.mass_cap, K, Q);
+        mx.K = K; mx.Q = mg.Q; mx.L = marg_layout(NFP, sd.mass_cap, K, mg.Q);
         mx.n_chunks_cap = mx.L.n_chunks;
         mx.n_wd_blocks = st.n_wd > 0 ? (8 * K + 127) / 128 : 0;
         mx.wsplit = g.wsplit;
-        if (split && !shares) return hipErrorInvalidValue;
-        if (st.n_wd > 0 && !wd_tab) return hipErrorInvalidValue;
-        mx.cut2 = prune ? 2.0 * B9_MARG_CUT : __builtin_inf();
-        mx.tab = tab; mx.wd_tab = wd_tab; mx.wd_stride = wd_stride; mx.shares = shares;
+        if (split && !mg.shares) return hipErrorInvalidValue;
+        if (st.n_wd > 0 && !mg.wd_tab) return hipErrorInvalidValue;
+        mx.cut2 = marg_cut2(mg);
+        mx.tab = mg.tab; mx.wd_tab = mg.wd_tab; mx.wd_stride = (long long)W * NPOPS * wd_doubles; mx.shares = mg.shares;      // (wd_stride: one candidate's WD tables)
         const int front = (W + W * 2 * NPOPS * (mx.n_chunks_cap + mx.n_wd_blocks) + 7) / 8 * 8;
         const int stars = 8 * g.per_xcd;
         const int wd = st.n_wd > 0 ? ((st.n_wd + 3) / 4) * W : 0;
         const size_t lds = b9k_marg_step_lds(NFP, sd.mass_cap);
         if (lds > B9_MSTEP_LDS_MAX(NFP)) return hipErrorInvalidValue;
         // this parity's two candidates, as the star roles read them (see MargStepSel)
-        const size_t rows = (size_t)W * NPOPS, c0 = (size_t)sd.set * 2;
-        const IsoHdr *hdr_rd = sd.cand_hdr + c0 * rows;
-        const double *par_rd = sd.cand_par + c0 * W * B9_NPARAM, *tab_rd = tab + c0 * rows * mx.L.total, *wd_rd = wd_tab ? wd_tab + c0 * wd_stride : nullptr;
+        const b9i::CandAt c0 = b9i::cand_at(sd.set, 0, W, NPOPS);
+        const IsoHdr *hdr_rd = sd.cand_hdr + c0.wp;
+        const double *par_rd = sd.cand_par + c0.row * B9_NPARAM, *tab_rd = mg.tab + c0.wp * mx.L.total, *wd_rd = mg.wd_tab ? mg.wd_tab + c0.wp * wd_doubles : nullptr;
         static_assert(B9_MSTEP_LDS_DOUBLES(NFP, 2) >= 4 * B9_TILE_DOUBLES(NFP), "the star role's row tiles borrow the builders' dynamic LDS");
         const auto kern = !split ? k_marg_step<NFP, NPOPS, false>
                         : marg_sparse((long long)st.mg_n_pieces * W, n_cu) ? k_marg_step<NFP, NPOPS, true, 2> : k_marg_step<NFP, NPOPS, true>;

@@ -373,6 +373,22 @@ void sizing_checks()
     CHECK(pack_iso_stride(120, 8) == 120 * 9);
     const WorkNeed w = work_need(8, 2, 120, 8);
     CHECK(w.hdr == 64 && w.iso == (size_t)1080 * 64 && w.params == (size_t)12 * 8 * 4 && w.logpost == 8);
+    // candidate c of parity p of a fused block: the expressions its callers wrote out (set c0 = 2 p + c of [2][2] sets, W walkers
+    // each: W parameter rows, rows = W n_pops headers / isochrones / node tables)
+    for (int W : {1, 3})
+        for (int n_pops : {1, 2})
+            for (int p = 0; p < 2; ++p)
+                for (int c = 0; c < 2; ++c) {
+                    const size_t rows = (size_t)W * n_pops, c0 = (size_t)p * 2 + c;
+                    const CandAt at = cand_at(p, c, W, n_pops);
+                    CHECK(at.row == c0 * W && at.wp == c0 * rows);
+                    CHECK(at.row * B9_NPARAM == c0 * W * B9_NPARAM);                                  // parameter doubles
+                    const size_t stride = (size_t)pack_iso_stride(120, 8), tab = 977, wd_stride = rows * 33;
+                    CHECK(at.wp * stride == c0 * rows * stride && at.wp * tab == c0 * rows * tab);     // isochrone and node-table doubles
+                    CHECK(at.wp * 33 == c0 * wd_stride);                                               // WD tables: wd_stride a candidate
+                    if (c == 0) CHECK(at.row == (size_t)p * 2 * W && at.wp == (size_t)p * 2 * rows);   // k_marg_step's c0 = set * 2
+                }
+    CHECK(cand_at(1, 0, 3, 2).row == 6 && cand_at(1, 0, 3, 2).wp == 12 && cand_at(0, 0, 3, 2).wp == 0 && cand_at(1, 1, 1, 1).row == 3);
     CHECK(tree_part_stride(3, 4) == 16 && tree_part_stride(3, 5) == 18);
     const TreeNeed t = tree_need(2, 2, 3, 100, 3, 4);
     CHECK(t.n_cand == 224 && t.hdr == 448 && t.iso == 44800 && t.par == 224 * 12 && t.partial == (size_t)2 * 2 * 7 * 16);
