@@ -442,6 +442,23 @@ int run_block_two_launch(b9_ctx *ctx, b9_mcmc_block *blk, const B9Groups &plan)
     return close_block(ctx, blk, f, fin, L.o_nacc, false);
 }
 
+/* The heavy role of a given-mass block keeps the pack's axes, its AGB tips and the candidates' mass columns in LDS
+ * (heavy_lds_doubles): a block whose pack asks for more than a CU has is refused here, on the host, before it uploads or launches
+ * anything.  With the tips staged as corner columns (n_age doubles each) it is the age axis that decides, and the message says so. */
+int check_step_lds(b9_ctx *ctx, int n_pops, B9StepKind kind, int n_groups)
+{
+    size_t dyn = 0, stat = 0;
+    HIPCHK(ctx, b9k_step_lds(ctx->pk, n_pops, ctx->work.mass_cap, kind, n_groups, &dyn, &stat));
+    if (dyn + stat <= B9_LDS_PER_CU) return B9_OK;
+    const bool corner_columns = (size_t)ctx->pk.n_feh * ctx->pk.n_y * ctx->pk.n_age > B9_TIPS_LDS_MAX;
+    const std::string what = corner_columns
+        ? "the age axis of " + std::to_string(ctx->pk.n_age) + " entries is too long for the sampler step"
+        : "the pack's tables (axes of " + std::to_string(ctx->pk.hc_len) + " entries, isochrones of up to " +
+          std::to_string(ctx->work.mass_cap) + " points) are too large for the sampler step";
+    return fail(ctx, B9_ERR_CAPACITY, "b9_mcmc_run_block: " + what + ": its heavy role needs " + std::to_string(dyn) + " dynamic + " +
+                std::to_string(stat) + " static bytes of LDS, a compute unit has " + std::to_string(B9_LDS_PER_CU));
+}
+
 }  // namespace
 
 extern "C" {
@@ -473,7 +490,13 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk)
     const B9Groups plan = make_plan(ctx, W, n_pops);
     if (ctx->opt.mode == B9_MODE_GIVEN_MASS && !ctx->two_launch_steps) {
         const TreePlan tp = make_tree_plan(ctx, W, n_pops);
+        rc = check_step_lds(ctx, n_pops, tp.depth >= 2 ? B9_STEP_TREE : B9_STEP_FUSED, tp.n_groups);
+        if (rc) return rc;
         return tp.depth >= 2 ? run_block_tree(ctx, blk, tp) : run_block_fused(ctx, blk, false);
+    }
+    if (ctx->opt.mode == B9_MODE_GIVEN_MASS) {          // two launches per step: k_star_like carries the heavy role
+        rc = check_step_lds(ctx, n_pops, B9_STEP_STAR_LIKE, 0);
+        if (rc) return rc;
     }
     if (ctx->opt.mode == B9_MODE_MARGINALISED && !ctx->two_launch_steps && marg_fused_ok(ctx)) return run_block_fused(ctx, blk, true);
     return run_block_two_launch(ctx, blk, plan);

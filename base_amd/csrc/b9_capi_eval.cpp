@@ -258,7 +258,7 @@ int b9_predict_mags(b9_ctx *ctx, const double *param_row, int64_t n, const doubl
     const int nf = pk.nf;
     B9IsoSet set{nullptr, nullptr, nullptr, 0, pack_mass_cap(pk.max_eep), n_pops};
     set.iso_stride = pack_iso_stride(set.mass_cap, pk.nfp);
-    if (b9k_predict_lds(pk.nfp, set.mass_cap, n_pops) > 160 * 1024)
+    if (b9k_predict_lds(pk.nfp, set.mass_cap, n_pops) > B9_LDS_PER_CU)
         return fail(ctx, B9_ERR_CAPACITY, "b9_predict_mags: the derived isochrones do not fit the kernel's LDS");
     RESERVE(ctx, ctx->d_pred_hdr, 2);
     RESERVE(ctx, ctx->d_pred_par, B9_NPARAM);

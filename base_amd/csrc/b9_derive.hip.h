@@ -30,9 +30,10 @@ __device__ __forceinline__ double interp_corner(const DevPack &pk, const Corners
     return lerp(vf[0], vf[1], c.t_feh);
 }
 
-// Largest i in [0, n-2] with ax[i] <= x, found by one wave in one step: lane l loads ax[l]
-// (axes have <= 64 * B9_AXIS_CHUNKS entries) and the bracket is a popcount of the ballot.
-// Equal to the oracle's bracket() for an ascending axis.
+// Largest i in [0, n-2] with ax[i] <= x on an axis of ANY length, found by one wave: the axis is walked in memory in chunks of
+// 64 entries -- lane l of a chunk loads ax[base + l], the lanes past the end of the last chunk are masked out -- and the
+// bracket is the sum of the chunks' ballot popcounts, less one.  bracket_regs takes this path for axes of more than 128
+// entries (no cap: b9_load_pack bounds no axis).  Equal to the oracle's bracket() for an ascending axis.
 __device__ __forceinline__ int bracket_wave(const double *__restrict__ ax, int n, double x, int lane)
 {
     int cnt = 0;

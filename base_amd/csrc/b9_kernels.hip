@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void k_finalize(const IsoHdr *__restrict__ hdr
 template <class K>
 static hipError_t lds_opt_in(K *kern, size_t lds)
 {
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > B9_LDS_PER_CU) return hipErrorInvalidValue;
     if (lds <= 64 * 1024) return hipSuccess;
     return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
@@ -191,13 +191,19 @@ static size_t heavy_lds_doubles(const DevPack &pk, int n_pops, int n_cand, int m
     return 8 + (size_t)pk.hc_len + tips + (size_t)n_pops * n_cand * mass_cap + (size_t)n_cand * B9_NPARAM + 8;
 }
 
+// dynamic LDS, bytes, of the kernels that evaluate ONE candidate per walker (k_star_like, k_mcmc_tree): the hot role's mass
+// columns (+ 8: find_bracket's last stage may read up to 6 entries past a column's end, masked out) or the heavy role's axes
+static size_t one_candidate_lds(const DevPack &pk, int n_pops, int mass_cap)
+{
+    return sizeof(double) * std::max((size_t)n_pops * mass_cap + 8, heavy_lds_doubles(pk, n_pops, 1, mass_cap));
+}
+
 hipError_t b9k_star_like(const DevPack &pk, const DevStars &st, const B9IsoSet &set, int n_walkers, const B9Partial &partial, double *perstar,
                          const B9Groups &gr, int heavy_parts, hipStream_t stream)
 {
     return dispatch(pk.nfp, set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        // + 8: find_bracket's last stage may read up to 6 entries past a column's end (masked out)
-        const auto k = with_lds(k_star_like<NFP, NPOPS>, sizeof(double) * std::max((size_t)NPOPS * set.mass_cap + 8, heavy_lds_doubles(pk, NPOPS, 1, set.mass_cap)));
+        const auto k = with_lds(k_star_like<NFP, NPOPS>, one_candidate_lds(pk, NPOPS, set.mass_cap));
         if (k.err != hipSuccess) return k.err;
         const int hot = 8 * ((gr.n_blocks * NPOPS + 7) / 8) * n_walkers;     // padded so every XCD sees whole walker sets (two populations: a workgroup per half tile)
         const int heavy = (n_walkers * heavy_parts + 7) / 8 * 8;     // heavy-star workgroups lead the grid
@@ -650,10 +656,15 @@ hipError_t b9k_marg_step(const DevPack &pk, const DevStars &st, const StepDev &s
 // ---- the fused sampler step (k_mcmc_step) ------------------------------------------------------------------------
 // k_mcmc_step's instance and its dynamic LDS: the hot role's mass columns of both candidates (+ 8: find_bracket's masked
 // over-read), or the heavy role's axes, whichever is larger
+static size_t mcmc_step_lds(const DevPack &pk, int n_pops, int mass_cap)
+{
+    return sizeof(double) * std::max((size_t)2 * n_pops * mass_cap + 8, heavy_lds_doubles(pk, n_pops, 2, mass_cap));
+}
+
 template <int NFP, int NPOPS>
 static auto mcmc_step_kernel(const DevPack &pk, int mass_cap)
 {
-    return with_lds(k_mcmc_step<NFP, NPOPS>, sizeof(double) * std::max((size_t)2 * NPOPS * mass_cap + 8, heavy_lds_doubles(pk, NPOPS, 2, mass_cap)));
+    return with_lds(k_mcmc_step<NFP, NPOPS>, mcmc_step_lds(pk, NPOPS, mass_cap));
 }
 
 // Workgroups of the fused step that one CU holds at once for the loaded pack (registers, LDS, wave slots of THIS
@@ -708,8 +719,28 @@ static bool tree_large(int n_groups) { return n_groups > 16 * B9_TREE_KD_SMALL; 
 template <int NFP, int NPOPS>
 static auto mcmc_tree_kernel(const DevPack &pk, int mass_cap, int n_groups)
 {
-    return with_lds(tree_large(n_groups) ? tree_kd5::k_mcmc_tree<NFP, NPOPS> : tree_kd3::k_mcmc_tree<NFP, NPOPS>,
-                    sizeof(double) * std::max((size_t)NPOPS * mass_cap + 8, heavy_lds_doubles(pk, NPOPS, 1, mass_cap)));
+    return with_lds(tree_large(n_groups) ? tree_kd5::k_mcmc_tree<NFP, NPOPS> : tree_kd3::k_mcmc_tree<NFP, NPOPS>, one_candidate_lds(pk, NPOPS, mass_cap));
+}
+
+// LDS of the launch that carries a given-mass block's heavy role -- the fused step, the tree launch's build for a catalogue of
+// n_groups canonical groups, or the two-launch form's k_star_like: the dynamic request and, where that alone passes 64 KB, the
+// kernel's static LDS beside it (no launch).
+hipError_t b9k_step_lds(const DevPack &pk, int n_pops, int mass_cap, B9StepKind kind, int n_groups, size_t *dynamic_bytes, size_t *static_bytes)
+{
+    *dynamic_bytes = kind == B9_STEP_FUSED ? mcmc_step_lds(pk, n_pops, mass_cap) : one_candidate_lds(pk, n_pops, mass_cap);
+    *static_bytes = 0;
+    if (*dynamic_bytes <= 64 * 1024) return hipSuccess;
+    return dispatch(pk.nfp, n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        const void *kern = kind == B9_STEP_FUSED ? reinterpret_cast<const void *>(k_mcmc_step<NFP, NPOPS>)
+                         : kind == B9_STEP_STAR_LIKE ? reinterpret_cast<const void *>(k_star_like<NFP, NPOPS>)
+                         : tree_large(n_groups) ? reinterpret_cast<const void *>(tree_kd5::k_mcmc_tree<NFP, NPOPS>)
+                                                : reinterpret_cast<const void *>(tree_kd3::k_mcmc_tree<NFP, NPOPS>);
+        hipFuncAttributes attr;
+        const hipError_t e = hipFuncGetAttributes(&attr, kern);
+        if (e == hipSuccess) *static_bytes = attr.sharedSizeBytes;
+        return e;
+    });
 }
 
 hipError_t b9k_mcmc_tree_occupancy(const DevPack &pk, int n_pops, int mass_cap, int n_groups, int *blocks_per_cu)

@@ -103,6 +103,14 @@ hipError_t b9k_mcmc_begin(const double *host_up, double *dev, int up_words, cons
 // the block's last decision only (one workgroup per walker)
 hipError_t b9k_mcmc_finish(const DevPack &pk, const StepDev &sd, const DevPriors &pr, hipStream_t stream);
 
+// LDS the launch that carries a given-mass block's heavy role asks for -- the fused step, the tree launch (n_groups: the
+// catalogue's canonical groups, which select the kernel build) or the two-launch form's k_star_like.  Once the tip table
+// passes B9_TIPS_LDS_MAX entries the heavy role stages 4 AGB-tip columns of n_age doubles per candidate and population, so the
+// age axis bounds it.  The caller refuses a block whose request passes B9_LDS_PER_CU before it launches anything.
+#define B9_LDS_PER_CU ((size_t)160 * 1024)
+enum B9StepKind { B9_STEP_FUSED, B9_STEP_TREE, B9_STEP_STAR_LIKE };
+hipError_t b9k_step_lds(const DevPack &pk, int n_pops, int mass_cap, B9StepKind kind, int n_groups, size_t *dynamic_bytes, size_t *static_bytes);
+
 // tree-speculative step (given-mass mode, few walkers): one launch = `depth` steps of every chain (TreeDev in b9_device.h)
 hipError_t b9k_mcmc_tree(const DevPack &pk, const DevStars &st, const TreeDev &td, const DevPriors &pr, int group_tiles /* tiles of a canonical group */,
                          int derive_parts, hipStream_t stream);

@@ -282,6 +282,10 @@ typedef struct b9_mcmc_block {
     void *rows_ready;            /* out: hipEvent_t                                            */
 } b9_mcmc_block;
 #define B9_ROW_DOUBLES(d) (15 + (d) + (d) * (d))
+/* B9_ERR_CAPACITY (given-mass mode, every launch form): the pack is too large for the LDS of the kernel that carries the heavy
+ * role -- which stages 4 AGB-tip columns of n_age doubles per candidate and population once the tip table passes 2048 entries,
+ * so in practice the age axis is too long.  Refused before anything is uploaded or launched; the message names the axis length
+ * (or, with the tips staged whole, the pack's table sizes) and the bytes asked for. */
 int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk);
 
 /*
