@@ -29,6 +29,10 @@ WDM_CONTINUE = 1
 HQ_PRIMARY, HQ_SECONDARY, HQ_SYSTEM = range(3)
 HIST_MAX_BINS = 64
 HIST_CONTINUE = 1
+# b9_ratio_hist: the most mass bins and cells (mass bins x ratio nodes) of a call and its flag
+RH_MAX_MBINS = 16
+RH_MAX_CELLS = 128
+RH_CONTINUE = 1
 # b9_star_bins: the most bins of a call and its flag (columns of acc: below, the bins, at or above, the total)
 SBIN_MAX_BINS = 30
 SBIN_CONTINUE = 1
@@ -219,7 +223,7 @@ ABI_SYMBOLS = [
     "b9_abi_version", "b9_ctx_create", "b9_ctx_destroy", "b9_last_error",
     "b9_load_pack", "b9_load_stars", "b9_set_priors", "b9_set_options", "b9_set_tuning", "b9_get_tuning",
     "b9_logpost", "b9_logpost_device", "b9_mcmc_run_block", "b9_mcmc_wait", "b9_sample_mass", "b9_derive_isochrone",
-    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_star_moments", "b9_wd_moments", "b9_mass_hist", "b9_star_bins", "b9_wd_bins", "b9_phot_resid", "b9_pointwise", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
+    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_star_moments", "b9_wd_moments", "b9_mass_hist", "b9_ratio_hist", "b9_star_bins", "b9_wd_bins", "b9_phot_resid", "b9_pointwise", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
     "b9_enable_timing", "b9_kernel_time_ms", "b9_calibrate_timing", "b9_clock_stamp", "b9_clock_mhz",
 ]
 
@@ -257,6 +261,7 @@ def load_hip_library(path: Optional[str] = None) -> C.CDLL:
     lib.b9_star_moments.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp]
     lib.b9_wd_moments.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp]
     lib.b9_mass_hist.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, _dp]
+    lib.b9_ratio_hist.argtypes = [vp, _dp, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, _dp]
     lib.b9_star_bins.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _dp]
     lib.b9_wd_bins.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _dp]
     lib.b9_phot_resid.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, _dp]

@@ -500,6 +500,25 @@ int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quan
     });
 }
 
+int b9_ratio_hist(b9_ctx *ctx, const double *params, int32_t n_rows, const double *mass_edges, int32_t n_mbins, int32_t flags,
+                  double *star_cells, double *row_cells)
+{
+    if (!ctx || !params || !mass_edges || n_rows < 1 || (!star_cells && !row_cells)) return B9_ERR_INVALID;
+    if (n_mbins < 1 || n_mbins > B9_RH_MAX_MBINS) return fail(ctx, B9_ERR_INVALID, "b9_ratio_hist: n_mbins must lie in 1 .. B9_RH_MAX_MBINS");
+    const int Q = marg_grid(ctx).Q;
+    if (Q < 1 || Q > B9_RH_MAX_Q) return fail(ctx, B9_ERR_INVALID, "b9_ratio_hist: marg_n_q must lie in 1 .. 64");
+    if ((size_t)n_mbins * (size_t)Q > B9_RH_MAX_CELLS) return fail(ctx, B9_ERR_INVALID, "b9_ratio_hist: n_mbins * marg_n_q must not exceed B9_RH_MAX_CELLS");
+    for (int b = 0; b <= n_mbins; ++b)
+        if (!std::isfinite(mass_edges[b]) || (b > 0 && !(mass_edges[b] > mass_edges[b - 1])))
+            return fail(ctx, B9_ERR_INVALID, "b9_ratio_hist: the mass edges must be finite and strictly ascending");
+    if (const int rc = chain_ready(ctx)) return rc;
+    const size_t ncol = (size_t)n_mbins * Q + 1;
+    const ChainCall c{"b9_ratio_hist", ncol, ncol, ncol, B9_HIST_MAX_ROWS, B9_HIST_SCRATCH_BYTES, (flags & B9_RH_CONTINUE) != 0, star_cells, row_cells, {}};
+    return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
+        return b9k_ratio_hist(ctx->pk, ctx->st, d, m, mass_edges, n_mbins, ctx->stream);
+    });
+}
+
 int b9_star_bins(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quantity, const double *edges, int32_t n_bins, int32_t flags, double *acc)
 {
     if (!ctx || !params || !edges || !acc || n_rows < 1) return B9_ERR_INVALID;

@@ -35,6 +35,8 @@
 //                                     grid (one lane per star, four waves sharing the node table), summed over the rows
 //   k_star_hist / _wd / k_hist_rows   b9_mass_hist: exact binned mass posteriors over the same grid (a
 //                                     per-wave LDS histogram per lane, bins worked in tiles), summed over the rows and the stars
+//   k_star_ratio / _wd                b9_ratio_hist: the joint table (primary-mass bin x mass-ratio node) of the same weights
+//                                     (k_star_hist's frame, a tile holds whole mass bins), summed over the rows and the stars
 //   k_star_bins / _wd                b9_star_bins: the same bins on every star's OWN edges with the two open ends kept (the
 //                                     bin is per lane, the edges staged in LDS), summed over the rows
 //   k_wd_bins                        b9_wd_bins: b9_wd_moments' node weights binned on every (WD-stage star, quantity)'s OWN
@@ -88,6 +90,7 @@ namespace tree_kd5 {
 #include "b9_star_moments.hip.h"
 #include "b9_wd_moments.hip.h"
 #include "b9_mass_hist.hip.h"
+#include "b9_ratio_hist.hip.h"
 #include "b9_star_bins.hip.h"
 #include "b9_wd_bins.hip.h"
 #include "b9_phot_resid.hip.h"
@@ -407,6 +410,36 @@ hipError_t b9k_mass_hist(const DevPack &pk, const DevStars &st, const B9Chain &c
             hipLaunchKernelGGL((k_star_hist_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, s.hdr, s.params, c.mg.K,
                                c.mg.wd_tab, ed, c.scratch);
         const int ncol = n_bins + 1;
+        if (c.acc) launch_chain_accumulate(c.scratch, n_rows, (long long)st.n * ncol, c.acc, stream);
+        if (c.rows)
+            hipLaunchKernelGGL(k_hist_rows, dim3((unsigned)((n_rows * ncol + 255) / 256)), dim3(256), 0, stream, c.scratch, n_rows, st.n, ncol, c.rows);
+        return hipGetLastError();
+    });
+}
+
+// ---- b9_ratio_hist: the node tables of a chunk of rows, the stars' (mass bin, ratio node) increments, the accumulation, the rows' sums
+hipError_t b9k_ratio_hist(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, const double *mass_edges, int n_mbins, hipStream_t stream)
+{
+    return dispatch(pk.nfp, c.set.n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        const B9IsoSet &s = c.set;
+        const int Q = c.mg.Q;
+        if (!mass_edges || n_mbins < 1 || n_mbins > B9_RH_MAX_MBINS || Q < 1 || Q > B9_RH_MAX_Q || n_mbins * Q > B9_RH_MAX_CELLS) return hipErrorInvalidValue;
+        HistEdges ed{};
+        for (int b = 0; b <= n_mbins; ++b) ed.e[b] = mass_edges[b];
+        ed.n_bins = n_mbins; ed.quantity = B9_HQ_PRIMARY;
+        const ChainTables t = chain_tables<NFP>(pk, st, c, n_rows, stream);
+        if (t.err != hipSuccess) return t.err;
+        // a tile of whole mass bins: one histogram [mass bins of the tile x Q][64] per wave
+        const int mpt = std::max(1, B9_HIST_TILE / Q), tc = std::min(n_mbins, mpt) * Q, n_tiles = (n_mbins + mpt - 1) / mpt;
+        const auto k = with_lds(k_star_ratio<NFP, NPOPS>, sizeof(double) * 64 * (NPOPS * 4 + 4 * 2 + 4 * (size_t)tc));      // seeds, states, histograms
+        if (k.err != hipSuccess) return k.err;
+        hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows, n_tiles), dim3(256), k.lds, stream, st, s.hdr, s.iso, s.iso_stride, s.mass_cap,
+                           s.params, c.mg.K, Q, c.mg.tab, t.L, t.cut2, ed, mpt, tc, c.scratch);
+        if (st.n_wd > 0)
+            hipLaunchKernelGGL((k_star_ratio_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, s.hdr, s.params, c.mg.K,
+                               Q, c.mg.wd_tab, ed, c.scratch);
+        const int ncol = n_mbins * Q + 1;
         if (c.acc) launch_chain_accumulate(c.scratch, n_rows, (long long)st.n * ncol, c.acc, stream);
         if (c.rows)
             hipLaunchKernelGGL(k_hist_rows, dim3((unsigned)((n_rows * ncol + 255) / 256)), dim3(256), 0, stream, c.scratch, n_rows, st.n, ncol, c.rows);

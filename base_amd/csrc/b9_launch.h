@@ -176,6 +176,12 @@ hipError_t b9k_star_moments(const DevPack &pk, const DevStars &st, const B9Chain
 hipError_t b9k_mass_hist(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, int quantity, const double *edges, int n_bins,
                          hipStream_t stream);
 
+// b9_ratio_hist: every star's (primary-mass bin, ratio node) increments into scratch [n_rows][st.n][n_mbins Q + 1] (Q = c.mg.Q,
+// at most B9_RH_MAX_Q), then acc [st.n][n_mbins Q + 1] (may be null) and rows [n_rows][n_mbins Q + 1] (may be null).
+// mass_edges: HOST, [n_mbins + 1], validated by the caller; they travel as kernel arguments.
+#define B9_RH_MAX_Q 64
+hipError_t b9k_ratio_hist(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, const double *mass_edges, int n_mbins, hipStream_t stream);
+
 // b9_star_bins: every star's increments on its own edges into scratch [n_rows][st.n][n_bins + 3] (below, the bins, at or above, the
 // total), then acc [st.n][n_bins + 3].  edges: DEVICE, [st.n][n_bins + 1] in the caller's star order, validated by the caller.
 hipError_t b9k_star_bins(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, int quantity, const double *edges, int n_bins,

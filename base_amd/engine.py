@@ -267,6 +267,30 @@ class Engine:
                                           ptr(sh), ptr(rh)))
         return sh, rh
 
+    def ratio_hist(self, rows: np.ndarray, mass_edges: np.ndarray, star_cells: Optional[np.ndarray] = None, want_star: bool = True,
+                   want_rows: bool = True) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+        """b9_ratio_hist: the exact mass-ratio posteriors by primary mass over `rows` for the mass bins `mass_edges`
+        [n_mbins + 1]: (star_cells [n_stars, n_mbins Q + 1] summed over the rows, row_cells [n_rows, n_mbins Q + 1] summed over
+        the stars), Q = max(1, options.marg_n_q); column b Q + j is (mass bin b, ratio node j), the last column the total (membership).
+        star_cells=None starts from zeros; else the call continues it (B9_RH_CONTINUE) and returns a new array.  want_star /
+        want_rows = False passes NULL for that output (None back)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        edges = np.ascontiguousarray(mass_edges, dtype=np.float64).reshape(-1)
+        n_mbins = len(edges) - 1
+        ncol = max(n_mbins, 0) * max(1, int(self.options.marg_n_q)) + 1
+        flags = 0
+        sc = rc = None
+        if want_star:
+            if star_cells is None:
+                sc = np.zeros((self.n_stars, ncol))
+            else:
+                sc, flags = np.array(star_cells, dtype=np.float64, order="C").reshape(self.n_stars, ncol), abi.RH_CONTINUE
+        if want_rows:
+            rc = np.zeros((rows.shape[0], ncol))
+        ptr = lambda a: a.ctypes.data_as(_dp) if a is not None else None      # noqa: E731
+        self._check(self.lib.b9_ratio_hist(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], edges.ctypes.data_as(_dp), n_mbins, flags, ptr(sc), ptr(rc)))
+        return sc, rc
+
     def star_bins(self, rows: np.ndarray, edges: np.ndarray, quantity: int = abi.HQ_PRIMARY, acc: Optional[np.ndarray] = None) -> np.ndarray:
         """b9_star_bins: every star's node weights over `rows` binned on that star's OWN edges `edges` [n_stars, n_bins + 1] of
         `quantity` (abi.HQ_*): acc [n_stars, n_bins + 3] -- below, the bins, at or above, the total (membership).  acc=None

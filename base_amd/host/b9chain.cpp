@@ -887,4 +887,199 @@ void read_pointwise(const std::string &path, std::vector<std::string> &ids, std:
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// binaryStats
+// ---------------------------------------------------------------------------------------------
+const ProgramFlags kBinaryStatsFlags = {{"nPops", "binaryStatsNPops", false}};
+
+BinaryStatsConfig binary_stats_config(const Settings &st, double max_mass, int Q)
+{
+    BinaryStatsConfig c;
+    c.q_min = st.num("binaryStats.qMin", 0.0);
+    if (!(c.q_min >= 0.0 && c.q_min <= 1.0)) fail("binaryStats.qMin must lie in 0 .. 1");
+    if (st.has("binaryStats.massEdges")) {
+        if (st.has("binaryStats.massBins")) fail("binaryStats: give massEdges or massBins, not both");
+        std::string ev = st.str("binaryStats.massEdges");
+        for (char &ch : ev) if (ch == ',' || ch == '[' || ch == ']') ch = ' ';
+        std::istringstream es(ev);
+        std::string tok;
+        while (es >> tok) {
+            char *end = nullptr;
+            const double v = std::strtod(tok.c_str(), &end);
+            if (end == tok.c_str() || *end) fail("binaryStats.massEdges: '" + tok + "' is not a number");
+            c.edges.push_back(v);
+        }
+    } else {
+        const long n = st.integer("binaryStats.massBins", std::max(1, std::min(8, B9_RH_MAX_CELLS / std::max(1, Q))));
+        if (n < 1 || n > B9_RH_MAX_MBINS) fail("binaryStats.massBins must lie in 1 .. " + std::to_string(B9_RH_MAX_MBINS));
+        const double lo = 0.1;
+        if (!std::isfinite(max_mass) || !(max_mass > lo)) fail("binaryStats: the models' largest mass must exceed 0.1");
+        c.edges.resize((size_t)n + 1);
+        for (long b = 0; b <= n; ++b) c.edges[(size_t)b] = lo * std::pow(max_mass / lo, (double)b / (double)n);
+        c.edges[0] = lo; c.edges[(size_t)n] = max_mass;
+    }
+    const long n_mbins = (long)c.edges.size() - 1;
+    if (n_mbins < 1 || n_mbins > B9_RH_MAX_MBINS) fail("binaryStats: 1 .. " + std::to_string(B9_RH_MAX_MBINS) + " mass bins (2 .. 17 edges) are allowed");
+    if (n_mbins * Q > B9_RH_MAX_CELLS) fail("binaryStats: mass bins x nMassRatios must not exceed " + std::to_string(B9_RH_MAX_CELLS));
+    for (long b = 0; b <= n_mbins; ++b)
+        if (!std::isfinite(c.edges[(size_t)b]) || (b > 0 && !(c.edges[(size_t)b] > c.edges[(size_t)b - 1])))
+            fail("binaryStats: the mass edges must be finite and strictly ascending");
+    return c;
+}
+
+namespace {
+// mean, population standard deviation and 16th / 50th / 84th percentiles of v (mass_function_table's arithmetic) -> t[0 .. 4]; v is sorted
+void five_stats(std::vector<double> &v, double *t)
+{
+    double sum = 0.0;
+    for (double x : v) sum += x;
+    const double mean = sum / (double)v.size();
+    double ss = 0.0;
+    for (double x : v) ss += (x - mean) * (x - mean);
+    std::sort(v.begin(), v.end());
+    t[0] = mean;
+    t[1] = std::sqrt(ss / (double)v.size());
+    t[2] = percentile_sorted(v, 0.16); t[3] = percentile_sorted(v, 0.50); t[4] = percentile_sorted(v, 0.84);
+}
+
+void check_ratio_grid(const char *who, int n_mbins, int Q, double q_min)
+{
+    if (n_mbins < 1 || Q < 1) fail(std::string(who) + ": n_mbins and Q must be positive");
+    if (!(q_min >= 0.0 && q_min <= 1.0)) fail(std::string(who) + ": q_min must lie in 0 .. 1");
+}
+
+// does ratio node j of Q count as a binary at q_min?
+bool ratio_counts(int j, int Q, double q_min) { return j >= 1 && (double)j / (double)Q >= q_min; }
+
+// The lines of b9_ratio_hist's row_cells [n_rows][n_mbins Q + 1]: line b < n_mbins is mass bin b, line n_mbins is "all" (the bins'
+// cells added in ascending b).  fn(line, rows, cells): rows = the rows with member column > 0 and N > 0 of that line, cells
+// [rows][Q] theirs, in row order.
+template <class Fn> void for_ratio_lines(const double *row_cells, long n_rows, int n_mbins, int Q, Fn &&fn)
+{
+    const size_t ncol = (size_t)n_mbins * Q + 1;
+    std::vector<double> line((size_t)Q), cells;
+    for (int ln = 0; ln <= n_mbins; ++ln) {
+        cells.clear();
+        long used = 0;
+        for (long r = 0; r < n_rows; ++r) {
+            const double *x = row_cells + (size_t)r * ncol;
+            if (!(x[ncol - 1] > 0.0)) continue;
+            for (int j = 0; j < Q; ++j) {
+                if (ln < n_mbins) { line[(size_t)j] = x[(size_t)ln * Q + j]; continue; }
+                double a = 0.0;
+                for (int b = 0; b < n_mbins; ++b) a = a + x[(size_t)b * Q + j];
+                line[(size_t)j] = a;
+            }
+            double N = 0.0;
+            for (int j = 0; j < Q; ++j) N = N + line[(size_t)j];
+            if (!(N > 0.0)) continue;
+            cells.insert(cells.end(), line.begin(), line.end());
+            ++used;
+        }
+        fn(ln, used, cells.data());
+    }
+}
+}  // namespace
+
+void binary_table(const double *row_cells, long n_rows, const double *mass_edges, int n_mbins, int Q, double q_min, double *table)
+{
+    check_ratio_grid("binary_table", n_mbins, Q, q_min);
+    for_ratio_lines(row_cells, n_rows, n_mbins, Q, [&](int ln, long used, const double *cells) {
+        double *t = table + (size_t)ln * kBinaryTableCols;
+        for (int c = 0; c < kBinaryTableCols; ++c) t[c] = 0.0;
+        t[0] = ln < n_mbins ? mass_edges[ln] : mass_edges[0];
+        t[1] = ln < n_mbins ? mass_edges[ln + 1] : mass_edges[n_mbins];
+        t[2] = (double)used;
+        if (!used) return;
+        std::vector<double> vn((size_t)used), vf((size_t)used);
+        for (long k = 0; k < used; ++k) {
+            const double *x = cells + (size_t)k * Q;
+            double N = 0.0, B = 0.0;
+            for (int j = 0; j < Q; ++j) N = N + x[j];
+            for (int j = 0; j < Q; ++j) if (ratio_counts(j, Q, q_min)) B = B + x[j];
+            vn[(size_t)k] = N; vf[(size_t)k] = B / N;
+        }
+        five_stats(vn, t + 3);
+        five_stats(vf, t + 8);
+    });
+}
+
+void ratio_dist_table(const double *row_cells, long n_rows, int n_mbins, int Q, double *table)
+{
+    check_ratio_grid("ratio_dist_table", n_mbins, Q, 0.0);
+    for_ratio_lines(row_cells, n_rows, n_mbins, Q, [&](int ln, long used, const double *cells) {
+        std::vector<double> v((size_t)used);
+        for (int j = 0; j < Q; ++j) {
+            double *t = table + ((size_t)ln * Q + j) * kRatioDistCols;
+            for (int c = 0; c < kRatioDistCols; ++c) t[c] = 0.0;
+            t[0] = (double)j; t[1] = (double)j / (double)Q; t[2] = (double)used;
+            if (!used) continue;
+            for (long k = 0; k < used; ++k) {
+                const double *x = cells + (size_t)k * Q;
+                double N = 0.0;
+                for (int i = 0; i < Q; ++i) N = N + x[i];
+                v[(size_t)k] = x[j] / N;
+            }
+            five_stats(v, t + 3);
+        }
+    });
+}
+
+void star_ratio_table(const double *star_cells, long n_stars, int n_mbins, int Q, double q_min, long n_rows_in_grid, double *table)
+{
+    check_ratio_grid("star_ratio_table", n_mbins, Q, q_min);
+    const size_t ncol = (size_t)n_mbins * Q + 1, tcol = 4 + (size_t)Q;
+    for (long i = 0; i < n_stars; ++i) {
+        const double *a = star_cells + (size_t)i * ncol, tot = a[ncol - 1];
+        double *t = table + (size_t)i * tcol;
+        for (size_t c = 0; c < tcol; ++c) t[c] = 0.0;
+        t[0] = (double)n_rows_in_grid;
+        if (n_rows_in_grid > 0) t[1] = tot / (double)n_rows_in_grid;
+        if (!(tot > 0.0)) continue;                          // no membership weight: every derived value is 0
+        double in = 0.0, above = 0.0;
+        for (int j = 0; j < Q; ++j) {
+            double s = 0.0;
+            for (int b = 0; b < n_mbins; ++b) s = s + a[(size_t)b * Q + j];
+            in = in + s;
+            if (ratio_counts(j, Q, q_min)) above = above + s;
+            t[4 + j] = s / tot;
+        }
+        t[2] = in / tot;
+        t[3] = above / tot;
+    }
+}
+
+namespace {
+std::vector<std::string> ratio_line_labels(int n_mbins, int per_line)
+{
+    std::vector<std::string> labels;
+    for (int ln = 0; ln <= n_mbins; ++ln)
+        for (int k = 0; k < per_line; ++k) labels.push_back(ln < n_mbins ? std::to_string(ln) : "all");
+    return labels;
+}
+}  // namespace
+
+void write_binary_fraction(const std::string &path, const double *table, int n_mbins)
+{
+    std::vector<TableColumn> cols = columns({"lo", "hi", "nRows", "N_mean", "N_sd", "N_p16", "N_p50", "N_p84", "f_mean", "f_sd", "f_p16", "f_p50", "f_p84"}, "%.17g");
+    cols[2].fmt = "%ld";
+    const std::vector<std::string> labels = ratio_line_labels(n_mbins, 1);
+    write_table(path, "bin", &labels, cols, n_mbins + 1, table, kBinaryTableCols);
+}
+
+void write_ratio_dist(const std::string &path, const double *table, int n_mbins, int Q)
+{
+    std::vector<TableColumn> cols = columns({"j", "q", "nRows", "mean", "sd", "p16", "p50", "p84"}, "%.17g");
+    cols[0].fmt = "%ld"; cols[2].fmt = "%ld";
+    const std::vector<std::string> labels = ratio_line_labels(n_mbins, Q);
+    write_table(path, "bin", &labels, cols, (long)(n_mbins + 1) * Q, table, kRatioDistCols);
+}
+
+void write_star_ratio(const std::string &path, const std::vector<std::string> &ids, const double *table, int Q)
+{
+    std::vector<TableColumn> cols = {{"rows", "%ld"}, {"member", "%.17g"}, {"inRange", "%.17g"}, {"pBinaryAbove", "%.17g"}};
+    for (int j = 0; j < Q; ++j) cols.push_back({"q" + std::to_string(j), "%.17g"});
+    write_table(path, "id", &ids, cols, (long)ids.size(), table, cols.size());
+}
+
 }  // namespace b9h

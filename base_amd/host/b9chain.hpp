@@ -1,5 +1,5 @@
 // b9chain.hpp -- what the programs over a saved chain (sampleMass, sampleWDMass, starSummary, wdSummary, wdIntervals, massFunction,
-// starIntervals, photResiduals, modelScore) share above the C ABI and below their mains: their settings, the loop over the
+// binaryStats, starIntervals, photResiduals, modelScore) share above the C ABI and below their mains: their settings, the loop over the
 // chain's rows, the tables derived from the device's sums and the files they are written to (docs/FORMATS.md).  Host arithmetic
 // only: nothing here needs a context or a GPU.  b9host.hpp includes this header.
 #pragma once
@@ -203,6 +203,41 @@ void filter_resid_table(const double *row_resid, long n_rows, int nf, double *ta
 // Numbers are written with 17 significant digits: the files read back to the tables' bits.
 void write_phot_resid(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &filters, const double *table);
 void write_filter_resid(const std::string &path, const std::vector<std::string> &filters, const double *table);
+
+// ---- binaryStats -----------------------------------------------------------------------------------
+// binaryStats.{massEdges, massBins, qMin} (flags --massEdges e0,e1,.. | --massBins N, --qMin q).  massEdges: the primary-mass
+// edges as given; else massBins (default min(8, floor(128 / Q))) log-spaced bins over [0.1, max_mass], the end points exactly.
+// 1 .. B9_RH_MAX_MBINS bins, bins x Q <= B9_RH_MAX_CELLS, finite strictly ascending edges, 0 <= qMin <= 1 (default 0).
+extern const ProgramFlags kBinaryStatsFlags;
+struct BinaryStatsConfig {
+    std::vector<double> edges;               // n_mbins + 1
+    double q_min;
+    int n_mbins() const { return (int)edges.size() - 1; }
+};
+BinaryStatsConfig binary_stats_config(const Settings &st, double max_mass, int Q);
+// The tables of b9_ratio_hist's outputs (DESIGN.md section 2 states the arithmetic).  A LINE is a mass bin b < n_mbins or, last, "all":
+// its cells per row are cell[j] = row_cells[r][b Q + j], for "all" the bins' cells added in ascending b.  Per row N = sum_j cell[j]
+// (ascending j), B = sum of the cell[j] with j >= 1 and (double)j / (double)Q >= q_min (ascending j), f = B / N.  A line's rows are
+// those with member column (the last) > 0 and N > 0; the statistics are the mean, the population standard deviation and the 16th /
+// 50th / 84th percentiles by mass_function_table's rule, every one 0 without such a row.
+//   binary_table      -> [n_mbins + 1][kBinaryTableCols]: lo, hi (the line's edges; "all": e_0, e_last), the number of rows, the
+//                        five statistics of N, the five of f
+//   ratio_dist_table  -> [n_mbins + 1][Q][kRatioDistCols]: j, q = j / Q, the number of rows, the five statistics of cell[j] / N
+//   star_ratio_table  b9_ratio_hist's star_cells [n_stars][n_mbins Q + 1] -> [n_stars][4 + Q]: rows = n_rows_in_grid (the call
+//                        does not count rows: the caller passes the number it summed), member = total / rows, then with
+//                        S_j = sum_b cell(b, j) (ascending b): inRange = (sum_j S_j) / total, pBinaryAbove = (sum of the S_j
+//                        that pass q_min) / total (both ascending j), and q<j> = S_j / total = P(q = j / Q | member) for every
+//                        j.  total == 0: every derived value is 0.
+constexpr int kBinaryTableCols = 13, kRatioDistCols = 8;
+void binary_table(const double *row_cells, long n_rows, const double *mass_edges, int n_mbins, int Q, double q_min, double *table);
+void ratio_dist_table(const double *row_cells, long n_rows, int n_mbins, int Q, double *table);
+void star_ratio_table(const double *star_cells, long n_stars, int n_mbins, int Q, double q_min, long n_rows_in_grid, double *table);
+// <base>.binaryFraction ("bin lo hi nRows N_mean .. N_p84 f_mean .. f_p84", bin = 0 .. n_mbins - 1 then "all"), <base>.ratioDist
+// ("bin j q nRows mean sd p16 p50 p84", Q lines per bin) and <base>.starRatio ("id rows member inRange pBinaryAbove q0 .. q<Q-1>",
+// one line per star in the order of ids).  17 significant digits: the files read back to the tables' bits.
+void write_binary_fraction(const std::string &path, const double *table, int n_mbins);
+void write_ratio_dist(const std::string &path, const double *table, int n_mbins, int Q);
+void write_star_ratio(const std::string &path, const std::vector<std::string> &ids, const double *table, int Q);
 
 // ---- modelScore ------------------------------------------------------------------------------------
 // b9_pointwise's acc [n_stars][8] and tail [n_stars][tail_len] (may be null: no PSIS fit is made) -> the per-star table

@@ -135,6 +135,7 @@ const std::map<std::string, std::string> &Settings::flag_map()
         {"quantities", "wdIntervals.quantities"}, {"wdIntervalsLevels", "wdIntervals.levels"}, {"wdIntervalsTol", "wdIntervals.tol"},
         {"wdIntervalsMaxPasses", "wdIntervals.maxPasses"}, {"wdIntervalsNMassNodes", "wdIntervals.nMassNodes"}, {"wdIntervalsNPops", "wdIntervals.nPops"},
         {"photResidualsPerStar", "photResiduals.perStar"}, {"photResidualsNPops", "photResiduals.nPops"},
+        {"massEdges", "binaryStats.massEdges"}, {"massBins", "binaryStats.massBins"}, {"qMin", "binaryStats.qMin"}, {"binaryStatsNPops", "binaryStats.nPops"},
         {"modelScorePerRow", "modelScore.perRow"}, {"modelScoreNPops", "modelScore.nPops"}, {"compareTo", "modelScore.compareTo"},
         {"nStars", "simCluster.nStars"}, {"percentBinary", "simCluster.percentBinary"}, {"percentDB", "simCluster.percentDB"},
         {"nFieldStars", "simCluster.nFieldStars"}, {"minMass", "simCluster.minMass"}, {"maxMass", "simCluster.maxMass"},

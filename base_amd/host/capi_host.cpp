@@ -230,6 +230,54 @@ int b9h_mass_function_settings(int argc, char **argv, double m_wd_up, char *out,
     });
 }
 
+int b9h_binary_table(const double *row_cells, long n_rows, const double *mass_edges, int n_mbins, int Q, double q_min, double *table)
+{
+    return guard([&] {
+        if (n_rows < 0 || !mass_edges || !table || (n_rows > 0 && !row_cells)) throw std::runtime_error("b9h_binary_table: invalid argument");
+        b9h::binary_table(row_cells, n_rows, mass_edges, n_mbins, Q, q_min, table);
+    });
+}
+
+int b9h_ratio_dist_table(const double *row_cells, long n_rows, int n_mbins, int Q, double *table)
+{
+    return guard([&] {
+        if (n_rows < 0 || !table || (n_rows > 0 && !row_cells)) throw std::runtime_error("b9h_ratio_dist_table: invalid argument");
+        b9h::ratio_dist_table(row_cells, n_rows, n_mbins, Q, table);
+    });
+}
+
+int b9h_star_ratio_table(const double *star_cells, long n_stars, int n_mbins, int Q, double q_min, long n_rows_in_grid, double *table)
+{
+    return guard([&] {
+        if (n_stars < 0 || n_rows_in_grid < 0 || (n_stars > 0 && (!star_cells || !table))) throw std::runtime_error("b9h_star_ratio_table: invalid argument");
+        b9h::star_ratio_table(star_cells, n_stars, n_mbins, Q, q_min, n_rows_in_grid, table);
+    });
+}
+
+int b9h_write_binary_fraction(const char *path, const double *table, int n_mbins)
+{
+    return guard([&] {
+        if (!path || !table || n_mbins < 1) throw std::runtime_error("b9h_write_binary_fraction: invalid argument");
+        b9h::write_binary_fraction(path, table, n_mbins);
+    });
+}
+
+int b9h_write_ratio_dist(const char *path, const double *table, int n_mbins, int Q)
+{
+    return guard([&] {
+        if (!path || !table || n_mbins < 1 || Q < 1) throw std::runtime_error("b9h_write_ratio_dist: invalid argument");
+        b9h::write_ratio_dist(path, table, n_mbins, Q);
+    });
+}
+
+int b9h_write_star_ratio(const char *path, const char *const *ids, long n_stars, const double *table, int Q)
+{
+    return guard([&] {
+        if (!path || n_stars < 0 || Q < 1 || (n_stars > 0 && (!ids || !table))) throw std::runtime_error("b9h_write_star_ratio: invalid argument");
+        b9h::write_star_ratio(path, strings(ids, n_stars), table, Q);
+    });
+}
+
 int b9h_refine_star_edges(const double *edges, const double *acc, long n_stars, int n_bins, const double *levels, int n_levels, double tol,
                           double *lo, double *hi, double *below, double *inside, double *value, int32_t *is_final, int32_t *flags, double *next_edges)
 {

@@ -1,5 +1,5 @@
 """Builds the C++ host programs (base_amd/host/): libbase9host.so + singlePopMcmc, multiPopMcmc,
-makeCMD, sampleMass, sampleWDMass, wdSummary, wdIntervals, starSummary, massFunction, starIntervals, photResiduals, modelScore, simCluster, scatterCluster.  Plain g++ against the C ABI; they link libbase9hip.so by rpath."""
+makeCMD, sampleMass, sampleWDMass, wdSummary, wdIntervals, starSummary, massFunction, binaryStats, starIntervals, photResiduals, modelScore, simCluster, scatterCluster.  Plain g++ against the C ABI; they link libbase9hip.so by rpath."""
 from __future__ import annotations
 
 import os
@@ -56,6 +56,7 @@ def build_host(force: bool = False) -> None:
              "makeCMD": ("makecmd_main.cpp", []), "sampleMass": ("samplemass_main.cpp", []), "sampleWDMass": ("samplewdmass_main.cpp", []),
              "wdSummary": ("wdsummary_main.cpp", []), "wdIntervals": ("wdintervals_main.cpp", []),
              "starSummary": ("starsummary_main.cpp", []), "massFunction": ("massfunction_main.cpp", []),
+             "binaryStats": ("binarystats_main.cpp", []),
              "starIntervals": ("starintervals_main.cpp", []),
              "photResiduals": ("photresiduals_main.cpp", []), "modelScore": ("modelscore_main.cpp", []),
              "simCluster": ("simcluster_main.cpp", []), "scatterCluster": ("scattercluster_main.cpp", [])}

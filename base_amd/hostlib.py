@@ -38,6 +38,7 @@ HOST_SYMBOLS = [
     "b9h_sim_draw_systems", "b9h_sim_field_mags", "b9h_scatter", "b9h_sim_settings", "b9h_read_res_rows",
     "b9h_star_table", "b9h_write_star_summary", "b9h_wd_table", "b9h_write_wd_summary",
     "b9h_mass_function_table", "b9h_write_mass_function", "b9h_write_star_mass_hist", "b9h_mass_function_settings",
+    "b9h_binary_table", "b9h_ratio_dist_table", "b9h_star_ratio_table", "b9h_write_binary_fraction", "b9h_write_ratio_dist", "b9h_write_star_ratio",
     "b9h_refine_star_edges", "b9h_star_intervals_table", "b9h_write_star_intervals", "b9h_star_intervals_settings",
     "b9h_wd_first_ranges", "b9h_wd_intervals_table", "b9h_write_wd_intervals", "b9h_wd_intervals_settings",
     "b9h_resid_table", "b9h_filter_resid_table", "b9h_write_phot_resid", "b9h_write_filter_resid", "b9h_phot_resid_settings",
@@ -97,6 +98,12 @@ def load() -> C.CDLL:
     lib.b9h_write_mass_function.argtypes = [C.c_char_p, _dp, C.c_int]
     lib.b9h_write_star_mass_hist.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int, C.c_long]
     lib.b9h_mass_function_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_double, C.c_char_p, C.c_int, _dp]
+    lib.b9h_binary_table.argtypes = [_dp, C.c_long, _dp, C.c_int, C.c_int, C.c_double, _dp]
+    lib.b9h_ratio_dist_table.argtypes = [_dp, C.c_long, C.c_int, C.c_int, _dp]
+    lib.b9h_star_ratio_table.argtypes = [_dp, C.c_long, C.c_int, C.c_int, C.c_double, C.c_long, _dp]
+    lib.b9h_write_binary_fraction.argtypes = [C.c_char_p, _dp, C.c_int]
+    lib.b9h_write_ratio_dist.argtypes = [C.c_char_p, _dp, C.c_int, C.c_int]
+    lib.b9h_write_star_ratio.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int]
     lib.b9h_refine_star_edges.argtypes = [_dp, _dp, C.c_long, C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
     lib.b9h_star_intervals_table.argtypes = [C.c_long, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
     lib.b9h_write_star_intervals.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int, _dp]
@@ -433,6 +440,65 @@ def mass_function_settings(args, m_wd_up: float = 8.0):
         k, v = line.split(" = ")
         d[k] = float(v) if k in ("minMass", "maxMass") else int(v)
     return d, edges[:d["nBins"] + 1].copy()
+
+
+BINARY_FRACTION_COLUMNS = ("lo", "hi", "nRows", "N_mean", "N_sd", "N_p16", "N_p50", "N_p84", "f_mean", "f_sd", "f_p16", "f_p50", "f_p84")
+RATIO_DIST_COLUMNS = ("j", "q", "nRows", "mean", "sd", "p16", "p50", "p84")
+
+
+def _row_cells(row_cells, n_mbins: int, Q: int) -> np.ndarray:
+    if int(n_mbins) < 1 or int(Q) < 1:
+        raise HostError("n_mbins and Q must be positive")
+    return np.ascontiguousarray(row_cells, dtype=np.float64).reshape(-1, int(n_mbins) * int(Q) + 1)
+
+
+def binary_table(row_cells, mass_edges, Q: int, q_min: float = 0.0) -> np.ndarray:
+    """b9h_binary_table: b9_ratio_hist's row_cells [n_rows, n_mbins Q + 1] -> [n_mbins + 1, 13] (BINARY_FRACTION_COLUMNS): one
+    line per mass bin, then the "all" line; N the line's expected members, f the fraction of them with a companion at
+    j >= 1 and j / Q >= q_min."""
+    edges = np.ascontiguousarray(mass_edges, dtype=np.float64).reshape(-1)
+    n_mbins = len(edges) - 1
+    rc = _row_cells(row_cells, n_mbins, Q)
+    out = np.empty((n_mbins + 1, 13))
+    _check(load().b9h_binary_table(rc.ctypes.data_as(_dp), rc.shape[0], edges.ctypes.data_as(_dp), n_mbins, int(Q), float(q_min), out.ctypes.data_as(_dp)))
+    return out
+
+
+def ratio_dist_table(row_cells, n_mbins: int, Q: int) -> np.ndarray:
+    """b9h_ratio_dist_table: row_cells -> [n_mbins + 1, Q, 8] (RATIO_DIST_COLUMNS): per line and ratio node the statistics of
+    cell / N over the line's rows."""
+    rc = _row_cells(row_cells, n_mbins, Q)
+    out = np.empty((int(n_mbins) + 1, int(Q), 8))
+    _check(load().b9h_ratio_dist_table(rc.ctypes.data_as(_dp), rc.shape[0], int(n_mbins), int(Q), out.ctypes.data_as(_dp)))
+    return out
+
+
+def star_ratio_table(star_cells, n_mbins: int, Q: int, n_rows_in_grid: int, q_min: float = 0.0) -> np.ndarray:
+    """b9h_star_ratio_table: b9_ratio_hist's star_cells [n_stars, n_mbins Q + 1] -> [n_stars, 4 + Q]: rows (= n_rows_in_grid,
+    the number of rows the caller summed), member, inRange, pBinaryAbove, then P(q = j / Q | member) for every j."""
+    sc = _row_cells(star_cells, n_mbins, Q)
+    out = np.empty((sc.shape[0], 4 + int(Q)))
+    _check(load().b9h_star_ratio_table(sc.ctypes.data_as(_dp), sc.shape[0], int(n_mbins), int(Q), float(q_min), int(n_rows_in_grid), out.ctypes.data_as(_dp)))
+    return out
+
+
+def write_binary_fraction(path: str, table) -> None:
+    """b9h_write_binary_fraction: the .binaryFraction file of a table [n_mbins + 1, 13]."""
+    table = np.ascontiguousarray(table, dtype=np.float64).reshape(-1, 13)
+    _check(load().b9h_write_binary_fraction(path.encode(), table.ctypes.data_as(_dp), table.shape[0] - 1))
+
+
+def write_ratio_dist(path: str, table) -> None:
+    """b9h_write_ratio_dist: the .ratioDist file of a table [n_mbins + 1, Q, 8]."""
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    _check(load().b9h_write_ratio_dist(path.encode(), table.ctypes.data_as(_dp), table.shape[0] - 1, table.shape[1]))
+
+
+def write_star_ratio(path: str, ids, table) -> None:
+    """b9h_write_star_ratio: the .starRatio file of a table [len(ids), 4 + Q]."""
+    table = np.ascontiguousarray(table, dtype=np.float64).reshape(len(ids), -1)
+    arr = (C.c_char_p * len(ids))(*[str(i).encode() for i in ids])
+    _check(load().b9h_write_star_ratio(path.encode(), arr, len(ids), table.ctypes.data_as(_dp), table.shape[1] - 4))
 
 
 STAR_INTERVALS_LEVELS = (0.025, 0.16, 0.5, 0.84, 0.975)

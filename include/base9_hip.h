@@ -298,7 +298,7 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk);
  * b9_set_priors or b9_set_options changes the posterior: the previous block's state carries a log-posterior of the old
  * one, so the next B9_BLOCK_CONTINUE block returns B9_ERR_STATE (the message names the call that intervened) and the chain
  * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags, b9_sample_wd_mass, b9_star_moments,
- * b9_wd_moments, b9_wd_bins, b9_mass_hist, b9_phot_resid and b9_pointwise (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
+ * b9_wd_moments, b9_wd_bins, b9_mass_hist, b9_ratio_hist, b9_phot_resid and b9_pointwise (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
  * context's work buffers: b9_logpost / b9_sample_mass / b9_derive_isochrone, the staging calls, b9_set_options and a block
  * with another n_walkers return B9_ERR_STATE until it has been collected.  A driver that adapts the proposal
  * from block b-1 while block b runs keeps the GPU's queue non-empty: enqueue b+1 (CONTINUE | ASYNC), wait(b), ...
@@ -522,6 +522,47 @@ int b9_mass_hist(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t quan
                  const double *edges /* [n_bins + 1] */, int32_t n_bins, int32_t flags,
                  double *star_hist /* host [n_stars][n_bins + 1], in/out, may be NULL */,
                  double *row_hist  /* host [n_rows][n_bins + 1], out,    may be NULL */);
+
+/*
+ * Exact mass-ratio posteriors by primary mass over a saved chain (the binaryStats counterpart).  Added in ABI 6 without a version
+ * change, as its siblings were: purely additive.  Where b9_star_moments keeps P(q > 0) and two moments of q, and b9_mass_hist bins
+ * one mass over the cluster, this call keeps the JOINT table (primary-mass bin x mass-ratio node): which primaries own the
+ * companions, at which ratios -- per star summed over the rows (star_cells) and per row summed over the stars (row_cells).
+ *
+ * Definition.  Grid, terms t_(k,n), L = logsumexp t, w = exp(t - L), the membership p and the pruning are exactly b9_mass_hist's:
+ * terms that are not finite do not take part; n_pops is honoured, mode ignored; b9_tuning.marg_no_pruning disables the pruning.
+ * Q is the grid's number of mass ratios (marg_n_q; the ratio of node j is (double)j / (double)Q, j = 0 .. Q - 1).  mass_edges
+ * (host, [n_mbins + 1]) must be finite and strictly ascending, 1 <= n_mbins <= B9_RH_MAX_MBINS, n_cells = n_mbins * Q <=
+ * B9_RH_MAX_CELLS, Q <= 64.  Mass bin b holds e_b <= M1 < e_(b+1) on the value's own bits, M1 being b9_mass_hist's B9_HQ_PRIMARY
+ * value (MS/RGB: fma(s, dM, a); WD stage: tip + dM j); a node outside the edges falls in no cell but still normalises.  Row r adds
+ * to star i the n_cells + 1 columns
+ *     x[b * Q + j] = p sum_{nodes of ratio j with M1 in bin b} w,        x[n_cells] = p   (the total column)
+ * WD-stage stars have ratio 0 only: their weight goes to column b * Q.  Every entry is 0 where b9_star_moments would add nothing:
+ * a row outside the grid, a star with no live node.
+ *
+ * Order of a column's sum (b9_mass_hist's): every live term is added to its column one at a time in the wave's walk order, the
+ * four waves are merged in wave order, the column is divided by the merged sum of weights, the populations are mixed with the
+ * membership's population weights, the result is multiplied by p.  Hence column n_cells is B9_MOM_MEMBER and b9_mass_hist's total
+ * bit for bit; with marg_n_q = 1 columns 0 .. n_mbins - 1 are b9_mass_hist(B9_HQ_PRIMARY)'s bit for bit; and a cell's bits do not
+ * depend on which other mass bins were asked for.
+ *
+ * star_cells (host, [n_stars][n_cells + 1], the caller's star order, in/out, nullable): acc + x_r, one plain add per row in
+ * ascending row order; flags = 0 starts from zeros, B9_RH_CONTINUE from the caller's values.  row_cells (host,
+ * [n_rows][n_cells + 1], out, nullable): sum_i x_r[i][c] over the caller's star order, ascending, one plain add per star.  The
+ * same bits for the call's own chunking (at most 32 rows at a time, fewer while the per-(row, star) scratch would exceed 64 MiB),
+ * for any split of the rows over continued calls, for any other stars in the catalogue, for a repeated call and after any other
+ * call on the context.  Synchronous; host pointers.  B9_ERR_INVALID (outputs untouched; checked on the host before anything is
+ * launched) for bad edges, n_mbins outside 1 .. B9_RH_MAX_MBINS, n_mbins * Q > B9_RH_MAX_CELLS, Q > 64, n_rows < 1, NULL params or
+ * mass_edges, or both outputs NULL; B9_ERR_STATE while a sampler block is outstanding; B9_ERR_CAPACITY as its siblings.  The call
+ * uses buffers of its own: a B9_BLOCK_CONTINUE block enqueued after it gives the same bits as one enqueued without it.
+ */
+#define B9_RH_MAX_MBINS 16
+#define B9_RH_MAX_CELLS 128
+#define B9_RH_CONTINUE 1
+int b9_ratio_hist(b9_ctx *ctx, const double *params, int32_t n_rows,
+                  const double *mass_edges /* [n_mbins + 1] */, int32_t n_mbins, int32_t flags,
+                  double *star_cells /* host [n_stars][n_mbins * Q + 1], in/out, may be NULL */,
+                  double *row_cells  /* host [n_rows][n_mbins * Q + 1], out,    may be NULL */);
 
 /*
  * Per-star bins over a saved chain (the starIntervals counterpart).  Added in ABI 6 without a version change, as its siblings

@@ -131,6 +131,27 @@ int b9h_mass_function_table(const double *row_hist, long n_rows, const double *e
 int b9h_write_mass_function(const char *path, const double *table, int n_bins);
 int b9h_write_star_mass_hist(const char *path, const char *const *ids, long n_stars, const double *star_hist, int n_bins, long n_rows);
 int b9h_mass_function_settings(int argc, char **argv, double m_wd_up, char *out, int cap, double *edges);
+/* binaryStats.  The tables of b9_ratio_hist's outputs, host arithmetic only.  A LINE is a mass bin b < n_mbins or, last, "all": its
+ * cells per row are cell[j] = row_cells[r][b Q + j], for "all" the bins' cells added in ascending b.  Per row N = sum_j cell[j]
+ * (ascending j), B = sum of the cell[j] with j >= 1 and (double)j / (double)Q >= q_min (ascending j; q_min exactly on a node counts
+ * it), f = B / N.  A line's rows are those with member column (the last) > 0 and N > 0; the statistics are the mean, the population
+ * standard deviation and the 16th / 50th / 84th percentiles by b9h_mass_function_table's rule, every one 0 without such a row.
+ * b9h_binary_table: row_cells [n_rows][n_mbins Q + 1] -> [n_mbins + 1][13]: lo, hi (the line's edges; "all": the first and the last),
+ * the number of rows, the five statistics of N, the five of f.
+ * b9h_ratio_dist_table: -> [n_mbins + 1][Q][8]: j, q = j / Q, the number of rows, the five statistics of cell[j] / N.
+ * b9h_star_ratio_table: star_cells [n_stars][n_mbins Q + 1] -> [n_stars][4 + Q]: rows = n_rows_in_grid (b9_ratio_hist does not count
+ * rows: the caller passes the number it summed), member = total / rows, then with S_j = sum_b cell(b, j) (ascending b): inRange =
+ * (sum_j S_j) / total, pBinaryAbove = (sum of the S_j that pass q_min) / total, and q<j> = S_j / total for every j; total == 0: every
+ * derived value is 0.
+ * Each fails (-1, b9h_last_error) for n_mbins < 1, Q < 1, q_min outside 0 .. 1 or a NULL pointer.
+ * b9h_write_binary_fraction / b9h_write_ratio_dist / b9h_write_star_ratio: the files <base>.binaryFraction, <base>.ratioDist and
+ * <base>.starRatio (docs/FORMATS.md) of those tables, 17 significant digits. */
+int b9h_binary_table(const double *row_cells, long n_rows, const double *mass_edges, int n_mbins, int Q, double q_min, double *table);
+int b9h_ratio_dist_table(const double *row_cells, long n_rows, int n_mbins, int Q, double *table);
+int b9h_star_ratio_table(const double *star_cells, long n_stars, int n_mbins, int Q, double q_min, long n_rows_in_grid, double *table);
+int b9h_write_binary_fraction(const char *path, const double *table, int n_mbins);
+int b9h_write_ratio_dist(const char *path, const double *table, int n_mbins, int Q);
+int b9h_write_star_ratio(const char *path, const char *const *ids, long n_stars, const double *table, int Q);
 /* starIntervals.  b9h_refine_star_edges: one pass of the per-star refinement, a pure function of that pass's edges
  * [n_stars][n_bins + 1], b9_star_bins' acc [n_stars][n_bins + 3] and the levels 0 < a_1 < .. < a_m < 1 (3 m <= n_bins + 1), taken on
  * the counted mass C = below + sum bins + above.  Per star and level ([n_stars][n_levels]): the bracket [lo, hi) of the column in
