@@ -49,6 +49,11 @@ PW_ROWS, PW_NINF, PW_VMAX, PW_SPOS, PW_RMAX, PW_SNEG, PW_MEAN, PW_M2 = range(8)
 PW_N = 8
 PW_MAX_TAIL = 256
 PW_CONTINUE = 1
+# b9_cmd_band: the spec's caps, the moments' columns (the unnamed enum) and the flag
+BAND_MAX_RATIOS, BAND_MAX_COLOURS, BAND_MAX_BINS = 4, 8, 30
+BAND_N, BAND_SUM, BAND_SUMSQ, BAND_MIN, BAND_MAX, BAND_NMOM = range(6)
+BAND_CONTINUE = 1
+BAND_WD_DA, BAND_WD_DB = 1, 2
 STAGE_MSRG, STAGE_WD, STAGE_NSBH, STAGE_BD, STAGE_DNE = 1, 3, 4, 5, 9
 IFMR_WEIDEMANN, IFMR_WILLIAMS, IFMR_SALARIS_LIN, IFMR_SALARIS_PW, IFMR_LINEAR, IFMR_QUADRATIC = range(6)
 MODE_GIVEN_MASS, MODE_MARGINALISED = 0, 1
@@ -113,6 +118,31 @@ class b9_mcmc_block(C.Structure):
                 ("params", _dp), ("logpost", _dp), ("samples", _dp), ("lps", _dp),
                 ("n_accept", C.c_int64),
                 ("row_origin", _dp), ("rows", _dp), ("d_rows", C.c_void_p), ("rows_ready", C.c_void_p)]
+
+
+class b9_band_spec(C.Structure):
+    _fields_ = [("eep0", C.c_int32), ("n_eep", C.c_int32), ("n_ratio", C.c_int32), ("ratio", _dp),
+                ("n_wd_nodes", C.c_int32), ("wd_types", C.c_int32), ("n_colour", C.c_int32), ("colour", _ip)]
+
+
+def make_band_spec(eep0=0, n_eep=0, ratios=(), n_wd_nodes=0, wd_types=0, colours=()) -> Pinned:
+    """A b9_band_spec: EEP ids eep0 .. eep0 + n_eep - 1 at the mass ratios `ratios`, n_wd_nodes WD points per atmosphere type of the
+    mask wd_types (BAND_WD_DA | BAND_WD_DB), colours [(f1, f2), ..] by filter index."""
+    k = {"ratio": _f64(ratios).ravel(), "colour": np.ascontiguousarray(colours, dtype=np.int32).reshape(-1, 2)}
+    s = b9_band_spec()
+    s.eep0, s.n_eep, s.n_ratio = int(eep0), int(n_eep), int(k["ratio"].size)
+    s.ratio = _ptr(k["ratio"], _dp)
+    s.n_wd_nodes, s.wd_types, s.n_colour = int(n_wd_nodes), int(wd_types), int(k["colour"].shape[0])
+    s.colour = _ptr(k["colour"], _ip)
+    return Pinned(s, k)
+
+
+def band_shape(spec: b9_band_spec, n_filt: int, n_pops: int):
+    """(P, C, n_lines) of a spec: points per population, columns per point, lines."""
+    n_types = bin(spec.wd_types & 3).count("1") if spec.n_wd_nodes > 0 else 0
+    P = spec.n_ratio * spec.n_eep + n_types * spec.n_wd_nodes
+    Cc = 1 + n_filt + spec.n_colour
+    return P, Cc, n_pops * P * Cc
 
 
 def row_doubles(d: int) -> int:
@@ -223,7 +253,7 @@ ABI_SYMBOLS = [
     "b9_abi_version", "b9_ctx_create", "b9_ctx_destroy", "b9_last_error",
     "b9_load_pack", "b9_load_stars", "b9_set_priors", "b9_set_options", "b9_set_tuning", "b9_get_tuning",
     "b9_logpost", "b9_logpost_device", "b9_mcmc_run_block", "b9_mcmc_wait", "b9_sample_mass", "b9_derive_isochrone",
-    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_star_moments", "b9_wd_moments", "b9_mass_hist", "b9_ratio_hist", "b9_star_bins", "b9_wd_bins", "b9_phot_resid", "b9_pointwise", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
+    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_star_moments", "b9_wd_moments", "b9_mass_hist", "b9_ratio_hist", "b9_star_bins", "b9_wd_bins", "b9_phot_resid", "b9_pointwise", "b9_cmd_band", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
     "b9_enable_timing", "b9_kernel_time_ms", "b9_calibrate_timing", "b9_clock_stamp", "b9_clock_mhz",
 ]
 
@@ -266,6 +296,7 @@ def load_hip_library(path: Optional[str] = None) -> C.CDLL:
     lib.b9_wd_bins.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _dp]
     lib.b9_phot_resid.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, _dp]
     lib.b9_pointwise.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]
+    lib.b9_cmd_band.argtypes = [vp, _dp, C.c_int32, C.POINTER(b9_band_spec), C.c_int32, _dp, _dp, _dp, C.c_int32, _dp]
     lib.b9_max_eep.argtypes = [vp]
     lib.b9_device_id.argtypes = [vp]
     lib.b9_bytes_per_star_eval.argtypes = [vp]

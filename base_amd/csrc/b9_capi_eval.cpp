@@ -4,7 +4,8 @@
 // (b9_star_moments), the binned mass posteriors (b9_mass_hist), the per-star bins (b9_star_bins), the posterior-predictive
 // residuals (b9_phot_resid) and the pointwise predictive densities (b9_pointwise) --; and the three calls on a WD mass grid of the
 // caller's own size through wd_grid_reduce -- the WD-stage stars' posterior draws (b9_sample_wd_mass), their exact posterior
-// moments (b9_wd_moments) and their per-line bins (b9_wd_bins).  Every launch wrapper takes its derived isochrone set as one
+// moments (b9_wd_moments) and their per-line bins (b9_wd_bins); and the loci a saved chain implies in the CMD (b9_cmd_band: a pack,
+// no stars, its own driver and arena).  Every launch wrapper takes its derived isochrone set as one
 // view (B9IsoSet, b9_launch.h): buffer_set hands out the context's, b9_predict_mags and the two drivers build theirs where they
 // carve their buffers.  A driver fills what its call works on once (ChainDev : B9Chain, WdGridDev : B9WdGrid) and a body hands
 // it to its wrapper whole, with the chunk's row count and the call's own few arguments.
@@ -285,6 +286,112 @@ int b9_predict_mags(b9_ctx *ctx, const double *param_row, int64_t n, const doubl
         HIPCHK(ctx, hipStreamSynchronize(s));      // (the host arrays of the next chunk reuse the same device buffers)
     }
     return B9_OK;
+}
+
+// ---- b9_cmd_band: the loci a saved chain's rows imply, reduced over the rows line by line; a pack, no stars ------------------
+#define B9_BAND_TABLE_BYTES ((size_t)64 << 20)
+#define B9_BAND_MAX_ROWS 256
+
+int b9_cmd_band(b9_ctx *ctx, const double *params, int32_t n_rows, const b9_band_spec *spec, int32_t flags, const double *pivot, double *mom,
+                const double *edges, int32_t n_bins, double *bins)
+{
+    if (!ctx || !params || !spec || n_rows < 1 || (!mom && !bins)) return B9_ERR_INVALID;
+    if (!ctx->have_pack) return fail(ctx, B9_ERR_STATE, "load the pack first");
+    if (block_outstanding(ctx)) return fail(ctx, B9_ERR_STATE, kBlockOutstanding);
+    const DevPack &pk = ctx->pk;
+    const int nf = pk.nf;
+    if (spec->n_eep < 0 || spec->n_ratio < 0 || spec->n_ratio > B9_BAND_MAX_RATIOS || (spec->n_ratio > 0 && !spec->ratio))
+        return fail(ctx, B9_ERR_INVALID, "b9_cmd_band: n_eep must not be negative and n_ratio must lie in 0 .. B9_BAND_MAX_RATIOS");
+    for (int s = 0; s < spec->n_ratio; ++s)
+        if (!std::isfinite(spec->ratio[s]) || spec->ratio[s] < 0.0 || spec->ratio[s] > 1.0) return fail(ctx, B9_ERR_INVALID, "b9_cmd_band: a mass ratio lies in [0, 1]");
+    if (spec->n_eep > 0 && spec->n_ratio == 0) return fail(ctx, B9_ERR_INVALID, "b9_cmd_band: MS/RGB points need a mass ratio");
+    if (spec->n_wd_nodes < 0 || (spec->n_wd_nodes > 0 && (spec->wd_types < 1 || spec->wd_types > 3)))
+        return fail(ctx, B9_ERR_INVALID, "b9_cmd_band: n_wd_nodes must not be negative and wd_types selects DA (1), DB (2) or both (3)");
+    if (spec->n_colour < 0 || spec->n_colour > B9_BAND_MAX_COLOURS || (spec->n_colour > 0 && !spec->colour))
+        return fail(ctx, B9_ERR_INVALID, "b9_cmd_band: n_colour must lie in 0 .. B9_BAND_MAX_COLOURS");
+    for (int c = 0; c < 2 * spec->n_colour; ++c)
+        if (spec->colour[c] < 0 || spec->colour[c] >= nf || spec->colour[c | 1] == spec->colour[c & ~1])
+            return fail(ctx, B9_ERR_INVALID, "b9_cmd_band: a colour takes two different filters of the pack");
+    B9Band b{};
+    B9BandSpec &sp = b.spec;
+    B9IsoSet &set = b.set;
+    set.n_pops = ctx->opt.n_pops == 2 ? 2 : 1;
+    sp.eep0 = spec->eep0; sp.n_eep = spec->n_eep; sp.n_ratio = spec->n_ratio; sp.n_wd_nodes = spec->n_wd_nodes; sp.n_colour = spec->n_colour;
+    for (int s = 0; s < sp.n_ratio; ++s) sp.ratio[s] = spec->ratio[s];
+    for (int c = 0; c < sp.n_colour; ++c) { sp.colour[c][0] = spec->colour[2 * c]; sp.colour[c][1] = spec->colour[2 * c + 1]; }
+    if (sp.n_wd_nodes > 0)
+        for (int t = 0; t < 2; ++t) if (spec->wd_types >> t & 1) sp.type_id[sp.n_types++] = t;
+    const size_t P = (size_t)sp.n_ratio * sp.n_eep + (size_t)sp.n_types * sp.n_wd_nodes, C = 1 + (size_t)nf + sp.n_colour;
+    const size_t n_lines = (size_t)set.n_pops * P * C;
+    if (P == 0) return fail(ctx, B9_ERR_INVALID, "b9_cmd_band: the spec has no lines");
+    if (P > (size_t)1 << 28) return fail(ctx, B9_ERR_CAPACITY, "b9_cmd_band: too many points");
+    sp.P = (int)P; sp.C = (int)C; sp.n_lines = (long long)n_lines;
+    const size_t ne = (size_t)n_bins + 1, nbc = (size_t)n_bins + 3;
+    if (bins) {
+        if (!edges) return fail(ctx, B9_ERR_INVALID, "b9_cmd_band: bins need edges");
+        if (n_bins < 1 || n_bins > B9_BAND_MAX_BINS) return fail(ctx, B9_ERR_INVALID, "b9_cmd_band: n_bins must lie in 1 .. B9_BAND_MAX_BINS");
+        for (size_t l = 0; l < n_lines; ++l)
+            for (size_t e = 0; e < ne; ++e)
+                if (!std::isfinite(edges[l * ne + e]) || (e > 0 && !(edges[l * ne + e] > edges[l * ne + e - 1])))
+                    return fail(ctx, B9_ERR_INVALID, "b9_cmd_band: line " + std::to_string(l) + ": the edges must be finite and strictly ascending");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    set.mass_cap = pack_mass_cap(pk.max_eep); set.iso_stride = pack_iso_stride(set.mass_cap, pk.nfp);
+    // rows of a chunk: at most B9_BAND_MAX_ROWS, and as few as keep the value table and the WD node table within 64 MiB each
+    const size_t tab_row = sp.n_types ? (size_t)set.n_pops * (size_t)b9k_wd_grid_table_doubles(pk.nfp, sp.n_wd_nodes, true) : 0;
+    if (std::max(tab_row, n_lines) > ((size_t)8 << 30) / sizeof(double)) return fail(ctx, B9_ERR_CAPACITY, "b9_cmd_band: one row's tables would exceed 8 GiB");
+    // ... and so does the lines' own state: pivot, moments, bin words, edges
+    if (n_lines > ((size_t)8 << 30) / sizeof(double) / (1 + B9_BAND_NMOM + (bins ? nbc + ne : 0)))
+        return fail(ctx, B9_ERR_CAPACITY, "b9_cmd_band: the lines' pivots, moments, bins and edges would exceed 8 GiB");
+    size_t chunk = std::min<size_t>({(size_t)n_rows, (size_t)B9_BAND_MAX_ROWS, B9_BAND_TABLE_BYTES / (n_lines * sizeof(double))});
+    if (tab_row) chunk = std::min(chunk, B9_BAND_TABLE_BYTES / (tab_row * sizeof(double)));
+    chunk = std::max<size_t>(1, chunk);
+    const BandArena a = band_arena(chunk, set.n_pops, set.iso_stride, tab_row, n_lines, mom ? B9_BAND_NMOM : 0, bins ? nbc : 0, bins ? ne : 0, sizeof(IsoHdr));
+    RESERVE(ctx, ctx->d_band, a.bytes);
+    char *base = ctx->d_band.get();
+    set.params = part<double>(base, a.o_par); set.hdr = part<IsoHdr>(base, a.o_hdr); set.iso = part<double>(base, a.o_iso);
+    b.wd_tab = tab_row ? part<double>(base, a.o_tab) : nullptr; b.values = part<double>(base, a.o_values); b.pivot = part<double>(base, a.o_pivot);
+    b.mom = mom ? part<double>(base, a.o_mom) : nullptr; b.bins = bins ? part<double>(base, a.o_bins) : nullptr;
+    b.edges_t = bins ? part<double>(base, a.o_edges) : nullptr; b.n_bins = bins ? n_bins : 0;
+    // the uploads' sources (they live until the wait below): the starting state when the call does not continue, the edges [b][line]
+    const bool cont = (flags & B9_BAND_CONTINUE) != 0;
+    std::vector<double> mom0, edges_t;
+    hipStream_t s = ctx->stream;
+    const auto enqueue = [&]() -> int {
+        if (pivot) HIPCHK(ctx, hipMemcpyAsync(b.pivot, pivot, sizeof(double) * n_lines, hipMemcpyHostToDevice, s));
+        else HIPCHK(ctx, hipMemsetAsync(b.pivot, 0, sizeof(double) * n_lines, s));
+        if (mom) {
+            if (!cont) {
+                mom0.assign(n_lines * B9_BAND_NMOM, 0.0);
+                for (size_t l = 0; l < n_lines; ++l) { mom0[l * B9_BAND_NMOM + B9_BAND_MIN] = INFINITY; mom0[l * B9_BAND_NMOM + B9_BAND_MAX] = -INFINITY; }
+            }
+            HIPCHK(ctx, hipMemcpyAsync(b.mom, cont ? mom : mom0.data(), sizeof(double) * n_lines * B9_BAND_NMOM, hipMemcpyHostToDevice, s));
+        }
+        if (bins) {
+            if (cont) HIPCHK(ctx, hipMemcpyAsync(b.bins, bins, sizeof(double) * n_lines * nbc, hipMemcpyHostToDevice, s));
+            else HIPCHK(ctx, hipMemsetAsync(b.bins, 0, sizeof(double) * n_lines * nbc, s));
+            edges_t.resize(n_lines * ne);
+            for (size_t l = 0; l < n_lines; ++l)
+                for (size_t e = 0; e < ne; ++e) edges_t[e * n_lines + l] = edges[l * ne + e];
+            HIPCHK(ctx, hipMemcpyAsync(b.edges_t, edges_t.data(), sizeof(double) * n_lines * ne, hipMemcpyHostToDevice, s));
+        }
+        const McmcDev off{};
+        for (int r0 = 0; r0 < n_rows; r0 += (int)chunk) {
+            const int m = std::min((int)chunk, n_rows - r0);
+            HIPCHK(ctx, hipMemcpyAsync(set.params, params + (size_t)r0 * B9_NPARAM, sizeof(double) * B9_NPARAM * m, hipMemcpyHostToDevice, s));
+            HIPCHK(ctx, b9k_derive_iso(pk, set, m, off, ctx->pr, no_prev(), s));
+            HIPCHK(ctx, b9k_cmd_band(pk, b, m, s));
+        }
+        // (the outputs leave only after everything has succeeded so far: a failed launch leaves them untouched)
+        if (mom) HIPCHK(ctx, hipMemcpyAsync(mom, b.mom, sizeof(double) * n_lines * B9_BAND_NMOM, hipMemcpyDeviceToHost, s));
+        if (bins) HIPCHK(ctx, hipMemcpyAsync(bins, b.bins, sizeof(double) * n_lines * nbc, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        return B9_OK;
+    };
+    // (a failure part-way: nothing may still be reading mom0 / edges_t when they go out of scope; the call's error stays in ctx->err)
+    const int rc = enqueue();
+    if (rc) (void)hipStreamSynchronize(s);
+    return rc;
 }
 
 int b9_n_wd_stars(const b9_ctx *ctx)

@@ -165,6 +165,10 @@ struct b9_ctx {
     // nothing on the device between them, so only one of them is using it at any time.
     b9i::DeviceBuf<char> d_chain;
 
+    // b9_cmd_band: an allocation of its own (grown on demand, never shrunk), for the same reason: a chunk of rows' parameters,
+    // headers, derived isochrones, WD node table and value table, the lines' pivots, moments, bins and edges (band_arena)
+    b9i::DeviceBuf<char> d_band;
+
     // timing of the dominant kernel
     int timing = 0;            // 0 off, n > 0: bracket every n-th launch of the dominant kernel with events
     unsigned long long launch_no = 0;

@@ -115,6 +115,20 @@ inline WdGridArena wd_grid_arena(size_t chunk, int n_pops, long long iso_stride,
     return a;
 }
 
+// b9_cmd_band, one chunk of rows: [params][headers][isochrones][WD node table][value table [chunk][n_lines]], then the lines'
+// pivots [n_lines], moments [n_lines][n_mom], bins [n_lines][n_bincol] and transposed edges [n_edges][n_lines].  tab_row: doubles
+// of one row's WD node table, all populations.  A part of 0 bytes is empty: it shares its offset with the next one.
+struct BandArena { size_t o_par, o_hdr, o_iso, o_tab, o_values, o_pivot, o_mom, o_bins, o_edges, bytes; };
+inline BandArena band_arena(size_t chunk, int n_pops, long long iso_stride, size_t tab_row, size_t n_lines, size_t n_mom, size_t n_bincol, size_t n_edges,
+                            size_t hdr_bytes)
+{
+    Carve c;
+    BandArena a{c.take(8 * B9_NPARAM * chunk), c.take(hdr_bytes * chunk * n_pops), c.take(8 * chunk * n_pops * (size_t)iso_stride), c.take(8 * chunk * tab_row),
+                c.take(8 * chunk * n_lines), c.take(8 * n_lines), c.take(8 * n_lines * n_mom), c.take(8 * n_lines * n_bincol), c.take(8 * n_lines * n_edges), 0};
+    a.bytes = c.total;
+    return a;
+}
+
 // The reductions over a saved chain (b9_star_moments, b9_mass_hist, b9_phot_resid, b9_pointwise), one chunk of rows:
 // [params][headers][isochrones][node table][WD node table][per-(row, star) increments [chunk][n_stars][n_col]], then the
 // accumulators [n_stars][n_acc], the chunk's per-row sums [chunk][n_rowcol], and the call's own extra parts in the order it

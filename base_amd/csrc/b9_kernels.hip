@@ -41,6 +41,8 @@
 //                                     bin is per lane, the edges staged in LDS), summed over the rows
 //   k_wd_bins                        b9_wd_bins: b9_wd_moments' node weights binned on every (WD-stage star, quantity)'s OWN
 //                                     edges, one selected quantity per blockIdx.z, summed over the rows
+//   k_band_points / k_band_wd_points / k_band_accumulate   b9_cmd_band: the MS/RGB loci and WD sequences a saved chain's rows imply
+//                                     (one lane per point into a chunk's value table), reduced over the rows one lane per line
 //   k_star_resid / _wd / k_resid_stage / k_resid_rows   b9_phot_resid: exact posterior-predictive magnitude
 //                                     moments per filter over the same grid, summed over the rows and, standardised, the stars
 //   k_star_lpd / _wd / k_pw_accumulate / k_pw_tail / k_pw_rows   b9_pointwise: every star's marginal log-likelihood per row over
@@ -95,6 +97,7 @@ namespace tree_kd5 {
 #include "b9_wd_bins.hip.h"
 #include "b9_phot_resid.hip.h"
 #include "b9_pointwise.hip.h"
+#include "b9_cmd_band.hip.h"
 
 // ------------------------------------------------------------------------------------------
 // k_finalize: one workgroup per walker: fixed-order sum of the partials + prior -> logpost[w]
@@ -309,6 +312,32 @@ hipError_t b9k_wd_bins(const DevPack &pk, const DevStars &st, const B9WdGrid &g,
         hipLaunchKernelGGL(k.kern, dim3((st.n_wd + 63) / 64, n_rows, n_sel), dim3(64), k.lds, stream, pk, st, g.set.hdr, g.set.params, g.n_nodes,
                            g.tab, n_wp, g.rank, quantity_mask, n_sel, g.edges, n_bins, g.scratch);
         launch_chain_accumulate(g.scratch, n_rows, (long long)st.n_wd * n_sel * (n_bins + 3), g.acc, stream);
+        return hipGetLastError();
+    });
+}
+
+// ---- b9_cmd_band: the chunk's WD node table (b9_wd_moments' kernel, as it is), the points' values, the accumulation over the rows ----
+hipError_t b9k_cmd_band(const DevPack &pk, const B9Band &b, int n_rows, hipStream_t stream)
+{
+    return dispatch_nfp(pk.nfp, [&](auto nfp_c) {
+        constexpr int NFP = decltype(nfp_c)::value;
+        const B9IsoSet &s = b.set;
+        const B9BandSpec &sp = b.spec;
+        const int n_wp = n_rows * s.n_pops, n_ms = sp.n_ratio * sp.n_eep, n_wd = sp.n_types * sp.n_wd_nodes;
+        if (!b.values || !b.pivot || (!b.mom && !b.bins) || n_rows < 1 || n_wp > 65535 || sp.n_lines < 1 || (n_wd > 0 && !b.wd_tab) ||
+            (b.bins && (!b.edges_t || b.n_bins < 1 || b.n_bins > B9_BAND_MAX_BINS)))
+            return hipErrorInvalidValue;
+        if (n_ms > 0)
+            hipLaunchKernelGGL(k_band_points<NFP>, dim3((n_ms + 255) / 256, n_wp), dim3(256), 0, stream, pk, s.hdr, s.iso, s.iso_stride, s.mass_cap, s.n_pops,
+                               s.params, sp, b.values);
+        if (n_wd > 0) {
+            hipLaunchKernelGGL(k_wd_node_table_status<NFP>, dim3((sp.n_wd_nodes + 63) / 64, n_wp), dim3(128), 0, stream, pk, s.hdr, s.iso, s.iso_stride,
+                               s.mass_cap, s.n_pops, s.params, sp.n_wd_nodes, b.wd_tab, n_wp);
+            hipLaunchKernelGGL(k_band_wd_points<NFP>, dim3((n_wd + 255) / 256, n_wp), dim3(256), 0, stream, pk, s.hdr, s.n_pops, b.wd_tab, n_wp, sp, b.values);
+        }
+        const size_t lds = b.bins ? sizeof(double) * 64 * (size_t)(2 * b.n_bins + 4) : 0;
+        hipLaunchKernelGGL(k_band_accumulate, dim3((unsigned)((sp.n_lines + 63) / 64)), dim3(64), lds, stream, b.values, n_rows, sp.n_lines, b.pivot, b.mom,
+                           b.bins, b.edges_t, b.n_bins);
         return hipGetLastError();
     });
 }

@@ -159,6 +159,30 @@ hipError_t b9k_wd_moments(const DevPack &pk, const DevStars &st, const B9WdGrid 
 // total), then acc [st.n_wd][n_sel][n_bins + 3]; n_sel: the bits of quantity_mask
 hipError_t b9k_wd_bins(const DevPack &pk, const DevStars &st, const B9WdGrid &g, int n_rows, int quantity_mask, int n_bins, hipStream_t stream);
 
+// b9_cmd_band: the call's spec as the kernels take it (by value), validated by the caller
+struct B9BandSpec {
+    int eep0, n_eep, n_ratio;
+    int n_wd_nodes, n_types, type_id[2];         // type_id[t]: the atmosphere type (0 DA, 1 DB) of the t-th selected one
+    int n_colour, colour[B9_BAND_MAX_COLOURS][2];
+    int P, C;                                    // points per population, columns per point (1 + nf + n_colour)
+    long long n_lines;                           // n_pops P C
+    double ratio[B9_BAND_MAX_RATIOS];
+};
+// ... and what it works on, one chunk of n_rows derived rows (n_rows * n_pops <= 65535).  Device pointers, all the caller's own.
+struct B9Band {
+    B9IsoSet set;               // the chunk's rows
+    B9BandSpec spec;
+    double *wd_tab;             // n_rows * n_pops * b9k_wd_grid_table_doubles(nfp, n_wd_nodes, true) doubles (n_wd_nodes == 0: not read)
+    double *values;             // the chunk's value table [n_rows][n_lines]
+    double *pivot;              // [n_lines]; only read
+    double *mom;                // [n_lines][B9_BAND_NMOM], in/out (null: not asked for)
+    double *bins;               // [n_lines][n_bins + 3], in/out (null: not asked for)
+    double *edges_t;            // [n_bins + 1][n_lines]: the lines' edges TRANSPOSED, validated by the caller (read with bins); only read
+    int n_bins;
+};
+// k_derive_iso'd rows -> [k_wd_node_table_status] + k_band_points + k_band_wd_points (the value table) + k_band_accumulate
+hipError_t b9k_cmd_band(const DevPack &pk, const B9Band &b, int n_rows, hipStream_t stream);
+
 // What a reduction over a saved chain works on, one chunk of n_rows derived rows (1 .. 65535).  Device pointers, all the caller's own.
 struct B9Chain {
     B9IsoSet set;               // the chunk's rows

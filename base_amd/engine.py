@@ -385,6 +385,37 @@ class Engine:
                                              mags.ctypes.data_as(_dp), stage.ctypes.data_as(_ip)))
         return mags, stage
 
+    def cmd_band(self, rows: np.ndarray, spec, pivot=None, mom=None, edges=None, bins=None, want_mom: bool = True,
+                 want_bins: Optional[bool] = None) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+        """b9_cmd_band: the isochrone and WD-sequence lines `spec` (abi.make_band_spec) selects, reduced over `rows`: (mom
+        [n_lines, abi.BAND_NMOM] -- N, SUM and SUMSQ about `pivot` [n_lines] (None: 0), MIN, MAX --, bins [n_lines, n_bins + 3] on the
+        lines' own `edges` [n_lines, n_bins + 1] -- below, the bins, at or above, the total).  Needs a pack, no stars.  mom / bins
+        given: the call continues them (B9_BAND_CONTINUE; both must be given where both are wanted) and returns new arrays.
+        want_mom = False passes NULL for the moments; bins are wanted when edges are given (want_bins overrides)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        st = spec.struct if isinstance(spec, abi.Pinned) else spec
+        n_lines = abi.band_shape(st, self.n_filt, 2 if self.options.n_pops == 2 else 1)[2]
+        if want_bins is None:
+            want_bins = edges is not None
+        cont = mom is not None or bins is not None
+        if cont and ((want_mom and mom is None) or (want_bins and bins is None)):
+            raise ValueError("cmd_band: a continued call takes every output it asks for")
+        n_bins = 0
+        e = None
+        if edges is not None:
+            e = np.ascontiguousarray(edges, dtype=np.float64).reshape(max(n_lines, 1), -1)
+            n_bins = e.shape[1] - 1
+        piv = None if pivot is None else np.ascontiguousarray(pivot, dtype=np.float64).reshape(n_lines)
+        m = b = None
+        if want_mom:
+            m = np.array(mom, dtype=np.float64, order="C").reshape(n_lines, abi.BAND_NMOM) if cont else np.zeros((n_lines, abi.BAND_NMOM))
+        if want_bins:
+            b = np.array(bins, dtype=np.float64, order="C").reshape(n_lines, n_bins + 3) if cont else np.zeros((n_lines, max(n_bins, 0) + 3))
+        ptr = lambda a: a.ctypes.data_as(_dp) if a is not None else None
+        self._check(self.lib.b9_cmd_band(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], C.byref(st), abi.BAND_CONTINUE if cont else 0, ptr(piv), ptr(m),
+                                         ptr(e), n_bins, ptr(b)))
+        return m, b
+
     # -- introspection --------------------------------------------------------------------
     def bytes_per_star_eval(self) -> int:
         return int(self.lib.b9_bytes_per_star_eval(self._ctx))

@@ -75,6 +75,9 @@ const ProgramFlags kMassFunctionFlags = {{"minMass", "massFunctionMinMass", fals
 const ProgramFlags kStarIntervalsFlags = {{"quantity", "starIntervalsQuantity", false}, {"nPops", "starIntervalsNPops", false}};
 const ProgramFlags kWdIntervalsFlags = {{"levels", "wdIntervalsLevels", false}, {"tol", "wdIntervalsTol", false}, {"maxPasses", "wdIntervalsMaxPasses", false},
                                         {"nMassNodes", "wdIntervalsNMassNodes", false}, {"nPops", "wdIntervalsNPops", false}};
+const ProgramFlags kCmdBandFlags = {{"ratios", "cmdBandRatios", false}, {"wdNodes", "cmdBandWdNodes", false}, {"wdTypes", "cmdBandWdTypes", false},
+                                    {"colours", "cmdBandColours", false}, {"levels", "cmdBandLevels", false}, {"tol", "cmdBandTol", false},
+                                    {"maxPasses", "cmdBandMaxPasses", false}, {"nPops", "cmdBandNPops", false}};
 const ProgramFlags kPhotResidFlags = {{"perStar", "photResidualsPerStar", true}, {"nPops", "photResidualsNPops", false}};
 const ProgramFlags kModelScoreFlags = {{"perRow", "modelScorePerRow", true}, {"nPops", "modelScoreNPops", false}};
 
@@ -617,6 +620,162 @@ void write_wd_intervals(const std::string &path, const std::vector<std::string> 
         cols.push_back({n + "_flags", "%.0f"});
     }
     write_table(path, "id", &ids, cols, (long)ids.size(), table, cols.size());
+}
+
+// ---------------------------------------------------------------------------------------------
+// cmdBand
+// ---------------------------------------------------------------------------------------------
+CmdBandConfig cmd_band_config(const Settings &st)
+{
+    CmdBandConfig c;
+    {
+        std::string rs = st.str("cmdBand.ratios", "0,1");
+        for (char &ch : rs) if (ch == ',' || ch == '[' || ch == ']') ch = ' ';
+        std::istringstream is(rs);
+        std::string tok;
+        while (is >> tok) {
+            char *end = nullptr;
+            const double v = std::strtod(tok.c_str(), &end);
+            if (end == tok.c_str() || *end) fail("cmdBand.ratios: '" + tok + "' is not a number");
+            if (!std::isfinite(v) || v < 0.0 || v > 1.0) fail("cmdBand.ratios: a mass ratio lies in [0, 1]");
+            c.ratios.push_back(v);
+        }
+        if (c.ratios.size() > B9_BAND_MAX_RATIOS) fail("cmdBand.ratios: at most " + std::to_string(B9_BAND_MAX_RATIOS) + " loci");
+    }
+    c.wd_nodes = st.integer("cmdBand.wdNodes", 256);
+    if (c.wd_nodes < 0 || c.wd_nodes > 2147483647l) fail("cmdBand.wdNodes must be a 32-bit number that is not negative");
+    {
+        std::string t = st.str("cmdBand.wdTypes", "da");
+        std::transform(t.begin(), t.end(), t.begin(), ::tolower);
+        c.wd_types = t == "da" ? 1 : (t == "db" ? 2 : (t == "both" ? 3 : 0));
+        if (!c.wd_types) fail("cmdBand.wdTypes must be da, db or both");
+    }
+    {
+        std::string cs = st.str("cmdBand.colours", "");
+        for (char &ch : cs) if (ch == ',' || ch == '[' || ch == ']') ch = ' ';
+        std::istringstream is(cs);
+        std::string tok;
+        while (is >> tok) {
+            const size_t dash = tok.find('-');
+            if (dash == std::string::npos || dash == 0 || dash + 1 == tok.size()) fail("cmdBand.colours: '" + tok + "' is not <filter>-<filter>");
+            c.colours.emplace_back(tok.substr(0, dash), tok.substr(dash + 1));
+        }
+        if (c.colours.size() > B9_BAND_MAX_COLOURS) fail("cmdBand.colours: at most " + std::to_string(B9_BAND_MAX_COLOURS) + " colours");
+    }
+    c.levels = parse_levels(st, "cmdBand.levels");
+    c.tol = st.num("cmdBand.tol", 1e-4);
+    c.max_passes = (int)st.integer("cmdBand.maxPasses", 12);
+    check_levels(c.levels.data(), (int)c.levels.size(), B9_BAND_MAX_BINS, "cmdBand.levels");
+    if (!(c.tol >= 0.0)) fail("cmdBand.tol must not be negative");
+    if (c.max_passes < 1) fail("cmdBand.maxPasses must be positive");
+    if (c.ratios.empty() && c.wd_nodes == 0) fail("cmdBand: no ratios and no WD nodes: nothing to do");
+    return c;
+}
+
+std::vector<int32_t> band_colour_ids(const CmdBandConfig &c, const std::vector<std::string> &filters)
+{
+    std::vector<int32_t> ids;
+    for (const auto &col : c.colours) {
+        for (const std::string &name : {col.first, col.second}) {
+            const auto it = std::find(filters.begin(), filters.end(), name);
+            if (it == filters.end()) fail("cmdBand.colours: '" + name + "' is not a filter of the model set");
+            ids.push_back((int32_t)(it - filters.begin()));
+        }
+        if (ids[ids.size() - 1] == ids[ids.size() - 2]) fail("cmdBand.colours: '" + col.first + "-" + col.second + "' takes one filter twice");
+    }
+    return ids;
+}
+
+std::vector<std::string> band_line_names(int n_pops, int eep0, int n_eep, int n_ratio, long wd_nodes, int wd_types, const std::vector<std::string> &filters,
+                                         const std::vector<int32_t> &colour_ids)
+{
+    std::vector<std::string> cols = {"mass"};
+    for (const std::string &f : filters) cols.push_back(f);
+    for (size_t c = 0; c + 1 < colour_ids.size(); c += 2) cols.push_back(filters[(size_t)colour_ids[c]] + "-" + filters[(size_t)colour_ids[c + 1]]);
+    std::vector<std::string> names;
+    for (int k = 0; k < n_pops; ++k) {
+        const std::string pop = "p" + std::to_string(k) + ".";
+        for (int s = 0; s < n_ratio; ++s)
+            for (int e = 0; e < n_eep; ++e)
+                for (const std::string &c : cols) names.push_back(pop + "q" + std::to_string(s) + ".eep" + std::to_string(eep0 + e) + "." + c);
+        for (int t = 0; t < 2; ++t) {
+            if (wd_nodes < 1 || !(wd_types >> t & 1)) continue;
+            for (long j = 1; j <= wd_nodes; ++j)
+                for (const std::string &c : cols) names.push_back(pop + (t ? "db" : "da") + ".n" + std::to_string(j) + "." + c);
+        }
+    }
+    return names;
+}
+
+void band_first_ranges(const double *mom, long n_lines, double *first_lo, double *first_hi)
+{
+    for (long l = 0; l < n_lines; ++l) {
+        const double *m = mom + (size_t)l * B9_BAND_NMOM;
+        double lo = 0.0, hi = 1.0;
+        if (m[B9_BAND_N] > 0.0 && std::isfinite(m[B9_BAND_MIN]) && std::isfinite(m[B9_BAND_MAX])) {
+            const double mn = m[B9_BAND_MIN], mx = m[B9_BAND_MAX];
+            const double pad = std::max(0.01 * (mx - mn), 1e-6 * std::max({1.0, std::fabs(mn), std::fabs(mx)}));
+            lo = mn - pad; hi = mx + pad;
+        }
+        first_lo[l] = lo; first_hi[l] = hi;
+    }
+}
+
+void band_first_edges(const double *mom, long n_lines, int n_bins, double *edges)
+{
+    if (n_bins < 1 || n_bins > B9_BAND_MAX_BINS) fail("band_first_edges: n_bins must lie in 1 .. B9_BAND_MAX_BINS");
+    std::vector<double> lo(n_lines), hi(n_lines);
+    band_first_ranges(mom, n_lines, lo.data(), hi.data());
+    for (long l = 0; l < n_lines; ++l)       // (interval_loop's cut)
+        for (int b = 0; b <= n_bins; ++b) edges[(size_t)l * (n_bins + 1) + b] = lo[l] + (hi[l] - lo[l]) * ((double)b / (double)n_bins);
+}
+
+CmdBand cmd_band(const BandMomentsFn &moments, const StarBinsFn &bins, long n_lines, long n_rows, const std::vector<double> &levels, double tol, int max_passes)
+{
+    CmdBand r;
+    r.n_lines = n_lines;
+    r.mom.assign((size_t)n_lines * B9_BAND_NMOM, 0.0);
+    std::vector<double> lo(n_lines), hi(n_lines);
+    moments(r.mom.data());
+    band_first_ranges(r.mom.data(), n_lines, lo.data(), hi.data());
+    r.lines = interval_loop(bins, n_lines, n_rows, B9_BAND_MAX_BINS, lo.data(), hi.data(), levels, tol, max_passes);
+    return r;
+}
+
+void band_table(const double *mom, const double *pivot, long n_lines, int n_levels, const double *value, const double *lo, const double *hi,
+                const int32_t *passes, const int32_t *flags, double *table)
+{
+    const int m = n_levels;
+    const size_t tcol = 5 + 3 * (size_t)m + 2;
+    for (long l = 0; l < n_lines; ++l) {
+        const double *a = mom + (size_t)l * B9_BAND_NMOM;
+        double *t = table + (size_t)l * tcol;
+        const double n = a[B9_BAND_N];
+        t[0] = n; t[1] = t[2] = std::nan(""); t[3] = a[B9_BAND_MIN]; t[4] = a[B9_BAND_MAX];
+        if (n > 0.0) {
+            const double d = a[B9_BAND_SUM] / n;
+            t[1] = (pivot ? pivot[l] : 0.0) + d;
+            t[2] = std::sqrt(std::max(0.0, a[B9_BAND_SUMSQ] / n - d * d));
+        }
+        for (int k = 0; k < m; ++k) {
+            const size_t o = (size_t)l * m + k;
+            t[5 + 3 * k] = value[o]; t[6 + 3 * k] = lo[o]; t[7 + 3 * k] = hi[o];
+        }
+        t[tcol - 2] = (double)passes[l]; t[tcol - 1] = (double)flags[l];
+    }
+}
+
+void write_cmd_band(const std::string &path, const std::vector<std::string> &names, const std::vector<double> &levels, const double *table)
+{
+    std::vector<TableColumn> cols = {{"N", "%.0f"}, {"mean", "%.17g"}, {"sd", "%.17g"}, {"min", "%.17g"}, {"max", "%.17g"}};
+    for (double a : levels) {
+        char q[40];
+        std::snprintf(q, sizeof q, "q%.12g", a);
+        for (const char *end : {"", "_lo", "_hi"}) cols.push_back({std::string(q) + end, "%.17g"});
+    }
+    cols.push_back({"passes", "%.0f"});
+    cols.push_back({"flags", "%.0f"});
+    write_table(path, "line", &names, cols, (long)names.size(), table, cols.size());
 }
 
 // ---------------------------------------------------------------------------------------------

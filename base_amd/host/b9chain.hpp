@@ -1,4 +1,4 @@
-// b9chain.hpp -- what the programs over a saved chain (sampleMass, sampleWDMass, starSummary, wdSummary, wdIntervals, massFunction,
+// b9chain.hpp -- what the programs over a saved chain (sampleMass, sampleWDMass, starSummary, wdSummary, wdIntervals, cmdBand, massFunction,
 // binaryStats, starIntervals, photResiduals, modelScore) share above the C ABI and below their mains: their settings, the loop over the
 // chain's rows, the tables derived from the device's sums and the files they are written to (docs/FORMATS.md).  Host arithmetic
 // only: nothing here needs a context or a GPU.  b9host.hpp includes this header.
@@ -183,6 +183,48 @@ void wd_intervals_table(const WdIntervals &r, double *table);
 // N, one line per WD-stage star in the order of ids, 17 significant digits
 void write_wd_intervals(const std::string &path, const std::vector<std::string> &ids, int quantity_mask, const std::vector<double> &levels,
                         const double *table);
+
+// ---- cmdBand ---------------------------------------------------------------------------------------
+// cmdBand.{ratios, wdNodes, wdTypes, colours, levels, tol, maxPasses, nPops} (flags --ratios a,b,.. --wdNodes n --wdTypes
+// da|db|both --colours f1-f2,.. --levels a,b,.. --tol --maxPasses --nPops).  Default: the loci q = 0 and q = 1, 256 WD points of
+// the DA sequence, no colours, starIntervals' levels, 1e-4 relative, 12 passes, one population.
+extern const ProgramFlags kCmdBandFlags;
+struct CmdBandConfig {
+    std::vector<double> ratios;                                   // 0 .. B9_BAND_MAX_RATIOS, each in [0, 1]
+    long wd_nodes;                                                // >= 0
+    int wd_types, max_passes;                                     // wd_types: bit 0 DA, bit 1 DB
+    std::vector<std::pair<std::string, std::string>> colours;     // filter names (f1, f2), at most B9_BAND_MAX_COLOURS
+    double tol;
+    std::vector<double> levels;
+};
+CmdBandConfig cmd_band_config(const Settings &st);
+// the colours' filter indices [n_colour][2] among `filters`; throws for a name that is none of them or a colour of one filter
+std::vector<int32_t> band_colour_ids(const CmdBandConfig &c, const std::vector<std::string> &filters);
+// The lines of a spec in b9_cmd_band's order, n_pops P C of them, named "p<k>.<locus>.<point>.<column>": locus q<s> with point
+// eep<e>, or da / db with point n<j>; column mass, a filter's name, or <f1>-<f2>.
+std::vector<std::string> band_line_names(int n_pops, int eep0, int n_eep, int n_ratio, long wd_nodes, int wd_types, const std::vector<std::string> &filters,
+                                         const std::vector<int32_t> &colour_ids);
+// The first pass's range of every line from b9_cmd_band's moments [n_lines][B9_BAND_NMOM]: [MIN - pad, MAX + pad] with pad =
+// max(0.01 (MAX - MIN), 1e-6 max(1, |MIN|, |MAX|)); a line with N = 0 gets [0, 1].  band_first_edges: the n_bins + 1 edges
+// interval_loop cuts that range into, lo + (hi - lo) (b / n_bins): strictly ascending, e_0 < MIN, e_B > MAX.
+void band_first_ranges(const double *mom, long n_lines, double *first_lo, double *first_hi);
+void band_first_edges(const double *mom, long n_lines, int n_bins, double *edges);
+// The loop: one `moments` pass over all the rows (b9_cmd_band with the pivots, from its starting state) gives the first ranges,
+// then interval_loop with `bins` (one b9_cmd_band bins pass over all the rows from zeros) over B9_BAND_MAX_BINS bins.
+struct CmdBand {
+    long n_lines = 0;
+    std::vector<double> mom;              // [n_lines][B9_BAND_NMOM]
+    StarIntervals lines;                  // n_stars = n_lines
+};
+using BandMomentsFn = std::function<void(double *mom /* [n_lines][B9_BAND_NMOM] */)>;
+CmdBand cmd_band(const BandMomentsFn &moments, const StarBinsFn &bins, long n_lines, long n_rows, const std::vector<double> &levels, double tol, int max_passes);
+// -> [n_lines][5 + 3 m + 2]: N, mean = pivot + SUM / N, sd = sqrt(max(0, SUMSQ / N - (SUM / N)^2)) (the population standard
+// deviation), min, max, then value, lo, hi per level, passes, flags.  N = 0: mean and sd NaN, min +inf, max -inf as accumulated.
+void band_table(const double *mom, const double *pivot, long n_lines, int n_levels, const double *value, const double *lo, const double *hi,
+                const int32_t *passes, const int32_t *flags, double *table);
+// <base>.cmdBand: "line N mean sd min max {q<a> q<a>_lo q<a>_hi} passes flags", one line per band line named by `names`, 17
+// significant digits
+void write_cmd_band(const std::string &path, const std::vector<std::string> &names, const std::vector<double> &levels, const double *table);
 
 // ---- photResiduals ---------------------------------------------------------------------------------
 // b9_phot_resid's star_resid [n_stars][2 + 2 nf] with the catalogue's obs / sigma [n_stars][nf] -> the per-star table

@@ -136,6 +136,8 @@ const std::map<std::string, std::string> &Settings::flag_map()
         {"wdIntervalsMaxPasses", "wdIntervals.maxPasses"}, {"wdIntervalsNMassNodes", "wdIntervals.nMassNodes"}, {"wdIntervalsNPops", "wdIntervals.nPops"},
         {"photResidualsPerStar", "photResiduals.perStar"}, {"photResidualsNPops", "photResiduals.nPops"},
         {"massEdges", "binaryStats.massEdges"}, {"massBins", "binaryStats.massBins"}, {"qMin", "binaryStats.qMin"}, {"binaryStatsNPops", "binaryStats.nPops"},
+        {"cmdBandRatios", "cmdBand.ratios"}, {"cmdBandWdNodes", "cmdBand.wdNodes"}, {"cmdBandWdTypes", "cmdBand.wdTypes"}, {"cmdBandColours", "cmdBand.colours"},
+        {"cmdBandLevels", "cmdBand.levels"}, {"cmdBandTol", "cmdBand.tol"}, {"cmdBandMaxPasses", "cmdBand.maxPasses"}, {"cmdBandNPops", "cmdBand.nPops"},
         {"modelScorePerRow", "modelScore.perRow"}, {"modelScoreNPops", "modelScore.nPops"}, {"compareTo", "modelScore.compareTo"},
         {"nStars", "simCluster.nStars"}, {"percentBinary", "simCluster.percentBinary"}, {"percentDB", "simCluster.percentDB"},
         {"nFieldStars", "simCluster.nFieldStars"}, {"minMass", "simCluster.minMass"}, {"maxMass", "simCluster.maxMass"},

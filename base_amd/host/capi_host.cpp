@@ -361,6 +361,54 @@ int b9h_wd_intervals_settings(int argc, char **argv, char *out, int cap)
     });
 }
 
+int b9h_band_first_ranges(const double *mom, long n_lines, double *first_lo, double *first_hi)
+{
+    return guard([&] {
+        if (n_lines < 0 || (n_lines > 0 && (!mom || !first_lo || !first_hi))) throw std::runtime_error("b9h_band_first_ranges: NULL argument");
+        b9h::band_first_ranges(mom, n_lines, first_lo, first_hi);
+    });
+}
+
+int b9h_band_first_edges(const double *mom, long n_lines, int n_bins, double *edges)
+{
+    return guard([&] {
+        if (n_lines < 0 || (n_lines > 0 && (!mom || !edges))) throw std::runtime_error("b9h_band_first_edges: NULL argument");
+        b9h::band_first_edges(mom, n_lines, n_bins, edges);
+    });
+}
+
+int b9h_band_table(const double *mom, const double *pivot, long n_lines, int n_levels, const double *value, const double *lo, const double *hi,
+                   const int32_t *passes, const int32_t *flags, double *table)
+{
+    return guard([&] {
+        if (n_lines < 0 || n_levels < 1 || (n_lines > 0 && (!mom || !value || !lo || !hi || !passes || !flags || !table)))
+            throw std::runtime_error("b9h_band_table: invalid argument");
+        b9h::band_table(mom, pivot, n_lines, n_levels, value, lo, hi, passes, flags, table);
+    });
+}
+
+int b9h_write_cmd_band(const char *path, const char *const *names, long n_lines, const double *levels, int n_levels, const double *table)
+{
+    return guard([&] {
+        if (!path || n_lines < 0 || n_levels < 1 || !levels || (n_lines > 0 && (!names || !table))) throw std::runtime_error("b9h_write_cmd_band: invalid argument");
+        b9h::write_cmd_band(path, strings(names, n_lines), std::vector<double>(levels, levels + n_levels), table);
+    });
+}
+
+int b9h_cmd_band_settings(int argc, char **argv, char *out, int cap)
+{
+    return settings_text("b9h_cmd_band_settings", argc, argv, b9h::kCmdBandFlags, out, cap, [&](const b9h::Settings &st) {
+        const b9h::CmdBandConfig c = b9h::cmd_band_config(st);
+        std::string rs, cs, lv;
+        for (size_t s = 0; s < c.ratios.size(); ++s) rs += (s ? "," : "") + g17(c.ratios[s]);
+        for (size_t k = 0; k < c.colours.size(); ++k) cs += (k ? "," : "") + c.colours[k].first + "-" + c.colours[k].second;
+        for (size_t l = 0; l < c.levels.size(); ++l) lv += (l ? "," : "") + g17(c.levels[l]);
+        return "ratios = " + rs + "\nwdNodes = " + std::to_string(c.wd_nodes) + "\nwdTypes = " + std::to_string(c.wd_types) + "\ncolours = " + cs +
+               "\nlevels = " + lv + "\ntol = " + g17(c.tol) + "\nmaxPasses = " + std::to_string(c.max_passes) + "\nnPops = " +
+               std::to_string(b9h::chain_n_pops(st, "cmdBand")) + "\n";
+    });
+}
+
 int b9h_resid_table(const double *star_resid, const double *obs, const double *sigma, long n_stars, int n_filt, double *table)
 {
     return guard([&] {

@@ -1,5 +1,5 @@
 """Builds the C++ host programs (base_amd/host/): libbase9host.so + singlePopMcmc, multiPopMcmc,
-makeCMD, sampleMass, sampleWDMass, wdSummary, wdIntervals, starSummary, massFunction, binaryStats, starIntervals, photResiduals, modelScore, simCluster, scatterCluster.  Plain g++ against the C ABI; they link libbase9hip.so by rpath."""
+makeCMD, cmdBand, sampleMass, sampleWDMass, wdSummary, wdIntervals, starSummary, massFunction, binaryStats, starIntervals, photResiduals, modelScore, simCluster, scatterCluster.  Plain g++ against the C ABI; they link libbase9hip.so by rpath."""
 from __future__ import annotations
 
 import os
@@ -53,7 +53,7 @@ def build_host(force: bool = False) -> None:
         _run(["g++", "-shared", "-o", lib] + objs + link + ["-L" + os.path.join(ROCM, "lib"), "-lrccl", "-lamdhip64",
                                                             "-Wl,-rpath," + os.path.join(ROCM, "lib")])
     progs = {"singlePopMcmc": ("mcmc_main.cpp", ["-DB9_N_POPS=1"]), "multiPopMcmc": ("mcmc_main.cpp", ["-DB9_N_POPS=2"]),
-             "makeCMD": ("makecmd_main.cpp", []), "sampleMass": ("samplemass_main.cpp", []), "sampleWDMass": ("samplewdmass_main.cpp", []),
+             "makeCMD": ("makecmd_main.cpp", []), "cmdBand": ("cmdband_main.cpp", []), "sampleMass": ("samplemass_main.cpp", []), "sampleWDMass": ("samplewdmass_main.cpp", []),
              "wdSummary": ("wdsummary_main.cpp", []), "wdIntervals": ("wdintervals_main.cpp", []),
              "starSummary": ("starsummary_main.cpp", []), "massFunction": ("massfunction_main.cpp", []),
              "binaryStats": ("binarystats_main.cpp", []),

@@ -41,6 +41,7 @@ HOST_SYMBOLS = [
     "b9h_binary_table", "b9h_ratio_dist_table", "b9h_star_ratio_table", "b9h_write_binary_fraction", "b9h_write_ratio_dist", "b9h_write_star_ratio",
     "b9h_refine_star_edges", "b9h_star_intervals_table", "b9h_write_star_intervals", "b9h_star_intervals_settings",
     "b9h_wd_first_ranges", "b9h_wd_intervals_table", "b9h_write_wd_intervals", "b9h_wd_intervals_settings",
+    "b9h_band_first_ranges", "b9h_band_first_edges", "b9h_band_table", "b9h_write_cmd_band", "b9h_cmd_band_settings",
     "b9h_resid_table", "b9h_filter_resid_table", "b9h_write_phot_resid", "b9h_write_filter_resid", "b9h_phot_resid_settings",
     "b9h_pointwise_table", "b9h_score_totals", "b9h_score_compare", "b9h_write_pointwise", "b9h_write_model_score", "b9h_model_score_settings",
 ]
@@ -112,6 +113,11 @@ def load() -> C.CDLL:
     lib.b9h_wd_intervals_table.argtypes = [C.c_long, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
     lib.b9h_write_wd_intervals.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, C.c_int, _dp, C.c_int, _dp]
     lib.b9h_wd_intervals_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
+    lib.b9h_band_first_ranges.argtypes = [_dp, C.c_long, _dp, _dp]
+    lib.b9h_band_first_edges.argtypes = [_dp, C.c_long, C.c_int, _dp]
+    lib.b9h_band_table.argtypes = [_dp, _dp, C.c_long, C.c_int, _dp, _dp, _dp, _ip, _ip, _dp]
+    lib.b9h_write_cmd_band.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp, C.c_int, _dp]
+    lib.b9h_cmd_band_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     lib.b9h_resid_table.argtypes = [_dp, _dp, _dp, C.c_long, C.c_int, _dp]
     lib.b9h_filter_resid_table.argtypes = [_dp, C.c_long, C.c_int, _dp]
     lib.b9h_write_phot_resid.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, C.POINTER(C.c_char_p), C.c_int, _dp]
@@ -687,6 +693,85 @@ def wd_intervals_settings(args) -> dict:
     for line in buf.value.decode().splitlines():
         k, v = line.split(" = ")
         d[k] = tuple(float(x) for x in v.split(",")) if k == "levels" else float(v) if k == "tol" else int(v)
+    return d
+
+
+def band_first_ranges(mom):
+    """b9h_band_first_ranges: every line's first range (lo, hi) [n_lines] from b9_cmd_band's moments [n_lines, 5]: [MIN - pad,
+    MAX + pad] with pad = max(0.01 (MAX - MIN), 1e-6 max(1, |MIN|, |MAX|)); [0, 1] for a line with N = 0.  What interval_loop cuts."""
+    mom = np.ascontiguousarray(mom, dtype=np.float64).reshape(-1, abi.BAND_NMOM)
+    lo, hi = np.zeros(mom.shape[0]), np.zeros(mom.shape[0])
+    _check(load().b9h_band_first_ranges(mom.ctypes.data_as(_dp), mom.shape[0], lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp)))
+    return lo, hi
+
+
+def band_first_edges(mom, n_bins: int = abi.BAND_MAX_BINS) -> np.ndarray:
+    """b9h_band_first_edges: every line's first edges [n_lines, n_bins + 1] from b9_cmd_band's moments [n_lines, 5]: strictly
+    ascending, e_0 < MIN and e_B > MAX; [0, 1] cut evenly for a line with N = 0."""
+    mom = np.ascontiguousarray(mom, dtype=np.float64).reshape(-1, abi.BAND_NMOM)
+    edges = np.zeros((mom.shape[0], int(n_bins) + 1))
+    _check(load().b9h_band_first_edges(mom.ctypes.data_as(_dp), mom.shape[0], int(n_bins), edges.ctypes.data_as(_dp)))
+    return edges
+
+
+def cmd_band(engine, rows, spec, levels=STAR_INTERVALS_LEVELS, tol: float = 1e-4, max_passes: int = 12, n_bins: int = abi.BAND_MAX_BINS) -> dict:
+    """Every line's moments and quantiles at `levels` over `rows`, exactly -- the program cmdBand's loop: engine.cmd_band
+    (b9_cmd_band) on the first row gives the pivots (that row's value, 0 where the line is absent there), one pass over all the
+    rows the moments about them, band_first_ranges the first ranges (interval_loop's even cut of them is band_first_edges), then the
+    bins pass and refine_star_edges are looped (interval_loop) until every bracket is final or max_passes is reached.  Returns
+    interval_loop's dict over the lines with pivot [n_lines], mom [n_lines, 5], first_lo and first_hi [n_lines]."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+    first, _ = engine.cmd_band(rows[:1], spec)
+    pivot = np.where(first[:, abi.BAND_N] > 0.0, first[:, abi.BAND_MIN], 0.0)
+    mom, _ = engine.cmd_band(rows, spec, pivot=pivot)
+    lo, hi = band_first_ranges(mom)
+    res = interval_loop(lambda e: engine.cmd_band(rows, spec, edges=e, want_mom=False)[1], lo, hi, rows.shape[0], levels, tol, max_passes, n_bins)
+    res.update(pivot=pivot, mom=mom, first_lo=lo, first_hi=hi)
+    return res
+
+
+def band_table(res: dict) -> np.ndarray:
+    """b9h_band_table: cmd_band's result -> [n_lines, 5 + 3 m + 2]: N, mean, sd, min, max, then value, lo, hi per level, passes,
+    flags."""
+    n, m = res["value"].shape
+    c = lambda a, t: np.ascontiguousarray(a, dtype=t)      # noqa: E731
+    mom, pivot, value, lo, hi = (c(res[k], np.float64) for k in ("mom", "pivot", "value", "lo", "hi"))
+    passes, flags = c(res["passes"], np.int32), c(res["flags"], np.int32)
+    out = np.zeros((n, 5 + 3 * m + 2))
+    _check(load().b9h_band_table(mom.ctypes.data_as(_dp), pivot.ctypes.data_as(_dp), n, m, value.ctypes.data_as(_dp), lo.ctypes.data_as(_dp),
+                                 hi.ctypes.data_as(_dp), passes.ctypes.data_as(_ip), flags.ctypes.data_as(_ip), out.ctypes.data_as(_dp)))
+    return out
+
+
+def write_cmd_band(path: str, names, levels, table) -> None:
+    """b9h_write_cmd_band: the .cmdBand file of band_table's table [len(names), 5 + 3 m + 2]."""
+    lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    table = np.ascontiguousarray(table, dtype=np.float64).reshape(len(names), 5 + 3 * len(lv) + 2)
+    arr = (C.c_char_p * len(names))(*[str(i).encode() for i in names])
+    _check(load().b9h_write_cmd_band(path.encode(), arr, len(names), lv.ctypes.data_as(_dp), len(lv), table.ctypes.data_as(_dp)))
+
+
+def read_cmd_band(path: str):
+    """(line names, columns, table [n_lines, 5 + 3 m + 2]) of a .cmdBand file."""
+    return read_table_file(path, "line")
+
+
+def cmd_band_settings(args) -> dict:
+    """cmdBand's settings as the program parses `args` (flags, --config file): a dict of its keys (ratios, levels: tuples of
+    floats; colours: a tuple of "f1-f2" strings; wdTypes: the mask)."""
+    argv = (C.c_char_p * (len(args) + 1))(b"cmdBand", *[str(a).encode() for a in args])
+    buf = C.create_string_buffer(4096)
+    _check(load().b9h_cmd_band_settings(len(args) + 1, argv, buf, 4096))
+    d = {}
+    for line in buf.value.decode().splitlines():
+        k, _, v = line.partition(" = ")
+        v = v.strip()
+        if k in ("ratios", "levels"):
+            d[k] = tuple(float(x) for x in v.split(",")) if v else ()
+        elif k == "colours":
+            d[k] = tuple(v.split(",")) if v else ()
+        else:
+            d[k] = float(v) if k == "tol" else int(v)
     return d
 
 

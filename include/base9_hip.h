@@ -731,6 +731,62 @@ int b9_pointwise(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flag
                  double *tail    /* host [n_stars][tail_len],  in/out, may be NULL */,
                  double *row_lpd /* host [n_rows],             out,    may be NULL */);
 
+/*
+ * Isochrone and WD-sequence bands over a saved chain (the cmdBand counterpart): the model locus the posterior implies in the
+ * CMD, with what a credible band needs.  Added in ABI 6 without a version change, as its siblings were: purely additive.  Needs a
+ * loaded pack and no stars, like b9_predict_mags; honours b9_options.n_pops and ignores everything else in the options.
+ *
+ * Lines.  Each population k has P = n_ratio n_eep + n_types n_wd_nodes points: MS/RGB point (s, e) at p = s n_eep + (e - eep0),
+ * WD point (t, j) at p = n_ratio n_eep + t n_wd_nodes + (j - 1), t counting the set bits of wd_types in ascending order,
+ * j = 1 .. n_wd_nodes.  Each point has C = 1 + n_filt + n_colour columns: its ZAMS mass, one apparent magnitude per filter, the
+ * colours.  Line (k P + p) C + c; n_lines = n_pops P C.
+ *
+ * Values.  MS/RGB point (k, s, e) exists in row r when b9_derive_isochrone(row, k) reports n > 0 and first <= e < first + n.  Its
+ * mass and primary magnitudes are that isochrone's point, the same bits; for q_s > 0 the secondary is the MS/RGB rule at q_s m_e
+ * on the same isochrone (below the first mass: no flux), combined by b9_predict_mags' expression under its rule that a filter in
+ * which neither component gives flux stays B9_MAG_NOFLUX; the apparent magnitude is x + (mod + (A_f / A_V - 1) A_V).  WD point
+ * (k, t, j) exists when population k is inside the grid, dM_k = (M_wd_up - tip_k) / n_wd_nodes > 0 and the node is COOLED
+ * (b9_wd_moments); its mass is tip_k + dM_k (double)j and its magnitudes are b9_wd_moments' node table's for type t.  A magnitude
+ * column enters only when its value is finite and not B9_MAG_NOFLUX; a colour only when both its filters enter, as one rounded
+ * subtraction of the two apparent magnitudes; a point that does not exist adds nothing to any column.
+ *
+ * Increments.  With v the value and d = v - pivot[line] (one rounded subtraction; pivot NULL: 0), row r updates mom[line] by
+ * N += 1, SUM += d, SUMSQ += d d, MIN = fmin(MIN, v), MAX = fmax(MAX, v), each one plain IEEE operation, rows ascending; and adds
+ * 1.0 to one word of bins[line] on the line's own finite edges e_0 < ... < e_B (B = n_bins): [0] below, [1 + b] e_b <= v < e_(b+1)
+ * decided on the value's bits, [B + 1] at or above, and 1.0 to [B + 2], the total -- b9_star_bins' layout, so
+ * b9h_refine_star_edges serves the lines with n_stars = n_lines.  flags = 0 starts from N = SUM = SUMSQ = 0, MIN = +inf,
+ * MAX = -inf and zero bins, B9_BAND_CONTINUE from the caller's arrays.  Either of mom and bins may be NULL, not both; edges and
+ * n_bins matter only with bins.
+ *
+ * The same bits for the call's own chunking (at most 256 rows, fewer while the chunk's value table or its WD node table would
+ * exceed 64 MiB, down to one row at a time; beyond 8 GiB per row, or for the lines' pivots, moments, bins and edges together,
+ * B9_ERR_CAPACITY), for any split of the rows over continued
+ * calls, a repeated call, any history of the context and any other lines in the spec.  Synchronous; host pointers.
+ * B9_ERR_INVALID (outputs untouched; checked on the host before anything is launched) for n_rows < 1, NULL params or spec, both
+ * outputs NULL, no lines, n_eep < 0, n_ratio outside 0 .. B9_BAND_MAX_RATIOS, a ratio outside [0, 1] or not finite, n_eep > 0
+ * with n_ratio = 0, n_wd_nodes < 0, n_wd_nodes > 0 with wd_types outside 1 .. 3, n_colour outside 0 .. B9_BAND_MAX_COLOURS, a
+ * colour with a filter out of range or f1 == f2, bins without edges, n_bins outside 1 .. B9_BAND_MAX_BINS, any line's edges not
+ * finite or not strictly ascending.  B9_ERR_STATE without a pack or while a sampler block is outstanding.  The call uses a
+ * buffer of its own: a B9_BLOCK_CONTINUE block enqueued after it gives the same bits as one enqueued without it.
+ */
+#define B9_BAND_MAX_RATIOS 4
+#define B9_BAND_MAX_COLOURS 8
+#define B9_BAND_MAX_BINS 30
+#define B9_BAND_CONTINUE 1
+enum { B9_BAND_N = 0, B9_BAND_SUM = 1, B9_BAND_SUMSQ = 2, B9_BAND_MIN = 3, B9_BAND_MAX = 4, B9_BAND_NMOM = 5 };
+typedef struct b9_band_spec {
+    int32_t eep0, n_eep;        /* MS/RGB points: EEP ids eep0 .. eep0 + n_eep - 1 (n_eep may be 0)   */
+    int32_t n_ratio;            /* 0 .. B9_BAND_MAX_RATIOS loci: mass ratio q_s in [0, 1], 0 = single */
+    const double *ratio;        /* [n_ratio]                                                          */
+    int32_t n_wd_nodes;         /* WD points per atmosphere type (0: none)                            */
+    int32_t wd_types;           /* bit 0 DA, bit 1 DB                                                 */
+    int32_t n_colour;           /* 0 .. B9_BAND_MAX_COLOURS                                           */
+    const int32_t *colour;      /* [n_colour][2]: filters f1 != f2, column = app_f1 - app_f2          */
+} b9_band_spec;
+int b9_cmd_band(b9_ctx *ctx, const double *params, int32_t n_rows, const b9_band_spec *spec, int32_t flags,
+                const double *pivot /* [n_lines], nullable: 0 */, double *mom /* [n_lines][5], in/out, nullable */,
+                const double *edges /* [n_lines][n_bins + 1] */, int32_t n_bins, double *bins /* [n_lines][n_bins + 3], in/out, nullable */);
+
 /* ---- introspection (used by bench/tests; no compute) --------------------------------- */
 int b9_max_eep(const b9_ctx *ctx);           /* longest isochrone in the loaded pack        */
 int b9_device_id(const b9_ctx *ctx);

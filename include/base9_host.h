@@ -187,6 +187,24 @@ int b9h_wd_intervals_table(long n_wd, int n_sel, int n_levels, const double *mem
                            const double *hi, const int32_t *passes, const int32_t *flags, double *table);
 int b9h_write_wd_intervals(const char *path, const char *const *ids, long n_wd, int quantity_mask, const double *levels, int n_levels, const double *table);
 int b9h_wd_intervals_settings(int argc, char **argv, char *out, int cap);
+/* cmdBand.  The lines are b9_cmd_band's, n_lines = n_pops P C; b9h_refine_star_edges serves them unchanged with n_stars = n_lines.
+ * b9h_band_first_ranges: from b9_cmd_band's moments [n_lines][B9_BAND_NMOM], per line, the first range [lo, hi] = [MIN - pad,
+ * MAX + pad], pad = max(0.01 (MAX - MIN), 1e-6 max(1, |MIN|, |MAX|)); a line with N = 0 gets [0, 1].  What the refinement loop
+ * (b9h::interval_loop, hostlib.interval_loop) cuts evenly for its first pass.
+ * b9h_band_first_edges: that cut, the n_bins + 1 strictly ascending edges lo + (hi - lo) (b / n_bins): e_0 < MIN and e_B > MAX.
+ * b9h_band_table: -> [n_lines][5 + 3 n_levels + 2]: N, mean = pivot + SUM / N (pivot NULL: 0), sd = sqrt(max(0, SUMSQ / N -
+ * (SUM / N)^2)), the population standard deviation, min, max, then value, lo, hi per level, passes, flags; N = 0: mean and sd NaN.
+ * b9h_write_cmd_band: the file <base>.cmdBand (docs/FORMATS.md) of that table through the shared table writer, 17 significant
+ * digits; names [n_lines]: the lines' labels.
+ * b9h_cmd_band_settings: cmdBand's command line (argv[0] is skipped) and YAML parsed as the program parses them -- "key = value"
+ * lines of ratios (comma-separated), wdNodes, wdTypes (the mask: 1 da, 2 db, 3 both), colours (f1-f2,..), levels, tol, maxPasses,
+ * nPops. */
+int b9h_band_first_ranges(const double *mom, long n_lines, double *first_lo, double *first_hi);
+int b9h_band_first_edges(const double *mom, long n_lines, int n_bins, double *edges);
+int b9h_band_table(const double *mom, const double *pivot, long n_lines, int n_levels, const double *value, const double *lo, const double *hi,
+                   const int32_t *passes, const int32_t *flags, double *table);
+int b9h_write_cmd_band(const char *path, const char *const *names, long n_lines, const double *levels, int n_levels, const double *table);
+int b9h_cmd_band_settings(int argc, char **argv, char *out, int cap);
 /* photResiduals.  b9h_resid_table: b9_phot_resid's star_resid [n_stars][2 + 2 n_filt] with the catalogue's obs and sigma
  * [n_stars][n_filt] (sigma <= 0: filter unused) -> the per-star table [n_stars][2 + 4 n_filt]: rows, member = acc[1] / rows,
  * then per filter predMag = c + acc[2 + 2f] / acc[1] (c = obs for a used filter, else 0), predSd = sqrt(max(0, acc[3 + 2f] / acc[1]
