@@ -1,8 +1,9 @@
 // b9_capi_eval.cpp -- one log-posterior evaluation through the C ABI: derive -> stars -> finalize (b9_logpost,
 // b9_logpost_device), the per-star mass draws (b9_sample_mass), the isochrone dump (b9_derive_isochrone) and the forward
-// model alone (b9_predict_mags); the five reductions over a saved chain through chain_reduce -- the per-star posterior moments
+// model alone (b9_predict_mags); the reductions over a saved chain through chain_reduce -- the per-star posterior moments
 // (b9_star_moments), the binned mass posteriors (b9_mass_hist), the per-star bins (b9_star_bins), the posterior-predictive
-// residuals (b9_phot_resid) and the pointwise predictive densities (b9_pointwise) --; and the three calls on a WD mass grid of the
+// residuals (b9_phot_resid), the leave-one-filter-out predictions (b9_filter_loo) and the pointwise predictive densities
+// (b9_pointwise) --; and the three calls on a WD mass grid of the
 // caller's own size through wd_grid_reduce -- the WD-stage stars' posterior draws (b9_sample_wd_mass), their exact posterior
 // moments (b9_wd_moments) and their per-line bins (b9_wd_bins); and the loci a saved chain implies in the CMD (b9_cmd_band: a pack,
 // no stars, its own driver and arena).  Every launch wrapper takes its derived isochrone set as one
@@ -405,7 +406,7 @@ int b9_n_wd_stars(const b9_ctx *ctx)
 
 namespace {
 
-// ---- the reductions over a saved chain: b9_star_moments, b9_mass_hist, b9_star_bins, b9_phot_resid, b9_pointwise ------------
+// ---- the reductions over a saved chain: b9_star_moments, b9_mass_hist, b9_star_bins, b9_phot_resid, b9_filter_loo, b9_pointwise
 // What one of them is to the driver below.  Rows are worked in chunks of at most max_rows, and of as few rows as keep the chunk's
 // increments [rows][n_stars][n_col] within scratch_bytes.
 struct ChainCall {
@@ -575,6 +576,8 @@ int wd_grid_reduce(b9_ctx *ctx, const WdGridCall &c, const double *params, int n
 #define B9_SBIN_MAX_ROWS 32
 #define B9_RESID_SCRATCH_BYTES ((size_t)64 << 20)
 #define B9_RESID_MAX_ROWS 32
+#define B9_LOO_SCRATCH_BYTES ((size_t)64 << 20)
+#define B9_LOO_MAX_ROWS 32
 // (B9_PW_MAX_ROWS: b9_launch.h -- the reducers hold a chunk's rows in registers; 32 rows up to 65536 stars)
 #define B9_PW_SCRATCH_BYTES ((size_t)16 << 20)
 
@@ -675,6 +678,40 @@ int b9_phot_resid(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t fla
         HIPCHK(ctx, hipMemcpyAsync(d.extra[0], piv.data(), sizeof(double) * piv.size(), hipMemcpyHostToDevice, ctx->stream));
         if (d.rows) HIPCHK(ctx, hipMemcpyAsync(isig(d), is.data(), sizeof(double) * is.size(), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, b9k_resid_stage(pk, ctx->st, reinterpret_cast<double *>(d.extra[0]), piv_mg(d), ctx->stream));
+        return (int)B9_OK;
+    });
+}
+
+int b9_filter_loo(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags, double *star_loo, double *row_loo)
+{
+    if (!ctx || !params || n_rows < 1 || (!star_loo && !row_loo)) return B9_ERR_INVALID;
+    if (const int rc = chain_ready(ctx)) return rc;
+    const DevPack &pk = ctx->pk;
+    const size_t n = (size_t)ctx->st.n, nf = (size_t)pk.nf, ncol = 2 + 3 * nf, n_mg = (size_t)ctx->st.mg_pad * pk.nfp;
+    // the call's parts: {the pivots, log(sigma sqrt(2 pi))} in the caller's order [2][n][nf] and in the mg_* copy's [2][mg_pad][nfp],
+    // and 1 / sigma [n][nf]
+    const ChainCall c{"b9_filter_loo", ncol, ncol, 1 + 6 * nf, B9_LOO_MAX_ROWS, B9_LOO_SCRATCH_BYTES, (flags & B9_LOO_CONTINUE) != 0, star_loo, row_loo,
+                      {2 * 8 * n * nf, 2 * 8 * n_mg, 8 * n * nf}};
+    auto in = [](const ChainDev &d) { return reinterpret_cast<double *>(d.extra[0]); };
+    auto mg = [](const ChainDev &d) { return reinterpret_cast<double *>(d.extra[1]); };
+    auto isig = [](const ChainDev &d) { return reinterpret_cast<double *>(d.extra[2]); };
+    std::vector<double> pl, is;          // (the uploads' sources: they live until the driver has waited for the stream)
+    return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
+        return b9k_filter_loo(pk, ctx->st, d, m, mg(d), mg(d) + n_mg, in(d) + n * nf, isig(d), ctx->stream);
+    }, [&](const ChainDev &d) {
+        // the pivots (the caller's obs bits where sigma > 0, else 0), log(sigma sqrt(2 pi)) (0: filter unused) and 1 / sigma (0: unused)
+        const HostStars &h = ctx->hs;
+        pl.resize(2 * n * nf); is.resize(n * nf);
+        for (size_t k = 0; k < n * nf; ++k) {
+            const bool used = h.sigma[k] > 0.0;
+            pl[k] = used ? h.obs[k] : 0.0;
+            pl[n * nf + k] = used ? std::log(h.sigma[k] * 2.5066282746310002) : 0.0;
+            is[k] = used ? 1.0 / h.sigma[k] : 0.0;
+        }
+        HIPCHK(ctx, hipMemcpyAsync(in(d), pl.data(), sizeof(double) * pl.size(), hipMemcpyHostToDevice, ctx->stream));
+        if (d.rows) HIPCHK(ctx, hipMemcpyAsync(isig(d), is.data(), sizeof(double) * is.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, b9k_resid_stage(pk, ctx->st, in(d), mg(d), ctx->stream));
+        HIPCHK(ctx, b9k_resid_stage(pk, ctx->st, in(d) + n * nf, mg(d) + n_mg, ctx->stream));
         return (int)B9_OK;
     });
 }

@@ -43,6 +43,7 @@
 //                                     edges, one selected quantity per blockIdx.z, summed over the rows
 //   k_band_points / k_band_wd_points / k_band_accumulate   b9_cmd_band: the MS/RGB loci and WD sequences a saved chain's rows imply
 //                                     (one lane per point into a chunk's value table), reduced over the rows one lane per line
+//   k_star_loo / _wd / k_loo_rows       b9_filter_loo: exact leave-one-filter-out predictions and densities (b9_filter_loo.hip.h)
 //   k_star_resid / _wd / k_resid_stage / k_resid_rows   b9_phot_resid: exact posterior-predictive magnitude
 //                                     moments per filter over the same grid, summed over the rows and, standardised, the stars
 //   k_star_lpd / _wd / k_pw_accumulate / k_pw_tail / k_pw_rows   b9_pointwise: every star's marginal log-likelihood per row over
@@ -96,6 +97,7 @@ namespace tree_kd5 {
 #include "b9_star_bins.hip.h"
 #include "b9_wd_bins.hip.h"
 #include "b9_phot_resid.hip.h"
+#include "b9_filter_loo.hip.h"
 #include "b9_pointwise.hip.h"
 #include "b9_cmd_band.hip.h"
 
@@ -529,6 +531,34 @@ hipError_t b9k_phot_resid(const DevPack &pk, const DevStars &st, const B9Chain &
         if (c.acc) launch_chain_accumulate(c.scratch, n_rows, (long long)st.n * (2 + 2 * nf), c.acc, stream);
         if (c.rows) {
             const auto kr = with_lds(k_resid_rows, sizeof(double) * 2 * B9_RESID_TILE * (2 + 3 * (size_t)nf));      // two tiles of {x, 1 / sigma}
+            if (kr.err != hipSuccess) return kr.err;
+            hipLaunchKernelGGL(kr.kern, dim3(n_rows), dim3(256), kr.lds, stream, c.scratch, isig, st.n, nf, c.rows);
+        }
+        return hipGetLastError();
+    });
+}
+
+// ---- b9_filter_loo: the node tables of a chunk of rows, the stars' leave-one-filter-out increments, the accumulation, the rows' sums
+hipError_t b9k_filter_loo(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, const double *piv_mg, const double *lsn_mg, const double *lsn,
+                          const double *isig, hipStream_t stream)
+{
+    return dispatch(pk.nfp, c.set.n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value, LT = LooTile<NFP>::LT;
+        const B9IsoSet &s = c.set;
+        if (!piv_mg || !lsn_mg || !lsn || (c.rows && !isig)) return hipErrorInvalidValue;
+        const int nf = pk.nf;
+        const ChainTables t = chain_tables<NFP>(pk, st, c, n_rows, stream);
+        if (t.err != hipSuccess) return t.err;
+        const auto k = with_lds(k_star_loo<NFP, NPOPS>, sizeof(double) * 64 * (NPOPS * 4 + 4 * (2 + 4 * (size_t)LT)));      // seeds, one population's states
+        if (k.err != hipSuccess) return k.err;
+        hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows, NFP / LT), dim3(256), k.lds, stream, st, nf, piv_mg, lsn_mg, s.hdr, s.iso, s.iso_stride,
+                           s.mass_cap, s.params, c.mg.K, c.mg.Q, c.mg.tab, t.L, t.cut2, c.scratch);
+        if (st.n_wd > 0)
+            hipLaunchKernelGGL((k_star_loo_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, nf, pk.m_wd_up, s.hdr, s.params, c.mg.K,
+                               c.mg.wd_tab, lsn, c.scratch);
+        if (c.acc) launch_chain_accumulate(c.scratch, n_rows, (long long)st.n * (2 + 3 * nf), c.acc, stream);
+        if (c.rows) {
+            const auto kr = with_lds(k_loo_rows, sizeof(double) * 2 * B9_LOO_TILE * (2 + 4 * (size_t)nf));      // two tiles of {x, 1 / sigma}
             if (kr.err != hipSuccess) return kr.err;
             hipLaunchKernelGGL(kr.kern, dim3(n_rows), dim3(256), kr.lds, stream, c.scratch, isig, st.n, nf, c.rows);
         }

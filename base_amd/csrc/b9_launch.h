@@ -218,6 +218,12 @@ hipError_t b9k_star_bins(const DevPack &pk, const DevStars &st, const B9Chain &c
 hipError_t b9k_resid_stage(const DevPack &pk, const DevStars &st, const double *piv_in, double *piv_mg, hipStream_t stream);
 hipError_t b9k_phot_resid(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, const double *piv_mg, const double *isig, hipStream_t stream);
 
+// b9_filter_loo: every star's increments into scratch [n_rows][st.n][2 + 3 nf], then acc [st.n][2 + 3 nf] (may be null) and rows
+// [n_rows][1 + 6 nf] (may be null; isig as b9k_phot_resid's).  piv_mg, lsn_mg: the pivots and log(sigma sqrt(2 pi)) (0 for an
+// unused filter) in the mg_* copy's order (b9k_resid_stage); lsn [st.n][nf]: the latter in the caller's star order.
+hipError_t b9k_filter_loo(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, const double *piv_mg, const double *lsn_mg, const double *lsn,
+                          const double *isig, hipStream_t stream);
+
 // rows of one b9k_pointwise launch: the reducers hold a chunk's rows in registers (k_pw_accumulate, k_pw_tail), and b9_pointwise
 // chunks its rows by the same number
 #define B9_PW_MAX_ROWS 32

@@ -328,6 +328,28 @@ class Engine:
         self._check(self.lib.b9_phot_resid(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], flags, ptr(sr), ptr(rr)))
         return sr, rr
 
+    def filter_loo(self, rows: np.ndarray, acc: Optional[np.ndarray] = None, want_star: bool = True,
+                   want_rows: bool = True) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+        """b9_filter_loo: the exact leave-one-filter-out predictions over `rows`: (star_loo [n_stars, 2 + 3 n_filt] summed over
+        the rows -- ROWS, MEMBER, then per filter p sum w^f d, p sum w^f d^2 about the star's pivot and p l_f, the log density of
+        the observation under what the other filters predict --, row_loo [n_rows, 1 + 6 n_filt] -- sum p, then per filter N, R,
+        C, W, D, E over the stars that have the filter).  acc=None starts from zeros; else the call continues it
+        (B9_LOO_CONTINUE) and returns a new array.  want_star / want_rows = False passes NULL for that output (None back)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        nf = self.n_filt
+        flags = 0
+        sl = rl = None
+        if want_star:
+            if acc is None:
+                sl = np.zeros((self.n_stars, 2 + 3 * nf))
+            else:
+                sl, flags = np.array(acc, dtype=np.float64, order="C").reshape(self.n_stars, 2 + 3 * nf), abi.LOO_CONTINUE
+        if want_rows:
+            rl = np.zeros((rows.shape[0], 1 + 6 * nf))
+        ptr = lambda a: a.ctypes.data_as(_dp) if a is not None else None      # noqa: E731
+        self._check(self.lib.b9_filter_loo(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], flags, ptr(sl), ptr(rl)))
+        return sl, rl
+
     def pointwise(self, rows: np.ndarray, tail_len: int = 0, acc: Optional[np.ndarray] = None, tail: Optional[np.ndarray] = None,
                   want_rows: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
         """b9_pointwise: every star's marginal log-likelihood v over `rows`, reduced: (acc [n_stars, 8] -- abi.PW_ROWS .. PW_M2 --,

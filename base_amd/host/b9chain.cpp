@@ -79,9 +79,12 @@ const ProgramFlags kCmdBandFlags = {{"ratios", "cmdBandRatios", false}, {"wdNode
                                     {"colours", "cmdBandColours", false}, {"levels", "cmdBandLevels", false}, {"tol", "cmdBandTol", false},
                                     {"maxPasses", "cmdBandMaxPasses", false}, {"nPops", "cmdBandNPops", false}};
 const ProgramFlags kPhotResidFlags = {{"perStar", "photResidualsPerStar", true}, {"nPops", "photResidualsNPops", false}};
+const ProgramFlags kFilterCheckFlags = {{"perStar", "filterCheckPerStar", true}, {"nPops", "filterCheckNPops", false}};
 const ProgramFlags kModelScoreFlags = {{"perRow", "modelScorePerRow", true}, {"nPops", "modelScoreNPops", false}};
 
 PhotResidConfig phot_resid_config(const Settings &st) { return {st.integer("photResiduals.perStar", 0) != 0}; }
+
+FilterCheckConfig filter_check_config(const Settings &st) { return {st.integer("filterCheck.perStar", 0) != 0}; }
 
 ModelScoreConfig model_score_config(const Settings &st) { return {st.integer("modelScore.perRow", 0) != 0, st.str("modelScore.compareTo", "")}; }
 
@@ -849,6 +852,79 @@ void write_filter_resid(const std::string &path, const std::vector<std::string> 
     for (const char *q : {"meanZ", "chi2", "offset"})
         for (const char *s : {"mean", "sd", "p16", "p50", "p84"}) cols.push_back({std::string(q) + "_" + s, "%.17g"});
     write_table(path, "filter", &filters, cols, (long)filters.size(), table, kFilterResidCols);
+}
+
+// ---------------------------------------------------------------------------------------------
+// filterCheck
+// ---------------------------------------------------------------------------------------------
+void loo_table(const double *star_loo, const double *obs, const double *sigma, long n_stars, int nf, double *table)
+{
+    const size_t ncol = 2 + 3 * (size_t)nf, tcol = 2 + 5 * (size_t)nf;
+    for (long i = 0; i < n_stars; ++i) {
+        const double *a = star_loo + (size_t)i * ncol;
+        double *t = table + (size_t)i * tcol;
+        for (size_t c = 0; c < tcol; ++c) t[c] = 0.0;
+        t[0] = a[0];
+        if (a[0] > 0.0) t[1] = a[1] / a[0];
+        if (!(a[1] > 0.0)) continue;                         // no membership weight: every derived value is 0
+        for (int f = 0; f < nf; ++f) {
+            const double sg = sigma[(size_t)i * nf + f], o = obs[(size_t)i * nf + f];
+            const bool used = sg > 0.0;
+            const double m1 = a[2 + 3 * f] / a[1], m2 = a[3 + 3 * f] / a[1], var = std::max(0.0, m2 - m1 * m1);
+            double *tf = t + 2 + 5 * (size_t)f;
+            tf[0] = (used ? o : 0.0) + m1;
+            tf[1] = std::sqrt(var);
+            if (used) { tf[2] = o - tf[0]; tf[3] = tf[2] / std::sqrt(sg * sg + var); tf[4] = a[4 + 3 * f] / a[1]; }
+        }
+    }
+}
+
+void filter_loo_table(const double *row_loo, long n_rows, int nf, double *table)
+{
+    const size_t ncol = 1 + 6 * (size_t)nf;
+    std::vector<double> v;
+    for (int f = 0; f < nf; ++f) {
+        double *t = table + (size_t)f * kFilterCheckCols;
+        for (int c = 0; c < kFilterCheckCols; ++c) t[c] = 0.0;
+        std::vector<long> use;
+        for (long r = 0; r < n_rows; ++r)
+            if (row_loo[(size_t)r * ncol + 1 + 6 * f] > 0.0) use.push_back(r);
+        t[0] = (double)use.size();
+        if (use.empty()) continue;
+        for (int q = 0; q < 4; ++q) {
+            v.resize(use.size());
+            double sum = 0.0;
+            for (size_t k = 0; k < use.size(); ++k) {
+                const double *x = row_loo + (size_t)use[k] * ncol + 1 + 6 * f;            // N, R, C, W, D, E
+                v[k] = q == 0 ? x[1] / x[0] : q == 1 ? x[2] / x[0] : q == 2 ? (x[3] > 0.0 ? x[4] / x[3] : 0.0) : x[5] / x[0];
+                sum += v[k];
+            }
+            const double mean = sum / (double)use.size();
+            double ss = 0.0;
+            for (double x : v) ss += (x - mean) * (x - mean);
+            std::sort(v.begin(), v.end());
+            double *tq = t + 1 + 5 * q;
+            tq[0] = mean;
+            tq[1] = std::sqrt(ss / (double)use.size());
+            tq[2] = percentile_sorted(v, 0.16); tq[3] = percentile_sorted(v, 0.50); tq[4] = percentile_sorted(v, 0.84);
+        }
+    }
+}
+
+void write_star_filter_check(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &filters, const double *table)
+{
+    std::vector<TableColumn> cols = columns({"rows", "member"}, "%.17g");
+    for (const std::string &n : filters)
+        for (const char *what : {"_looMag", "_looSd", "_resid", "_z", "_lpd"}) cols.push_back({n + what, "%.17g"});
+    write_table(path, "id", &ids, cols, (long)ids.size(), table, cols.size());
+}
+
+void write_filter_check(const std::string &path, const std::vector<std::string> &filters, const double *table)
+{
+    std::vector<TableColumn> cols = {{"nRows", "%.17g"}};
+    for (const char *q : {"meanZ", "chi2", "offset", "lpd"})
+        for (const char *s : {"mean", "sd", "p16", "p50", "p84"}) cols.push_back({std::string(q) + "_" + s, "%.17g"});
+    write_table(path, "filter", &filters, cols, (long)filters.size(), table, kFilterCheckCols);
 }
 
 // ---------------------------------------------------------------------------------------------

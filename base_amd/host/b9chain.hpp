@@ -1,5 +1,5 @@
 // b9chain.hpp -- what the programs over a saved chain (sampleMass, sampleWDMass, starSummary, wdSummary, wdIntervals, cmdBand, massFunction,
-// binaryStats, starIntervals, photResiduals, modelScore) share above the C ABI and below their mains: their settings, the loop over the
+// binaryStats, starIntervals, photResiduals, filterCheck, modelScore) share above the C ABI and below their mains: their settings, the loop over the
 // chain's rows, the tables derived from the device's sums and the files they are written to (docs/FORMATS.md).  Host arithmetic
 // only: nothing here needs a context or a GPU.  b9host.hpp includes this header.
 #pragma once
@@ -25,7 +25,7 @@ long wd_mass_nodes(const Settings &st, const std::string &section);
 
 // Each program's own spellings of shared flags (Settings::parse_args' second table): the short names belong to simCluster
 // (--minMass --maxMass --nPops) and massFunction (--quantity --perStar) in the shared table.
-extern const ProgramFlags kMassFunctionFlags, kStarIntervalsFlags, kPhotResidFlags, kModelScoreFlags;
+extern const ProgramFlags kMassFunctionFlags, kStarIntervalsFlags, kPhotResidFlags, kFilterCheckFlags, kModelScoreFlags;
 
 // massFunction.{nBins, minMass, maxMass, linearBins, quantity, perStar} (flags --nBins --minMass --maxMass --linearBins --quantity
 // --perStar).  Default: 24 log-spaced bins over [0.1, M_wd_up] of the primary mass.
@@ -46,6 +46,9 @@ StarIntervalsConfig star_intervals_config(const Settings &st);
 // photResiduals.perStar (--perStar): the per-star file as well
 struct PhotResidConfig { bool per_star; };
 PhotResidConfig phot_resid_config(const Settings &st);
+// filterCheck.perStar (--perStar): the per-star file as well
+struct FilterCheckConfig { bool per_star; };
+FilterCheckConfig filter_check_config(const Settings &st);
 // modelScore.{perRow, compareTo} (--perRow, --compareTo otherBase): the per-row file as well; compare two fits instead
 struct ModelScoreConfig { bool per_row; std::string compare_to; };
 ModelScoreConfig model_score_config(const Settings &st);
@@ -245,6 +248,24 @@ void filter_resid_table(const double *row_resid, long n_rows, int nf, double *ta
 // Numbers are written with 17 significant digits: the files read back to the tables' bits.
 void write_phot_resid(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &filters, const double *table);
 void write_filter_resid(const std::string &path, const std::vector<std::string> &filters, const double *table);
+
+// ---- filterCheck -----------------------------------------------------------------------------------
+// b9_filter_loo's star_loo [n_stars][2 + 3 nf] with the catalogue's obs / sigma [n_stars][nf] -> the per-star table
+// [n_stars][2 + 5 nf]: rows, member (acc[1] / acc[0]), then per filter
+//   looMag = c + acc[2 + 3f] / acc[1]           (c = obs where sigma > 0, else 0: the magnitude the OTHER filters predict)
+//   looSd  = sqrt(max(0, acc[3 + 3f] / acc[1] - (acc[2 + 3f] / acc[1])^2))       (the between-node spread of that prediction)
+//   resid  = obs - looMag,   z = resid / sqrt(sigma^2 + looSd^2)   (the predictive z: a calibrated fit spreads it like N(0, 1)),
+//   lpd    = acc[4 + 3f] / acc[1]               (the mean log predictive density);   resid, z, lpd are 0 for an unused filter.
+// A star without membership weight (acc[1] == 0) has every derived value 0.
+void loo_table(const double *star_loo, const double *obs, const double *sigma, long n_stars, int nf, double *table);
+// b9_filter_loo's row_loo [n_rows][1 + 6 nf] -> the per-filter table [nf][kFilterCheckCols]: the number of rows with N_f > 0, then
+// over those rows the mean, population sd and 16th / 50th / 84th percentiles of R_f / N_f, C_f / N_f, D_f / W_f and E_f / N_f
+constexpr int kFilterCheckCols = 21;
+void filter_loo_table(const double *row_loo, long n_rows, int nf, double *table);
+// <base>.starFilterCheck: "id rows member {<filter>_looMag <filter>_looSd <filter>_resid <filter>_z <filter>_lpd}", one line per
+// star in the order of ids; <base>.filterCheck: "filter nRows {meanZ chi2 offset lpd}_{mean sd p16 p50 p84}", one line per filter.
+void write_star_filter_check(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &filters, const double *table);
+void write_filter_check(const std::string &path, const std::vector<std::string> &filters, const double *table);
 
 // ---- binaryStats -----------------------------------------------------------------------------------
 // binaryStats.{massEdges, massBins, qMin} (flags --massEdges e0,e1,.. | --massBins N, --qMin q).  massEdges: the primary-mass

@@ -135,6 +135,7 @@ const std::map<std::string, std::string> &Settings::flag_map()
         {"quantities", "wdIntervals.quantities"}, {"wdIntervalsLevels", "wdIntervals.levels"}, {"wdIntervalsTol", "wdIntervals.tol"},
         {"wdIntervalsMaxPasses", "wdIntervals.maxPasses"}, {"wdIntervalsNMassNodes", "wdIntervals.nMassNodes"}, {"wdIntervalsNPops", "wdIntervals.nPops"},
         {"photResidualsPerStar", "photResiduals.perStar"}, {"photResidualsNPops", "photResiduals.nPops"},
+        {"filterCheckPerStar", "filterCheck.perStar"}, {"filterCheckNPops", "filterCheck.nPops"},
         {"massEdges", "binaryStats.massEdges"}, {"massBins", "binaryStats.massBins"}, {"qMin", "binaryStats.qMin"}, {"binaryStatsNPops", "binaryStats.nPops"},
         {"cmdBandRatios", "cmdBand.ratios"}, {"cmdBandWdNodes", "cmdBand.wdNodes"}, {"cmdBandWdTypes", "cmdBand.wdTypes"}, {"cmdBandColours", "cmdBand.colours"},
         {"cmdBandLevels", "cmdBand.levels"}, {"cmdBandTol", "cmdBand.tol"}, {"cmdBandMaxPasses", "cmdBand.maxPasses"}, {"cmdBandNPops", "cmdBand.nPops"},

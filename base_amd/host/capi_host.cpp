@@ -441,6 +441,45 @@ int b9h_write_filter_resid(const char *path, const char *const *filters, int n_f
     });
 }
 
+int b9h_loo_table(const double *star_loo, const double *obs, const double *sigma, long n_stars, int n_filt, double *table)
+{
+    return guard([&] {
+        if (n_stars < 0 || n_filt < 1 || !table || (n_stars > 0 && (!star_loo || !obs || !sigma))) throw std::runtime_error("b9h_loo_table: invalid argument");
+        b9h::loo_table(star_loo, obs, sigma, n_stars, n_filt, table);
+    });
+}
+
+int b9h_filter_loo_table(const double *row_loo, long n_rows, int n_filt, double *table)
+{
+    return guard([&] {
+        if (n_rows < 0 || n_filt < 1 || !table || (n_rows > 0 && !row_loo)) throw std::runtime_error("b9h_filter_loo_table: invalid argument");
+        b9h::filter_loo_table(row_loo, n_rows, n_filt, table);
+    });
+}
+
+int b9h_write_star_filter_check(const char *path, const char *const *ids, long n_stars, const char *const *filters, int n_filt, const double *table)
+{
+    return guard([&] {
+        if (!path || n_stars < 0 || n_filt < 1 || !filters || (n_stars > 0 && (!ids || !table))) throw std::runtime_error("b9h_write_star_filter_check: invalid argument");
+        b9h::write_star_filter_check(path, strings(ids, n_stars), strings(filters, n_filt), table);
+    });
+}
+
+int b9h_write_filter_check(const char *path, const char *const *filters, int n_filt, const double *table)
+{
+    return guard([&] {
+        if (!path || n_filt < 1 || !filters || !table) throw std::runtime_error("b9h_write_filter_check: invalid argument");
+        b9h::write_filter_check(path, strings(filters, n_filt), table);
+    });
+}
+
+int b9h_filter_check_settings(int argc, char **argv, char *out, int cap)
+{
+    return settings_text("b9h_filter_check_settings", argc, argv, b9h::kFilterCheckFlags, out, cap, [&](const b9h::Settings &st) {
+        return grid_text(b9h::chain_grid(st, "filterCheck")) + "perStar = " + std::to_string((int)b9h::filter_check_config(st).per_star) + "\n";
+    });
+}
+
 int b9h_phot_resid_settings(int argc, char **argv, char *out, int cap)
 {
     return settings_text("b9h_phot_resid_settings", argc, argv, b9h::kPhotResidFlags, out, cap, [&](const b9h::Settings &st) {

@@ -43,6 +43,7 @@ HOST_SYMBOLS = [
     "b9h_wd_first_ranges", "b9h_wd_intervals_table", "b9h_write_wd_intervals", "b9h_wd_intervals_settings",
     "b9h_band_first_ranges", "b9h_band_first_edges", "b9h_band_table", "b9h_write_cmd_band", "b9h_cmd_band_settings",
     "b9h_resid_table", "b9h_filter_resid_table", "b9h_write_phot_resid", "b9h_write_filter_resid", "b9h_phot_resid_settings",
+    "b9h_loo_table", "b9h_filter_loo_table", "b9h_write_star_filter_check", "b9h_write_filter_check", "b9h_filter_check_settings",
     "b9h_pointwise_table", "b9h_score_totals", "b9h_score_compare", "b9h_write_pointwise", "b9h_write_model_score", "b9h_model_score_settings",
 ]
 
@@ -123,6 +124,11 @@ def load() -> C.CDLL:
     lib.b9h_write_phot_resid.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, C.POINTER(C.c_char_p), C.c_int, _dp]
     lib.b9h_write_filter_resid.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, _dp]
     lib.b9h_phot_resid_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
+    lib.b9h_loo_table.argtypes = [_dp, _dp, _dp, C.c_long, C.c_int, _dp]
+    lib.b9h_filter_loo_table.argtypes = [_dp, C.c_long, C.c_int, _dp]
+    lib.b9h_write_star_filter_check.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, C.POINTER(C.c_char_p), C.c_int, _dp]
+    lib.b9h_write_filter_check.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, _dp]
+    lib.b9h_filter_check_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     lib.b9h_pointwise_table.argtypes = [_dp, _dp, C.c_int, C.c_long, _dp]
     lib.b9h_score_totals.argtypes = [_dp, C.c_long, _dp]
     lib.b9h_score_compare.argtypes = [_dp, C.POINTER(C.c_char_p), C.c_long, _dp, C.POINTER(C.c_char_p), C.c_long, _dp]
@@ -850,6 +856,60 @@ def phot_resid_settings(args):
     argv = (C.c_char_p * (len(args) + 1))(b"photResiduals", *[str(a).encode() for a in args])
     buf = C.create_string_buffer(1024)
     _check(load().b9h_phot_resid_settings(len(args) + 1, argv, buf, 1024))
+    return {k: int(v) for k, v in (line.split(" = ") for line in buf.value.decode().splitlines())}
+
+
+LOO_STAR_COLUMNS = ("looMag", "looSd", "resid", "z", "lpd")
+FILTER_CHECK_COLUMNS = ("nRows",) + tuple(q + "_" + s for q in ("meanZ", "chi2", "offset", "lpd") for s in ("mean", "sd", "p16", "p50", "p84"))
+
+
+def loo_table(star_loo, obs, sigma) -> np.ndarray:
+    """b9h_loo_table: b9_filter_loo's star_loo [n_stars, 2 + 3 nf] with the catalogue's obs / sigma [n_stars, nf] -> the
+    per-star table [n_stars, 2 + 5 nf]: rows, member, then LOO_STAR_COLUMNS per filter."""
+    obs = np.ascontiguousarray(obs, dtype=np.float64)
+    n, nf = obs.shape
+    sigma = np.ascontiguousarray(sigma, dtype=np.float64).reshape(n, nf)
+    sl = np.ascontiguousarray(star_loo, dtype=np.float64).reshape(n, 2 + 3 * nf)
+    out = np.empty((n, 2 + 5 * nf))
+    _check(load().b9h_loo_table(sl.ctypes.data_as(_dp), obs.ctypes.data_as(_dp), sigma.ctypes.data_as(_dp), n, nf, out.ctypes.data_as(_dp)))
+    return out
+
+
+def filter_loo_table(row_loo, n_filt: int) -> np.ndarray:
+    """b9h_filter_loo_table: b9_filter_loo's row_loo [n_rows, 1 + 6 nf] -> the per-filter table [nf, 21] (FILTER_CHECK_COLUMNS)."""
+    rl = np.ascontiguousarray(row_loo, dtype=np.float64).reshape(-1, 1 + 6 * n_filt)
+    out = np.empty((n_filt, 21))
+    _check(load().b9h_filter_loo_table(rl.ctypes.data_as(_dp), rl.shape[0], int(n_filt), out.ctypes.data_as(_dp)))
+    return out
+
+
+def write_star_filter_check(path: str, ids, filters, table) -> None:
+    """b9h_write_star_filter_check: the .starFilterCheck file of a per-star table [len(ids), 2 + 5 len(filters)]."""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(len(ids), 2 + 5 * len(filters))
+    _check(load().b9h_write_star_filter_check(path.encode(), _names(ids), len(ids), _names(filters), len(filters), t.ctypes.data_as(_dp)))
+
+
+def write_filter_check(path: str, filters, table) -> None:
+    """b9h_write_filter_check: the .filterCheck file of a per-filter table [len(filters), 21]."""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(len(filters), 21)
+    _check(load().b9h_write_filter_check(path.encode(), _names(filters), len(filters), t.ctypes.data_as(_dp)))
+
+
+def read_star_filter_check(path: str):
+    """(ids, columns, table [n_stars, 2 + 5 nf]) of a .starFilterCheck file."""
+    return read_table_file(path, "id")
+
+
+def read_filter_check(path: str):
+    """(filters, columns, table [nf, 21]) of a .filterCheck file."""
+    return read_table_file(path, "filter")
+
+
+def filter_check_settings(args):
+    """filterCheck's settings as the program parses `args` (flags, --config file): a dict of its four keys."""
+    argv = (C.c_char_p * (len(args) + 1))(b"filterCheck", *[str(a).encode() for a in args])
+    buf = C.create_string_buffer(1024)
+    _check(load().b9h_filter_check_settings(len(args) + 1, argv, buf, 1024))
     return {k: int(v) for k, v in (line.split(" = ") for line in buf.value.decode().splitlines())}
 
 

@@ -298,7 +298,7 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk);
  * b9_set_priors or b9_set_options changes the posterior: the previous block's state carries a log-posterior of the old
  * one, so the next B9_BLOCK_CONTINUE block returns B9_ERR_STATE (the message names the call that intervened) and the chain
  * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags, b9_sample_wd_mass, b9_star_moments,
- * b9_wd_moments, b9_wd_bins, b9_mass_hist, b9_ratio_hist, b9_phot_resid and b9_pointwise (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
+ * b9_wd_moments, b9_wd_bins, b9_mass_hist, b9_ratio_hist, b9_phot_resid, b9_filter_loo and b9_pointwise (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
  * context's work buffers: b9_logpost / b9_sample_mass / b9_derive_isochrone, the staging calls, b9_set_options and a block
  * with another n_walkers return B9_ERR_STATE until it has been collected.  A driver that adapts the proposal
  * from block b-1 while block b runs keeps the GPU's queue non-empty: enqueue b+1 (CONTINUE | ASYNC), wait(b), ...
@@ -680,6 +680,50 @@ int b9_wd_bins(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t n_node
 int b9_phot_resid(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags,
                   double *star_resid /* host [n_stars][2 + 2 n_filt], in/out, may be NULL */,
                   double *row_resid  /* host [n_rows][1 + 5 n_filt], out,    may be NULL */);
+
+/*
+ * Exact leave-one-filter-out predictions over a saved chain (the filterCheck counterpart).  Added in ABI 6 without a version
+ * change, as its siblings were: purely additive.  b9_phot_resid's residuals are in-sample -- the band being judged helped choose
+ * the node weights --; this call gives, for every filter, the magnitude the star's OTHER filters predict and the density of the
+ * observed value under that prediction, from one walk of the node table.
+ *
+ * Definition.  The grid, the terms t_(k,n), the finite-term rule, L = logsumexp t, the membership p and the WD-stage steps are
+ * exactly b9_star_moments'; p is the FULL-DATA membership (no leave-out has one of its own).  For a filter f the star uses
+ * (sigma_if > 0) let g_f(n) = ((pred_f(n) - obs_if) / sigma_if)^2 / 2, the node's share of its own chi^2, formed from the same
+ * scaled pair as the node's chi^2; for an unused filter g_f = 0.  Leave-out f has the terms t^f = t + g_f over the same node
+ * set, L^f = logsumexp t^f -- the populations mixed by that leave-out's own weights e^(log lambda_k + lg^f_k) / sum -- and the
+ * weights w^f = exp(t^f - L^f).  With d_f = pred_f - c_if (b9_phot_resid's pivot, one rounded subtraction) row r adds to star i
+ * the 2 + 3 n_filt columns
+ *     x[0] = 1 (ROWS),  x[1] = p (MEMBER),  x[2 + 3f] = p sum w^f d_f,  x[3 + 3f] = p sum w^f d_f^2,  x[4 + 3f] = p l_f
+ * with l_f = (L - L^f) - log(sigma_if sqrt(2 pi)) = log p(obs_f | the other filters, row, member); l_f = 0 exactly for an unused
+ * filter, whose two sums are then the in-sample ones.  Where b9_star_moments adds nothing this call adds nothing either, ROWS
+ * included.
+ *
+ * Pruning.  A node may be left out of leave-out f's sums only when t^f lies more than 40 e-folds below a data-only lower bound
+ * of max t^f: the star's seed (a valid bound because t^f >= t), then that leave-out's own running maximum.  A chunk's or unit's
+ * box is skipped only when every leave-out may skip it (the box's chi^2 bound less its largest per-filter part) and the
+ * full-data sum may.  What is dropped is below N_nodes e^-40 of that sum's weight; b9_tuning.marg_no_pruning: nothing is.
+ * x[0] and x[1] are b9_phot_resid's bits.
+ *
+ * star_loo (host, [n_stars][2 + 3 n_filt], the caller's star order, in/out, nullable): acc + x_r, one plain add per row in
+ * ascending row order; flags = 0 starts from zeros, B9_LOO_CONTINUE from the caller's values.  looMag_f = c_f + acc[2 + 3f] /
+ * acc[1], its between-node variance acc[3 + 3f] / acc[1] - (acc[2 + 3f] / acc[1])^2, the mean log predictive density
+ * acc[4 + 3f] / acc[1].
+ *
+ * row_loo (host, [n_rows][1 + 6 n_filt], out, nullable): column 0 is sum_i p_i over all stars.  For filter f, over the stars
+ * with sigma_if > 0 only, in the caller's ascending star order, one plain add each: N_f, R_f, C_f, W_f, D_f by b9_phot_resid's
+ * five formulas on the leave-out sums at [1 + 6f .. 5 + 6f], and E_f = sum x[4 + 3f] at [6 + 6f].
+ *
+ * The same bits for the call's own chunking (at most 32 rows at a time, fewer while the per-(row, star) scratch would exceed
+ * 64 MiB), any split of the rows over continued calls, a repeated call, any history of the context, any other stars in the
+ * catalogue, and either output being NULL.  Synchronous; host pointers.  B9_ERR_INVALID (outputs untouched) for n_rows < 1, NULL
+ * params or both outputs NULL; B9_ERR_STATE while a sampler block is outstanding; B9_ERR_CAPACITY as its siblings.  The call
+ * uses buffers of its own: a B9_BLOCK_CONTINUE block enqueued after it gives the same bits as one enqueued without it.
+ */
+#define B9_LOO_CONTINUE 1
+int b9_filter_loo(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags,
+                  double *star_loo /* host [n_stars][2 + 3 n_filt], in/out, may be NULL */,
+                  double *row_loo  /* host [n_rows][1 + 6 n_filt], out,    may be NULL */);
 
 /*
  * Exact pointwise predictive densities over a saved chain (the modelScore counterpart): what WAIC, PSIS-LOO and the paired

@@ -221,6 +221,23 @@ int b9h_filter_resid_table(const double *row_resid, long n_rows, int n_filt, dou
 int b9h_write_phot_resid(const char *path, const char *const *ids, long n_stars, const char *const *filters, int n_filt, const double *table);
 int b9h_write_filter_resid(const char *path, const char *const *filters, int n_filt, const double *table);
 int b9h_phot_resid_settings(int argc, char **argv, char *out, int cap);
+/* filterCheck.  b9h_loo_table: b9_filter_loo's star_loo [n_stars][2 + 3 n_filt] with the catalogue's obs and sigma
+ * [n_stars][n_filt] (sigma <= 0: filter unused) -> the per-star table [n_stars][2 + 5 n_filt]: rows, member = acc[1] / rows,
+ * then per filter looMag = c + acc[2 + 3f] / acc[1] (c = obs for a used filter, else 0), looSd = sqrt(var), var = max(0,
+ * acc[3 + 3f] / acc[1] - (acc[2 + 3f] / acc[1])^2) the between-node variance, and, for used filters (0 otherwise), resid = obs -
+ * looMag, z = resid / sqrt(sigma^2 + var) -- the predictive z, which a calibrated fit spreads like N(0, 1) -- and lpd =
+ * acc[4 + 3f] / acc[1]; every derived value is 0 when acc[1] == 0.
+ * b9h_filter_loo_table: row_loo [n_rows][1 + 6 n_filt] -> the per-filter table [n_filt][21]: the number of rows with N_f > 0,
+ * then over them the mean, population standard deviation and 16th / 50th / 84th percentiles (b9h_mass_function_table's rule) of
+ * meanZ = R_f / N_f, chi2 = C_f / N_f, offset = D_f / W_f and lpd = E_f / N_f; zeros without such a row.
+ * b9h_write_star_filter_check / b9h_write_filter_check: the files <base>.starFilterCheck and <base>.filterCheck
+ * (docs/FORMATS.md) of those tables, 17 significant digits.  b9h_filter_check_settings: filterCheck's command line (argv[0] is
+ * skipped) and YAML parsed as the program parses them -- "key = value" lines of margIsoIncrem, nMassRatios, nPops, perStar. */
+int b9h_loo_table(const double *star_loo, const double *obs, const double *sigma, long n_stars, int n_filt, double *table);
+int b9h_filter_loo_table(const double *row_loo, long n_rows, int n_filt, double *table);
+int b9h_write_star_filter_check(const char *path, const char *const *ids, long n_stars, const char *const *filters, int n_filt, const double *table);
+int b9h_write_filter_check(const char *path, const char *const *filters, int n_filt, const double *table);
+int b9h_filter_check_settings(int argc, char **argv, char *out, int cap);
 /* modelScore.  b9h_pointwise_table: b9_pointwise's acc [n_stars][8] and tail [n_stars][tail_len] (NULL or tail_len 0: no PSIS
  * fit) -> the per-star table [n_stars][9]: rows, nInf, lppd, pWaic, elpdWaic, elpdIs, paretoK, elpdLoo, pLoo.  With n_f = rows -
  * nInf: lppd = VMAX + log SPOS - log rows, pWaic = M2 / (n_f - 1) (0 for n_f < 2), elpdWaic = lppd - pWaic, elpdIs = log n_f -
