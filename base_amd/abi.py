@@ -47,6 +47,10 @@ RESID_CONTINUE = 1
 # b9_filter_loo: the first two columns of star_loo (then 2 + 3f, 3 + 3f, 4 + 3f per filter) and its flag
 LOO_ROWS, LOO_MEMBER = 0, 1
 LOO_CONTINUE = 1
+# b9_star_offset: the first two columns of star_off (then 2 + 3j, 3 + 3j, 4 + 3j per direction), its flag and the most directions
+OFF_ROWS, OFF_MEMBER = 0, 1
+OFF_CONTINUE = 1
+OFF_MAX_DIRECTIONS = 4
 # b9_pointwise: the columns of acc, the tail's cap and the flag
 PW_ROWS, PW_NINF, PW_VMAX, PW_SPOS, PW_RMAX, PW_SNEG, PW_MEAN, PW_M2 = range(8)
 PW_N = 8
@@ -256,7 +260,7 @@ ABI_SYMBOLS = [
     "b9_abi_version", "b9_ctx_create", "b9_ctx_destroy", "b9_last_error",
     "b9_load_pack", "b9_load_stars", "b9_set_priors", "b9_set_options", "b9_set_tuning", "b9_get_tuning",
     "b9_logpost", "b9_logpost_device", "b9_mcmc_run_block", "b9_mcmc_wait", "b9_sample_mass", "b9_derive_isochrone",
-    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_star_moments", "b9_wd_moments", "b9_mass_hist", "b9_ratio_hist", "b9_star_bins", "b9_wd_bins", "b9_phot_resid", "b9_filter_loo", "b9_pointwise", "b9_cmd_band", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
+    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_star_moments", "b9_wd_moments", "b9_mass_hist", "b9_ratio_hist", "b9_star_bins", "b9_wd_bins", "b9_phot_resid", "b9_filter_loo", "b9_star_offset", "b9_pointwise", "b9_cmd_band", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
     "b9_enable_timing", "b9_kernel_time_ms", "b9_calibrate_timing", "b9_clock_stamp", "b9_clock_mhz",
 ]
 
@@ -299,6 +303,7 @@ def load_hip_library(path: Optional[str] = None) -> C.CDLL:
     lib.b9_wd_bins.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, _dp]
     lib.b9_phot_resid.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, _dp]
     lib.b9_filter_loo.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, _dp]
+    lib.b9_star_offset.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]
     lib.b9_pointwise.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]
     lib.b9_cmd_band.argtypes = [vp, _dp, C.c_int32, C.POINTER(b9_band_spec), C.c_int32, _dp, _dp, _dp, C.c_int32, _dp]
     lib.b9_max_eep.argtypes = [vp]

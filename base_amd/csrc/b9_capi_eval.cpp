@@ -2,7 +2,7 @@
 // b9_logpost_device), the per-star mass draws (b9_sample_mass), the isochrone dump (b9_derive_isochrone) and the forward
 // model alone (b9_predict_mags); the reductions over a saved chain through chain_reduce -- the per-star posterior moments
 // (b9_star_moments), the binned mass posteriors (b9_mass_hist), the per-star bins (b9_star_bins), the posterior-predictive
-// residuals (b9_phot_resid), the leave-one-filter-out predictions (b9_filter_loo) and the pointwise predictive densities
+// residuals (b9_phot_resid), the leave-one-filter-out predictions (b9_filter_loo), the per-star offsets (b9_star_offset) and the pointwise predictive densities
 // (b9_pointwise) --; and the three calls on a WD mass grid of the
 // caller's own size through wd_grid_reduce -- the WD-stage stars' posterior draws (b9_sample_wd_mass), their exact posterior
 // moments (b9_wd_moments) and their per-line bins (b9_wd_bins); and the loci a saved chain implies in the CMD (b9_cmd_band: a pack,
@@ -406,7 +406,7 @@ int b9_n_wd_stars(const b9_ctx *ctx)
 
 namespace {
 
-// ---- the reductions over a saved chain: b9_star_moments, b9_mass_hist, b9_star_bins, b9_phot_resid, b9_filter_loo, b9_pointwise
+// ---- the reductions over a saved chain: b9_star_moments, b9_mass_hist, b9_star_bins, b9_phot_resid, b9_filter_loo, b9_star_offset, b9_pointwise
 // What one of them is to the driver below.  Rows are worked in chunks of at most max_rows, and of as few rows as keep the chunk's
 // increments [rows][n_stars][n_col] within scratch_bytes.
 struct ChainCall {
@@ -578,6 +578,8 @@ int wd_grid_reduce(b9_ctx *ctx, const WdGridCall &c, const double *params, int n
 #define B9_RESID_MAX_ROWS 32
 #define B9_LOO_SCRATCH_BYTES ((size_t)64 << 20)
 #define B9_LOO_MAX_ROWS 32
+#define B9_OFF_SCRATCH_BYTES ((size_t)64 << 20)
+#define B9_OFF_MAX_ROWS 32
 // (B9_PW_MAX_ROWS: b9_launch.h -- the reducers hold a chunk's rows in registers; 32 rows up to 65536 stars)
 #define B9_PW_SCRATCH_BYTES ((size_t)16 << 20)
 
@@ -712,6 +714,44 @@ int b9_filter_loo(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t fla
         if (d.rows) HIPCHK(ctx, hipMemcpyAsync(isig(d), is.data(), sizeof(double) * is.size(), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, b9k_resid_stage(pk, ctx->st, in(d), mg(d), ctx->stream));
         HIPCHK(ctx, b9k_resid_stage(pk, ctx->st, in(d) + n * nf, mg(d) + n_mg, ctx->stream));
+        return (int)B9_OK;
+    });
+}
+
+int b9_star_offset(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags, int32_t n_dir, const double *k, const double *tau, double *star_off,
+                   double *row_off)
+{
+    if (!ctx || !params || n_rows < 1 || (!star_off && !row_off) || n_dir < 1 || n_dir > B9_OFF_MAX_DIRECTIONS || !k || !tau) return B9_ERR_INVALID;
+    for (int j = 0; j < n_dir; ++j)
+        if (!(tau[j] > 0.0) || !std::isfinite(tau[j])) return B9_ERR_INVALID;
+    if (const int rc = chain_ready(ctx)) return rc;
+    const DevPack &pk = ctx->pk;
+    const size_t n = (size_t)ctx->st.n, nf = (size_t)pk.nf, D = (size_t)n_dir, ncol = 2 + 3 * D, n_mg = (size_t)ctx->st.mg_pad * pk.nfp;
+    for (size_t q = 0; q < D * nf; ++q)
+        if (!std::isfinite(k[q])) return B9_ERR_INVALID;
+    // the call's parts: the scaled directions in the caller's order [D][n][nf] and in the mg_* copy's [D][mg_pad][nfp], and the
+    // stars' {C, V} and {pruning factor, Occam term} [2][n][D][2]
+    const ChainCall c{"b9_star_offset", ncol, ncol, 1 + 4 * D, B9_OFF_MAX_ROWS, B9_OFF_SCRATCH_BYTES, (flags & B9_OFF_CONTINUE) != 0, star_off, row_off,
+                      {8 * D * n * nf, 8 * D * n_mg, 2 * 8 * n * D * 2}};
+    std::vector<double> cs;              // (the upload's source: it lives until the driver has waited for the stream)
+    B9Offset o{n_dir, k, tau, nullptr, nullptr, nullptr, nullptr};
+    return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
+        return b9k_star_offset(pk, ctx->st, d, m, o, ctx->stream);
+    }, [&](const ChainDev &d) {
+        // c_f = k_f / sigma_f (0: filter unused), per direction in the caller's star order
+        const HostStars &h = ctx->hs;
+        cs.resize(D * n * nf);
+        for (size_t j = 0; j < D; ++j)
+            for (size_t i = 0; i < n; ++i)
+                for (size_t f = 0; f < nf; ++f) {
+                    const double sg = h.sigma[i * nf + f];
+                    cs[(j * n + i) * nf + f] = sg > 0.0 ? k[j * nf + f] / sg : 0.0;
+                }
+        double *const c_in = reinterpret_cast<double *>(d.extra[0]);
+        o.c_in = c_in; o.c_mg = reinterpret_cast<double *>(d.extra[1]);
+        o.cv = reinterpret_cast<double *>(d.extra[2]); o.ob = o.cv + n * D * 2;
+        HIPCHK(ctx, hipMemcpyAsync(c_in, cs.data(), sizeof(double) * cs.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, b9k_offset_stage(pk, ctx->st, o, ctx->stream));
         return (int)B9_OK;
     });
 }

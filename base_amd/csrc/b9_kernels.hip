@@ -44,6 +44,7 @@
 //   k_band_points / k_band_wd_points / k_band_accumulate   b9_cmd_band: the MS/RGB loci and WD sequences a saved chain's rows imply
 //                                     (one lane per point into a chunk's value table), reduced over the rows one lane per line
 //   k_star_loo / _wd / k_loo_rows       b9_filter_loo: exact leave-one-filter-out predictions and densities (b9_filter_loo.hip.h)
+//   k_star_off / _wd / k_offset_stage / k_off_rows   b9_star_offset: exact per-star reddening / distance offsets (b9_star_offset.hip.h)
 //   k_star_resid / _wd / k_resid_stage / k_resid_rows   b9_phot_resid: exact posterior-predictive magnitude
 //                                     moments per filter over the same grid, summed over the rows and, standardised, the stars
 //   k_star_lpd / _wd / k_pw_accumulate / k_pw_tail / k_pw_rows   b9_pointwise: every star's marginal log-likelihood per row over
@@ -98,6 +99,7 @@ namespace tree_kd5 {
 #include "b9_wd_bins.hip.h"
 #include "b9_phot_resid.hip.h"
 #include "b9_filter_loo.hip.h"
+#include "b9_star_offset.hip.h"
 #include "b9_pointwise.hip.h"
 #include "b9_cmd_band.hip.h"
 
@@ -561,6 +563,72 @@ hipError_t b9k_filter_loo(const DevPack &pk, const DevStars &st, const B9Chain &
             const auto kr = with_lds(k_loo_rows, sizeof(double) * 2 * B9_LOO_TILE * (2 + 4 * (size_t)nf));      // two tiles of {x, 1 / sigma}
             if (kr.err != hipSuccess) return kr.err;
             hipLaunchKernelGGL(kr.kern, dim3(n_rows), dim3(256), kr.lds, stream, c.scratch, isig, st.n, nf, c.rows);
+        }
+        return hipGetLastError();
+    });
+}
+
+// ---- b9_star_offset: the call's directions staged; then the node tables of a chunk of rows, the stars' offset increments, the
+// accumulation, the rows' sums
+static OffDirs off_dirs(const DevPack &pk, const B9Offset &o)
+{
+    OffDirs d{};
+    for (int j = 0; j < o.n_dir; ++j) {
+        for (int f = 0; f < pk.nf; ++f) d.k[j][f] = o.k[(size_t)j * pk.nf + f];
+        d.tau2[j] = o.tau[j] * o.tau[j];
+        d.itau2[j] = 1.0 / d.tau2[j];
+    }
+    return d;
+}
+static bool off_ok(const DevPack &pk, const B9Offset &o)
+{
+    return o.n_dir >= 1 && o.n_dir <= B9_OFF_MAX_DIR && pk.nf <= B9_MAX_FILT && o.k && o.tau && o.c_in && o.c_mg && o.cv && o.ob;
+}
+
+hipError_t b9k_offset_stage(const DevPack &pk, const DevStars &st, const B9Offset &o, hipStream_t stream)
+{
+    return dispatch_nfp(pk.nfp, [&](auto nfp_c) {
+        constexpr int NFP = decltype(nfp_c)::value;
+        if (!off_ok(pk, o)) return hipErrorInvalidValue;
+        const long long lanes = std::max((long long)st.mg_pad * NFP * o.n_dir, (long long)st.n * o.n_dir);
+        hipLaunchKernelGGL(k_offset_stage<NFP>, dim3((unsigned)((lanes + 255) / 256), 2), dim3(256), 0, stream, st, pk.nf, o.n_dir, off_dirs(pk, o), o.c_in, o.c_mg,
+                           o.cv, o.ob);
+        return hipGetLastError();
+    });
+}
+
+template <int NFP, int NPOPS, int DT>
+static hipError_t launch_star_off(const DevStars &st, const B9Chain &c, const ChainTables &t, int n_rows, const B9Offset &o, hipStream_t stream)
+{
+    const B9IsoSet &s = c.set;
+    const auto k = with_lds(k_star_off<NFP, NPOPS, DT>, sizeof(double) * 64 * (NPOPS * 4 + 4 * (2 + 4 * (size_t)DT)));      // seeds, one population's states
+    if (k.err != hipSuccess) return k.err;
+    hipLaunchKernelGGL(k.kern, dim3(st.mg_pad / 64, n_rows, (o.n_dir + DT - 1) / DT), dim3(256), k.lds, stream, st, o.n_dir, o.c_mg, o.cv, o.ob, s.hdr, s.iso,
+                       s.iso_stride, s.mass_cap, s.params, c.mg.K, c.mg.Q, c.mg.tab, t.L, t.cut2, c.scratch);
+    return hipGetLastError();
+}
+
+hipError_t b9k_star_offset(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, const B9Offset &o, hipStream_t stream)
+{
+    return dispatch(pk.nfp, c.set.n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value, DT_MAX = OffTile<NFP>::DT_MAX;
+        if (!off_ok(pk, o)) return hipErrorInvalidValue;
+        const int D = o.n_dir;
+        const ChainTables t = chain_tables<NFP>(pk, st, c, n_rows, stream);
+        if (t.err != hipSuccess) return t.err;
+        hipError_t err;
+        if (D == 1) err = launch_star_off<NFP, NPOPS, 1>(st, c, t, n_rows, o, stream);
+        else if (D == 2 || DT_MAX == 2) err = launch_star_off<NFP, NPOPS, 2>(st, c, t, n_rows, o, stream);
+        else err = launch_star_off<NFP, NPOPS, DT_MAX>(st, c, t, n_rows, o, stream);
+        if (err != hipSuccess) return err;
+        if (st.n_wd > 0)
+            hipLaunchKernelGGL((k_star_off_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, D, off_dirs(pk, o), pk.m_wd_up, c.set.hdr, c.set.params,
+                               c.mg.K, c.mg.wd_tab, c.scratch);
+        if (c.acc) launch_chain_accumulate(c.scratch, n_rows, (long long)st.n * (2 + 3 * D), c.acc, stream);
+        if (c.rows) {
+            const auto kr = with_lds(k_off_rows, sizeof(double) * 2 * B9_OFF_TILE * (2 + 5 * (size_t)D));      // two tiles of {x, C, V}
+            if (kr.err != hipSuccess) return kr.err;
+            hipLaunchKernelGGL(kr.kern, dim3(n_rows), dim3(256), kr.lds, stream, c.scratch, o.cv, st.n, D, c.rows);
         }
         return hipGetLastError();
     });

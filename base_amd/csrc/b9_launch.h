@@ -224,6 +224,21 @@ hipError_t b9k_phot_resid(const DevPack &pk, const DevStars &st, const B9Chain &
 hipError_t b9k_filter_loo(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, const double *piv_mg, const double *lsn_mg, const double *lsn,
                           const double *isig, hipStream_t stream);
 
+// b9_star_offset.  The call's directions: k [n_dir][nf] and tau [n_dir] on the HOST (they travel as kernel arguments); c_in
+// [n_dir][st.n][nf] the scaled directions k_f / sigma_f (0: filter unused) in the caller's star order, and what b9k_offset_stage
+// forms from them: c_mg [n_dir][mg_pad][nfp] in the mg_* copy's order, cv [st.n][n_dir][2] = {C, V} and ob [st.n][n_dir][2] = {the
+// pruning factor, the Occam term} (device).
+struct B9Offset {
+    int n_dir;
+    const double *k, *tau;
+    const double *c_in;
+    double *c_mg, *cv, *ob;
+};
+hipError_t b9k_offset_stage(const DevPack &pk, const DevStars &st, const B9Offset &o, hipStream_t stream);
+// every star's increments into scratch [n_rows][st.n][2 + 3 n_dir], then acc [st.n][2 + 3 n_dir] (may be null) and rows
+// [n_rows][1 + 4 n_dir] (may be null)
+hipError_t b9k_star_offset(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, const B9Offset &o, hipStream_t stream);
+
 // rows of one b9k_pointwise launch: the reducers hold a chunk's rows in registers (k_pw_accumulate, k_pw_tail), and b9_pointwise
 // chunks its rows by the same number
 #define B9_PW_MAX_ROWS 32

@@ -350,6 +350,31 @@ class Engine:
         self._check(self.lib.b9_filter_loo(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], flags, ptr(sl), ptr(rl)))
         return sl, rl
 
+    def star_offset(self, rows: np.ndarray, k, tau, acc: Optional[np.ndarray] = None, want_star: bool = True,
+                    want_rows: bool = True) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+        """b9_star_offset: the exact per-star offsets over `rows` along the directions k [n_dir, n_filt] (mag per unit offset)
+        with the prior widths tau [n_dir] (mag; a scalar serves every direction): (star_off [n_stars, 2 + 3 n_dir] summed over
+        the rows -- ROWS, MEMBER, then per direction p E[delta], p E[mu^2] and p times the log Bayes factor of the star having an
+        offset of its own --, row_off [n_rows, 1 + 4 n_dir] -- sum p, then per direction N, M1, M2, E over the stars the
+        direction touches).  acc=None starts from zeros; else the call continues it (B9_OFF_CONTINUE) and returns a new array.
+        want_star / want_rows = False passes NULL for that output (None back)."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        k = np.ascontiguousarray(k, dtype=np.float64).reshape(-1, self.n_filt)
+        nd = k.shape[0]
+        tau = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, dtype=np.float64), (nd,)))
+        flags = 0
+        so = ro = None
+        if want_star:
+            if acc is None:
+                so = np.zeros((self.n_stars, 2 + 3 * nd))
+            else:
+                so, flags = np.array(acc, dtype=np.float64, order="C").reshape(self.n_stars, 2 + 3 * nd), abi.OFF_CONTINUE
+        if want_rows:
+            ro = np.zeros((rows.shape[0], 1 + 4 * nd))
+        ptr = lambda a: a.ctypes.data_as(_dp) if a is not None else None      # noqa: E731
+        self._check(self.lib.b9_star_offset(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], flags, nd, ptr(k), ptr(tau), ptr(so), ptr(ro)))
+        return so, ro
+
     def pointwise(self, rows: np.ndarray, tail_len: int = 0, acc: Optional[np.ndarray] = None, tail: Optional[np.ndarray] = None,
                   want_rows: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
         """b9_pointwise: every star's marginal log-likelihood v over `rows`, reduced: (acc [n_stars, 8] -- abi.PW_ROWS .. PW_M2 --,

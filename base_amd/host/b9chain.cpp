@@ -80,6 +80,7 @@ const ProgramFlags kCmdBandFlags = {{"ratios", "cmdBandRatios", false}, {"wdNode
                                     {"maxPasses", "cmdBandMaxPasses", false}, {"nPops", "cmdBandNPops", false}};
 const ProgramFlags kPhotResidFlags = {{"perStar", "photResidualsPerStar", true}, {"nPops", "photResidualsNPops", false}};
 const ProgramFlags kFilterCheckFlags = {{"perStar", "filterCheckPerStar", true}, {"nPops", "filterCheckNPops", false}};
+const ProgramFlags kStarOffsetsFlags = {{"nPops", "starOffsetsNPops", false}};
 const ProgramFlags kModelScoreFlags = {{"perRow", "modelScorePerRow", true}, {"nPops", "modelScoreNPops", false}};
 
 PhotResidConfig phot_resid_config(const Settings &st) { return {st.integer("photResiduals.perStar", 0) != 0}; }
@@ -925,6 +926,135 @@ void write_filter_check(const std::string &path, const std::vector<std::string> 
     for (const char *q : {"meanZ", "chi2", "offset", "lpd"})
         for (const char *s : {"mean", "sd", "p16", "p50", "p84"}) cols.push_back({std::string(q) + "_" + s, "%.17g"});
     write_table(path, "filter", &filters, cols, (long)filters.size(), table, kFilterCheckCols);
+}
+
+// ---------------------------------------------------------------------------------------------
+// starOffsets
+// ---------------------------------------------------------------------------------------------
+StarOffsetsConfig star_offsets_config(const Settings &st)
+{
+    StarOffsetsConfig c;
+    std::istringstream ds(st.str("starOffsets.direction", "absorption distance"));
+    std::string tok;
+    while (ds >> tok) c.directions.push_back(tok);
+    if (c.directions.empty() || c.directions.size() > B9_OFF_MAX_DIRECTIONS)
+        fail("starOffsets.direction: between 1 and " + std::to_string(B9_OFF_MAX_DIRECTIONS) + " directions");
+    std::istringstream ts(st.str("starOffsets.tau", "0.1"));
+    while (ts >> tok) {
+        char *end = nullptr;
+        const double v = std::strtod(tok.c_str(), &end);
+        if (end == tok.c_str() || *end || !(v > 0.0) || !std::isfinite(v)) fail("starOffsets.tau: '" + tok + "' is not a positive number");
+        c.tau.push_back(v);
+    }
+    if (c.tau.size() == 1) c.tau.assign(c.directions.size(), c.tau[0]);
+    if (c.tau.size() != c.directions.size()) fail("starOffsets.tau: one width, or one per direction");
+    return c;
+}
+
+std::vector<double> offset_direction(const std::string &spec, const std::vector<std::string> &filters, const std::vector<double> &abs_coeff)
+{
+    const size_t nf = filters.size();
+    std::vector<double> k(nf, 0.0);
+    if (spec == "absorption") {
+        if (abs_coeff.size() < nf) fail("starOffsets.direction: the model pack has no absorption coefficients");
+        for (size_t f = 0; f < nf; ++f) k[f] = abs_coeff[f];
+    } else if (spec == "distance") {
+        for (size_t f = 0; f < nf; ++f) k[f] = 1.0;
+    } else if (spec.rfind("filter:", 0) == 0) {
+        const auto it = std::find(filters.begin(), filters.end(), spec.substr(7));
+        if (it == filters.end()) fail("starOffsets.direction: no filter '" + spec.substr(7) + "'");
+        k[(size_t)(it - filters.begin())] = 1.0;
+    } else {
+        std::string lv = spec;
+        for (char &ch : lv) if (ch == ',') ch = ' ';
+        std::istringstream ls(lv);
+        std::string tok;
+        size_t f = 0;
+        while (ls >> tok) {
+            char *end = nullptr;
+            const double v = std::strtod(tok.c_str(), &end);
+            if (end == tok.c_str() || *end || !std::isfinite(v)) fail("starOffsets.direction: '" + spec + "' is neither a named direction nor a list of numbers");
+            if (f < nf) k[f] = v;
+            ++f;
+        }
+        if (f != nf) fail("starOffsets.direction: '" + spec + "' must hold one value per filter (" + std::to_string(nf) + ")");
+    }
+    return k;
+}
+
+void offset_table(const double *star_off, const double *sigma, const double *k, const double *tau, long n_stars, int nf, int nd, double *table)
+{
+    const size_t ncol = 2 + 3 * (size_t)nd, tcol = 2 + 4 * (size_t)nd;
+    for (long i = 0; i < n_stars; ++i) {
+        const double *a = star_off + (size_t)i * ncol;
+        double *t = table + (size_t)i * tcol;
+        for (size_t c = 0; c < tcol; ++c) t[c] = 0.0;
+        t[0] = a[0];
+        if (a[0] > 0.0) t[1] = a[1] / a[0];
+        if (!(a[1] > 0.0)) continue;                         // no membership weight: every derived value is 0
+        for (int j = 0; j < nd; ++j) {
+            double C = 0.0;
+            for (int f = 0; f < nf; ++f) {
+                const double sg = sigma[(size_t)i * nf + f];
+                if (sg > 0.0) { const double c = k[(size_t)j * nf + f] / sg; C += c * c; }
+            }
+            const double V = 1.0 / (C + 1.0 / (tau[j] * tau[j]));
+            const double m1 = a[2 + 3 * j] / a[1], m2 = a[3 + 3 * j] / a[1];
+            double *tj = t + 2 + 4 * (size_t)j;
+            tj[0] = m1;
+            tj[1] = std::sqrt(std::max(0.0, m2 - m1 * m1) + V);
+            tj[2] = m1 / tj[1];
+            tj[3] = a[4 + 3 * j] / a[1];
+        }
+    }
+}
+
+void offset_dist_table(const double *row_off, long n_rows, int nd, double *table)
+{
+    const size_t ncol = 1 + 4 * (size_t)nd;
+    std::vector<double> v;
+    for (int j = 0; j < nd; ++j) {
+        double *t = table + (size_t)j * kOffsetDistCols;
+        for (int c = 0; c < kOffsetDistCols; ++c) t[c] = 0.0;
+        std::vector<long> use;
+        for (long r = 0; r < n_rows; ++r)
+            if (row_off[(size_t)r * ncol + 1 + 4 * j] > 0.0) use.push_back(r);
+        t[0] = (double)use.size();
+        if (use.empty()) continue;
+        for (int q = 0; q < 3; ++q) {
+            v.resize(use.size());
+            double sum = 0.0;
+            for (size_t u = 0; u < use.size(); ++u) {
+                const double *x = row_off + (size_t)use[u] * ncol + 1 + 4 * j;            // N, M1, M2, E
+                v[u] = q == 0 ? x[1] / x[0] : q == 1 ? std::sqrt(x[2] / x[0]) : x[3] / x[0];
+                sum += v[u];
+            }
+            const double mean = sum / (double)use.size();
+            double ss = 0.0;
+            for (double x : v) ss += (x - mean) * (x - mean);
+            std::sort(v.begin(), v.end());
+            double *tq = t + 1 + 5 * q;
+            tq[0] = mean;
+            tq[1] = std::sqrt(ss / (double)use.size());
+            tq[2] = percentile_sorted(v, 0.16); tq[3] = percentile_sorted(v, 0.50); tq[4] = percentile_sorted(v, 0.84);
+        }
+    }
+}
+
+void write_star_offsets(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &directions, const double *table)
+{
+    std::vector<TableColumn> cols = columns({"rows", "member"}, "%.17g");
+    for (const std::string &n : directions)
+        for (const char *what : {"_mean", "_sd", "_z", "_logBF"}) cols.push_back({n + what, "%.17g"});
+    write_table(path, "id", &ids, cols, (long)ids.size(), table, cols.size());
+}
+
+void write_offset_dist(const std::string &path, const std::vector<std::string> &directions, const double *table)
+{
+    std::vector<TableColumn> cols = {{"nRows", "%.17g"}};
+    for (const char *q : {"mean", "rms", "logBF"})
+        for (const char *s : {"mean", "sd", "p16", "p50", "p84"}) cols.push_back({std::string(q) + "_" + s, "%.17g"});
+    write_table(path, "direction", &directions, cols, (long)directions.size(), table, kOffsetDistCols);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // b9chain.hpp -- what the programs over a saved chain (sampleMass, sampleWDMass, starSummary, wdSummary, wdIntervals, cmdBand, massFunction,
-// binaryStats, starIntervals, photResiduals, filterCheck, modelScore) share above the C ABI and below their mains: their settings, the loop over the
+// binaryStats, starIntervals, photResiduals, filterCheck, starOffsets, modelScore) share above the C ABI and below their mains: their settings, the loop over the
 // chain's rows, the tables derived from the device's sums and the files they are written to (docs/FORMATS.md).  Host arithmetic
 // only: nothing here needs a context or a GPU.  b9host.hpp includes this header.
 #pragma once
@@ -266,6 +266,32 @@ void filter_loo_table(const double *row_loo, long n_rows, int nf, double *table)
 // star in the order of ids; <base>.filterCheck: "filter nRows {meanZ chi2 offset lpd}_{mean sd p16 p50 p84}", one line per filter.
 void write_star_filter_check(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &filters, const double *table);
 void write_filter_check(const std::string &path, const std::vector<std::string> &filters, const double *table);
+
+// ---- starOffsets -----------------------------------------------------------------------------------
+// starOffsets.{direction, tau} (flags --direction spec, repeatable, --tau t, repeatable; in YAML one whitespace-separated
+// scalar each).  A spec is `absorption` (k = the pack's absorption coefficients: more dust at the same true distance), `distance`
+// (k = 1 in every filter), `filter:NAME` (a unit vector) or n_filt comma-separated values.  Default: absorption and distance.
+// tau: one width (mag) for every direction or one per direction; default 0.1.  At most B9_OFF_MAX_DIRECTIONS directions.
+extern const ProgramFlags kStarOffsetsFlags;
+struct StarOffsetsConfig { std::vector<std::string> directions; std::vector<double> tau; };
+StarOffsetsConfig star_offsets_config(const Settings &st);
+// k [n_filt] of a spec; throws on an unknown name or filter or a list of another length
+std::vector<double> offset_direction(const std::string &spec, const std::vector<std::string> &filters, const std::vector<double> &abs_coeff);
+// b9_star_offset's star_off [n_stars][2 + 3 D] with the catalogue's sigma [n_stars][nf] and the call's k [D][nf], tau [D] -> the
+// per-star table [n_stars][2 + 4 D]: rows, member (acc[1] / acc[0]), then per direction
+//   mean  = acc[2 + 3j] / acc[1]                       (E[delta], mag)
+//   sd    = sqrt(max(0, acc[3 + 3j] / acc[1] - mean^2) + V),   V = 1 / (sum_f (k_f / sigma_f)^2 + tau^-2) over the used filters
+//   z     = mean / sd,   logBF = acc[4 + 3j] / acc[1]  (the mean log Bayes factor of an own offset against none).
+// A star without membership weight (acc[1] == 0) has every derived value 0.
+void offset_table(const double *star_off, const double *sigma, const double *k, const double *tau, long n_stars, int nf, int nd, double *table);
+// b9_star_offset's row_off [n_rows][1 + 4 D] -> the per-direction table [D][kOffsetDistCols]: the number of rows with N > 0, then
+// over those rows the mean, population sd and 16th / 50th / 84th percentiles of M1 / N, sqrt(M2 / N) and E / N
+constexpr int kOffsetDistCols = 16;
+void offset_dist_table(const double *row_off, long n_rows, int nd, double *table);
+// <base>.starOffsets: "id rows member {<direction>_mean <direction>_sd <direction>_z <direction>_logBF}", one line per star in the
+// order of ids; <base>.offsetDist: "direction nRows {mean rms logBF}_{mean sd p16 p50 p84}", one line per direction.
+void write_star_offsets(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &directions, const double *table);
+void write_offset_dist(const std::string &path, const std::vector<std::string> &directions, const double *table);
 
 // ---- binaryStats -----------------------------------------------------------------------------------
 // binaryStats.{massEdges, massBins, qMin} (flags --massEdges e0,e1,.. | --massBins N, --qMin q).  massEdges: the primary-mass

@@ -136,6 +136,7 @@ const std::map<std::string, std::string> &Settings::flag_map()
         {"wdIntervalsMaxPasses", "wdIntervals.maxPasses"}, {"wdIntervalsNMassNodes", "wdIntervals.nMassNodes"}, {"wdIntervalsNPops", "wdIntervals.nPops"},
         {"photResidualsPerStar", "photResiduals.perStar"}, {"photResidualsNPops", "photResiduals.nPops"},
         {"filterCheckPerStar", "filterCheck.perStar"}, {"filterCheckNPops", "filterCheck.nPops"},
+        {"direction", "starOffsets.direction"}, {"tau", "starOffsets.tau"}, {"starOffsetsNPops", "starOffsets.nPops"},
         {"massEdges", "binaryStats.massEdges"}, {"massBins", "binaryStats.massBins"}, {"qMin", "binaryStats.qMin"}, {"binaryStatsNPops", "binaryStats.nPops"},
         {"cmdBandRatios", "cmdBand.ratios"}, {"cmdBandWdNodes", "cmdBand.wdNodes"}, {"cmdBandWdTypes", "cmdBand.wdTypes"}, {"cmdBandColours", "cmdBand.colours"},
         {"cmdBandLevels", "cmdBand.levels"}, {"cmdBandTol", "cmdBand.tol"}, {"cmdBandMaxPasses", "cmdBand.maxPasses"}, {"cmdBandNPops", "cmdBand.nPops"},
@@ -153,6 +154,7 @@ const std::map<std::string, std::string> &Settings::flag_map()
 
 void Settings::parse_args(int argc, char **argv, const ProgramFlags &own)
 {
+    std::vector<std::string> listed;                          // list-valued keys this command line has set: a repeat appends
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a.rfind("--", 0) != 0) fail("unexpected argument '" + a + "'");
@@ -170,7 +172,11 @@ void Settings::parse_args(int argc, char **argv, const ProgramFlags &own)
         if (a == "config") { load_yaml(value); continue; }
         auto it = flag_map().find(a);
         if (it == flag_map().end()) fail("unknown flag --" + a);
-        kv[it->second] = value;
+        const std::string &key = it->second;
+        const bool list = key == "starOffsets.direction" || key == "starOffsets.tau";        // (repeatable: space-joined)
+        if (list && std::find(listed.begin(), listed.end(), key) != listed.end()) kv[key] += " " + value;
+        else kv[key] = value;
+        if (list) listed.push_back(key);
     }
 }
 

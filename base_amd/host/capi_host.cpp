@@ -480,6 +480,64 @@ int b9h_filter_check_settings(int argc, char **argv, char *out, int cap)
     });
 }
 
+int b9h_offset_direction(const char *spec, const char *const *filters, int n_filt, const double *abs_coeff, double *k)
+{
+    return guard([&] {
+        if (!spec || n_filt < 1 || !filters || !k) throw std::runtime_error("b9h_offset_direction: invalid argument");
+        const std::vector<double> ac = abs_coeff ? std::vector<double>(abs_coeff, abs_coeff + n_filt) : std::vector<double>();
+        const std::vector<double> v = b9h::offset_direction(spec, strings(filters, n_filt), ac);
+        std::copy(v.begin(), v.end(), k);
+    });
+}
+
+int b9h_offset_table(const double *star_off, const double *sigma, const double *k, const double *tau, long n_stars, int n_filt, int n_dir, double *table)
+{
+    return guard([&] {
+        if (n_stars < 0 || n_filt < 1 || n_dir < 1 || !k || !tau || !table || (n_stars > 0 && (!star_off || !sigma)))
+            throw std::runtime_error("b9h_offset_table: invalid argument");
+        b9h::offset_table(star_off, sigma, k, tau, n_stars, n_filt, n_dir, table);
+    });
+}
+
+int b9h_offset_dist_table(const double *row_off, long n_rows, int n_dir, double *table)
+{
+    return guard([&] {
+        if (n_rows < 0 || n_dir < 1 || !table || (n_rows > 0 && !row_off)) throw std::runtime_error("b9h_offset_dist_table: invalid argument");
+        b9h::offset_dist_table(row_off, n_rows, n_dir, table);
+    });
+}
+
+int b9h_write_star_offsets(const char *path, const char *const *ids, long n_stars, const char *const *directions, int n_dir, const double *table)
+{
+    return guard([&] {
+        if (!path || n_stars < 0 || n_dir < 1 || !directions || (n_stars > 0 && (!ids || !table))) throw std::runtime_error("b9h_write_star_offsets: invalid argument");
+        b9h::write_star_offsets(path, strings(ids, n_stars), strings(directions, n_dir), table);
+    });
+}
+
+int b9h_write_offset_dist(const char *path, const char *const *directions, int n_dir, const double *table)
+{
+    return guard([&] {
+        if (!path || n_dir < 1 || !directions || !table) throw std::runtime_error("b9h_write_offset_dist: invalid argument");
+        b9h::write_offset_dist(path, strings(directions, n_dir), table);
+    });
+}
+
+int b9h_star_offsets_settings(int argc, char **argv, char *out, int cap)
+{
+    return settings_text("b9h_star_offsets_settings", argc, argv, b9h::kStarOffsetsFlags, out, cap, [&](const b9h::Settings &st) {
+        const b9h::StarOffsetsConfig c = b9h::star_offsets_config(st);
+        std::string dirs, taus;
+        char buf[40];
+        for (size_t j = 0; j < c.directions.size(); ++j) {
+            std::snprintf(buf, sizeof buf, "%.17g", c.tau[j]);
+            dirs += (j ? " " : "") + c.directions[j];
+            taus += (j ? " " : "") + std::string(buf);
+        }
+        return grid_text(b9h::chain_grid(st, "starOffsets")) + "direction = " + dirs + "\ntau = " + taus + "\n";
+    });
+}
+
 int b9h_phot_resid_settings(int argc, char **argv, char *out, int cap)
 {
     return settings_text("b9h_phot_resid_settings", argc, argv, b9h::kPhotResidFlags, out, cap, [&](const b9h::Settings &st) {

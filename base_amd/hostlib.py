@@ -44,6 +44,7 @@ HOST_SYMBOLS = [
     "b9h_band_first_ranges", "b9h_band_first_edges", "b9h_band_table", "b9h_write_cmd_band", "b9h_cmd_band_settings",
     "b9h_resid_table", "b9h_filter_resid_table", "b9h_write_phot_resid", "b9h_write_filter_resid", "b9h_phot_resid_settings",
     "b9h_loo_table", "b9h_filter_loo_table", "b9h_write_star_filter_check", "b9h_write_filter_check", "b9h_filter_check_settings",
+    "b9h_offset_direction", "b9h_offset_table", "b9h_offset_dist_table", "b9h_write_star_offsets", "b9h_write_offset_dist", "b9h_star_offsets_settings",
     "b9h_pointwise_table", "b9h_score_totals", "b9h_score_compare", "b9h_write_pointwise", "b9h_write_model_score", "b9h_model_score_settings",
 ]
 
@@ -129,6 +130,12 @@ def load() -> C.CDLL:
     lib.b9h_write_star_filter_check.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, C.POINTER(C.c_char_p), C.c_int, _dp]
     lib.b9h_write_filter_check.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, _dp]
     lib.b9h_filter_check_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
+    lib.b9h_offset_direction.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, _dp, _dp]
+    lib.b9h_offset_table.argtypes = [_dp, _dp, _dp, _dp, C.c_long, C.c_int, C.c_int, _dp]
+    lib.b9h_offset_dist_table.argtypes = [_dp, C.c_long, C.c_int, _dp]
+    lib.b9h_write_star_offsets.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, C.POINTER(C.c_char_p), C.c_int, _dp]
+    lib.b9h_write_offset_dist.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, _dp]
+    lib.b9h_star_offsets_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     lib.b9h_pointwise_table.argtypes = [_dp, _dp, C.c_int, C.c_long, _dp]
     lib.b9h_score_totals.argtypes = [_dp, C.c_long, _dp]
     lib.b9h_score_compare.argtypes = [_dp, C.POINTER(C.c_char_p), C.c_long, _dp, C.POINTER(C.c_char_p), C.c_long, _dp]
@@ -911,6 +918,85 @@ def filter_check_settings(args):
     buf = C.create_string_buffer(1024)
     _check(load().b9h_filter_check_settings(len(args) + 1, argv, buf, 1024))
     return {k: int(v) for k, v in (line.split(" = ") for line in buf.value.decode().splitlines())}
+
+
+OFFSET_STAR_COLUMNS = ("mean", "sd", "z", "logBF")
+OFFSET_DIST_COLUMNS = ("nRows",) + tuple(q + "_" + s for q in ("mean", "rms", "logBF") for s in ("mean", "sd", "p16", "p50", "p84"))
+
+
+def offset_direction(spec, filters, abs_coeff=None) -> np.ndarray:
+    """b9h_offset_direction: k [len(filters)] of a direction: "absorption" (k = abs_coeff: more dust at the same true
+    distance), "distance" (k = 1), "filter:NAME" (a unit vector), or an explicit list of values (a sequence, or a
+    comma-separated string)."""
+    if not isinstance(spec, str):
+        spec = ",".join(repr(float(v)) for v in spec)
+    nf = len(filters)
+    ac = None if abs_coeff is None else np.ascontiguousarray(abs_coeff, dtype=np.float64).reshape(nf)
+    out = np.empty(nf)
+    _check(load().b9h_offset_direction(spec.encode(), _names(filters), nf, None if ac is None else ac.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
+    return out
+
+
+def offset_directions(specs, filters, abs_coeff=None) -> np.ndarray:
+    """k [len(specs), len(filters)] of several directions (offset_direction each): what Engine.star_offset takes."""
+    return np.stack([offset_direction(s, filters, abs_coeff) for s in specs])
+
+
+def offset_table(star_off, sigma, k, tau) -> np.ndarray:
+    """b9h_offset_table: b9_star_offset's star_off [n_stars, 2 + 3 D] with the catalogue's sigma [n_stars, nf] and the call's
+    k [D, nf], tau [D] (a scalar serves every direction) -> the per-star table [n_stars, 2 + 4 D]: rows, member, then
+    OFFSET_STAR_COLUMNS per direction."""
+    sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+    n, nf = sigma.shape
+    k = np.ascontiguousarray(k, dtype=np.float64).reshape(-1, nf)
+    nd = k.shape[0]
+    tau = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, dtype=np.float64), (nd,)))
+    so = np.ascontiguousarray(star_off, dtype=np.float64).reshape(n, 2 + 3 * nd)
+    out = np.empty((n, 2 + 4 * nd))
+    _check(load().b9h_offset_table(so.ctypes.data_as(_dp), sigma.ctypes.data_as(_dp), k.ctypes.data_as(_dp), tau.ctypes.data_as(_dp), n, nf, nd,
+                                   out.ctypes.data_as(_dp)))
+    return out
+
+
+def offset_dist_table(row_off, n_dir: int) -> np.ndarray:
+    """b9h_offset_dist_table: b9_star_offset's row_off [n_rows, 1 + 4 D] -> the per-direction table [D, 16] (OFFSET_DIST_COLUMNS)."""
+    ro = np.ascontiguousarray(row_off, dtype=np.float64).reshape(-1, 1 + 4 * n_dir)
+    out = np.empty((n_dir, 16))
+    _check(load().b9h_offset_dist_table(ro.ctypes.data_as(_dp), ro.shape[0], int(n_dir), out.ctypes.data_as(_dp)))
+    return out
+
+
+def write_star_offsets(path: str, ids, directions, table) -> None:
+    """b9h_write_star_offsets: the .starOffsets file of a per-star table [len(ids), 2 + 4 len(directions)]."""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(len(ids), 2 + 4 * len(directions))
+    _check(load().b9h_write_star_offsets(path.encode(), _names(ids), len(ids), _names(directions), len(directions), t.ctypes.data_as(_dp)))
+
+
+def write_offset_dist(path: str, directions, table) -> None:
+    """b9h_write_offset_dist: the .offsetDist file of a per-direction table [len(directions), 16]."""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(len(directions), 16)
+    _check(load().b9h_write_offset_dist(path.encode(), _names(directions), len(directions), t.ctypes.data_as(_dp)))
+
+
+def read_star_offsets(path: str):
+    """(ids, columns, table [n_stars, 2 + 4 D]) of a .starOffsets file."""
+    return read_table_file(path, "id")
+
+
+def read_offset_dist(path: str):
+    """(directions, columns, table [D, 16]) of an .offsetDist file."""
+    return read_table_file(path, "direction")
+
+
+def star_offsets_settings(args):
+    """starOffsets' settings as the program parses `args` (flags, --config file): margIsoIncrem, nMassRatios, nPops (ints),
+    direction (a list of specs) and tau (a list of floats, one per direction)."""
+    argv = (C.c_char_p * (len(args) + 1))(b"starOffsets", *[str(a).encode() for a in args])
+    buf = C.create_string_buffer(2048)
+    _check(load().b9h_star_offsets_settings(len(args) + 1, argv, buf, 2048))
+    d = dict(line.split(" = ") for line in buf.value.decode().splitlines())
+    return dict(margIsoIncrem=int(d["margIsoIncrem"]), nMassRatios=int(d["nMassRatios"]), nPops=int(d["nPops"]),
+                direction=d["direction"].split(), tau=[float(v) for v in d["tau"].split()])
 
 
 POINTWISE_COLUMNS = ("rows", "nInf", "lppd", "pWaic", "elpdWaic", "elpdIs", "paretoK", "elpdLoo", "pLoo")

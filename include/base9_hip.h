@@ -298,7 +298,7 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk);
  * b9_set_priors or b9_set_options changes the posterior: the previous block's state carries a log-posterior of the old
  * one, so the next B9_BLOCK_CONTINUE block returns B9_ERR_STATE (the message names the call that intervened) and the chain
  * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags, b9_sample_wd_mass, b9_star_moments,
- * b9_wd_moments, b9_wd_bins, b9_mass_hist, b9_ratio_hist, b9_phot_resid, b9_filter_loo and b9_pointwise (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
+ * b9_wd_moments, b9_wd_bins, b9_mass_hist, b9_ratio_hist, b9_phot_resid, b9_filter_loo, b9_star_offset and b9_pointwise (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
  * context's work buffers: b9_logpost / b9_sample_mass / b9_derive_isochrone, the staging calls, b9_set_options and a block
  * with another n_walkers return B9_ERR_STATE until it has been collected.  A driver that adapts the proposal
  * from block b-1 while block b runs keeps the GPU's queue non-empty: enqueue b+1 (CONTINUE | ASYNC), wait(b), ...
@@ -724,6 +724,58 @@ int b9_phot_resid(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t fla
 int b9_filter_loo(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags,
                   double *star_loo /* host [n_stars][2 + 3 n_filt], in/out, may be NULL */,
                   double *row_loo  /* host [n_rows][1 + 6 n_filt], out,    may be NULL */);
+
+/*
+ * Exact per-star reddening and distance offsets over a saved chain (the starOffsets counterpart).  Added in ABI 6 without a
+ * version change, as its siblings were: purely additive.  Every other saved-chain call assumes one extinction and one distance
+ * modulus for every member; this call asks, star by star, how far the star lies off the cluster's values along up to
+ * B9_OFF_MAX_DIRECTIONS fixed directions in magnitude space, and how strongly the data want that freedom.
+ *
+ * Definition.  The grid, the terms t_(k,n), the finite-term rule, L = logsumexp t, the FULL-DATA membership p and the WD-stage
+ * steps are exactly b9_star_moments'.  Direction j is a vector k[j][f] over the pack's filters and a prior width tau[j] > 0, both
+ * in mag: the star's predicted magnitudes are pred_f + delta k_f with delta ~ N(0, tau^2).  Predicted magnitudes are linear in
+ * the modulus (k_f = 1) and in A_V (k_f = the pack's absorption coefficients), so those two offsets are exact.  For star i let
+ * c_f = k_f / sigma_if for the filters it uses (sigma_if > 0), else 0;  C = sum_f c_f^2 (f ascending);  V = 1 / (C + tau^-2).  For a
+ * node with dd_f = fma(sw_f, pred_f, -so_f), the scaled pair its chi^2 is formed from:  B~ = -sum_f c_f dd_f (one fma chain, f
+ * ascending),  mu = V B~ (the node-conditional posterior mean of delta),  g = V B~^2 / 2,  t' = t + g: delta integrated out of
+ * the node analytically.  In the WD stage the same from d_f = pred_f - obs_f and wgt_f:  B = -sum k_f (wgt_f d_f),  C = sum k_f^2
+ * wgt_f.  L' = logsumexp t' -- the populations mixed by that direction's own weights --, w' = exp(t' - L').  Row r adds to star i
+ * the 2 + 3 n_dir columns
+ *     x[0] = 1 (ROWS),  x[1] = p (MEMBER),  x[2 + 3j] = p sum w' mu,  x[3 + 3j] = p sum w' mu^2,
+ *     x[4 + 3j] = p ((L' - L) - log1p(C tau^2) / 2)
+ * the last being p times the log Bayes factor of "this star has an offset of its own" against "it has none", Occam term
+ * included.  A star with C = 0 for a direction has exact zeros in that direction's three columns.  Where b9_star_moments adds
+ * nothing this call adds nothing either, ROWS included.  A direction's columns do not depend on which other directions are in
+ * the call.
+ *
+ * Pruning.  A node may be left out of direction j's sums only when t' lies more than 40 e-folds below a data-only lower bound
+ * of max t': the star's seed (valid because t' >= t), then that direction's own running maximum.  A chunk's or unit's box is
+ * skipped only when the full-data sum may skip it and every direction may: X - 2 g >= (1 - C V) lb + nbmin (Cauchy-Schwarz).  What
+ * is dropped is below N_nodes e^-40 of that sum's weight; b9_tuning.marg_no_pruning: nothing is.  x[0] and x[1] are
+ * b9_phot_resid's bits.
+ *
+ * star_off (host, [n_stars][2 + 3 n_dir], the caller's star order, in/out, nullable): acc + x_r, one plain add per row in
+ * ascending row order; flags = 0 starts from zeros, B9_OFF_CONTINUE from the caller's values.  E[delta] = acc[2 + 3j] / acc[1],
+ * Var[delta] = acc[3 + 3j] / acc[1] - E[delta]^2 + V, the mean log Bayes factor acc[4 + 3j] / acc[1].
+ *
+ * row_off (host, [n_rows][1 + 4 n_dir], out, nullable): column 0 is sum_i p_i over all stars.  For direction j, over the stars
+ * with C > 0 only, in the caller's ascending star order, one plain add each:  N = sum p,  M1 = sum x[2 + 3j],
+ * M2 = sum (x[3 + 3j] + p V_i),  E = sum x[4 + 3j]  at [1 + 4j .. 4 + 4j]  (V_i = 1 / (sum_f (k_f / sigma_if)^2 + tau^-2)).
+ *
+ * The same bits for the call's own chunking (at most 32 rows at a time, fewer while the per-(row, star) scratch would exceed
+ * 64 MiB), any split of the rows over continued calls, a repeated call, any history of the context, any other stars in the
+ * catalogue, and either output being NULL.  Synchronous; host pointers.  B9_ERR_INVALID (outputs untouched) for n_rows < 1, NULL
+ * params, k or tau, both outputs NULL, n_dir outside 1 .. B9_OFF_MAX_DIRECTIONS, a tau that is not positive and finite or a k
+ * that is not finite; B9_ERR_STATE while a sampler block is outstanding; B9_ERR_CAPACITY as its siblings.  The call uses buffers
+ * of its own: a B9_BLOCK_CONTINUE block enqueued after it gives the same bits as one enqueued without it.
+ */
+#define B9_OFF_CONTINUE 1
+#define B9_OFF_MAX_DIRECTIONS 4
+int b9_star_offset(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags, int32_t n_dir,
+                   const double *k   /* host [n_dir][n_filt], mag per unit offset */,
+                   const double *tau /* host [n_dir], mag, > 0 */,
+                   double *star_off  /* host [n_stars][2 + 3 n_dir], in/out, may be NULL */,
+                   double *row_off   /* host [n_rows][1 + 4 n_dir], out,    may be NULL */);
 
 /*
  * Exact pointwise predictive densities over a saved chain (the modelScore counterpart): what WAIC, PSIS-LOO and the paired

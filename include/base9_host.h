@@ -238,6 +238,27 @@ int b9h_filter_loo_table(const double *row_loo, long n_rows, int n_filt, double 
 int b9h_write_star_filter_check(const char *path, const char *const *ids, long n_stars, const char *const *filters, int n_filt, const double *table);
 int b9h_write_filter_check(const char *path, const char *const *filters, int n_filt, const double *table);
 int b9h_filter_check_settings(int argc, char **argv, char *out, int cap);
+/* starOffsets.  b9h_offset_direction: k [n_filt] of a direction spec -- "absorption" (abs_coeff [n_filt], the pack's absorption
+ * coefficients; NULL: an error for this spec), "distance" (1 in every filter), "filter:NAME" (a unit vector) or n_filt
+ * comma-separated values.
+ * b9h_offset_table: b9_star_offset's star_off [n_stars][2 + 3 n_dir] with the catalogue's sigma [n_stars][n_filt] (sigma <= 0:
+ * filter unused) and the call's k [n_dir][n_filt], tau [n_dir] -> the per-star table [n_stars][2 + 4 n_dir]: rows, member =
+ * acc[1] / rows, then per direction mean = acc[2 + 3j] / acc[1], sd = sqrt(max(0, acc[3 + 3j] / acc[1] - mean^2) + V) with
+ * V = 1 / (sum_f (k_f / sigma_f)^2 + tau^-2), z = mean / sd and logBF = acc[4 + 3j] / acc[1]; every derived value is 0 when
+ * acc[1] == 0.
+ * b9h_offset_dist_table: row_off [n_rows][1 + 4 n_dir] -> the per-direction table [n_dir][16]: the number of rows with N > 0,
+ * then over them the mean, population standard deviation and 16th / 50th / 84th percentiles (b9h_mass_function_table's rule) of
+ * mean = M1 / N, rms = sqrt(M2 / N) and logBF = E / N; zeros without such a row.
+ * b9h_write_star_offsets / b9h_write_offset_dist: the files <base>.starOffsets and <base>.offsetDist (docs/FORMATS.md) of those
+ * tables, 17 significant digits; `directions` names the columns / lines.  b9h_star_offsets_settings: starOffsets' command line
+ * (argv[0] is skipped) and YAML parsed as the program parses them -- "key = value" lines of margIsoIncrem, nMassRatios, nPops,
+ * direction, tau (the last two space-separated, one tau per direction). */
+int b9h_offset_direction(const char *spec, const char *const *filters, int n_filt, const double *abs_coeff, double *k);
+int b9h_offset_table(const double *star_off, const double *sigma, const double *k, const double *tau, long n_stars, int n_filt, int n_dir, double *table);
+int b9h_offset_dist_table(const double *row_off, long n_rows, int n_dir, double *table);
+int b9h_write_star_offsets(const char *path, const char *const *ids, long n_stars, const char *const *directions, int n_dir, const double *table);
+int b9h_write_offset_dist(const char *path, const char *const *directions, int n_dir, const double *table);
+int b9h_star_offsets_settings(int argc, char **argv, char *out, int cap);
 /* modelScore.  b9h_pointwise_table: b9_pointwise's acc [n_stars][8] and tail [n_stars][tail_len] (NULL or tail_len 0: no PSIS
  * fit) -> the per-star table [n_stars][9]: rows, nInf, lppd, pWaic, elpdWaic, elpdIs, paretoK, elpdLoo, pLoo.  With n_f = rows -
  * nInf: lppd = VMAX + log SPOS - log rows, pWaic = M2 / (n_f - 1) (0 for n_f < 2), elpdWaic = lppd - pWaic, elpdIs = log n_f -
