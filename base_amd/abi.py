@@ -56,6 +56,21 @@ PW_ROWS, PW_NINF, PW_VMAX, PW_SPOS, PW_RMAX, PW_SNEG, PW_MEAN, PW_M2 = range(8)
 PW_N = 8
 PW_MAX_TAIL = 256
 PW_CONTINUE = 1
+# b9_star_influence: the head columns of acc (then WQ, WQ2, MQ, CVQ at 6 + 4j .. 9 + 4j per quantity), the caps and the flag
+INF_ROWS, INF_NINF, INF_RMAX, INF_SNEG, INF_SNEG2, INF_MEANV = range(6)
+INF_HEAD = 6
+INF_MAX_Q, INF_MAX_GROUPS = 12, 8
+INF_CONTINUE = 1
+
+
+def INF_WQ(j: int) -> int:
+    return 6 + 4 * j
+
+
+def INF_N(n_q: int) -> int:
+    return 6 + 4 * n_q
+
+
 # b9_cmd_band: the spec's caps, the moments' columns (the unnamed enum) and the flag
 BAND_MAX_RATIOS, BAND_MAX_COLOURS, BAND_MAX_BINS = 4, 8, 30
 BAND_N, BAND_SUM, BAND_SUMSQ, BAND_MIN, BAND_MAX, BAND_NMOM = range(6)
@@ -260,7 +275,7 @@ ABI_SYMBOLS = [
     "b9_abi_version", "b9_ctx_create", "b9_ctx_destroy", "b9_last_error",
     "b9_load_pack", "b9_load_stars", "b9_set_priors", "b9_set_options", "b9_set_tuning", "b9_get_tuning",
     "b9_logpost", "b9_logpost_device", "b9_mcmc_run_block", "b9_mcmc_wait", "b9_sample_mass", "b9_derive_isochrone",
-    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_star_moments", "b9_wd_moments", "b9_mass_hist", "b9_ratio_hist", "b9_star_bins", "b9_wd_bins", "b9_phot_resid", "b9_filter_loo", "b9_star_offset", "b9_pointwise", "b9_cmd_band", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
+    "b9_predict_mags", "b9_n_wd_stars", "b9_sample_wd_mass", "b9_star_moments", "b9_wd_moments", "b9_mass_hist", "b9_ratio_hist", "b9_star_bins", "b9_wd_bins", "b9_phot_resid", "b9_filter_loo", "b9_star_offset", "b9_pointwise", "b9_star_influence", "b9_cmd_band", "b9_max_eep", "b9_device_id", "b9_bytes_per_star_eval", "b9_step_tiles_per_block", "b9_step_depth",
     "b9_enable_timing", "b9_kernel_time_ms", "b9_calibrate_timing", "b9_clock_stamp", "b9_clock_mhz",
 ]
 
@@ -305,6 +320,7 @@ def load_hip_library(path: Optional[str] = None) -> C.CDLL:
     lib.b9_filter_loo.argtypes = [vp, _dp, C.c_int32, C.c_int32, _dp, _dp]
     lib.b9_star_offset.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]
     lib.b9_pointwise.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]
+    lib.b9_star_influence.argtypes = [vp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int32), _dp]
     lib.b9_cmd_band.argtypes = [vp, _dp, C.c_int32, C.POINTER(b9_band_spec), C.c_int32, _dp, _dp, _dp, C.c_int32, _dp]
     lib.b9_max_eep.argtypes = [vp]
     lib.b9_device_id.argtypes = [vp]

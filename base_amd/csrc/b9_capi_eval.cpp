@@ -2,8 +2,8 @@
 // b9_logpost_device), the per-star mass draws (b9_sample_mass), the isochrone dump (b9_derive_isochrone) and the forward
 // model alone (b9_predict_mags); the reductions over a saved chain through chain_reduce -- the per-star posterior moments
 // (b9_star_moments), the binned mass posteriors (b9_mass_hist), the per-star bins (b9_star_bins), the posterior-predictive
-// residuals (b9_phot_resid), the leave-one-filter-out predictions (b9_filter_loo), the per-star offsets (b9_star_offset) and the pointwise predictive densities
-// (b9_pointwise) --; and the three calls on a WD mass grid of the
+// residuals (b9_phot_resid), the leave-one-filter-out predictions (b9_filter_loo), the per-star offsets (b9_star_offset), the pointwise predictive densities
+// (b9_pointwise) and the star influence (b9_star_influence) --; and the three calls on a WD mass grid of the
 // caller's own size through wd_grid_reduce -- the WD-stage stars' posterior draws (b9_sample_wd_mass), their exact posterior
 // moments (b9_wd_moments) and their per-line bins (b9_wd_bins); and the loci a saved chain implies in the CMD (b9_cmd_band: a pack,
 // no stars, its own driver and arena).  Every launch wrapper takes its derived isochrone set as one
@@ -406,7 +406,8 @@ int b9_n_wd_stars(const b9_ctx *ctx)
 
 namespace {
 
-// ---- the reductions over a saved chain: b9_star_moments, b9_mass_hist, b9_star_bins, b9_phot_resid, b9_filter_loo, b9_star_offset, b9_pointwise
+// ---- the reductions over a saved chain: b9_star_moments, b9_mass_hist, b9_star_bins, b9_phot_resid, b9_filter_loo, b9_star_offset, b9_pointwise,
+// b9_star_influence
 // What one of them is to the driver below.  Rows are worked in chunks of at most max_rows, and of as few rows as keep the chunk's
 // increments [rows][n_stars][n_col] within scratch_bytes.
 struct ChainCall {
@@ -772,6 +773,54 @@ int b9_pointwise(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flag
     return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
         return b9k_pointwise(ctx->pk, ctx->st, d, m, reinterpret_cast<int *>(d.extra[0]), d_tail(d), T, ctx->stream);
     }, [&](const ChainDev &d) {
+        if (!T) return (int)B9_OK;
+        if (cont) HIPCHK(ctx, hipMemcpyAsync(d_tail_io(d), tail, tail_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, b9k_pw_tail_load(cont ? d_tail_io(d) : nullptr, n, T, d_tail(d), ctx->stream));
+        return (int)B9_OK;
+    }, [&](const ChainDev &d) {
+        if (!T) return (int)B9_OK;
+        HIPCHK(ctx, b9k_pw_tail_store(d_tail(d), n, T, d_tail_io(d), ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(tail, d_tail_io(d), tail_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return (int)B9_OK;
+    });
+}
+
+int b9_star_influence(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags, int32_t n_q, const double *q, double *acc, int32_t tail_len, double *tail,
+                      int32_t n_groups, const int32_t *group, double *group_lpd)
+{
+    if (!ctx || !params || n_rows < 1 || (!acc && !group_lpd)) return B9_ERR_INVALID;
+    if (acc && (n_q < 1 || n_q > B9_INF_MAX_Q || !q)) return fail(ctx, B9_ERR_INVALID, "b9_star_influence: acc needs q and n_q in 1 .. B9_INF_MAX_Q");
+    if (tail_len < 0 || tail_len > B9_PW_MAX_TAIL) return fail(ctx, B9_ERR_INVALID, "b9_star_influence: tail_len must lie in 0 .. B9_PW_MAX_TAIL");
+    if (tail && !acc) return fail(ctx, B9_ERR_INVALID, "b9_star_influence: tail requires acc");
+    if (group_lpd && (n_groups < 1 || n_groups > B9_INF_MAX_GROUPS || !group))
+        return fail(ctx, B9_ERR_INVALID, "b9_star_influence: group_lpd needs group and n_groups in 1 .. B9_INF_MAX_GROUPS");
+    const size_t Q = acc ? (size_t)n_q : 0, G = group_lpd ? (size_t)n_groups : 0;
+    for (size_t k = 0; k < (size_t)n_rows * Q; ++k)
+        if (!std::isfinite(q[k])) return fail(ctx, B9_ERR_INVALID, "b9_star_influence: q must be finite");
+    if (!ctx->have_stars) return fail(ctx, B9_ERR_STATE, "load the pack and the stars first");
+    for (size_t i = 0; G && i < (size_t)ctx->hs.n; ++i)
+        if (group[i] < -1 || group[i] >= n_groups) return fail(ctx, B9_ERR_INVALID, "b9_star_influence: star " + std::to_string(i) + ": group id outside -1 .. n_groups - 1");
+    if (const int rc = chain_ready(ctx)) return rc;
+    const int n = ctx->st.n, T = (tail && tail_len > 0) ? tail_len : 0;
+    const bool cont = (flags & B9_INF_CONTINUE) != 0;
+    const size_t tail_bytes = sizeof(double) * (size_t)n * T;
+    // the call's parts: {the rows' inside-the-grid words, the chunk's rows of q, the stars' group ids}, and the tail twice as b9_pointwise's
+    const size_t o_q = 256, o_group = o_q + 8 * (size_t)B9_PW_MAX_ROWS * B9_INF_MAX_Q;
+    const ChainCall c{"b9_star_influence", 1, B9_INF_N(Q), G, B9_PW_MAX_ROWS, B9_PW_SCRATCH_BYTES, cont, acc, group_lpd, {o_group + 4 * (size_t)n, tail_bytes, tail_bytes}};
+    auto d_tail = [&](const ChainDev &d) { return T ? reinterpret_cast<double *>(d.extra[1]) : nullptr; };
+    auto d_tail_io = [](const ChainDev &d) { return reinterpret_cast<double *>(d.extra[2]); };
+    int r0 = 0;                          // the chunk's first row: the driver takes the chunks in ascending order
+    return chain_reduce(ctx, c, params, n_rows, [&](const ChainDev &d, int m) {
+        double *const d_q = reinterpret_cast<double *>(d.extra[0] + o_q);
+        if (Q) {
+            const hipError_t e = hipMemcpyAsync(d_q, q + (size_t)r0 * Q, sizeof(double) * m * Q, hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) return e;
+        }
+        r0 += m;
+        const B9Influence f{(int)Q, d_q, (int)G, reinterpret_cast<const int *>(d.extra[0] + o_group)};
+        return b9k_star_influence(ctx->pk, ctx->st, d, m, reinterpret_cast<int *>(d.extra[0]), d_tail(d), T, f, ctx->stream);
+    }, [&](const ChainDev &d) {
+        if (G) HIPCHK(ctx, hipMemcpyAsync(d.extra[0] + o_group, group, sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
         if (!T) return (int)B9_OK;
         if (cont) HIPCHK(ctx, hipMemcpyAsync(d_tail_io(d), tail, tail_bytes, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, b9k_pw_tail_load(cont ? d_tail_io(d) : nullptr, n, T, d_tail(d), ctx->stream));

@@ -4,7 +4,7 @@
 //   b9_capi_stage.cpp   validation and staging of the model pack and the star catalogue into HBM (b9_load_pack, b9_load_stars)
 //   b9_capi_plan.cpp    launch plans: canonical tile groups, the fused step's and the tree step's plans
 //   b9_capi_margplan.cpp  the marginalised mode's catalogue plan: measured dispatch order, pieces of small catalogues
-//   b9_capi_eval.cpp    b9_logpost / b9_logpost_device / b9_sample_mass / b9_derive_isochrone / b9_predict_mags / b9_sample_wd_mass / b9_star_moments / b9_mass_hist / b9_phot_resid / b9_filter_loo / b9_star_offset / b9_pointwise
+//   b9_capi_eval.cpp    b9_logpost / b9_logpost_device / b9_sample_mass / b9_derive_isochrone / b9_predict_mags / b9_sample_wd_mass / b9_star_moments / b9_mass_hist / b9_phot_resid / b9_filter_loo / b9_star_offset / b9_pointwise / b9_star_influence
 //   b9_capi_blocks.cpp  the sampler's device-resident blocks (fused, tree-speculative, two-launch), b9_mcmc_run_block / b9_mcmc_wait
 // and, shared by all of them,
 //   b9_devbuf.h         who owns the memory: the owning buffer, the upload list, the arena carve, the sizing rules (no HIP in it;
@@ -159,7 +159,7 @@ struct b9_ctx {
     // accumulators, the stars' columns and the lines' edges (wd_grid_arena)
     b9i::DeviceBuf<char> d_wds;
 
-    // b9_star_moments, b9_mass_hist, b9_phot_resid, b9_pointwise: one allocation for the four (grown on demand, never shrunk),
+    // b9_star_moments, b9_mass_hist, b9_phot_resid, b9_pointwise, b9_star_influence: one allocation for them all (grown on demand, never shrunk),
     // for the same reason: a chunk of rows' parameters, headers, derived isochrones and node tables, the chunk's increments,
     // the accumulators, the chunk's per-row sums and the call's own parts (chain_arena).  The calls are synchronous and keep
     // nothing on the device between them, so only one of them is using it at any time.

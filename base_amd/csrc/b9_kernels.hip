@@ -49,6 +49,8 @@
 //                                     moments per filter over the same grid, summed over the rows and, standardised, the stars
 //   k_star_lpd / _wd / k_pw_accumulate / k_pw_tail / k_pw_rows   b9_pointwise: every star's marginal log-likelihood per row over
 //                                     the same grid, reduced over the rows (online log-sum-exps, Welford, largest -v) and the stars
+//   k_infl_accumulate / k_infl_groups   b9_star_influence: the same values as leave-one-star-out weights of the caller's per-row
+//                                     quantities (one lane per star, quantities tiled), and summed over the stars of each group
 //
 // The kernels live in the *.hip.h files included below (one translation unit); this file holds
 // k_finalize and the host-callable launch wrappers.
@@ -101,6 +103,7 @@ namespace tree_kd5 {
 #include "b9_filter_loo.hip.h"
 #include "b9_star_offset.hip.h"
 #include "b9_pointwise.hip.h"
+#include "b9_star_influence.hip.h"
 #include "b9_cmd_band.hip.h"
 
 // ------------------------------------------------------------------------------------------
@@ -652,29 +655,85 @@ hipError_t b9k_pw_tail_store(const double *tail, int n_stars, int tail_len, doub
     return hipGetLastError();
 }
 
+// the value half, shared with b9k_star_influence: scratch [n_rows][st.n] and row_in [n_rows]
+template <int NFP, int NPOPS>
+static hipError_t launch_pw_values(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, int *row_in, hipStream_t stream)
+{
+    const B9IsoSet &s = c.set;
+    const ChainTables t = chain_tables<NFP>(pk, st, c, n_rows, stream);
+    if (t.err != hipSuccess) return t.err;
+    hipLaunchKernelGGL((k_star_lpd<NFP, NPOPS>), dim3(st.mg_pad / 64, n_rows), dim3(256), 0, stream, st, s.hdr, s.iso, s.iso_stride, s.mass_cap,
+                       s.params, c.mg.K, c.mg.Q, c.mg.tab, t.L, t.cut2, c.scratch, row_in);
+    if (st.n_wd > 0)
+        hipLaunchKernelGGL((k_star_lpd_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, s.hdr, s.params, c.mg.K,
+                           c.mg.wd_tab, c.scratch);
+    return hipSuccess;
+}
+// ... and the tails
+static hipError_t launch_pw_tail(const DevStars &st, const B9Chain &c, int n_rows, const int *row_in, double *tail, int tail_len, hipStream_t stream)
+{
+    const auto kt = with_lds(k_pw_tail, sizeof(double) * 64 * (size_t)tail_len);          // the wave's 64 lists
+    if (kt.err != hipSuccess) return kt.err;
+    hipLaunchKernelGGL(kt.kern, dim3((unsigned)((st.n + 63) / 64)), dim3(64), kt.lds, stream, c.scratch, row_in, n_rows, st.n, tail_len, tail);
+    return hipSuccess;
+}
+
 hipError_t b9k_pointwise(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, int *row_in, double *tail, int tail_len, hipStream_t stream)
 {
     return dispatch(pk.nfp, c.set.n_pops, [&](auto nfp_c, auto npops_c) {
         constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
-        const B9IsoSet &s = c.set;
         if (!row_in || n_rows > B9_PW_MAX_ROWS || (tail && (!c.acc || tail_len < 1 || tail_len > B9_PW_MAX_TAIL))) return hipErrorInvalidValue;
-        const ChainTables t = chain_tables<NFP>(pk, st, c, n_rows, stream);
-        if (t.err != hipSuccess) return t.err;
-        hipLaunchKernelGGL((k_star_lpd<NFP, NPOPS>), dim3(st.mg_pad / 64, n_rows), dim3(256), 0, stream, st, s.hdr, s.iso, s.iso_stride, s.mass_cap,
-                           s.params, c.mg.K, c.mg.Q, c.mg.tab, t.L, t.cut2, c.scratch, row_in);
-        if (st.n_wd > 0)
-            hipLaunchKernelGGL((k_star_lpd_wd<NFP, NPOPS>), dim3((st.n_wd + 3) / 4, n_rows), dim3(256), 0, stream, st, pk.m_wd_up, s.hdr, s.params, c.mg.K,
-                               c.mg.wd_tab, c.scratch);
+        if (const hipError_t e = launch_pw_values<NFP, NPOPS>(pk, st, c, n_rows, row_in, stream)) return e;
         const unsigned star_wgs = (unsigned)((st.n + 255) / 256);
         if (c.acc)
             hipLaunchKernelGGL(k_pw_accumulate, dim3(star_wgs), dim3(256), 0, stream, c.scratch, row_in, n_rows, st.n, c.acc);
-        if (tail) {
-            const auto kt = with_lds(k_pw_tail, sizeof(double) * 64 * (size_t)tail_len);          // the wave's 64 lists
-            if (kt.err != hipSuccess) return kt.err;
-            hipLaunchKernelGGL(kt.kern, dim3((unsigned)((st.n + 63) / 64)), dim3(64), kt.lds, stream, c.scratch, row_in, n_rows, st.n, tail_len, tail);
-        }
+        if (tail)
+            if (const hipError_t e = launch_pw_tail(st, c, n_rows, row_in, tail, tail_len, stream)) return e;
         if (c.rows)
             hipLaunchKernelGGL(k_pw_rows, dim3((unsigned)n_rows), dim3(64), 0, stream, c.scratch, row_in, st.n, c.rows);
+        return hipGetLastError();
+    });
+}
+
+// ---- b9_star_influence: b9_pointwise's values of a chunk of rows, then the per-star influence state, the tails, the groups' sums
+template <int QT>
+static void launch_infl_accumulate(const DevStars &st, const B9Chain &c, int n_rows, const int *row_in, const B9Influence &f, hipStream_t stream)
+{
+    // one launch per tile, in stream order: every tile reads the head as the chunk found it, the last one stores the new head
+    const int tiles = (f.n_q + QT - 1) / QT;
+    for (int t = 0; t < tiles; ++t)
+        hipLaunchKernelGGL(k_infl_accumulate<QT>, dim3((unsigned)((st.n + 255) / 256)), dim3(256), 0, stream, c.scratch, row_in, n_rows, st.n, f.q, f.n_q, t,
+                           t == tiles - 1 ? 1 : 0, c.acc);
+}
+template <int NG>
+static void launch_infl_groups(const DevStars &st, const B9Chain &c, int n_rows, const int *row_in, const B9Influence &f, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_infl_groups<NG>, dim3((unsigned)n_rows), dim3(64), 0, stream, c.scratch, row_in, st.n, f.group, f.n_groups, c.rows);
+}
+
+hipError_t b9k_star_influence(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, int *row_in, double *tail, int tail_len, const B9Influence &f,
+                              hipStream_t stream)
+{
+    return dispatch(pk.nfp, c.set.n_pops, [&](auto nfp_c, auto npops_c) {
+        constexpr int NFP = decltype(nfp_c)::value, NPOPS = decltype(npops_c)::value;
+        if (!row_in || n_rows > B9_PW_MAX_ROWS || (tail && (!c.acc || tail_len < 1 || tail_len > B9_PW_MAX_TAIL))) return hipErrorInvalidValue;
+        if (c.acc && (!f.q || f.n_q < 1 || f.n_q > B9_INF_MAX_Q)) return hipErrorInvalidValue;
+        if (c.rows && (!f.group || f.n_groups < 1 || f.n_groups > B9_INF_MAX_GROUPS)) return hipErrorInvalidValue;
+        if (const hipError_t e = launch_pw_values<NFP, NPOPS>(pk, st, c, n_rows, row_in, stream)) return e;
+        if (c.acc) {
+            // quantities per instance: every tile is a launch and recomputes the head, so as few tiles as the registers carry
+            if (f.n_q == 1) launch_infl_accumulate<1>(st, c, n_rows, row_in, f, stream);
+            else if (f.n_q == 2) launch_infl_accumulate<2>(st, c, n_rows, row_in, f, stream);
+            else launch_infl_accumulate<4>(st, c, n_rows, row_in, f, stream);
+        }
+        if (tail)
+            if (const hipError_t e = launch_pw_tail(st, c, n_rows, row_in, tail, tail_len, stream)) return e;
+        if (c.rows) {
+            if (f.n_groups == 1) launch_infl_groups<1>(st, c, n_rows, row_in, f, stream);
+            else if (f.n_groups == 2) launch_infl_groups<2>(st, c, n_rows, row_in, f, stream);
+            else if (f.n_groups <= 4) launch_infl_groups<4>(st, c, n_rows, row_in, f, stream);
+            else launch_infl_groups<8>(st, c, n_rows, row_in, f, stream);
+        }
         return hipGetLastError();
     });
 }

@@ -250,6 +250,18 @@ hipError_t b9k_pw_tail_load(const double *tail_io, int n_stars, int tail_len, do
 hipError_t b9k_pw_tail_store(const double *tail, int n_stars, int tail_len, double *tail_io, hipStream_t stream);
 hipError_t b9k_pointwise(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, int *row_in, double *tail, int tail_len, hipStream_t stream);
 
+// b9_star_influence: b9k_pointwise's values and row_in, then -- each optional -- acc [st.n][B9_INF_N(n_q)] through the influence
+// recurrence (k_infl_accumulate), tail as b9k_pointwise's, rows [n_rows][n_groups] the groups' sums (k_infl_groups).  q [n_rows][n_q]:
+// the chunk's rows of the caller's quantities; group [st.n]: the stars' group ids, the caller's order.  Device pointers.
+struct B9Influence {
+    int n_q;
+    const double *q;
+    int n_groups;
+    const int *group;
+};
+hipError_t b9k_star_influence(const DevPack &pk, const DevStars &st, const B9Chain &c, int n_rows, int *row_in, double *tail, int tail_len, const B9Influence &f,
+                              hipStream_t stream);
+
 hipError_t b9k_noop(hipStream_t stream);
 hipError_t b9k_spin(double microseconds, hipStream_t stream);
 constexpr int B9_CLOCK_SLOTS = 8 * 256;      // (XCD, HW_ID[15:8]) -> one slot per compute unit

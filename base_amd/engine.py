@@ -399,6 +399,38 @@ class Engine:
         self._check(self.lib.b9_pointwise(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], flags, int(tail_len), ptr(a), ptr(t), ptr(rl)))
         return a, t, rl
 
+    def star_influence(self, rows: np.ndarray, q=None, tail_len: int = 0, groups=None, n_groups: int = 0,
+                       state=None) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], Optional[np.ndarray]]:
+        """b9_star_influence: the leave-one-star-out state of the per-row quantities q [n_rows, n_q] and the groups' sums of v
+        over `rows`: (acc [n_stars, 6 + 4 n_q] -- abi.INF_ROWS .. INF_MEANV, then WQ, WQ2, MQ, CVQ per quantity; None for
+        q = None --, tail [n_stars, tail_len] -- as Engine.pointwise's; None for tail_len = 0 --, group_lpd [n_rows, n_groups] --
+        the sum of v over the stars i with groups[i] == g; None for groups = None).  state=None starts from zeros (the tail
+        from -inf); else state = (acc, tail) of the calls before is continued (B9_INF_CONTINUE) and new arrays come back."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, abi.B9_NPARAM)
+        flags, nq = 0, 0
+        a = t = gl = g = None
+        if q is not None:
+            q = np.ascontiguousarray(q, dtype=np.float64).reshape(rows.shape[0], -1)
+            nq = q.shape[1]
+            if state is None:
+                a = np.zeros((self.n_stars, abi.INF_N(nq)))
+                t = np.full((self.n_stars, tail_len), -np.inf) if tail_len > 0 else None
+            else:
+                flags = abi.INF_CONTINUE
+                a = np.array(state[0], dtype=np.float64, order="C").reshape(self.n_stars, abi.INF_N(nq))
+                if tail_len > 0:
+                    if state[1] is None:
+                        raise ValueError("continuing with tail_len > 0 needs the tail of the calls before")
+                    t = np.array(state[1], dtype=np.float64, order="C").reshape(self.n_stars, tail_len)
+        if groups is not None:
+            g = np.ascontiguousarray(groups, dtype=np.int32).reshape(self.n_stars)
+            gl = np.zeros((rows.shape[0], max(int(n_groups), 0)))
+        ptr = lambda x: x.ctypes.data_as(_dp) if x is not None else None      # noqa: E731
+        gp = g.ctypes.data_as(C.POINTER(C.c_int32)) if g is not None else None
+        self._check(self.lib.b9_star_influence(self._ctx, rows.ctypes.data_as(_dp), rows.shape[0], flags, nq, ptr(q), ptr(a), int(tail_len), ptr(t),
+                                               int(n_groups), gp, ptr(gl)))
+        return a, t, gl
+
     def derive_isochrone(self, param_row: np.ndarray, pop: int = 0, cap: int = 4096) -> Tuple[int, np.ndarray, np.ndarray, float]:
         row = np.ascontiguousarray(param_row, dtype=np.float64)
         mass = np.empty(cap)

@@ -82,6 +82,7 @@ const ProgramFlags kPhotResidFlags = {{"perStar", "photResidualsPerStar", true},
 const ProgramFlags kFilterCheckFlags = {{"perStar", "filterCheckPerStar", true}, {"nPops", "filterCheckNPops", false}};
 const ProgramFlags kStarOffsetsFlags = {{"nPops", "starOffsetsNPops", false}};
 const ProgramFlags kModelScoreFlags = {{"perRow", "modelScorePerRow", true}, {"nPops", "modelScoreNPops", false}};
+const ProgramFlags kStarInfluenceFlags = {{"quantity", "starInfluenceQuantity", false}, {"noGroups", "noGroups", true}, {"nPops", "starInfluenceNPops", false}};
 
 PhotResidConfig phot_resid_config(const Settings &st) { return {st.integer("photResiduals.perStar", 0) != 0}; }
 
@@ -1063,20 +1064,21 @@ void write_offset_dist(const std::string &path, const std::vector<std::string> &
 namespace {
 const double kInf = std::numeric_limits<double>::infinity(), kNaN = std::numeric_limits<double>::quiet_NaN();
 
-// PSIS of one star: r[0 .. n_t) the finite tail values, descending (r[0] = RMAX); -> paretoK, elpdLoo (elpd_is where no fit is made)
-void psis_star(const double *r, long n_t, double n_f, double rmax, double sneg, double elpd_is, double &pareto_k, double &elpd_loo)
+// Steps (1) - (6) of the PSIS statement on r[0 .. n_t), finite and descending: the tail's length M,
+// rho[0 .. M] = r - r[0], paretoK and w[j - 1], the smoothed weight of the j-th SMALLEST of the M tail values.  false: no fit.
+struct PsisFit { long M = 0; double k_hat = 0.0; std::vector<double> rho, w; };
+bool psis_fit(const double *r, long n_t, double n_f, PsisFit &fit)
 {
-    pareto_k = kNaN;
-    elpd_loo = elpd_is;
     const long M = std::min({(long)std::floor(n_f / 5.0), (long)std::ceil(3.0 * std::sqrt(n_f)), n_t - 1});
-    if (M < 5) return;
+    if (M < 5) return false;
     const long N = M;
-    std::vector<double> rho((size_t)M + 1), x((size_t)M);
+    std::vector<double> &rho = fit.rho, x((size_t)M);
+    rho.assign((size_t)M + 1, 0.0);
     for (long j = 0; j <= M; ++j) rho[(size_t)j] = r[j] - r[0];
     const double ec = std::exp(rho[(size_t)M]);
     for (long j = 0; j < M; ++j) x[(size_t)(M - 1 - j)] = std::exp(rho[(size_t)j]) - ec;          // ascending: rho descends
     const double x_n = x[(size_t)N - 1], x_star = x[(size_t)std::floor((double)N / 4.0 + 0.5) - 1];
-    if (x_n == 0.0 || !(x_star > 0.0)) return;
+    if (x_n == 0.0 || !(x_star > 0.0)) return false;
     // Zhang & Stephens' profile fit of the generalised Pareto distribution, with the weakly informative prior on k
     const long m = 30 + (long)std::floor(std::sqrt((double)N));
     std::vector<double> theta((size_t)m), ell((size_t)m);
@@ -1096,18 +1098,34 @@ void psis_star(const double *r, long n_t, double n_f, double rmax, double sneg, 
     double k_hat = mean_log1p(theta_hat);
     const double sigma = -k_hat / theta_hat;
     k_hat = ((double)N * k_hat + 5.0) / ((double)N + 10.0);
-    // the smoothed weights, paired by rank: the j-th smallest tail value takes the quantile at p_j = (j - 1/2) / M
-    double num = n_f - (double)M, tail_raw = 0.0, tail_smooth = 0.0;
+    // the smoothed weights, by rank: the j-th smallest tail value takes the quantile at p_j = (j - 1/2) / M
+    fit.w.assign((size_t)M, 0.0);
     for (long j = 1; j <= M; ++j) {
         const double p = ((double)j - 0.5) / (double)M, lp = std::log1p(-p);
         const double q = k_hat == 0.0 ? -sigma * lp : sigma * std::expm1(-k_hat * lp) / k_hat;
-        const double w = std::min(1.0, ec + q), rh = rho[(size_t)(M - j)];
+        fit.w[(size_t)j - 1] = std::min(1.0, ec + q);
+    }
+    fit.M = M; fit.k_hat = k_hat;
+    return true;
+}
+
+// PSIS of one star: r[0 .. n_t) the finite tail values, descending (r[0] = RMAX); -> paretoK, elpdLoo (elpd_is where no fit is made)
+void psis_star(const double *r, long n_t, double n_f, double rmax, double sneg, double elpd_is, double &pareto_k, double &elpd_loo)
+{
+    pareto_k = kNaN;
+    elpd_loo = elpd_is;
+    PsisFit fit;
+    if (!psis_fit(r, n_t, n_f, fit)) return;
+    const long M = fit.M;
+    double num = n_f - (double)M, tail_raw = 0.0, tail_smooth = 0.0;
+    for (long j = 1; j <= M; ++j) {                       // step (7), paired by rank
+        const double w = fit.w[(size_t)j - 1], rh = fit.rho[(size_t)(M - j)];
         num += std::exp(std::log(w) - rh);
         tail_smooth += w;
         tail_raw += std::exp(rh);
     }
     const double den = std::max(0.0, sneg - tail_raw) + tail_smooth;
-    pareto_k = k_hat;
+    pareto_k = fit.k_hat;
     elpd_loo = std::log(num) - std::log(den) - rmax;
 }
 
@@ -1250,6 +1268,202 @@ void read_pointwise(const std::string &path, std::vector<std::string> &ids, std:
             table.push_back(std::strtod(word.c_str(), nullptr));         // (strtod reads inf / -inf / nan as printf wrote them)
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// starInfluence
+// ---------------------------------------------------------------------------------------------
+StarInfluenceConfig star_influence_config(const Settings &st)
+{
+    StarInfluenceConfig c;
+    std::istringstream qs(st.str("starInfluence.quantity", ""));
+    std::string tok;
+    while (qs >> tok) c.quantities.push_back(tok);
+    if (c.quantities.size() > B9_INF_MAX_Q) fail("starInfluence.quantity: at most " + std::to_string(B9_INF_MAX_Q) + " quantities");
+    c.group_file = st.str("starInfluence.groupFile", "");
+    c.no_groups = st.integer("starInfluence.noGroups", 0) != 0;
+    if (c.no_groups && !c.group_file.empty()) fail("starInfluence: give groupFile or noGroups, not both");
+    return c;
+}
+
+InfluenceQuantities influence_quantities(const StarInfluenceConfig &c, const double *rows, const double *log_post, long n_rows)
+{
+    if (n_rows < 2) fail("starInfluence: the chain needs at least two main-run rows");
+    InfluenceQuantities out;
+    std::vector<int> col;                                 // B9_P_* index, or -1: logPost
+    auto column = [&](int k, long r) { return k < 0 ? log_post[r] : rows[(size_t)r * B9_NPARAM + k]; };
+    if (c.quantities.empty()) {
+        for (int k = 0; k < B9_NPARAM; ++k) {
+            bool varies = false;
+            for (long r = 1; r < n_rows && !varies; ++r) varies = column(k, r) != column(k, 0);
+            if (varies) col.push_back(k);
+        }
+        if (col.empty()) fail("starInfluence: no cluster parameter varies over the main-run rows");
+        if (col.size() > B9_INF_MAX_Q) fail("starInfluence: more than " + std::to_string(B9_INF_MAX_Q) + " parameters vary: name the quantities (--quantity)");
+    } else {
+        for (const std::string &name : c.quantities) {
+            int idx = -2;
+            if (name == "logPost") idx = -1;
+            for (int k = 0; k < B9_NPARAM; ++k) if (name == param_name(k)) idx = k;
+            if (idx == -2) fail("starInfluence.quantity: '" + name + "' is neither a cluster parameter nor logPost");
+            if (idx == -1 && !log_post) fail("starInfluence.quantity: the chain has no logPost column");
+            col.push_back(idx);
+        }
+    }
+    const size_t Q = col.size();
+    out.q.assign((size_t)n_rows * Q, 0.0);
+    for (size_t j = 0; j < Q; ++j) {
+        const int k = col[j];
+        out.names.push_back(k < 0 ? "logPost" : param_name(k));
+        double sum = 0.0, ss = 0.0;                       // two passes: the mean, then the squares about it
+        for (long r = 0; r < n_rows; ++r) sum += column(k, r);
+        const double mean = sum / (double)n_rows;
+        for (long r = 0; r < n_rows; ++r) { const double d = column(k, r) - mean; ss += d * d; }
+        const double sd = std::sqrt(ss / (double)(n_rows - 1));
+        if (!(sd > 0.0) || !std::isfinite(sd)) fail("starInfluence.quantity: '" + out.names.back() + "' does not vary over the main-run rows");
+        out.mean.push_back(mean); out.sd.push_back(sd);
+        for (long r = 0; r < n_rows; ++r) out.q[(size_t)r * Q + j] = (column(k, r) - mean) / sd;
+    }
+    return out;
+}
+
+InfluenceGroups influence_groups(const StarInfluenceConfig &c, const std::vector<std::string> &ids, const std::vector<int32_t> &stage)
+{
+    InfluenceGroups g;
+    if (c.no_groups) return g;
+    g.id.assign(ids.size(), -1);
+    if (c.group_file.empty()) {
+        g.names = {"ms", "wd"};
+        for (size_t i = 0; i < ids.size(); ++i) g.id[i] = stage[i] == B9_STAGE_WD ? 1 : stage[i] == B9_STAGE_MSRG ? 0 : -1;
+        return g;
+    }
+    std::ifstream in(c.group_file);
+    if (!in) fail("cannot read " + c.group_file);
+    std::string line, id, name;
+    while (std::getline(in, line)) {
+        std::istringstream ls(line);
+        if (!(ls >> id) || id[0] == '#') continue;
+        if (!(ls >> name)) fail(c.group_file + ": no group name for star '" + id + "'");
+        const auto it = std::find(ids.begin(), ids.end(), id);
+        if (it == ids.end()) fail(c.group_file + ": unknown star id '" + id + "'");
+        auto gt = std::find(g.names.begin(), g.names.end(), name);
+        if (gt == g.names.end()) {
+            if (g.names.size() >= B9_INF_MAX_GROUPS) fail(c.group_file + ": at most " + std::to_string(B9_INF_MAX_GROUPS) + " groups");
+            g.names.push_back(name);
+            gt = g.names.end() - 1;
+        }
+        g.id[(size_t)(it - ids.begin())] = (int32_t)(gt - g.names.begin());
+    }
+    if (g.names.empty()) fail(c.group_file + ": no group");
+    return g;
+}
+
+void influence_table(const double *acc, const double *tail, int tail_len, long n_stars, int n_q, double *table)
+{
+    const size_t n_acc = (size_t)B9_INF_N(n_q), n_col = (size_t)kInfluenceHead + 3 * (size_t)n_q;
+    for (long i = 0; i < n_stars; ++i) {
+        const double *a = acc + (size_t)i * n_acc;
+        double *t = table + (size_t)i * n_col;
+        for (size_t c = 0; c < n_col; ++c) t[c] = 0.0;
+        const double rows = a[B9_INF_ROWS], n_inf = a[B9_INF_NINF], n_f = rows - n_inf;
+        t[0] = rows; t[1] = n_inf;
+        if (n_inf > 0.0) {                               // a row gives the star no likelihood at all: no finite weight there
+            for (size_t c = 3; c < n_col; ++c) t[c] = kNaN;
+            continue;
+        }
+        if (!(n_f > 0.0)) continue;
+        const double sneg = a[B9_INF_SNEG];
+        t[2] = sneg * sneg / a[B9_INF_SNEG2];
+        t[3] = kNaN;
+        const double *r = tail ? tail + (size_t)i * (size_t)tail_len : nullptr;
+        long n_t = 0;
+        while (r && n_t < tail_len && std::isfinite(r[n_t])) ++n_t;
+        PsisFit fit;
+        if (psis_fit(r, n_t, n_f, fit)) t[3] = fit.k_hat;
+        for (int j = 0; j < n_q; ++j) {
+            const double *w = a + B9_INF_WQ(j);
+            const double m = w[0] / sneg;
+            t[kInfluenceHead + 3 * j] = m - w[2];
+            t[kInfluenceHead + 3 * j + 1] = n_f >= 2.0 ? -w[3] / (n_f - 1.0) : 0.0;
+            t[kInfluenceHead + 3 * j + 2] = std::sqrt(std::max(0.0, w[1] / sneg - m * m));
+        }
+    }
+}
+
+void group_influence_table(const double *group_lpd, long n_rows, int n_groups, const double *q, int n_q, const int32_t *group, long n_stars, double *table)
+{
+    const size_t n_col = (size_t)kGroupInfluenceHead + 3 * (size_t)n_q;
+    for (int g = 0; g < n_groups; ++g) {
+        double *t = table + (size_t)g * n_col;
+        for (size_t c = 0; c < n_col; ++c) t[c] = 0.0;
+        for (long i = 0; i < n_stars; ++i) t[0] += group[i] == g ? 1.0 : 0.0;
+        t[1] = (double)n_rows;
+        for (long r = 0; r < n_rows; ++r) t[2] += std::isfinite(group_lpd[(size_t)r * n_groups + g]) ? 0.0 : 1.0;
+        if (n_rows == 0) continue;
+        if (t[2] > 0.0) {
+            for (size_t c = 4; c < n_col; ++c) t[c] = kNaN;
+            continue;
+        }
+        // rho = -group_lpd, descending (ties: the earlier row first), the raw weights e^(rho - max rho) and the smoothed ones
+        std::vector<long> order((size_t)n_rows);
+        for (long r = 0; r < n_rows; ++r) order[(size_t)r] = r;
+        auto rho = [&](long r) { return -group_lpd[(size_t)r * n_groups + g]; };
+        std::stable_sort(order.begin(), order.end(), [&](long a, long b) { return rho(a) > rho(b); });
+        const double top = rho(order[0]);
+        std::vector<double> raw((size_t)n_rows), w, sorted((size_t)n_rows);
+        for (long r = 0; r < n_rows; ++r) raw[(size_t)r] = std::exp(rho(r) - top);
+        for (long k = 0; k < n_rows; ++k) sorted[(size_t)k] = rho(order[(size_t)k]);
+        w = raw;
+        PsisFit fit;
+        t[4] = kNaN;
+        if (psis_fit(sorted.data(), n_rows, (double)n_rows, fit)) {
+            t[4] = fit.k_hat;
+            for (long j = 1; j <= fit.M; ++j) w[(size_t)order[(size_t)(fit.M - j)]] = fit.w[(size_t)j - 1];
+        }
+        double s1 = 0.0, s2 = 0.0;
+        for (double x : raw) { s1 += x; s2 += x * x; }
+        t[3] = s1 * s1 / s2;
+        for (int j = 0; j < n_q; ++j) {
+            double mq = 0.0;
+            for (long r = 0; r < n_rows; ++r) mq += q[(size_t)r * n_q + j];
+            mq /= (double)n_rows;
+            auto mean_of = [&](const std::vector<double> &wt, double &m, double &sd) {
+                double sw = 0.0, a = 0.0, b = 0.0;
+                for (long r = 0; r < n_rows; ++r) { const double y = q[(size_t)r * n_q + j]; sw += wt[(size_t)r]; a += wt[(size_t)r] * y; b += wt[(size_t)r] * y * y; }
+                m = a / sw;
+                sd = std::sqrt(std::max(0.0, b / sw - m * m));
+            };
+            double m_raw, sd_raw, m, sd;
+            mean_of(raw, m_raw, sd_raw);
+            mean_of(w, m, sd);
+            t[kGroupInfluenceHead + 3 * j] = m_raw - mq;
+            t[kGroupInfluenceHead + 3 * j + 1] = m - mq;
+            t[kGroupInfluenceHead + 3 * j + 2] = sd;
+        }
+    }
+}
+
+void write_star_influence(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &quantities, const double *table)
+{
+    std::vector<TableColumn> cols = columns({"rows", "nInf", "ess", "paretoK"}, "%.17g");
+    for (const std::string &n : quantities)
+        for (const char *what : {"shift_", "lin_", "looSd_"}) cols.push_back({what + n, "%.17g"});
+    write_table(path, "id", &ids, cols, (long)ids.size(), table, cols.size());
+}
+
+void write_group_influence(const std::string &path, const std::vector<std::string> &groups, const std::vector<std::string> &quantities, const double *table)
+{
+    std::vector<TableColumn> cols = columns({"nStars", "rows", "nInf", "ess", "paretoK"}, "%.17g");
+    for (const std::string &n : quantities)
+        for (const char *what : {"shiftRaw_", "shift_", "looSd_"}) cols.push_back({what + n, "%.17g"});
+    write_table(path, "group", &groups, cols, (long)groups.size(), table, cols.size());
+}
+
+void write_influence_scale(const std::string &path, const std::vector<std::string> &quantities, const double *mean, const double *sd)
+{
+    std::vector<double> table;
+    for (size_t j = 0; j < quantities.size(); ++j) { table.push_back(mean[j]); table.push_back(sd[j]); }
+    write_table(path, "name", &quantities, columns({"mean", "sd"}, "%.17g"), (long)quantities.size(), table.data(), 2);
 }
 
 // ---------------------------------------------------------------------------------------------

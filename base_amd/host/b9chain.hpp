@@ -1,5 +1,5 @@
 // b9chain.hpp -- what the programs over a saved chain (sampleMass, sampleWDMass, starSummary, wdSummary, wdIntervals, cmdBand, massFunction,
-// binaryStats, starIntervals, photResiduals, filterCheck, starOffsets, modelScore) share above the C ABI and below their mains: their settings, the loop over the
+// binaryStats, starIntervals, photResiduals, filterCheck, starOffsets, modelScore, starInfluence) share above the C ABI and below their mains: their settings, the loop over the
 // chain's rows, the tables derived from the device's sums and the files they are written to (docs/FORMATS.md).  Host arithmetic
 // only: nothing here needs a context or a GPU.  b9host.hpp includes this header.
 #pragma once
@@ -354,5 +354,39 @@ void write_model_score(const std::string &path, const double *totals);
 void write_model_compare(const std::string &path, const double *cmp);
 void write_row_lpd(const std::string &path, const double *row_lpd, long n_rows);
 void read_pointwise(const std::string &path, std::vector<std::string> &ids, std::vector<double> &table);
+
+// ---- starInfluence ---------------------------------------------------------------------------------
+// starInfluence.{quantity, groupFile, noGroups} (flags --quantity NAME, repeatable; --groupFile FILE; --noGroups; in YAML the
+// quantities are one whitespace-separated scalar).  A quantity is a cluster parameter's name as the .res header spells it, or
+// logPost; at most B9_INF_MAX_Q.  Default: every cluster parameter that varies over the main-run rows, in B9_P_* order.
+extern const ProgramFlags kStarInfluenceFlags;
+struct StarInfluenceConfig { std::vector<std::string> quantities; std::string group_file; bool no_groups = false; };
+StarInfluenceConfig star_influence_config(const Settings &st);
+// The quantities as the call takes them: q [n_rows][Q] = (theta - mean) / sd with a two-pass mean and the ddof-1 sd over the rows
+// [n_rows][B9_NPARAM] (log_post [n_rows], may be null: no logPost).  Throws for an unknown name, a quantity that does not vary, more
+// than B9_INF_MAX_Q of them or fewer than two rows.
+struct InfluenceQuantities { std::vector<std::string> names; std::vector<double> q, mean, sd; };
+InfluenceQuantities influence_quantities(const StarInfluenceConfig &c, const double *rows, const double *log_post, long n_rows);
+// The groups: by default ms (stage 1) = 0 and wd (stage 3) = 1, every other star -1; with a group file its lines "id name" (names
+// numbered in the order they first appear, at most B9_INF_MAX_GROUPS; a star the file does not list: -1; an unknown id throws);
+// noGroups: no names, no ids.
+struct InfluenceGroups { std::vector<std::string> names; std::vector<int32_t> id; };
+InfluenceGroups influence_groups(const StarInfluenceConfig &c, const std::vector<std::string> &ids, const std::vector<int32_t> &stage);
+// b9_star_influence's acc [n_stars][B9_INF_N(Q)] and tail (may be null) -> the per-star table [n_stars][kInfluenceHead + 3 Q]:
+// rows, nInf, ess = SNEG^2 / SNEG2, paretoK (the PSIS fit of the tail; NaN without a tail or where the fit is refused), then per
+// quantity shift = WQ / SNEG - MQ, lin = -CVQ / (n_f - 1) (0 for n_f < 2), looSd = sqrt(max(0, WQ2 / SNEG - (WQ / SNEG)^2)).
+// nInf > 0: ess = 0, paretoK and every per-quantity value NaN.  rows = 0: every value 0.
+constexpr int kInfluenceHead = 4, kGroupInfluenceHead = 5;
+void influence_table(const double *acc, const double *tail, int tail_len, long n_stars, int n_q, double *table);
+// b9_star_influence's group_lpd [n_rows][G] with the call's q [n_rows][Q] and the stars' ids -> [G][kGroupInfluenceHead + 3 Q]:
+// nStars, rows (= n_rows), nInf (the rows whose sum is -inf: a row outside the grid is one), ess, paretoK, then per quantity
+// shiftRaw (self-normalised with e^(rho - max rho), rho = -group_lpd), shift (the M largest weights replaced by the smoothed ones;
+// = shiftRaw where the fit is refused) and looSd (with shift's weights).  nInf > 0: ess = 0, the rest NaN.
+void group_influence_table(const double *group_lpd, long n_rows, int n_groups, const double *q, int n_q, const int32_t *group, long n_stars, double *table);
+// <base>.starInfluence ("id rows nInf ess paretoK {shift_<q> lin_<q> looSd_<q>}"), <base>.groupInfluence ("group nStars rows nInf
+// ess paretoK {shiftRaw_<q> shift_<q> looSd_<q>}") and <base>.influenceScale ("name mean sd").  17 significant digits.
+void write_star_influence(const std::string &path, const std::vector<std::string> &ids, const std::vector<std::string> &quantities, const double *table);
+void write_group_influence(const std::string &path, const std::vector<std::string> &groups, const std::vector<std::string> &quantities, const double *table);
+void write_influence_scale(const std::string &path, const std::vector<std::string> &quantities, const double *mean, const double *sd);
 
 }  // namespace b9h

@@ -141,6 +141,8 @@ const std::map<std::string, std::string> &Settings::flag_map()
         {"cmdBandRatios", "cmdBand.ratios"}, {"cmdBandWdNodes", "cmdBand.wdNodes"}, {"cmdBandWdTypes", "cmdBand.wdTypes"}, {"cmdBandColours", "cmdBand.colours"},
         {"cmdBandLevels", "cmdBand.levels"}, {"cmdBandTol", "cmdBand.tol"}, {"cmdBandMaxPasses", "cmdBand.maxPasses"}, {"cmdBandNPops", "cmdBand.nPops"},
         {"modelScorePerRow", "modelScore.perRow"}, {"modelScoreNPops", "modelScore.nPops"}, {"compareTo", "modelScore.compareTo"},
+        {"starInfluenceQuantity", "starInfluence.quantity"}, {"groupFile", "starInfluence.groupFile"}, {"noGroups", "starInfluence.noGroups"},
+        {"starInfluenceNPops", "starInfluence.nPops"},
         {"nStars", "simCluster.nStars"}, {"percentBinary", "simCluster.percentBinary"}, {"percentDB", "simCluster.percentDB"},
         {"nFieldStars", "simCluster.nFieldStars"}, {"minMass", "simCluster.minMass"}, {"maxMass", "simCluster.maxMass"},
         {"minMassRatio", "simCluster.minMassRatio"}, {"memberPrior", "simCluster.memberPrior"}, {"nPops", "simCluster.nPops"},
@@ -173,7 +175,7 @@ void Settings::parse_args(int argc, char **argv, const ProgramFlags &own)
         auto it = flag_map().find(a);
         if (it == flag_map().end()) fail("unknown flag --" + a);
         const std::string &key = it->second;
-        const bool list = key == "starOffsets.direction" || key == "starOffsets.tau";        // (repeatable: space-joined)
+        const bool list = key == "starOffsets.direction" || key == "starOffsets.tau" || key == "starInfluence.quantity";        // (repeatable: space-joined)
         if (list && std::find(listed.begin(), listed.end(), key) != listed.end()) kv[key] += " " + value;
         else kv[key] = value;
         if (list) listed.push_back(key);

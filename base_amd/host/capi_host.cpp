@@ -594,6 +594,83 @@ int b9h_model_score_settings(int argc, char **argv, char *out, int cap)
     });
 }
 
+int b9h_influence_table(const double *acc, const double *tail, int tail_len, long n_stars, int n_q, double *table)
+{
+    return guard([&] {
+        if (n_stars < 0 || !table || tail_len < 0 || n_q < 1 || n_q > B9_INF_MAX_Q || (n_stars > 0 && !acc)) throw std::runtime_error("b9h_influence_table: invalid argument");
+        b9h::influence_table(acc, tail_len > 0 ? tail : nullptr, tail_len, n_stars, n_q, table);
+    });
+}
+
+int b9h_group_influence_table(const double *group_lpd, long n_rows, int n_groups, const double *q, int n_q, const int32_t *group, long n_stars, double *table)
+{
+    return guard([&] {
+        if (n_rows < 0 || n_groups < 1 || n_groups > B9_INF_MAX_GROUPS || n_q < 1 || n_q > B9_INF_MAX_Q || n_stars < 0 || !table || (n_rows > 0 && (!group_lpd || !q)) ||
+            (n_stars > 0 && !group))
+            throw std::runtime_error("b9h_group_influence_table: invalid argument");
+        b9h::group_influence_table(group_lpd, n_rows, n_groups, q, n_q, group, n_stars, table);
+    });
+}
+
+int b9h_influence_quantities(int argc, char **argv, const double *rows, const double *log_post, long n_rows, char *names, int cap, double *q, double *mean, double *sd,
+                             int *n_q)
+{
+    return guard([&] {
+        if (!rows || !names || !q || !mean || !sd || !n_q) throw std::runtime_error("b9h_influence_quantities: invalid argument");
+        b9h::Settings st;
+        st.parse_args(argc, argv, b9h::kStarInfluenceFlags);
+        const b9h::InfluenceQuantities iq = b9h::influence_quantities(b9h::star_influence_config(st), rows, log_post, n_rows);
+        std::string joined;
+        for (size_t j = 0; j < iq.names.size(); ++j) joined += (j ? " " : "") + iq.names[j];
+        if ((int)joined.size() + 1 > cap) throw std::runtime_error("b9h_influence_quantities: the names do not fit");
+        std::copy(joined.begin(), joined.end(), names); names[joined.size()] = 0;
+        std::copy(iq.q.begin(), iq.q.end(), q); std::copy(iq.mean.begin(), iq.mean.end(), mean); std::copy(iq.sd.begin(), iq.sd.end(), sd);
+        *n_q = (int)iq.names.size();
+    });
+}
+
+int b9h_influence_groups(int argc, char **argv, const char *const *ids, const int32_t *stage, long n_stars, char *names, int cap, int32_t *group, int *n_groups)
+{
+    return guard([&] {
+        if (n_stars < 0 || !names || !n_groups || (n_stars > 0 && (!ids || !stage || !group))) throw std::runtime_error("b9h_influence_groups: invalid argument");
+        b9h::Settings st;
+        st.parse_args(argc, argv, b9h::kStarInfluenceFlags);
+        const b9h::InfluenceGroups g = b9h::influence_groups(b9h::star_influence_config(st), strings(ids, n_stars), std::vector<int32_t>(stage, stage + n_stars));
+        std::string joined;
+        for (size_t j = 0; j < g.names.size(); ++j) joined += (j ? " " : "") + g.names[j];
+        if ((int)joined.size() + 1 > cap) throw std::runtime_error("b9h_influence_groups: the names do not fit");
+        std::copy(joined.begin(), joined.end(), names); names[joined.size()] = 0;
+        std::copy(g.id.begin(), g.id.end(), group);
+        *n_groups = (int)g.names.size();
+    });
+}
+
+int b9h_write_star_influence(const char *path, const char *const *ids, long n_stars, const char *const *quantities, int n_q, const double *table)
+{
+    return guard([&] {
+        if (!path || n_stars < 0 || n_q < 1 || !quantities || (n_stars > 0 && (!ids || !table))) throw std::runtime_error("b9h_write_star_influence: invalid argument");
+        b9h::write_star_influence(path, strings(ids, n_stars), strings(quantities, n_q), table);
+    });
+}
+
+int b9h_write_group_influence(const char *path, const char *const *groups, int n_groups, const char *const *quantities, int n_q, const double *table)
+{
+    return guard([&] {
+        if (!path || n_groups < 1 || n_q < 1 || !groups || !quantities || !table) throw std::runtime_error("b9h_write_group_influence: invalid argument");
+        b9h::write_group_influence(path, strings(groups, n_groups), strings(quantities, n_q), table);
+    });
+}
+
+int b9h_star_influence_settings(int argc, char **argv, char *out, int cap)
+{
+    return settings_text("b9h_star_influence_settings", argc, argv, b9h::kStarInfluenceFlags, out, cap, [&](const b9h::Settings &st) {
+        const b9h::StarInfluenceConfig c = b9h::star_influence_config(st);
+        std::string qs;
+        for (size_t j = 0; j < c.quantities.size(); ++j) qs += (j ? " " : "") + c.quantities[j];
+        return grid_text(b9h::chain_grid(st, "starInfluence")) + "quantity = " + qs + "\ngroupFile = " + c.group_file + "\nnoGroups = " + std::to_string((int)c.no_groups) + "\n";
+    });
+}
+
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part)
 {
     return guard([&] { b9h::merge_result_parts(final_path, world, walkers_per_rank, rows_per_part); });

@@ -395,8 +395,10 @@ McmcResult run_mcmc(Session &s, Exchange &ex, const std::vector<std::string> &co
     return res;
 }
 
-std::vector<double> read_res_rows(const std::string &res_path, const std::vector<double> &start, int stage)
+std::vector<double> read_res_rows(const std::string &res_path, const std::vector<double> &start, int stage, std::vector<double> *log_post)
 {
+    int col_log_post = -1;
+    if (log_post) log_post->clear();
     if ((int)start.size() < B9_NPARAM) throw std::runtime_error("read_res_rows: the starting row needs B9_NPARAM values");
     std::ifstream in(res_path);
     if (!in) throw std::runtime_error("cannot read " + res_path + " (run singlePopMcmc first)");
@@ -409,6 +411,7 @@ std::vector<double> read_res_rows(const std::string &res_path, const std::vector
         std::istringstream hs(line);
         std::string name;
         while (hs >> name) {
+            if (name == "logPost") col_log_post = (int)col_param.size();
             if (name == "logPost" || name == "stage") { col_param.push_back(-1); continue; }
             int idx = -2;
             for (int k = 0; k < B9_NPARAM; ++k) if (name == param_name(k)) idx = k;
@@ -428,6 +431,7 @@ std::vector<double> read_res_rows(const std::string &res_path, const std::vector
         std::vector<double> row(start.begin(), start.begin() + B9_NPARAM);
         for (size_t c = 0; c < col_param.size(); ++c) if (col_param[c] >= 0) row[col_param[c]] = v[c];
         rows.insert(rows.end(), row.begin(), row.end());
+        if (log_post && col_log_post >= 0) log_post->push_back(v[(size_t)col_log_post]);
     }
     return rows;
 }
@@ -441,7 +445,7 @@ SavedChain open_saved_chain(Session &s, const ChainGrid &g)
     }
     SavedChain c;
     const std::string res_path = s.output_base + ".res";
-    c.rows = read_res_rows(res_path, s.start, 3);
+    c.rows = read_res_rows(res_path, s.start, 3, &c.log_post);
     c.n_rows = (long)(c.rows.size() / B9_NPARAM);
     if (c.n_rows == 0) throw std::runtime_error(res_path + " holds no main-run (stage 3) rows");
     return c;

@@ -61,7 +61,8 @@ void merge_result_parts(const std::string &final_path, int world, int per, long 
 // names the sampled parameters, then "logPost stage"; a column that is no parameter name is an error; data lines that do
 // not hold one number per column are skipped.  Throws when the file cannot be read, is empty or has a malformed header.
 // What sampleMass and sampleWDMass read (libbase9host exports it as b9h_read_res_rows).
-std::vector<double> read_res_rows(const std::string &res_path, const std::vector<double> &start, int stage);
+// log_post (may be null): the rows' logPost column, empty when the file has none.
+std::vector<double> read_res_rows(const std::string &res_path, const std::vector<double> &start, int stage, std::vector<double> *log_post = nullptr);
 
 // What every program over a saved chain does before its own work, from s.settings: opens the session with the grid's
 // population count, sets the options {given-mass mode, n_pops, K, Q} -- K = 0 (sampleWDMass, wdSummary: their calls read the
@@ -69,6 +70,7 @@ std::vector<double> read_res_rows(const std::string &res_path, const std::vector
 // "<path> holds no main-run (stage 3) rows" when there are none.
 struct SavedChain {
     std::vector<double> rows;             // [n_rows][B9_NPARAM]
+    std::vector<double> log_post;         // [n_rows] (empty: the file has no logPost column)
     long n_rows = 0;
     const double *row(long r) const { return rows.data() + (size_t)r * B9_NPARAM; }
 };

@@ -1,5 +1,5 @@
 """Builds the C++ host programs (base_amd/host/): libbase9host.so + singlePopMcmc, multiPopMcmc,
-makeCMD, cmdBand, sampleMass, sampleWDMass, wdSummary, wdIntervals, starSummary, massFunction, binaryStats, starIntervals, photResiduals, filterCheck, starOffsets, modelScore, simCluster, scatterCluster.  Plain g++ against the C ABI; they link libbase9hip.so by rpath."""
+makeCMD, cmdBand, sampleMass, sampleWDMass, wdSummary, wdIntervals, starSummary, massFunction, binaryStats, starIntervals, photResiduals, filterCheck, starOffsets, modelScore, starInfluence, simCluster, scatterCluster.  Plain g++ against the C ABI; they link libbase9hip.so by rpath."""
 from __future__ import annotations
 
 import os
@@ -58,7 +58,7 @@ def build_host(force: bool = False) -> None:
              "starSummary": ("starsummary_main.cpp", []), "massFunction": ("massfunction_main.cpp", []),
              "binaryStats": ("binarystats_main.cpp", []),
              "starIntervals": ("starintervals_main.cpp", []),
-             "photResiduals": ("photresiduals_main.cpp", []), "filterCheck": ("filtercheck_main.cpp", []), "starOffsets": ("staroffsets_main.cpp", []), "modelScore": ("modelscore_main.cpp", []),
+             "photResiduals": ("photresiduals_main.cpp", []), "filterCheck": ("filtercheck_main.cpp", []), "starOffsets": ("staroffsets_main.cpp", []), "modelScore": ("modelscore_main.cpp", []), "starInfluence": ("starinfluence_main.cpp", []),
              "simCluster": ("simcluster_main.cpp", []), "scatterCluster": ("scattercluster_main.cpp", [])}
     for name, (src, defs) in progs.items():
         exe = os.path.join(BIN, name)

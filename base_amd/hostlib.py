@@ -46,6 +46,8 @@ HOST_SYMBOLS = [
     "b9h_loo_table", "b9h_filter_loo_table", "b9h_write_star_filter_check", "b9h_write_filter_check", "b9h_filter_check_settings",
     "b9h_offset_direction", "b9h_offset_table", "b9h_offset_dist_table", "b9h_write_star_offsets", "b9h_write_offset_dist", "b9h_star_offsets_settings",
     "b9h_pointwise_table", "b9h_score_totals", "b9h_score_compare", "b9h_write_pointwise", "b9h_write_model_score", "b9h_model_score_settings",
+    "b9h_influence_table", "b9h_group_influence_table", "b9h_influence_quantities", "b9h_influence_groups", "b9h_write_star_influence",
+    "b9h_write_group_influence", "b9h_star_influence_settings",
 ]
 
 _lib = None
@@ -142,6 +144,13 @@ def load() -> C.CDLL:
     lib.b9h_write_pointwise.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, _dp]
     lib.b9h_write_model_score.argtypes = [C.c_char_p, _dp]
     lib.b9h_model_score_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
+    lib.b9h_influence_table.argtypes = [_dp, _dp, C.c_int, C.c_long, C.c_int, _dp]
+    lib.b9h_group_influence_table.argtypes = [_dp, C.c_long, C.c_int, _dp, C.c_int, _ip, C.c_long, _dp]
+    lib.b9h_influence_quantities.argtypes = [C.c_int, C.POINTER(C.c_char_p), _dp, _dp, C.c_long, C.c_char_p, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int)]
+    lib.b9h_influence_groups.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _ip, C.c_long, C.c_char_p, C.c_int, _ip, C.POINTER(C.c_int)]
+    lib.b9h_write_star_influence.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_long, C.POINTER(C.c_char_p), C.c_int, _dp]
+    lib.b9h_write_group_influence.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, _dp]
+    lib.b9h_star_influence_settings.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, C.c_int]
     lib.b9h_sim_draw_systems.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_int, C.c_double, _dp, _dp, _dp, _ip, _ip]
     lib.b9h_sim_field_mags.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int, _dp, _dp, _dp]
@@ -1122,3 +1131,96 @@ def sim_settings(program: str, args: Sequence[str]) -> dict:
         k, v = line.split(" = ", 1)
         out[k] = float(v)
     return out
+
+
+INFLUENCE_HEAD = ("rows", "nInf", "ess", "paretoK")
+GROUP_INFLUENCE_HEAD = ("nStars", "rows", "nInf", "ess", "paretoK")
+
+
+def influence_table(acc, tail=None) -> np.ndarray:
+    """b9h_influence_table: b9_star_influence's acc [n_stars, 6 + 4 Q] and tail [n_stars, tail_len] (None: no PSIS fit) -> the
+    per-star table [n_stars, 4 + 3 Q]: INFLUENCE_HEAD, then shift, lin, looSd per quantity."""
+    a = np.ascontiguousarray(acc, dtype=np.float64)
+    n, nq = a.shape[0], (a.shape[1] - 6) // 4
+    t = None if tail is None else np.ascontiguousarray(tail, dtype=np.float64).reshape(n, -1)
+    out = np.empty((n, 4 + 3 * nq))
+    _check(load().b9h_influence_table(a.ctypes.data_as(_dp), t.ctypes.data_as(_dp) if t is not None else None, 0 if t is None else t.shape[1], n, nq,
+                                      out.ctypes.data_as(_dp)))
+    return out
+
+
+def group_influence_table(group_lpd, q, groups) -> np.ndarray:
+    """b9h_group_influence_table: b9_star_influence's group_lpd [n_rows, G], the call's q [n_rows, Q] and the stars' group ids ->
+    the per-group table [G, 5 + 3 Q]: GROUP_INFLUENCE_HEAD, then shiftRaw, shift, looSd per quantity."""
+    L = np.ascontiguousarray(group_lpd, dtype=np.float64)
+    q = np.ascontiguousarray(q, dtype=np.float64).reshape(L.shape[0], -1)
+    g = np.ascontiguousarray(groups, dtype=np.int32)
+    out = np.empty((L.shape[1], 5 + 3 * q.shape[1]))
+    _check(load().b9h_group_influence_table(L.ctypes.data_as(_dp), L.shape[0], L.shape[1], q.ctypes.data_as(_dp), q.shape[1],
+                                            g.ctypes.data_as(C.POINTER(C.c_int32)), len(g), out.ctypes.data_as(_dp)))
+    return out
+
+
+def _argv(prog, args):
+    return (C.c_char_p * (len(args) + 1))(prog, *[str(a).encode() for a in args])
+
+
+def influence_quantities(args, rows, log_post=None):
+    """b9h_influence_quantities: (names, q [n_rows, Q], mean [Q], sd [Q]) as starInfluence forms them from `args` and the main-run
+    rows [n_rows, B9_NPARAM] (log_post [n_rows] or None)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    n = rows.shape[0]
+    lp = None if log_post is None else np.ascontiguousarray(log_post, dtype=np.float64)
+    names, q, mean, sd, nq = C.create_string_buffer(1024), np.empty(n * 12), np.empty(12), np.empty(12), C.c_int(0)
+    _check(load().b9h_influence_quantities(len(args) + 1, _argv(b"starInfluence", args), rows.ctypes.data_as(_dp), lp.ctypes.data_as(_dp) if lp is not None else None,
+                                           n, names, 1024, q.ctypes.data_as(_dp), mean.ctypes.data_as(_dp), sd.ctypes.data_as(_dp), C.byref(nq)))
+    k = nq.value
+    return names.value.decode().split(), q[:n * k].reshape(n, k).copy(), mean[:k].copy(), sd[:k].copy()
+
+
+def influence_groups(args, ids, stage):
+    """b9h_influence_groups: (names, ids [n_stars] int32) as starInfluence forms the groups from `args`, the catalogue's star ids
+    and stages."""
+    st = np.ascontiguousarray(stage, dtype=np.int32)
+    names, g, ng = C.create_string_buffer(1024), np.full(len(ids), -1, np.int32), C.c_int(0)
+    ip = C.POINTER(C.c_int32)
+    _check(load().b9h_influence_groups(len(args) + 1, _argv(b"starInfluence", args), _names(ids), st.ctypes.data_as(ip), len(ids), names, 1024,
+                                       g.ctypes.data_as(ip), C.byref(ng)))
+    return names.value.decode().split(), g
+
+
+def write_star_influence(path: str, ids, quantities, table) -> None:
+    """b9h_write_star_influence: the .starInfluence file of a per-star table [len(ids), 4 + 3 len(quantities)]."""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(len(ids), 4 + 3 * len(quantities))
+    _check(load().b9h_write_star_influence(path.encode(), _names(ids), len(ids), _names(quantities), len(quantities), t.ctypes.data_as(_dp)))
+
+
+def write_group_influence(path: str, groups, quantities, table) -> None:
+    """b9h_write_group_influence: the .groupInfluence file of a per-group table [len(groups), 5 + 3 len(quantities)]."""
+    t = np.ascontiguousarray(table, dtype=np.float64).reshape(len(groups), 5 + 3 * len(quantities))
+    _check(load().b9h_write_group_influence(path.encode(), _names(groups), len(groups), _names(quantities), len(quantities), t.ctypes.data_as(_dp)))
+
+
+def read_star_influence(path: str):
+    """(ids, columns, table [n_stars, 4 + 3 Q]) of a .starInfluence file."""
+    return read_table_file(path, "id")
+
+
+def read_group_influence(path: str):
+    """(groups, columns, table [G, 5 + 3 Q]) of a .groupInfluence file."""
+    return read_table_file(path, "group")
+
+
+def read_influence_scale(path: str):
+    """(names, columns, table [Q, 2]: mean, sd) of an .influenceScale file."""
+    return read_table_file(path, "name")
+
+
+def star_influence_settings(args):
+    """starInfluence's settings as the program parses `args` (flags, --config file): margIsoIncrem, nMassRatios, nPops, noGroups
+    (ints), quantity (a list of names) and groupFile."""
+    buf = C.create_string_buffer(4096)
+    _check(load().b9h_star_influence_settings(len(args) + 1, _argv(b"starInfluence", args), buf, 4096))
+    d = dict(line.split(" = ") if " = " in line else (line.rstrip(" ="), "") for line in buf.value.decode().splitlines())
+    return dict(margIsoIncrem=int(d["margIsoIncrem"]), nMassRatios=int(d["nMassRatios"]), nPops=int(d["nPops"]), quantity=d["quantity"].split(),
+                groupFile=d["groupFile"], noGroups=int(d["noGroups"]))

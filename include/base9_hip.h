@@ -298,7 +298,7 @@ int b9_mcmc_run_block(b9_ctx *ctx, b9_mcmc_block *blk);
  * b9_set_priors or b9_set_options changes the posterior: the previous block's state carries a log-posterior of the old
  * one, so the next B9_BLOCK_CONTINUE block returns B9_ERR_STATE (the message names the call that intervened) and the chain
  * restarts from host state.  b9_set_tuning (plans change rounding only), b9_predict_mags, b9_sample_wd_mass, b9_star_moments,
- * b9_wd_moments, b9_wd_bins, b9_mass_hist, b9_ratio_hist, b9_phot_resid, b9_filter_loo, b9_star_offset and b9_pointwise (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
+ * b9_wd_moments, b9_wd_bins, b9_mass_hist, b9_ratio_hist, b9_phot_resid, b9_filter_loo, b9_star_offset, b9_pointwise and b9_star_influence (buffers of their own) between continued blocks are allowed.  While a block is outstanding it owns the
  * context's work buffers: b9_logpost / b9_sample_mass / b9_derive_isochrone, the staging calls, b9_set_options and a block
  * with another n_walkers return B9_ERR_STATE until it has been collected.  A driver that adapts the proposal
  * from block b-1 while block b runs keeps the GPU's queue non-empty: enqueue b+1 (CONTINUE | ASYNC), wait(b), ...
@@ -826,6 +826,65 @@ int b9_pointwise(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flag
                  double *acc     /* host [n_stars][B9_PW_N],   in/out, may be NULL */,
                  double *tail    /* host [n_stars][tail_len],  in/out, may be NULL */,
                  double *row_lpd /* host [n_rows],             out,    may be NULL */);
+
+/*
+ * Star influence over a saved chain (the starInfluence counterpart): which stars and which groups of stars drive the cluster
+ * parameters.  Added in ABI 6 without a version change, as its siblings were: purely additive.  Stars are independent given the
+ * cluster parameters, so the posterior without star i is the chain reweighted by exp(-v_ri), and the posterior without a group G
+ * of stars is the chain reweighted by exp(-sum_{i in G} v_ri): the call reduces both on the device.
+ *
+ * Definition.  The grid, the terms, the pruning (b9_tuning.marg_no_pruning), the treatment of n_pops / mode and the value
+ * v = logaddexp(la_i, l) of (row r, star i) are exactly b9_pointwise's.  A row outside the grid touches no star.  q (host,
+ * [n_rows][n_q], 1 <= n_q <= B9_INF_MAX_Q, finite) holds the caller's own per-row scalars; the library gives them no meaning.
+ *
+ * acc (host, [n_stars][B9_INF_N(n_q)], the caller's star order, in/out, nullable): updated one row at a time in ascending row
+ * order; with k = ROWS - NINF before the row, the row's value v and r = -v:
+ *     ROWS + 1 for every row inside the grid;  NINF + 1 if v = -inf, and such a row touches nothing else;
+ *     k = 0:  RMAX = r, SNEG = 1, SNEG2 = 1, MEANV = v;  per j: WQ = q_j, WQ2 = q_j q_j, MQ = q_j, CVQ = 0;
+ *     k > 0, r > RMAX, f = exp(RMAX - r), ff = f f:  SNEG = fma(SNEG, f, 1), SNEG2 = fma(SNEG2, ff, 1), WQ_j = fma(WQ_j, f, q_j),
+ *             WQ2_j = fma(WQ2_j, f, q_j q_j), RMAX = r;
+ *     k > 0 otherwise, e = exp(r - RMAX):  SNEG = SNEG + e, SNEG2 = fma(e, e, SNEG2), WQ_j = fma(e, q_j, WQ_j),
+ *             WQ2_j = fma(e q_j, q_j, WQ2_j);
+ *     k > 0, after either:  dv = v - MEANV, MEANV += dv / (k + 1);  per j: dq = q_j - MQ_j, MQ_j += dq / (k + 1),
+ *             CVQ_j = fma(dv, q_j - MQ_j, CVQ_j) with the new MQ_j                                           (Welford).
+ * One exp; contractions only where written.  (ROWS, NINF, RMAX, SNEG) are b9_pointwise's words, bit for bit.  The state is
+ * carried whole, so the bits are the same for the call's own chunking (b9_pointwise's: at most 32 rows, the same 16 MiB rule) and
+ * for any split of the rows over B9_INF_CONTINUE calls; flags = 0 starts from zeros.  A quantity's four columns depend on that
+ * quantity alone: not on n_q, its position or the other quantities.  SNEG^2 / SNEG2 is the effective sample size of the chain
+ * without star i; WQ / SNEG the mean of q_j without it; -CVQ / (ROWS - NINF - 1) the first-order move of that mean.
+ *
+ * tail / tail_len: exactly b9_pointwise's (the tail_len largest -v per star, descending, padded with -inf; requires acc).
+ *
+ * group_lpd (host, [n_rows][n_groups], out, nullable; 1 <= n_groups <= B9_INF_MAX_GROUPS): group (host, [n_stars]) gives every
+ * star's group, -1 for none.  group_lpd[r][g] = sum of v_ri over the stars with group[i] == g, in ascending caller order from
+ * +0.0, one plain add per star; -inf propagates; an empty group inside the grid gives 0.0; a row outside the grid gives -inf for
+ * every group.  A row's sums depend on that row alone and a group's sums do not depend on the other groups.  An empty catalogue
+ * gives all-zero group_lpd.
+ *
+ * Synchronous; host pointers.  B9_ERR_INVALID (every output untouched) for NULL ctx or params, n_rows < 1, both acc and
+ * group_lpd NULL, acc with n_q outside 1 .. B9_INF_MAX_Q or NULL q, a q that is not finite, tail_len outside
+ * [0, B9_PW_MAX_TAIL], tail without acc, group_lpd with n_groups outside 1 .. B9_INF_MAX_GROUPS, NULL group or an id outside
+ * -1 .. n_groups - 1; B9_ERR_STATE while a sampler block is outstanding; B9_ERR_CAPACITY as its siblings.  The call uses buffers
+ * of its own: a B9_BLOCK_CONTINUE block enqueued after it gives the same bits as one enqueued without it.
+ */
+#define B9_INF_ROWS 0
+#define B9_INF_NINF 1
+#define B9_INF_RMAX 2
+#define B9_INF_SNEG 3
+#define B9_INF_SNEG2 4
+#define B9_INF_MEANV 5
+#define B9_INF_HEAD 6
+#define B9_INF_WQ(j)  (6 + 4 * (j))      /* then WQ2, MQ, CVQ at +1, +2, +3 */
+#define B9_INF_N(Q)   (6 + 4 * (Q))
+#define B9_INF_MAX_Q 12
+#define B9_INF_MAX_GROUPS 8
+#define B9_INF_CONTINUE 1
+int b9_star_influence(b9_ctx *ctx, const double *params, int32_t n_rows, int32_t flags,
+                      int32_t n_q, const double *q   /* host [n_rows][n_q] */,
+                      double *acc                    /* host [n_stars][B9_INF_N(n_q)], in/out, may be NULL */,
+                      int32_t tail_len, double *tail /* host [n_stars][tail_len], in/out, may be NULL */,
+                      int32_t n_groups, const int32_t *group /* host [n_stars], -1 or 0 .. n_groups-1 */,
+                      double *group_lpd              /* host [n_rows][n_groups], out, may be NULL */);
 
 /*
  * Isochrone and WD-sequence bands over a saved chain (the cmdBand counterpart): the model locus the posterior implies in the

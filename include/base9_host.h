@@ -279,6 +279,28 @@ int b9h_score_compare(const double *table_a, const char *const *ids_a, long n_a,
 int b9h_write_pointwise(const char *path, const char *const *ids, long n_stars, const double *table);
 int b9h_write_model_score(const char *path, const double *totals);
 int b9h_model_score_settings(int argc, char **argv, char *out, int cap);
+/* starInfluence.  b9h_influence_table: b9_star_influence's acc [n_stars][6 + 4 n_q] and tail (NULL or tail_len 0: no PSIS fit) ->
+ * the per-star table [n_stars][4 + 3 n_q]: rows, nInf, ess = SNEG^2 / SNEG2, paretoK (modelScore's fit of the tail; NaN where none is
+ * made), then per quantity shift = WQ / SNEG - MQ (the move of the quantity's mean when the star is deleted), lin = -CVQ / (n_f - 1)
+ * (its first-order form, 0 for n_f < 2) and looSd = sqrt(max(0, WQ2 / SNEG - (WQ / SNEG)^2)).  nInf > 0: ess = 0, the rest NaN.
+ * rows = 0: every value 0.
+ * b9h_group_influence_table: group_lpd [n_rows][n_groups], the call's q [n_rows][n_q] and the stars' ids [n_stars] -> the per-group
+ * table [n_groups][5 + 3 n_q]: nStars, rows, nInf (the rows whose sum is -inf), ess, paretoK, then per quantity shiftRaw, shift (the M
+ * largest weights Pareto-smoothed; = shiftRaw where the fit is refused) and looSd.  nInf > 0: ess = 0, the rest NaN.
+ * b9h_influence_quantities / b9h_influence_groups: what the program passes to the call, from its command line (argv[0] is skipped)
+ * and YAML: the quantities' names (space-joined into names), their z-scores q [n_rows][n_q] over rows [n_rows][B9_NPARAM] (log_post
+ * may be NULL) with mean and sd [n_q]; the groups' names and every star's id (-1: none) from the catalogue's ids and stages.  The
+ * arrays hold B9_INF_MAX_Q / B9_INF_MAX_GROUPS entries per row / in all.
+ * b9h_write_star_influence / b9h_write_group_influence: the files <base>.starInfluence and <base>.groupInfluence (docs/FORMATS.md).
+ * b9h_star_influence_settings: "key = value" lines of margIsoIncrem, nMassRatios, nPops, quantity, groupFile, noGroups into out. */
+int b9h_influence_table(const double *acc, const double *tail, int tail_len, long n_stars, int n_q, double *table);
+int b9h_group_influence_table(const double *group_lpd, long n_rows, int n_groups, const double *q, int n_q, const int32_t *group, long n_stars, double *table);
+int b9h_influence_quantities(int argc, char **argv, const double *rows, const double *log_post, long n_rows, char *names, int cap, double *q, double *mean, double *sd,
+                             int *n_q);
+int b9h_influence_groups(int argc, char **argv, const char *const *ids, const int32_t *stage, long n_stars, char *names, int cap, int32_t *group, int *n_groups);
+int b9h_write_star_influence(const char *path, const char *const *ids, long n_stars, const char *const *quantities, int n_q, const double *table);
+int b9h_write_group_influence(const char *path, const char *const *groups, int n_groups, const char *const *quantities, int n_q, const double *table);
+int b9h_star_influence_settings(int argc, char **argv, char *out, int cap);
 /* rank 0's merge of <final_path>.part<r> into <final_path> after a --gpus N run (b9h::merge_result_parts; exposed for tests) */
 int b9h_merge_parts(const char *final_path, int world, int walkers_per_rank, long rows_per_part);
 
